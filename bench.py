@@ -8,6 +8,13 @@ permutation generation -> permutation exceedance counts, inputs resident in
 HBM.  tests per step = G*T*P.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` (tests/s over the
+timed steps) and `ms_per_step`.  ``--full`` adds everything else the line has carried: per-kernel
+times, the roofline objects, clock / power telemetry, the sustained window, the K1 cold sweep, the
+strong curve (`scaling_strong`) and the CPU baselines.  ``--dump-outputs DIR`` writes what the
+last timed step returned (dump_outputs).
 
 ``--gpus N`` with N > 1 runs N ranks by itself (re-executes under
 ``torch.distributed.run --nproc-per-node N``) unless it is already running under a
@@ -79,7 +86,7 @@ def parse(argv=None):
                          "table in (scoary/exampledata/Gene_presence_absence.csv: 100, ..., 0 isolates)")
     ap.add_argument("--strong-extra", default="auto", choices=["auto", "on", "off"],
                     help="also time the strong split of cfg3 and cfg4 over the ranks of this run "
-                         "(`scaling_strong`); auto: on for the default cfg3 weak line")
+                         "(`scaling_strong`); auto: on for the default cfg3 weak line with --full")
     ap.add_argument("--genes", type=int, default=None, help="override G (per GPU / total)")
     ap.add_argument("--permutations", type=int, default=None, help="override P")
     ap.add_argument("--isolates", type=int, default=None, help="override N (shape experiments)")
@@ -87,7 +94,14 @@ def parse(argv=None):
     ap.add_argument("--gene-kind", default=None, choices=["uniform", "rare", "ushaped", "balanced"],
                     help="gene-frequency spectrum instead of the config's own (evidence lines next to the "
                          "BASELINE configs: ushaped = Beta(0.15, 0.15), a pan-genome-like spectrum)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure everything else the line reports (per-kernel times, "
+                         "rooflines, telemetry, sustained window, K1 cold sweep, strong curve, CPU baselines); "
+                         "a plain run times the steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of the genes above that); rank 0's own")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--exercise-exchange", action="store_true",
                     help="run the RCCL exchange step even at world size 1 (launched under "
                          "torch.distributed.run with one rank): a 1-GPU check of the N>1 code path")
@@ -100,7 +114,7 @@ def parse(argv=None):
                          "(AssociationEngine.auto_graph_eligible)")
     ap.add_argument("--no-graph", action="store_true", help="never replay a hipGraph (eager launches)")
     ap.add_argument("--cpu-seconds", type=float, default=6.0,
-                    help="target wall time of each cpu_baseline sample")
+                    help="--full: target wall time of each cpu_baseline sample")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend of a multi-rank run: nccl (= RCCL over xGMI, the real "
                          "thing) or gloo (host-staged; lets several ranks share ONE GPU with --share-gpu, "
@@ -112,7 +126,7 @@ def parse(argv=None):
                     help="after the timed region rank 0 recomputes every rank's shard by itself and "
                          "compares the gathered records with it bit for bit (gather_matches_single_rank)")
     ap.add_argument("--telemetry-ms", type=float, default=4.0,
-                    help="sampling period of the shader-clock / socket-power side thread during the "
+                    help="--full: sampling period of the shader-clock / socket-power side thread during the "
                          "timed region (amdsmi or hwmon); 0 switches it off")
     ap.add_argument("--inject-gather-fault", action="store_true", help=argparse.SUPPRESS)   # tests: corrupt one
     # received record before --verify-gather looks at it; every rank must then exit non-zero, together
@@ -123,16 +137,19 @@ def parse(argv=None):
                          "on the BASELINE shapes)")
     ap.add_argument("--k1-cold", action="store_true", help=argparse.SUPPRESS)     # the default since round 5
     ap.add_argument("--no-k1-cold", action="store_true",
-                    help="skip roofline_k1.cold: k_counts timed on a working set the 256 MiB Infinity Cache cannot "
+                    help="--full: skip roofline_k1.cold: k_counts timed on a working set the 256 MiB Infinity Cache cannot "
                          "hold (cfg5's 125 000 x 10 000 shard shape with T = 1 and 4, eight 160 MB matrices in "
                          "rotation; single GPU only, ~1 s and 1.3 GB)")
     ap.add_argument("--sustain-seconds", type=float, default=6.0,
-                    help="after the timed region (single GPU): run the step back to back this long and report "
+                    help="--full, after the timed region (single GPU): run the step back to back this long and report "
                          "the clock / power the box sustains (the `sustained` object); 0 skips it")
     ap.add_argument("--dry-exchange", action="store_true",
                     help="CPU-only check of the launcher + exchange path (gloo, fabricated "
                          "records, no kernels): what tests/test_dist_gloo.py drives")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # --------------------------------------------------------------- launcher -----
@@ -786,6 +803,56 @@ def k1_cold_report(eng, args, G=125_000, N=10_000, copies=8, rounds=3):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(torch, res, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays one associate() step returns, as out_dir/<name>.npy -- counts [T, G, 4],
+    margins [T, 2], p / odds [T, G], crit [T, G, 2] and r [T, G] (the exceedance counts, unsigned).  Integer
+    arrays are written as float32 when every value is below 2**24, else float64: exact either way.  Every file
+    holds finite numbers only: an array with non-finite entries (odds of a table with an empty cell: +-inf, 0/0)
+    is written with 0 in their place, next to <name>_nonfinite.npy (float32, same shape: 0 finite, 1 +inf,
+    2 -inf, 3 NaN), so nothing is lost.  If the arrays would exceed ``limit`` bytes in all, the same fixed,
+    seeded sample of the genes (axis 1) is taken from each and its indices are written as gene_index.npy.
+    Returns {name: shape}."""
+    arrays = {}
+    for name in ("counts", "margins", "p", "odds", "crit", "r"):
+        t = res.get(name)
+        if t is None:
+            continue
+        if name == "r":
+            t = t.to(torch.int64) & 0xFFFFFFFF             # uint32 bit pattern held in int32
+        if not t.is_floating_point():
+            t = t.to(torch.float32 if int(t.abs().max().item()) < (1 << 24) else torch.float64)
+        finite = torch.isfinite(t)
+        if not bool(finite.all()):
+            code = torch.zeros(t.shape, dtype=torch.float32, device=t.device)
+            code[t == float("inf")] = 1
+            code[t == float("-inf")] = 2
+            code[torch.isnan(t)] = 3
+            t = torch.where(finite, t, torch.zeros_like(t))
+            arrays[name + "_nonfinite"] = code
+        arrays[name] = t
+    gene_axis = [k for k in arrays if k != "margins"]
+    limit -= 4096                                          # the .npy headers
+    total = sum(t.numel() * t.element_size() for t in arrays.values())
+    if total > limit:
+        G = arrays["p"].shape[1]
+        per_gene = sum(arrays[k].numel() * arrays[k].element_size() for k in gene_axis) // G + 8
+        fixed = sum(t.numel() * t.element_size() for k, t in arrays.items() if k not in gene_axis)
+        keep = (limit - fixed) // per_gene
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(G, size=keep, replace=False))
+        sel = torch.from_numpy(idx).to(arrays["p"].device)
+        for k in gene_axis:
+            arrays[k] = arrays[k].index_select(1, sel)
+        arrays["gene_index"] = torch.from_numpy(idx.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    return {k: tuple(t.shape) for k, t in arrays.items()}
+
+
 def make_step(torch, eng, gm, trv, mkv, P, seed, ws, use_lists, plan, exchange, use_graph):
     """-> (step(i), graphs): one pass of the hot path on this rank's genes + (sharded) the submit of
     its records to the exchange.  With ``use_graph`` the local step is a hipGraph replay; a sharded
@@ -1026,10 +1093,13 @@ def main():
             eng.build_lists(gm_)                   # on the device, from the tiled matrix
         torch.cuda.synchronize()
         return gm_, trv_, mkv_, ul, plan_
-    setup()                                        # first call pays module loads; time the second
-    t0 = time.perf_counter()
+    setup_ms = None
+    if args.full:
+        setup()                                    # first call pays module loads; time the second
+        t0 = time.perf_counter()
     gm, trv, mkv, use_lists, plan = setup()
-    setup_ms = (time.perf_counter() - t0) * 1e3
+    if args.full:
+        setup_ms = (time.perf_counter() - t0) * 1e3
 
     pbatch = eng.perm_batch(T, N, P)
     ws = eng.workspace(gm, T, P, use_lists=use_lists)
@@ -1061,12 +1131,13 @@ def main():
     # A launch-bound run (cfg2: a 1-2 ms timed region of 0.06 ms graph launches) is not sampled from
     # inside: one amdsmi read costs a few hundred microseconds of interpreter time and would be the
     # largest thing in the region.  It gets one reading right before and one right after instead.
-    tele = Telemetry(local_rank, period_s=max(0.001, args.telemetry_ms * 1e-3)) if args.telemetry_ms > 0 else None
+    tele = Telemetry(local_rank, period_s=max(0.001, args.telemetry_ms * 1e-3)) \
+        if args.full and args.telemetry_ms > 0 else None
     tele_inside = tele is not None and not eng.auto_graph_eligible(gm, T, P)
     for _ in range(args.warmup):
         step()
     barrier()
-    if graph is None:
+    if graph is None and args.full:                 # per-kernel events inside the timed steps
         eng.set_timing(True)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     edge = []
@@ -1077,7 +1148,7 @@ def main():
     t0 = time.perf_counter()
     ev[0].record()
     for i in range(args.steps):
-        step()
+        res = step()
         ev[i + 1].record()
     # how long the HOST took to issue the steps (launches, graph replays, the exchange's submit): when this
     # is close to the whole timed region the run is bound by the interpreter, not by the GPU
@@ -1105,87 +1176,91 @@ def main():
             telemetry["sampled"] = "inside the timed region"
     step_ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2] if step_ms else None
-    if graph is not None:                           # per-kernel times: a few eager steps afterwards
-        eng.set_timing(True)
-        for _ in range(5):
-            eng.associate(gm, trv, mkv, permutations=P, seed=seed, use_lists=use_lists, workspace=ws, plan=plan,
-                          graph=False)
-        torch.cuda.synchronize()
-    k3_name = eng.list_kernel_name(N) if use_lists else "k_permute"
-    k3_ms = eng.kernel_ms(k3_name)
-    names = ("k_counts", "k_fisher") + (
-        ("k_perm_generate_tiles", k3_name, "k_lists_reduce") if use_lists else
-        ("k_perm_generate", "k_permute"))
-    kernel_ms = {k: eng.kernel_ms(k) for k in names}
-    eng.set_timing(False)
-    # K1 and K2 by themselves (roofline_k1 / roofline_k2): inside a step k_fisher shares the chip with
-    # the label-tile generator on the side stream, so its in-step duration is not its own
-    iso = {}
-    saved_shards, ws.label_shards = ws.label_shards, None     # the generator alone: all tiles, no collective
-    gen = ()
-    if use_lists and P > 0:
-        gen = (("k_perm_generate_tiles",
-                lambda: eng.perm_generate_tiles(mkv, plan.margins, N, min(ws.batch, P), 0, seed, out=ws.tiles)),)
-    for name, fn in gen + (("k_counts", lambda: eng.counts(gm, trv, mkv, out=(ws.counts,), plan=plan)),
-                     ("k_fisher", lambda: eng.fisher(ws.counts, out=(ws.p, ws.odds, ws.crit),
-                                                     **({"lists": gm.lists, "lcrit": ws.lcrit} if use_lists and P > 0
-                                                        else {})))):
-        fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(5):
-            fn()
-        e1.record()
-        e1.synchronize()
-        iso[name] = e0.elapsed_time(e1) / 5
-    ws.label_shards = saved_shards
-    # The command line's output-fidelity pass (scoary_fisher_scipy: SciPy's own digits for what gets printed above
-    # 170 isolates) is NOT in the timed step -- the path's p is k_fisher's, within 1e-12 --; its cost, for the record:
-    scipy_digits = None
-    if N > 170 and hasattr(eng, "fisher_scipy"):
-        pcopy = ws.p.clone()
-        eng.fisher_scipy(ws.counts, pcopy)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        eng.fisher_scipy(ws.counts, pcopy)
-        e1.record()
-        e1.synchronize()
-        scipy_digits = {"kernel": "k_fisher_scipy", "kernel_ms": e0.elapsed_time(e1), "tables": int(G) * int(T),
-                        "in_timed_step": False,
-                        "what": "scipy.stats.fisher_exact's own double for every table (Boost's prime-factorised pmf "
-                                "restated): run by the command line over what it prints, so that its result files are "
-                                "the reference's bytes; the benchmarked step keeps k_fisher's p (within 1e-12)",
-                        "max_abs_change_of_p": float((pcopy - ws.p).abs().max().item())}
-        del pcopy
-    k1_cold = k1_cold_report(eng, args) if (not args.no_k1_cold and not sharded) else None
-
-    # The box under SUSTAINED load (single GPU, outside the timed region, GPU still warm): the same
-    # step back to back for --sustain-seconds, clock and power from the second half of the window.
-    # amdsmi's readings inside a 0.1 s region that follows an idle GPU are not a calibrated clock
-    # (1.73 ... 2.22 GHz reported across runs whose kernel times agree to 0.5 %; the socket power
-    # is a moving average still on its way up); after a second at the power cap they are
-    # (2.19-2.21 GHz at 1.33-1.36 kW, as rocm-smi says).  This is what tells a slow box from a
-    # slow kernel: the sustained clock the box grants this kernel, and lane-ops per that clock.
-    sustained = None
-    if args.sustain_seconds > 0 and not sharded and median_ms and median_ms < 200.0 \
-            and tele is not None and tele._read is not None:
-        tele2 = Telemetry(local_rank, period_s=0.01).start()
-        s0 = time.perf_counter()
-        nsteps = 0
-        burst = max(1, int(50.0 / median_ms))                 # ~50 ms of steps per synchronize
-        while time.perf_counter() - s0 < args.sustain_seconds:
-            for _ in range(burst):
-                step()
-            nsteps += burst
+    if args.dump_outputs and rank == 0:            # before anything else reuses the workspace
+        dump_outputs(torch, res, args.dump_outputs)
+    kernel_ms = iso = k3_name = k3_ms = scipy_digits = k1_cold = sustained = None
+    if args.full:
+        if graph is not None:                       # per-kernel times: a few eager steps afterwards
+            eng.set_timing(True)
+            for _ in range(5):
+                eng.associate(gm, trv, mkv, permutations=P, seed=seed, use_lists=use_lists, workspace=ws, plan=plan,
+                              graph=False)
             torch.cuda.synchronize()
-        s1 = time.perf_counter()
-        sustained = tele2.stop(s0 + 0.5 * (s1 - s0), s1)
-        sustained.update({"steps": nsteps, "seconds": s1 - s0, "ms_per_step": (s1 - s0) / nsteps * 1e3,
-                          "value": G * T * P * nsteps / (s1 - s0),
-                          "what": "the same step back to back after the timed region; clock / power over the "
-                                  "second half of the window"})
+        k3_name = eng.list_kernel_name(N) if use_lists else "k_permute"
+        k3_ms = eng.kernel_ms(k3_name)
+        names = ("k_counts", "k_fisher") + (
+            ("k_perm_generate_tiles", k3_name, "k_lists_reduce") if use_lists else
+            ("k_perm_generate", "k_permute"))
+        kernel_ms = {k: eng.kernel_ms(k) for k in names}
+        eng.set_timing(False)
+        # K1 and K2 by themselves (roofline_k1 / roofline_k2): inside a step k_fisher shares the chip with
+        # the label-tile generator on the side stream, so its in-step duration is not its own
+        iso = {}
+        saved_shards, ws.label_shards = ws.label_shards, None     # the generator alone: all tiles, no collective
+        gen = ()
+        if use_lists and P > 0:
+            gen = (("k_perm_generate_tiles",
+                    lambda: eng.perm_generate_tiles(mkv, plan.margins, N, min(ws.batch, P), 0, seed, out=ws.tiles)),)
+        for name, fn in gen + (("k_counts", lambda: eng.counts(gm, trv, mkv, out=(ws.counts,), plan=plan)),
+                         ("k_fisher", lambda: eng.fisher(ws.counts, out=(ws.p, ws.odds, ws.crit),
+                                                         **({"lists": gm.lists, "lcrit": ws.lcrit} if use_lists and P > 0
+                                                            else {})))):
+            fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(5):
+                fn()
+            e1.record()
+            e1.synchronize()
+            iso[name] = e0.elapsed_time(e1) / 5
+        ws.label_shards = saved_shards
+        # The command line's output-fidelity pass (scoary_fisher_scipy: SciPy's own digits for what gets printed above
+        # 170 isolates) is NOT in the timed step -- the path's p is k_fisher's, within 1e-12 --; its cost, for the record:
+        scipy_digits = None
+        if N > 170 and hasattr(eng, "fisher_scipy"):
+            pcopy = ws.p.clone()
+            eng.fisher_scipy(ws.counts, pcopy)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            eng.fisher_scipy(ws.counts, pcopy)
+            e1.record()
+            e1.synchronize()
+            scipy_digits = {"kernel": "k_fisher_scipy", "kernel_ms": e0.elapsed_time(e1), "tables": int(G) * int(T),
+                            "in_timed_step": False,
+                            "what": "scipy.stats.fisher_exact's own double for every table (Boost's prime-factorised pmf "
+                                    "restated): run by the command line over what it prints, so that its result files are "
+                                    "the reference's bytes; the benchmarked step keeps k_fisher's p (within 1e-12)",
+                            "max_abs_change_of_p": float((pcopy - ws.p).abs().max().item())}
+            del pcopy
+        k1_cold = k1_cold_report(eng, args) if (not args.no_k1_cold and not sharded) else None
+
+        # The box under SUSTAINED load (single GPU, outside the timed region, GPU still warm): the same
+        # step back to back for --sustain-seconds, clock and power from the second half of the window.
+        # amdsmi's readings inside a 0.1 s region that follows an idle GPU are not a calibrated clock
+        # (1.73 ... 2.22 GHz reported across runs whose kernel times agree to 0.5 %; the socket power
+        # is a moving average still on its way up); after a second at the power cap they are
+        # (2.19-2.21 GHz at 1.33-1.36 kW, as rocm-smi says).  This is what tells a slow box from a
+        # slow kernel: the sustained clock the box grants this kernel, and lane-ops per that clock.
+        sustained = None
+        if args.sustain_seconds > 0 and not sharded and median_ms and median_ms < 200.0 \
+                and tele is not None and tele._read is not None:
+            tele2 = Telemetry(local_rank, period_s=0.01).start()
+            s0 = time.perf_counter()
+            nsteps = 0
+            burst = max(1, int(50.0 / median_ms))                 # ~50 ms of steps per synchronize
+            while time.perf_counter() - s0 < args.sustain_seconds:
+                for _ in range(burst):
+                    step()
+                nsteps += burst
+                torch.cuda.synchronize()
+            s1 = time.perf_counter()
+            sustained = tele2.stop(s0 + 0.5 * (s1 - s0), s1)
+            sustained.update({"steps": nsteps, "seconds": s1 - s0, "ms_per_step": (s1 - s0) / nsteps * 1e3,
+                              "value": G * T * P * nsteps / (s1 - s0),
+                              "what": "the same step back to back after the timed region; clock / power over the "
+                                      "second half of the window"})
     dt_own = dt
     per_rank = None
     if sharded:                                      # MAX over ranks
@@ -1258,7 +1333,7 @@ def main():
                     and args.isolates is None and args.traits is None and args.gene_kind is None
                     and args.scaling == "weak")
     scaling_strong = None
-    if args.strong_extra == "on" or (args.strong_extra == "auto" and default_line):
+    if args.strong_extra == "on" or (args.strong_extra == "auto" and default_line and args.full):
         scaling_strong = {"what": "the config's genes split over the n_gpus ranks of this run (stride domains, "
                                   "scoary_amd.dist.GenePartition), exchange included; value = the config's "
                                   "G x T x P tests / the slowest rank's time; speed-up over one GPU = value / the "
@@ -1309,21 +1384,27 @@ def main():
             "gather_matches_single_rank": gather_ok,
             "per_rank": per_rank,
             "scaling_strong": scaling_strong,
+            # SURVEY 8d's end-to-end figure: the observed tables count as tests too, G*T*(P+1)
+            "value_incl_observed_tables": G_total * T * (P + 1) * args.steps / dt,
+        }
+        out["config"]["scaling_strong"] = None if scaling_strong is None else {
+            k: {f: v.get(f) for f in ("n_gpus", "value", "ms_per_step", "hip_graph", "rccl_ranks", "genes_per_gpu")}
+            for k, v in scaling_strong.items() if isinstance(v, dict)}
+    if rank == 0 and args.full:
+        out.update({
             # once per data set, outside the timed region: H2D of the packed bits + device tiling +
             # device list build + trait vectors and their plan (margins, mask classes); host
             # bit-packing and parsing excluded
             "setup_ms": setup_ms,
             "value_incl_setup": tests_per_step * args.steps / (dt + setup_ms * 1e-3),
             "value_single_step_incl_setup": tests_per_step / (dt / args.steps + setup_ms * 1e-3),
-            # SURVEY 8d's end-to-end figure: the observed tables count as tests too, G*T*(P+1)
-            "value_incl_observed_tables": G_total * T * (P + 1) * args.steps / dt,
             "roofline": roofline_report(
                 args, eng, use_lists, G, N, T, P, ws.batch if use_lists else pbatch, k3_name, k3_ms,
                 adders=list_adder_work(eng, gm, genes, T, P, ws.batch) if use_lists else None,
                 telemetry=telemetry),
             "telemetry": telemetry,
             "kernel_ms": kernel_ms,
-        }
+        })
         cls = plan.mask_class.cpu().numpy()
         tpp = int(eng.lib.scoary_counts_traits_per_pass(T))       # classes are counted once per PASS
         out["kernel_source_sha256"] = kernel_source_sha()      # same hash + another time = another box
@@ -1342,9 +1423,6 @@ def main():
         out["roofline"]["sustained"] = None if sustained is None else {
             k: sustained.get(k) for k in ("value", "ms_per_step", "seconds", "steps", "sclk_mhz_mean",
                                           "socket_power_w_mean", "ops_per_clock_frac")}
-        out["config"]["scaling_strong"] = None if scaling_strong is None else {
-            k: {f: v.get(f) for f in ("n_gpus", "value", "ms_per_step", "hip_graph", "rccl_ranks", "genes_per_gpu")}
-            for k, v in scaling_strong.items() if isinstance(v, dict)}
         out["fisher_scipy_digits"] = scipy_digits
         out["kernel_ms_isolated"] = iso            # five back-to-back launches of the kernel alone
         out["kernel_ms_note"] = ("kernel_ms: hipEvent durations inside the timed steps -- there the label generator "
@@ -1369,6 +1447,7 @@ def main():
                 out["cpu_baseline"] = {"value": None, "kind": "scipy-restatement",
                                        "error": "%s: %s" % (type(e).__name__, e)}
             out["cpu_baseline_port"] = port
+    if rank == 0:
         print(json.dumps(out))
     if sharded:
         dist.destroy_process_group()

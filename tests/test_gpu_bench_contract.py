@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 def _run(extra):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--genes", "3000",
-                          "--permutations", "1024", "--steps", "3", "--warmup", "1"] + extra,
+                          "--permutations", "1024", "--steps", "3", "--warmup", "1", "--full"] + extra,
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -127,7 +127,7 @@ def test_bench_headline_line_explains_itself():
     own roofline entries (item 4)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     r, tel = d["roofline"], d["telemetry"]
@@ -161,3 +161,42 @@ def test_bench_headline_line_explains_itself():
         assert 0 < r["ops_per_clock"] < 32768 and abs(r["ops_per_clock_frac"] - r["ops_per_clock"] / 32768) < 1e-12
         # frac is taken against 2.4 GHz, ops_per_clock against the clock the box granted
         assert abs(r["frac"] * 2400.0 / tel["sclk_mhz_mean"] - r["ops_per_clock_frac"]) < 1e-9
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times the steps and prints the headline only; --dump-outputs writes what the
+    last timed step returned, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--genes", "3000", "--permutations",
+                              "1024", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["higher_is_better"] is True and d["unit"] == "tests/s"
+        G, T, P = d["config"]["genes_per_gpu"], d["config"]["traits"], d["config"]["permutations"]
+        assert abs(d["value"] - G * T * P / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for k in ("roofline", "kernel_ms", "telemetry", "sustained", "cpu_baseline", "roofline_k1"):
+            assert k not in d, k
+        assert d["scaling_strong"] is None
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)})
+    a, b = dumps
+    names = ["counts", "crit", "margins", "odds", "p", "r"]
+    assert sorted(k for k in a if not k.endswith("_nonfinite")) == names
+    assert a["counts"].shape == (T, G, 4) and a["p"].shape == a["r"].shape == (T, G)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    # non-finite entries (odds of a table with an empty cell) are coded beside their array, not lost
+    for k in a:
+        if k.endswith("_nonfinite"):
+            base = k[:-len("_nonfinite")]
+            assert base in names and a[k].shape == a[base].shape and set(np.unique(a[k])) <= {0, 1, 2, 3}
+            assert (a[base][a[k] != 0] == 0).all()
+    # every table of a trait holds its valid isolates (margins: positives, valid); r counts of P permutations
+    assert np.array_equal(a["counts"].sum(axis=2), np.broadcast_to(a["margins"][:, 1:2], (T, G)))
+    assert a["r"].min() >= 0 and a["r"].max() <= P
+    for k in a:
+        assert np.array_equal(a[k], b[k], equal_nan=True), k

@@ -28,7 +28,7 @@ def _bench(extra, ranks=2, config="cfg2", steps=4):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--share-gpu",
                           "--backend", "gloo", "--config", config, "--steps", str(steps), "--warmup", "1",
-                          "--verify-gather"] + extra,
+                          "--verify-gather", "--full"] + extra,
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

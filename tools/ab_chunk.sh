@@ -11,12 +11,12 @@ pick='import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); 
 echo "# tools/ab_chunk.sh: MB of index lists per k_permute_lists block (tree: 2)"
 for v in 2 8 16 2 8; do          # (2, 4, 8, 16 MB twice over: profiles/r02_ab_list_chunk_bytes.txt)
   export SCOARY_LIST_CHUNK_MB=$v
-  python bench.py --no-cpu-baseline 2>/dev/null | python -c "$pick" $v cfg3
-  python bench.py --no-cpu-baseline --config cfg4 2>/dev/null | python -c "$pick" $v cfg4
+  python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "$pick" $v cfg3
+  python bench.py --full --no-cpu-baseline --config cfg4 2>/dev/null | python -c "$pick" $v cfg4
 done
 for v in 2 8; do
   export SCOARY_LIST_CHUNK_MB=$v
-  python bench.py --no-cpu-baseline --config cfg5 --genes 30000 --permutations 12800 --steps 3 --warmup 1 2>/dev/null | python -c "$pick" $v "cfg5 proxy 30k x 10k x 50"
+  python bench.py --full --no-cpu-baseline --config cfg5 --genes 30000 --permutations 12800 --steps 3 --warmup 1 2>/dev/null | python -c "$pick" $v "cfg5 proxy 30k x 10k x 50"
 done
 cd /tmp && export TMPDIR=/tmp
 for v in 2 8; do

@@ -4,7 +4,7 @@
 # re-loaded once per chunk: 2 MB chunks re-load every tile 8x as often as 16 MB chunks.   tools/ab_chunk_cfg5.sh [genes]
 cd "$(dirname "$0")/.."
 REPO=$(pwd); G=${1:-30000}
-ARGS="--no-cpu-baseline --sustain-seconds 0 --telemetry-ms 0 --config cfg5 --genes $G --permutations 43520 --steps 3 --warmup 1"
+ARGS="--full --no-cpu-baseline --sustain-seconds 0 --telemetry-ms 0 --config cfg5 --genes $G --permutations 43520 --steps 3 --warmup 1"
 pick='import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("chunk %-3s MB  step %9.3f ms  k_permute_lists %9.3f ms  value %.4e" % (sys.argv[1], d["ms_per_step"], d["kernel_ms"]["k_permute_lists"], d["value"]))'
 for v in 2 8 16 32 2 16; do
   SCOARY_LIST_CHUNK_MB=$v python bench.py $ARGS 2>/dev/null | python -c "$pick" $v

@@ -7,7 +7,7 @@ for args in "--config cfg3" "--config cfg4" "--config cfg4 --genes 25000" "--con
   for i in 1 2; do
     for v in prev new; do
       lib=""; [ $v = prev ] && lib="$PWD/_ab/prefisher.so"
-      SCOARY_HIP_LIB=$lib python bench.py --no-cpu-baseline --no-k1-cold --sustain-seconds 0 --strong-extra off --telemetry-ms 0 $args 2>/dev/null | python -c "$pick" $v "$args"
+      SCOARY_HIP_LIB=$lib python bench.py --full --no-cpu-baseline --no-k1-cold --sustain-seconds 0 --strong-extra off --telemetry-ms 0 $args 2>/dev/null | python -c "$pick" $v "$args"
     done
   done
 done

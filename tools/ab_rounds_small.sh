@@ -7,7 +7,7 @@ pick='import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); 
 for args in "--config cfg4 --genes 25000" "--config cfg4 --genes 50000" "--config cfg3 --genes 6250" "--config cfg2" "--config cfg4"; do
   for i in 1 2; do
     for r in 16 4 2; do
-      SCOARY_LIST_ROUNDS=$r python bench.py --no-cpu-baseline --no-k1-cold --sustain-seconds 0 --strong-extra off --telemetry-ms 0 $args 2>/dev/null | python -c "$pick" $r "$args"
+      SCOARY_LIST_ROUNDS=$r python bench.py --full --no-cpu-baseline --no-k1-cold --sustain-seconds 0 --strong-extra off --telemetry-ms 0 $args 2>/dev/null | python -c "$pick" $r "$args"
     done
   done
 done

@@ -9,7 +9,7 @@ ARGS="${*:---config cfg5 --steps 3 --warmup 1}"
 pick='import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d["roofline"]; t=d.get("telemetry") or {}; print("%-10s step %.2f ms  k_permute_lists %.2f ms  value %.4e  sclk %s MHz  power %s W  useful_frac %.3f" % (sys.argv[1], d["ms_per_step"], d["kernel_ms"]["k_permute_lists"], d["value"], t.get("sclk_mhz_mean") and round(t["sclk_mhz_mean"]), t.get("socket_power_w_mean") and round(t["socket_power_w_mean"]), r["useful_frac"]))'
 for i in 1 2; do
   for v in 0 1; do
-    SCOARY_LIST_XCD_MAP=$v python bench.py --no-cpu-baseline --no-k1-cold --sustain-seconds 0 $ARGS 2>/dev/null | python -c "$pick" xcd_map=$v
+    SCOARY_LIST_XCD_MAP=$v python bench.py --full --no-cpu-baseline --no-k1-cold --sustain-seconds 0 $ARGS 2>/dev/null | python -c "$pick" xcd_map=$v
   done
 done
 cd /tmp && export TMPDIR=/tmp

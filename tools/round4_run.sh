@@ -10,10 +10,10 @@ PARTS="${*:-configs cfg5 wide exchange soak}"
 has() { case " $PARTS " in *" $1 "*) return 0;; esac; return 1; }
 if has configs; then
 # the driver's own command, first thing on the fresh box
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_cfg3_driver_command.json 2> $O/bench_cfg3_driver_command.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_cfg3_driver_command.json 2> $O/bench_cfg3_driver_command.err
 # counter profiles + bench lines (with the CPU baselines) of the single-GPU BASELINE configs
 bash tools/profile_configs.sh r04 cfg3 cfg4 cfg2 > $O/profile_configs.log 2>&1
-python bench.py --config cfg2 --no-graph > $O/bench_cfg2_eager.json 2>/dev/null
+python bench.py --full --config cfg2 --no-graph > $O/bench_cfg2_eager.json 2>/dev/null
 fi
 if has cfg5; then
 bash tools/profile_configs.sh r04 cfg5 > $O/profile_cfg5.log 2>&1
@@ -22,23 +22,23 @@ if has wide; then
 # the wide (segmented) shape of VERDICT r3 item 3
 bash tools/profile.sh r04_wide --genes 20000 --isolates 50000 --traits 2 --permutations 1024 > $O/profile_wide.log 2>&1
 find gpurun_out/prof_r04_wide -type f ! -name '*.db' ! -name '*.txt' ! -name '*.log' -delete
-python bench.py --genes 20000 --isolates 50000 --traits 2 --permutations 1024 --no-cpu-baseline > $O/bench_wide_50000_lists.json 2>/dev/null
-python bench.py --genes 20000 --isolates 50000 --traits 2 --permutations 1024 --no-cpu-baseline --kernel dense > $O/bench_wide_50000_dense.json 2>/dev/null
+python bench.py --full --genes 20000 --isolates 50000 --traits 2 --permutations 1024 --no-cpu-baseline > $O/bench_wide_50000_lists.json 2>/dev/null
+python bench.py --full --genes 20000 --isolates 50000 --traits 2 --permutations 1024 --no-cpu-baseline --kernel dense > $O/bench_wide_50000_dense.json 2>/dev/null
 python tools/sweep_isolates.py --permutations 8192 --traits 4 > $O/sweep_isolates.txt 2>&1
 # a pan-genome-shaped evidence line next to cfg3
-python bench.py --gene-kind ushaped --no-cpu-baseline > $O/bench_cfg3_ushaped.json 2>/dev/null
-python bench.py --config cfg4 --gene-kind ushaped --no-cpu-baseline > $O/bench_cfg4_shape_ushaped.json 2>/dev/null
+python bench.py --full --gene-kind ushaped --no-cpu-baseline > $O/bench_cfg3_ushaped.json 2>/dev/null
+python bench.py --full --config cfg4 --gene-kind ushaped --no-cpu-baseline > $O/bench_cfg4_shape_ushaped.json 2>/dev/null
 fi
 if has exchange; then
 # one rank through RCCL, weak and strong
 for sc in weak strong; do
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 \
-    bench.py --exercise-exchange --verify-gather --no-cpu-baseline --steps 10 --warmup 2 --scaling $sc \
+    bench.py --full --exercise-exchange --verify-gather --no-cpu-baseline --steps 10 --warmup 2 --scaling $sc \
     > $O/bench_exchange_${sc}_1rank.json 2> $O/bench_exchange_$sc.err
 done
 # sustained clock / power (rocm-smi next to 3000 back-to-back steps; the line itself carries amdsmi's samples)
 tools/clock_sample.sh > $O/clock_power.txt 2>&1
-python bench.py --steps 3000 --warmup 5 --no-cpu-baseline > $O/bench_cfg3_sustained_3000_steps.json 2>/dev/null
+python bench.py --full --steps 3000 --warmup 5 --no-cpu-baseline > $O/bench_cfg3_sustained_3000_steps.json 2>/dev/null
 # the command line end to end on a cfg3-sized table
 python tools/e2e_synth.py --genes 50000 --isolates 2000 --traits 10 --permute 10000 > $O/e2e_cli_cfg3.txt 2>&1
 fi

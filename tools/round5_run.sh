@@ -8,10 +8,10 @@ mkdir -p $O gpurun_out/profiles_r05
 PARTS="${*:-configs cfg5 extras soak}"
 has() { case " $PARTS " in *" $1 "*) return 0;; esac; return 1; }
 if has configs; then
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_cfg3_driver_command.json 2> $O/bench_cfg3_driver_command.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_cfg3_driver_command.json 2> $O/bench_cfg3_driver_command.err
 bash tools/profile_configs.sh r05 cfg3 cfg4 cfg2 > $O/profile_configs.log 2>&1
-python bench.py --config cfg2 --no-graph > $O/bench_cfg2_eager.json 2>/dev/null
-python bench.py --config cfg4 --genes 25000 --no-cpu-baseline > $O/bench_cfg4_rank_of_8.json 2>/dev/null
+python bench.py --full --config cfg2 --no-graph > $O/bench_cfg2_eager.json 2>/dev/null
+python bench.py --full --config cfg4 --genes 25000 --no-cpu-baseline > $O/bench_cfg4_rank_of_8.json 2>/dev/null
 fi
 if has cfg5; then
 bash tools/profile_configs.sh r05 cfg5 > $O/profile_cfg5.log 2>&1
@@ -20,12 +20,12 @@ if has extras; then
 bash tools/profile.sh r05_wide --genes 20000 --isolates 50000 --traits 2 --permutations 1024 > $O/profile_wide.log 2>&1
 python tools/rocpd_summary.py gpurun_out/prof_r05_wide profiles/r05_wide50000 wide50000 >> $O/profile_wide.log 2>&1
 find gpurun_out/prof_r05_wide -type f ! -name '*.db' ! -name '*.txt' ! -name '*.log' -delete
-python bench.py --genes 20000 --isolates 50000 --traits 2 --permutations 1024 --no-cpu-baseline > $O/bench_wide_50000_lists.json 2>/dev/null
-python bench.py --gene-kind balanced --no-cpu-baseline > $O/bench_cfg3_balanced.json 2>/dev/null
-python bench.py --gene-kind ushaped --no-cpu-baseline > $O/bench_cfg3_ushaped.json 2>/dev/null
+python bench.py --full --genes 20000 --isolates 50000 --traits 2 --permutations 1024 --no-cpu-baseline > $O/bench_wide_50000_lists.json 2>/dev/null
+python bench.py --full --gene-kind balanced --no-cpu-baseline > $O/bench_cfg3_balanced.json 2>/dev/null
+python bench.py --full --gene-kind ushaped --no-cpu-baseline > $O/bench_cfg3_ushaped.json 2>/dev/null
 for sc in weak strong; do
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 \
-    bench.py --exercise-exchange --verify-gather --no-cpu-baseline --steps 10 --warmup 2 --scaling $sc \
+    bench.py --full --exercise-exchange --verify-gather --no-cpu-baseline --steps 10 --warmup 2 --scaling $sc \
     > $O/bench_exchange_${sc}_1rank.json 2> $O/bench_exchange_$sc.err
 done
 for c in "2000 10 10000" "5000 1 10000" "10000 50 4096" "50000 2 1024"; do python tools/gen_time.py $c; done 2>&1 | grep "^N=" > $O/generator_alone.txt

@@ -12,14 +12,14 @@ if has tests; then
 tail -5 $O/pytest_gpu.log
 fi
 if has bench; then
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_cfg3_driver_command.json 2> $O/bench_cfg3_driver_command.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_cfg3_driver_command.json 2> $O/bench_cfg3_driver_command.err
 tail -c 600 $O/bench_cfg3_driver_command.err
 fi
 if has driver; then
 # the driver's command, twice, with its wall clock (the default line now also times cfg4 for scaling_strong)
 for i in 1 2; do
   SECONDS=0
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_cfg3_driver_command_$i.json 2> $O/bench_cfg3_driver_command_$i.err
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_cfg3_driver_command_$i.json 2> $O/bench_cfg3_driver_command_$i.err
   echo "driver command run $i: wall ${SECONDS} s"
 done
 fi
@@ -30,20 +30,20 @@ python tools/shard_balance.py --exampledata tests/golden/exampledata/Gene_presen
 grep -h "^#\|max / mean\|partition\|=>" $O/shard_balance_*.txt
 # the 8-rank shared-GPU rehearsal on frequency-sorted genes, both partitions (functional + per_rank lines)
 for part in stride contiguous; do
-python bench.py --gpus 8 --share-gpu --backend gloo --config cfg3 --scaling strong --gene-order sorted --partition $part \
+python bench.py --full --gpus 8 --share-gpu --backend gloo --config cfg3 --scaling strong --gene-order sorted --partition $part \
   --verify-gather --no-cpu-baseline --steps 5 --warmup 2 > $O/bench_cfg3_sorted_8ranks_shared_$part.json 2> $O/bench_cfg3_sorted_8ranks_shared_$part.err
 done
 fi
 if has rank8; then
 for i in 1 2; do
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 2951$i \
-  bench.py --exercise-exchange --verify-gather --no-cpu-baseline --config cfg4 --genes 25000 --scaling strong \
+  bench.py --full --exercise-exchange --verify-gather --no-cpu-baseline --config cfg4 --genes 25000 --scaling strong \
   > $O/bench_cfg4_rank_of_8_sharded_$i.json 2> $O/bench_cfg4_rank_of_8_sharded_$i.err
 done
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29513 \
-  bench.py --exercise-exchange --verify-gather --no-cpu-baseline --config cfg4 --genes 25000 --scaling strong --no-graph \
+  bench.py --full --exercise-exchange --verify-gather --no-cpu-baseline --config cfg4 --genes 25000 --scaling strong --no-graph \
   > $O/bench_cfg4_rank_of_8_sharded_eager.json 2>/dev/null
-python bench.py --config cfg4 --genes 25000 --no-cpu-baseline > $O/bench_cfg4_rank_of_8_single_process.json 2>/dev/null
+python bench.py --full --config cfg4 --genes 25000 --no-cpu-baseline > $O/bench_cfg4_rank_of_8_single_process.json 2>/dev/null
 fi
 if has e2e; then
 python tools/e2e_vcf.py > $O/e2e_cli_cfg4_vcf.txt 2>&1
@@ -56,7 +56,7 @@ if has k1; then
 for i in 1 2; do
   for v in r5 new; do
     lib=""; [ $v = r5 ] && lib="$PWD/_ab/r5.so"
-    SCOARY_HIP_LIB=$lib python bench.py --no-cpu-baseline --sustain-seconds 0 --strong-extra off --steps 5 --warmup 2 2>/dev/null \
+    SCOARY_HIP_LIB=$lib python bench.py --full --no-cpu-baseline --sustain-seconds 0 --strong-extra off --steps 5 --warmup 2 2>/dev/null \
       | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); c = d['roofline_k1']['cold']
@@ -95,7 +95,7 @@ if has seg; then
 python tools/ab_conflicts.py --shapes wide > $O/ab_seg_conflicts.txt 2>&1
 cat $O/ab_seg_conflicts.txt
 for p in 1024 4096; do
-python bench.py --genes 20000 --isolates 50000 --traits 2 --permutations $p --no-cpu-baseline --strong-extra off > $O/bench_wide_50000_P$p.json 2>/dev/null
+python bench.py --full --genes 20000 --isolates 50000 --traits 2 --permutations $p --no-cpu-baseline --strong-extra off > $O/bench_wide_50000_P$p.json 2>/dev/null
 done
 fi
 if has profiles; then

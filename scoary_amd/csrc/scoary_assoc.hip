@@ -1016,38 +1016,26 @@ int scoary_permute(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d_p
   nch = (P + pchunk - 1) / pchunk;
   dim3 grid((unsigned)gene_waves, (unsigned)nch, (unsigned)T);
 
-  // Tuning knob (experiments only): SCOARY_PERMUTE_VARIANT=reg|c8x8|c8x16|c4x16|c8x4
-  const char* variant = std::getenv("SCOARY_PERMUTE_VARIANT");
-  const bool force_chunk = variant && variant[0] == 'c';
-  const bool use_reg = Qp <= kMaxRegQuads && !force_chunk && (Qp <= kAutoRegQuads || (variant && variant[0] == 'r'));
+  // tiled rows are a kRegQuads size up to kMaxRegQuads quads, multiples of kChunkQuads beyond
+  if (Qp > kMaxRegQuads && Qp % kChunkQuads != 0)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_permute: unsupported tiled row size");
   KernelTimer kt(h, s, "k_permute");
-  if (use_reg) {
+  if (Qp <= kMaxRegQuads) {
     switch (Qp) {
 #define CASE_RQ(RQ)                                                                          \
   case RQ:                                                                                   \
     launch_permute_reg<RQ, 1>(grid, s, d_tiled, d_perms, d_crit, (int)G, (int)Gp, P, pchunk, d_r); \
     break;
       CASE_RQ(1) CASE_RQ(2) CASE_RQ(4) CASE_RQ(6) CASE_RQ(8) CASE_RQ(12) CASE_RQ(16) CASE_RQ(20)
-      CASE_RQ(24) CASE_RQ(32) CASE_RQ(40) CASE_RQ(48)
+      CASE_RQ(24)
 #undef CASE_RQ
       default:
         return fail(h, SCOARY_ERR_SIZE, "scoary_permute: unsupported tiled row size");
     }
   } else {
-    const uint4* t4 = reinterpret_cast<const uint4*>(d_tiled);
-    const uint2* c2 = reinterpret_cast<const uint2*>(d_crit);
-    const std::string v = variant ? variant : "";
-#define LAUNCH_CHUNK(CQ, PB)                                                                  \
-  hipLaunchKernelGGL((k_permute_chunked<CQ, PB>), grid, dim3(kWave), 0, s, t4, d_perms, c2, (int)G, \
-                     (int)Gp, (int)Qp, P, pchunk, d_r)
-    if (v == "c8x16" && Qp % 8 == 0) LAUNCH_CHUNK(8, 16);
-    else if (v == "c4x16" && Qp % 4 == 0) LAUNCH_CHUNK(4, 16);
-    else if (v == "c8x4" && Qp % 8 == 0) LAUNCH_CHUNK(8, 4);
-    else if (Qp % 8 == 0) LAUNCH_CHUNK(8, 8);
-    else if (Qp % 4 == 0) LAUNCH_CHUNK(4, 16);
-    else if (Qp % 2 == 0) LAUNCH_CHUNK(2, 16);
-    else LAUNCH_CHUNK(1, 16);
-#undef LAUNCH_CHUNK
+    hipLaunchKernelGGL((k_permute_chunked<kChunkQuads, 8>), grid, dim3(kWave), 0, s,
+                       reinterpret_cast<const uint4*>(d_tiled), d_perms,
+                       reinterpret_cast<const uint2*>(d_crit), (int)G, (int)Gp, (int)Qp, P, pchunk, d_r);
   }
   HIP_TRY(h, hipGetLastError());
   return SCOARY_OK;

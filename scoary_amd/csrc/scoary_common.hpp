@@ -22,6 +22,9 @@ struct scoary_ctx {
   bool timing = false;
   int lists_lds_optin = 0;   // k_permute_lists instances (by tile width) with the 160 KB LDS opt-in done
   int labels_lds_optin = 0;  // k_labels instances with it
+  uint32_t* scipy_primes = nullptr;  // scoary_fisher_scipy's prime table and reciprocals (device,
+  float* scipy_inv = nullptr;        // built on the handle's first call, freed by scoary_destroy)
+  int scipy_nprimes = 0;
   struct Timed {
     std::string name;
     hipEvent_t start, stop;
@@ -36,9 +39,9 @@ constexpr int kGeneAlign = 256;
 
 // Row sizes (in quads of four 32-bit words) for which a gene row is held
 // entirely in VGPRs by k_permute_reg.
-constexpr int kRegQuads[] = {1, 2, 4, 6, 8, 12, 16, 20, 24, 32, 40, 48};
-constexpr int kMaxRegQuads = 48;
-constexpr int kAutoRegQuads = 24;  // longer rows: the chunked kernel wins (measured 1.39x at N=5000)
+// Longer rows go to k_permute_chunked (measured 1.39x faster than registers at N=5000).
+constexpr int kRegQuads[] = {1, 2, 4, 6, 8, 12, 16, 20, 24};
+constexpr int kMaxRegQuads = 24;
 constexpr int kChunkQuads = 8;  // k_permute_chunked: quads per register chunk
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }

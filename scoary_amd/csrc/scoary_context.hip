@@ -40,6 +40,11 @@ void scoary_destroy(scoary_handle h) {
     (void)hipEventDestroy(t.start);
     (void)hipEventDestroy(t.stop);
   }
+  if (h->scipy_primes) {
+    DeviceGuard guard(h->device);
+    (void)hipFree(h->scipy_primes);
+    (void)hipFree(h->scipy_inv);
+  }
   delete h;
 }
 

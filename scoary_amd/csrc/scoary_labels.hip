@@ -93,7 +93,6 @@ struct LabelArgs {
   int trait_base;
   uint32_t k0, k1;
   int elt_log2;              // log2 of the permutations of a dword column one block keeps (5: all 32)
-  int debug;                 // SCOARY_LABELS_DEBUG (timing experiments): 1 = no fix-up, 2 = no round 0
   // tiles
   int ntiles, TW;
   int64_t first_flat, nflat; // flat (trait, tile) range of this launch
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
 #pragma unroll
     for (int w = 0; w < NB; ++w) {
       x[w] = 0u;
-      if (valid && !(a.debug & 2))
+      if (valid)
         x[w] = ((bern_word((uint32_t)row, Bglob + (uint32_t)w, tglob, plan.q, a.k0, a.k1) & live[w]) >> bit0) &
                fieldmask;
       uint32_t carry = x[w];
@@ -217,7 +216,6 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
   // ---- marks per permutation: butterfly over the wavefront, then one LDS atomic per wavefront ----
 #pragma unroll
   for (int w = 0; w < NB; ++w) {
-    if (a.debug & 8) break;
     uint32_t c[kSumPlanes];
 #pragma unroll
     for (int k = 0; k < kSumPlanes; ++k) c[k] = k < kCntPlanes ? cp[w][k] : 0u;
@@ -264,7 +262,7 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
     const int w = pidx >> 5, j = pidx & 31;
     const bool alive = in_group && ((live[NB == 1 ? 0 : (w & (NB - 1))] >> (bit0 + j)) & 1u);
     const uint32_t pi = (Bglob + (uint32_t)w) * 32u + (uint32_t)(bit0 + j);
-    int d = alive && !(a.debug & 1) ? (int)plan.m - kc[in_group ? pidx : 0] : 0;   // > 0: add marks, < 0: remove
+    int d = alive ? (int)plan.m - kc[in_group ? pidx : 0] : 0;   // > 0: add marks, < 0: remove
     const uint32_t reject_below = (uint32_t)(((uint64_t)1 << 32) % (uint64_t)N);
     const uint64_t gmask = (L == 64 ? ~(uint64_t)0 : (((uint64_t)1 << L) - 1)) << (lane & ~(L - 1));
     const int leader = lane & ~(L - 1);
@@ -364,7 +362,6 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
     }
     return f;
   };
-  if (a.debug & 4) return;
   if constexpr (OUT == 0) {
     const bool seg = a.TW == kSegTW;                  // two-dword tiles: segmented above N = 20479
     auto row_off = [&](int64_t row) -> int64_t { return seg ? list_row_dword(N, row) : row * a.TW; };
@@ -435,15 +432,6 @@ int labels_elt(int64_t N, int min_elt) {
     if (labels_lds_bytes(N, elt, 1) <= kLabelsMaxLds) return elt;
   return 0;
 }
-// tuning experiments (tools/gen_time.py): SCOARY_LABELS_TPB / SCOARY_LABELS_NB override the launch geometry
-int labels_env(const char* name) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) : 0;
-}
-int labels_debug() {
-  static const int v = [] { const char* e = std::getenv("SCOARY_LABELS_DEBUG"); return e ? std::atoi(e) : 0; }();
-  return v;
-}
 int ilog2(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;
@@ -462,8 +450,7 @@ int labels_threads(int64_t blocks, int64_t N, int num_cu) {
 template <int NB, int OUT>
 int launch_labels(scoary_handle h, hipStream_t s, const LabelArgs& a, dim3 grid, int tpb, int elt) {
   const size_t lds = (size_t)labels_lds_bytes(a.N, elt, NB);
-  // the per-lane mark counters would wrap (labels_threads never picks such a geometry; an
-  // SCOARY_LABELS_TPB override can)
+  // the per-lane mark counters would wrap (labels_threads never picks such a geometry)
   if (tpb < 64 || tpb > 1024 || (tpb & (tpb - 1)) || (a.N + tpb - 1) / tpb > kMaxRowsPerThread)
     return fail(h, SCOARY_ERR_SIZE, "k_labels: more than 1023 isolates per thread (or a block size that is no "
                                     "power of two in 64..1024)");
@@ -507,7 +494,6 @@ int scoary_perm_generate(scoary_handle h, const uint32_t* d_masks, const int32_t
   a.masks = d_masks, a.margins = d_margins, a.N = (int)N, a.Wp = (int)scoary_row_words(N);
   a.P = P, a.perm_base = perm_base, a.trait_base = (int)trait_base;
   a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.elt_log2 = ilog2(elt), a.out = d_perms;
-  a.debug = labels_debug();
   const int64_t nblk32 = ((perm_base + P - 1) >> 5) - (perm_base >> 5) + 1;   // Philox blocks touched
   const int64_t gx = nblk32 * (32 / elt);
   if (gx > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate: grid too large");
@@ -544,7 +530,6 @@ int scoary_perm_generate_tiles_range(scoary_handle h, const uint32_t* d_masks, c
   a.P = P, a.perm_base = perm_base, a.trait_base = (int)trait_base;
   a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.elt_log2 = ilog2(elt);
   a.ntiles = (int)ntiles, a.TW = TW, a.first_flat = first_tile, a.nflat = n_tiles, a.out = d_tiles;
-  a.debug = labels_debug();
   // dword columns per block: as many as keep >= 2 blocks per CU in the launch and >= 2 blocks
   // of LDS per CU (wider pieces per tile row, fewer count reductions)
   // (four columns per block were measured too: the fix-up then has two lanes per permutation and
@@ -557,12 +542,10 @@ int scoary_perm_generate_tiles_range(scoary_handle h, const uint32_t* d_masks, c
         NB = nb;
         break;
       }
-  if (elt == 32 && labels_env("SCOARY_LABELS_NB") && labels_env("SCOARY_LABELS_NB") <= (TW < 2 ? TW : 2)) NB = labels_env("SCOARY_LABELS_NB");
   const int64_t units = (int64_t)TW * (32 / elt) / NB;
   const int64_t gx = (n_tiles + 7) / 8 * 8 * units;
   if (gx > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles: grid too large");
-  int tpb = labels_threads(n_tiles * units, N, h->num_cu);
-  if (labels_env("SCOARY_LABELS_TPB")) tpb = labels_env("SCOARY_LABELS_TPB");
+  const int tpb = labels_threads(n_tiles * units, N, h->num_cu);
   KernelTimer kt(h, s, "k_perm_generate_tiles");
   if (NB == 2) return launch_labels<2, 0>(h, s, a, dim3((unsigned)gx), tpb, elt);
   return launch_labels<1, 0>(h, s, a, dim3((unsigned)gx), tpb, elt);

@@ -245,12 +245,6 @@ struct Carry4 { uint32_t w[4]; };
 // wavefront, NW permutation words per lane (4; 2 / 1 for the 2- / 1-dword rows of
 // N > 10239 / 20479, one lane per gene).  Lists are walked in sub-steps of 4 entries: lane j of a gene
 // group holds entries 4j..4j+3 of each 4*LPG-entry piece.
-// Cache policy of the tile's LDS-DMA loads (A/B builds: -DSCOARY_TILE_LOAD_POLICY='" nt"').  A tile is
-// read once per block and never again by that CU; the index lists next to it in L2 are re-read by
-// every block of the chunk.
-#ifndef SCOARY_TILE_LOAD_POLICY
-#define SCOARY_TILE_LOAD_POLICY ""
-#endif
 template <int LPG, int NW, int KC>
 __global__ __launch_bounds__(1024) void k_permute_lists(const uint32_t* __restrict__ tiles,
                                                         const uint32_t* __restrict__ lidx,
@@ -288,10 +282,6 @@ __global__ __launch_bounds__(1024) void k_permute_lists(const uint32_t* __restri
   // interleaved lists (piece = TW entries): the wavefront's 64 lanes read 64 consecutive
   // 16-byte index vectors per piece; lane l reads vector piece*64 + l of its group
   struct alignas(16) Ent { uint32_t e[4]; };
-#ifndef SCOARY_LIST_LOAD_POLICY
-#define SCOARY_LIST_LOAD_POLICY 0
-#endif
-  constexpr int kListLoadPolicy = SCOARY_LIST_LOAD_POLICY;
   // A wave group's list: its length in half-steps of 16 entries (lists are padded to 16: a last
   // half step costs half a step, where padding to 32 made the average list 3 % longer), its last
   // piece, and a buffer resource on it -- group base in the descriptor (SGPRs), piece offset in
@@ -310,7 +300,7 @@ __global__ __launch_bounds__(1024) void k_permute_lists(const uint32_t* __restri
   };
   auto load_from = [&](const Group& gr, int p) -> Ent {
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
-        gr.rsrc, lane_off, min(p, gr.last) * (kWave * (int)sizeof(Ent)), kListLoadPolicy);
+        gr.rsrc, lane_off, min(p, gr.last) * (kWave * (int)sizeof(Ent)), 0);
     return Ent{{v.x, v.y, v.z, v.w}};
   };
   // The first four index vectors of a group are requested one group AHEAD: at the start of the
@@ -333,7 +323,7 @@ __global__ __launch_bounds__(1024) void k_permute_lists(const uint32_t* __restri
       if (i + lane < n4) {
         uint32_t m0_saved;     // M0 is handed back as it was: nothing else may be assumed about it
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %2, %3" SCOARY_TILE_LOAD_POLICY "\n\ts_mov_b32 m0, %0"
+                     "global_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
                      : "=&s"(m0_saved)
                      : "s"(lds0 + (uint32_t)i * 16u), "v"(lane_off), "s"(src4 + i)
                      : "memory");
@@ -419,7 +409,7 @@ __global__ __launch_bounds__(1024) void k_permute_seglists(const uint32_t* __res
   static_assert(kSegTW == 2, "two permutation words per lane");
   // Grid as in k_permute_lists: (trait, tile) fastest, chunk of wave groups in y -- the dispatcher
   // hands the next block to whichever CU is free.  (Round 4 also tried the XCD-aware map of
-  // tools/xcd_map.patch here, every XCD one chunk of each row of eight: FETCH 4.2 -> 0.8 GB per
+  // `git show f0b16cf:tools/xcd_map.patch` here, every XCD one chunk of each row of eight: FETCH 4.2 -> 0.8 GB per
   // launch at 20 000 x 50 000 and no gain in time -- with 16-bit entries the kernel is no longer
   // fetch-bound -- and a 3x LOSS whenever there are fewer than eight chunks, XCDs standing idle:
   // 2432 genes x 40 959 isolates x 4 traits, P = 8192, 2.7 -> 9.1 ms.  Dropped.)
@@ -432,7 +422,6 @@ __global__ __launch_bounds__(1024) void k_permute_seglists(const uint32_t* __res
   const uint32_t lane_off = (uint32_t)lane * 16u;
   uint16_t* out = partial + (int64_t)blockIdx.x * ((int64_t)ngroups * GPW);
   struct alignas(16) Ent { uint32_t e[4]; };
-  constexpr int kListLoadPolicy = SCOARY_LIST_LOAD_POLICY;
   struct Group { int nhalf, last; __amdgpu_buffer_rsrc_t rsrc; };
   auto open_group = [&](int qq, int sgm) -> Group {
     const int64_t slot = (int64_t)sgm * G + (int64_t)qq * GPW;
@@ -447,7 +436,7 @@ __global__ __launch_bounds__(1024) void k_permute_seglists(const uint32_t* __res
   };
   auto load_from = [&](const Group& gr, int p) -> Ent {
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
-        gr.rsrc, lane_off, min(p, gr.last) * (kWave * (int)sizeof(Ent)), kListLoadPolicy);
+        gr.rsrc, lane_off, min(p, gr.last) * (kWave * (int)sizeof(Ent)), 0);
     return Ent{{v.x, v.y, v.z, v.w}};
   };
   const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t*)tile_lds;
@@ -564,20 +553,14 @@ int scoary_list_params(int64_t N, int64_t* out5) {
 }
 
 extern "C++" {
-// Bytes of index lists one k_permute_lists block walks against its LDS tile.  SCOARY_LIST_CHUNK_MB
-// (1..64) overrides it for same-box A/B runs (tools/ab_chunk.sh); read once per process.
+// Bytes of index lists one k_permute_lists block walks against its LDS tile.
 static int64_t list_chunk_bytes(int TW) {
-  static const long env_mb = [] {
-    const char* e = std::getenv("SCOARY_LIST_CHUNK_MB");
-    const long mb = e ? std::strtol(e, nullptr, 10) : 0;
-    return (mb >= 1 && mb <= 64) ? mb : 0L;
-  }();
   // One lane per gene (TW <= 4, N > 5119): sixteen wave groups of 64 genes are ~10 MB of lists at
-  // N = 10 000 whatever is asked for here, more than an L2 holds -- the lists of such a launch
+  // N = 10 000, more than an L2 holds -- the lists of such a launch
   // stream from the Infinity Cache / HBM once per wave of concurrent blocks either way, and larger
   // chunks re-load the 160 KB tile less often: 16 MB is -1.7 % of kernel time on a cfg5-shaped
   // shard (profiles/r05_ab_cfg5_traffic.txt; round 3 measured -1.2 %).
-  return (int64_t)(env_mb ? env_mb : (TW <= 4 ? 16 : kListChunkMB)) << 20;
+  return (int64_t)(TW <= 4 ? 16 : kListChunkMB) << 20;
 }
 // Launch geometry of k_permute_lists (also sizes the scratch)
 struct ListGeom {
@@ -593,13 +576,7 @@ static ListGeom list_geom(int num_cu, int64_t G, int64_t T, int64_t N, int64_t P
   // enough blocks for >= 16 rounds over the CUs, and gene chunks whose index lists
   // (~2 MB) stay in an XCD's 4 MB L2 while the (trait, tile) blocks of the chunk run;
   // each chunk a multiple of 16 wave groups (one per wavefront)
-  // (SCOARY_LIST_ROUNDS = 1..64 replaces the 16 for same-box A/B runs, tools/ab_rounds_small.sh)
-  static const long env_rounds = [] {
-    const char* e = std::getenv("SCOARY_LIST_ROUNDS");
-    const long v = e ? std::strtol(e, nullptr, 10) : 0;
-    return (v >= 1 && v <= 64) ? v : 16L;
-  }();
-  int64_t chunks = ((int64_t)num_cu * env_rounds + g.ntiles * T - 1) / (g.ntiles * T);
+  int64_t chunks = ((int64_t)num_cu * 16 + g.ntiles * T - 1) / (g.ntiles * T);
   const int64_t chunk_bytes = list_chunk_bytes(TW);
   const int64_t by_l2 = (entries * 4 + chunk_bytes - 1) / chunk_bytes;
   if (chunks < by_l2) chunks = by_l2;

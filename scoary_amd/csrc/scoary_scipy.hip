@@ -211,39 +211,35 @@ __global__ __launch_bounds__(64) void k_fisher_scipy(const int4* __restrict__ ta
   p_out[i] = p;
 }
 
-// the primes up to 104 729, once per device (40 KB; lives until the process ends)
-constexpr int kMaxDevices = 64;
-uint32_t* g_primes[kMaxDevices] = {};
-float* g_inv[kMaxDevices] = {};
-int g_nprimes = 0;
-
-int primes_on_device(scoary_handle h, const uint32_t** out, const float** inv_out, int* n) {
-  if (h->device < 0 || h->device >= kMaxDevices) return fail(h, SCOARY_ERR_ARG, "scoary_fisher_scipy: device index");
-  if (!g_primes[h->device]) {
-    const int top = 104730;
-    std::vector<uint8_t> sieve((size_t)top + 1, 0);
-    std::vector<uint32_t> pr;
-    pr.reserve(kMaxPrimes);
-    for (int i = 2; i <= top; ++i) {
-      if (sieve[i]) continue;
-      pr.push_back((uint32_t)i);
-      for (int64_t j = (int64_t)i * i; j <= top; j += i) sieve[(size_t)j] = 1;
-    }
-    std::vector<float> inv(pr.size());
-    for (size_t i = 0; i < pr.size(); ++i) inv[i] = 1.0f / (float)pr[i];
-    uint32_t* dev = nullptr;
-    float* dinv = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&dev), pr.size() * sizeof(uint32_t)));
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&dinv), pr.size() * sizeof(float)));
-    HIP_TRY(h, hipMemcpy(dev, pr.data(), pr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(dinv, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice));
-    g_nprimes = (int)pr.size();
-    g_inv[h->device] = dinv;
-    g_primes[h->device] = dev;
+// the primes up to 104 729 and their reciprocals (40 KB each): built on the handle's first call,
+// freed by scoary_destroy
+int primes_on_device(scoary_handle h) {
+  if (h->scipy_primes) return SCOARY_OK;
+  const int top = 104730;
+  std::vector<uint8_t> sieve((size_t)top + 1, 0);
+  std::vector<uint32_t> pr;
+  pr.reserve(kMaxPrimes);
+  for (int i = 2; i <= top; ++i) {
+    if (sieve[i]) continue;
+    pr.push_back((uint32_t)i);
+    for (int64_t j = (int64_t)i * i; j <= top; j += i) sieve[(size_t)j] = 1;
   }
-  *out = g_primes[h->device];
-  *inv_out = g_inv[h->device];
-  *n = g_nprimes;
+  std::vector<float> inv(pr.size());
+  for (size_t i = 0; i < pr.size(); ++i) inv[i] = 1.0f / (float)pr[i];
+  uint32_t* dev = nullptr;
+  float* dinv = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), pr.size() * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dinv), inv.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(dev, pr.data(), pr.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dinv, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(dev);   // hipFree(nullptr) does nothing
+    (void)hipFree(dinv);
+    return fail(h, SCOARY_ERR_HIP, std::string("scoary_fisher_scipy: prime tables: ") + hipGetErrorString(e));
+  }
+  h->scipy_primes = dev;
+  h->scipy_inv = dinv;
+  h->scipy_nprimes = (int)pr.size();
   return SCOARY_OK;
 }
 
@@ -259,16 +255,13 @@ int scoary_fisher_scipy(scoary_handle h, const int32_t* d_tables, int64_t M, dou
   if (!d_tables || !d_p || M < 1) return fail(h, SCOARY_ERR_ARG, "scoary_fisher_scipy: bad argument");
   if ((M + kWave - 1) / kWave > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_fisher_scipy: M too large");
   DeviceGuard guard(h->device);
-  const uint32_t* primes = nullptr;
-  const float* inv = nullptr;
-  int nprimes = 0;
-  const int rc = primes_on_device(h, &primes, &inv, &nprimes);
+  const int rc = primes_on_device(h);
   if (rc != SCOARY_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   KernelTimer kt(h, s, "k_fisher_scipy");
   hipLaunchKernelGGL(k_fisher_scipy, dim3((unsigned)((M + kWave - 1) / kWave)), dim3(kWave), 0, s,
-                     reinterpret_cast<const int4*>(d_tables), M, d_p, primes, inv, nprimes,
-                     reinterpret_cast<unsigned long long*>(d_skipped));
+                     reinterpret_cast<const int4*>(d_tables), M, d_p, h->scipy_primes, h->scipy_inv,
+                     h->scipy_nprimes, reinterpret_cast<unsigned long long*>(d_skipped));
   HIP_TRY(h, hipGetLastError());
   return SCOARY_OK;
 }

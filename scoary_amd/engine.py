@@ -633,23 +633,16 @@ class AssociationEngine:
             # shares the chip with the generator and its own duration -- the path's one HBM
             # stream, reported as roofline_k1 -- can no longer be read off the step.)
             # (Round 5, with the 0.04-0.08 ms generator: the overlap is still worth 0.3 % at cfg3 and
-            # 2.5 % on a 25 000-gene shard of cfg4, nothing on cfg4 itself; SCOARY_GEN_SIDE_STREAM=0
-            # runs the two back to back on the main stream for such A/B runs.)
-            import os
+            # 2.5 % on a 25 000-gene shard of cfg4, nothing on cfg4 itself.)
             main = torch.cuda.current_stream(self.device)
             nb0 = min(ws.batch, permutations)
-            if os.environ.get("SCOARY_GEN_SIDE_STREAM", "1") == "1":
-                side = self._side_stream()
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    self._label_tiles(ws, masks, margins, genes.N, nb0, 0, seed)
-                p, odds, crit, lcrit = self.fisher(counts, out=(ws.p, ws.odds, ws.crit),
-                                                   lists=genes.lists, lcrit=ws.lcrit)
-                main.wait_stream(side)
-            else:
+            side = self._side_stream()
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
                 self._label_tiles(ws, masks, margins, genes.N, nb0, 0, seed)
-                p, odds, crit, lcrit = self.fisher(counts, out=(ws.p, ws.odds, ws.crit),
-                                                   lists=genes.lists, lcrit=ws.lcrit)
+            p, odds, crit, lcrit = self.fisher(counts, out=(ws.p, ws.odds, ws.crit),
+                                               lists=genes.lists, lcrit=ws.lcrit)
+            main.wait_stream(side)
             done = 0
             while done < permutations:
                 nb = min(ws.batch, permutations - done)

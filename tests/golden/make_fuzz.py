@@ -45,7 +45,7 @@ REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
 # The committed corpora: a plain run writes fuzz_corpus.json.gz (SEED, 200 cases, NS) and fuzz_args_corpus.json.gz (the
 # flag surface: ARGS_SEED, 200 odd command lines on small tables).  FUZZ_SEED / FUZZ_NCASES / FUZZ_NS / FUZZ_ARGMUT=1 /
-# FUZZ_KEEP_CRASHES=1 / FUZZ_OUT: ONE one-off extra corpus instead (tools/round6_run.sh fuzzextra).
+# FUZZ_KEEP_CRASHES=1 / FUZZ_OUT: ONE one-off extra corpus instead (read by tools/fuzz_report.py).
 SEED = int(os.environ.get("FUZZ_SEED", "20261001"))
 NCASES = int(os.environ.get("FUZZ_NCASES", "200"))
 NS = [int(x) for x in os.environ.get("FUZZ_NS", "4,5,7,12,20,33,48,64,65,70,180,256,400").split(",")]   # isolates

@@ -49,6 +49,17 @@ def test_abi_layout_arithmetic():
         assert lib.scoary_tiled_genes(G) == gp
     assert lib.scoary_tiled_bytes(50000, 2000) == 16 * 16 * 50176
 
+    # every N up to 200 000 against the rule as first written: the register sizes
+    # 1 ... 48 quads, then multiples of 8 quads
+    def tiled_quads(N):
+        q = max(((N + 31) // 32 + 3) // 4, 1)
+        for r in (1, 2, 4, 6, 8, 12, 16, 20, 24, 32, 40, 48):
+            if r >= q:
+                return r
+        return (q + 7) // 8 * 8
+    for N in range(1, 200001):
+        assert lib.scoary_tiled_quads(N) == tiled_quads(N), N
+
 
 def test_no_gpu_means_loud_failure():
     """The product path never falls back to the CPU."""

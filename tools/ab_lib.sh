@@ -1,19 +1,22 @@
 #!/bin/bash
 # A/B of two builds of libscoary_hip.so on one box: time (bench.py) and FETCH_SIZE / WRITE_SIZE (rocprofv3 --pmc,
-# separate passes).   tools/ab_lib.sh <alt.so> [bench args]
+# separate passes).  Every GPU step has its own time limit; the first failing step ends the script.
+#   tools/ab_lib.sh <alt.so> [bench args]
+set -euo pipefail
 cd "$(dirname "$0")/.."
 REPO=$(pwd); ALT=$REPO/$1; shift
 pick='import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("%-8s step %.3f ms  k_permute_lists %.3f ms  tiles %.4f ms  value %.3e" % (sys.argv[1], d["ms_per_step"], d["kernel_ms"]["k_permute_lists"], d["kernel_ms"].get("k_perm_generate_tiles", 0), d["value"]))'
 for i in 1 2 3; do
-  python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "$pick" default
-  SCOARY_HIP_LIB=$ALT python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "$pick" alt
+  timeout -k 10 600 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "$pick" default
+  SCOARY_HIP_LIB=$ALT timeout -k 10 600 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "$pick" alt
 done
 cd /tmp && export TMPDIR=/tmp
 for v in default alt; do
   [ $v = alt ] && export SCOARY_HIP_LIB=$ALT
   for c in FETCH_SIZE WRITE_SIZE; do
-    rm -rf /tmp/abpmc_$v_$c
-    rocprofv3 --kernel-trace --pmc $c -d /tmp/abpmc_${v}_$c -o p -- python $REPO/bench.py --no-cpu-baseline --steps 2 --warmup 1 "$@" > /dev/null 2>&1
+    rm -rf /tmp/abpmc_${v}_$c
+    timeout -k 10 600 rocprofv3 --kernel-trace --pmc $c -d /tmp/abpmc_${v}_$c -o p -- \
+      python $REPO/bench.py --no-cpu-baseline --steps 2 --warmup 1 "$@" > /dev/null 2>&1
     python - "$v" "$c" /tmp/abpmc_${v}_$c <<'PY'
 import sqlite3, sys, glob
 v, c, d = sys.argv[1:4]

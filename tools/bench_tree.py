@@ -95,7 +95,7 @@ def main():
     #     algorithmic bytes (bit matrix once + N^2 counts) against 8 TB/s;
     #   k_tree_dp: lane = one (gene, permutation) tree evaluation, tips - 1 node merges of ~80 VALU ops
     #     (two packed integer keys per state: adds and v_max); ceiling = the nominal SIMD peak, 78.6 T lane-ops/s.
-    # SQ_INSTS_VALU x 64 from the committed PMC pass (tools/round6_run.sh tree) replaces the op estimates.
+    # SQ_INSTS_VALU x 64 from the committed PMC pass (profiles/r06_tree5000_pmc.json) replaces the op estimates.
     W32 = (args.all_genes + 31) // 32
     ham_ops = 2.0 * N * N * W32
     ham_bytes = N * W32 * 4.0 + 4.0 * N * N

@@ -5,6 +5,7 @@
 set -e
 cd "$(dirname "$0")/.."
 NAME=$1; REV=$2; shift 2
+rm -rf _ab/src_$NAME
 mkdir -p _ab/src_$NAME/csrc _ab/src_$NAME/include
 if [ "$REV" = WORKTREE ]; then
   cp scoary_amd/csrc/*.hip scoary_amd/csrc/*.hpp scoary_amd/csrc/*.inc _ab/src_$NAME/csrc/
@@ -15,6 +16,5 @@ else
 fi
 S=_ab/src_$NAME/csrc
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -I_ab/src_$NAME/include "$@" \
-  $S/scoary_context.hip $S/scoary_assoc.hip $S/scoary_lists.hip $S/scoary_listbuild.hip $S/scoary_labels.hip $S/scoary_tree.hip \
-  -o _ab/$NAME.so
+  $S/*.hip -o _ab/$NAME.so
 ls -la _ab/$NAME.so

@@ -24,6 +24,6 @@ def main():
             eng.perm_generate_tiles(masks, margins, N, P, 0, 7, out=out)
         e1.record(); torch.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1) / reps)
-    print("N=%d T=%d P=%d frac=%.2f debug=%s: %.4f ms per launch" % (N, T, P, frac, os.environ.get("SCOARY_LABELS_DEBUG", "0"), best))
+    print("N=%d T=%d P=%d frac=%.2f: %.4f ms per launch" % (N, T, P, frac, best))
 
 main()

@@ -2,7 +2,7 @@
 // the body of k_permute_lists and k_permute_seglists (scoary_lists.hip): adds the tile rows of
 // one wave group's index list into the bit-sliced counter planes c0..c3.
 // Expects in scope: LPG, NW, KC (template parameters); cur (Group), ring[4] (the group's first
-// four index vectors, already requested), nhalf, nsuper, colb, load_from; c0..c3[16];
+// four index vectors, already requested), nhalf, nsuper, colb, lane_off; c0..c3[16];
 // kVecSub = sub-steps (of 4 entries per gene) one 16-byte index vector feeds -- LPG in
 // k_permute_lists (32-bit entries, lane h of a gene's group holds sub-step h's four), 2 in
 // k_permute_seglists (eight 16-bit entries per lane) -- and the macro SCOARY_READ4(H, X, E):
@@ -36,7 +36,7 @@
     // slot of every piece is a compile-time constant).  Reads past the end of the
     // list re-read its last piece (valid rows, never summed).
     int piece = 0;                                   // piece whose vector is ring[piece % 4]
-    auto load_piece = [&](int p) -> Ent { return load_from(cur, p); };
+    auto load_piece = [&](int p) -> Ent { return load_from(cur, lane_off, p); };
     SCOARY_READ4(0, xa, ring[0].e);
     // sub-step S of step K (both literals): issue the reads of the next sub-step into
     // `other`, sum `mine`

@@ -77,32 +77,35 @@ __global__ __launch_bounds__(64) void k_sort_hist(const int32_t* __restrict__ in
   __syncthreads();
   for (int d = lane; d < 256; d += 64) hist[(int64_t)d * nblk + b] = h[d];
 }
-// exclusive prefix sum of n int32 values in place, one block
-__global__ __launch_bounds__(1024) void k_scan_excl(int32_t* __restrict__ v, int64_t n) {
-  __shared__ int32_t wsum[16];
-  __shared__ int32_t carry_s;
+// out[i] = scale * (in[0] + ... + in[i - 1]) for i < n, one block; *total = the sum of all n when
+// total is given.  out may be in (the radix-sort histogram is scanned in place).
+template <typename In, typename Out>
+__global__ __launch_bounds__(1024) void k_scan_excl(const In* in, int64_t n, Out scale, Out* out, Out* total) {
+  __shared__ Out wsum[16];
+  __shared__ Out carry_s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) carry_s = 0;
   __syncthreads();
-  for (int64_t base = 0; base < n; base += 1024) {
-    const int64_t i = base + tid;
-    const int32_t x = i < n ? v[i] : 0;
-    int32_t s = x;
+  for (int64_t i0 = 0; i0 < n; i0 += 1024) {
+    const int64_t i = i0 + tid;
+    const Out x = i < n ? (Out)in[i] * scale : 0;
+    Out s = x;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-      const int32_t y = __shfl_up(s, off);
+      const Out y = __shfl_up(s, off);
       if (lane >= off) s += y;
     }
     if (lane == 63) wsum[wave] = s;
     __syncthreads();
-    int32_t wo = 0;
+    Out wo = 0;
     for (int w = 0; w < wave; ++w) wo += wsum[w];
-    const int32_t carry = carry_s;
-    if (i < n) v[i] = carry + wo + s - x;
+    const Out carry = carry_s;
+    if (i < n) out[i] = carry + wo + s - x;
     __syncthreads();
     if (tid == 1023) carry_s = carry + wo + s;
     __syncthreads();
   }
+  if (tid == 0 && total) *total = carry_s;
 }
 __global__ __launch_bounds__(64) void k_sort_scatter(const int32_t* __restrict__ in_order,
                                                      const int32_t* __restrict__ len, int G,
@@ -132,55 +135,6 @@ __global__ __launch_bounds__(64) void k_sort_scatter(const int32_t* __restrict__
     if (valid && rank == 0) cnt[d] += __popcll(peers);
     __syncthreads();
   }
-}
-
-// Padded list length of every wavefront group (the longest list of the group, rounded
-// up to kListPad) and the first entry of the group: exclusive prefix sum, one block.
-__global__ __launch_bounds__(1024) void k_lists_plan(const int32_t* __restrict__ len,
-                                                     const int32_t* __restrict__ order, int G,
-                                                     int gpw, int64_t nwg,
-                                                     int32_t* __restrict__ padded,
-                                                     int64_t* __restrict__ base) {
-  __shared__ int64_t wsum[16];
-  __shared__ int64_t carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (int64_t q0 = 0; q0 < nwg; q0 += 1024) {
-    const int64_t q = q0 + tid;
-    int32_t L = 0;
-    if (q < nwg) {
-      L = (len[order[q * gpw]] + kListPad - 1) / kListPad * kListPad;
-      padded[q] = L;
-    }
-    const int64_t x = (int64_t)L * gpw;
-    int64_t s = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int64_t y = __shfl_up(s, off);
-      if (lane >= off) s += y;
-    }
-    if (lane == 63) wsum[wave] = s;
-    __syncthreads();
-    int64_t wo = 0;
-    for (int w = 0; w < wave; ++w) wo += wsum[w];
-    const int64_t carry = carry_s;
-    if (q < nwg) base[q] = carry + wo + s - x;
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + wo + s;
-    __syncthreads();
-  }
-  if (tid == 0) base[nwg] = carry_s;
-}
-__global__ __launch_bounds__(256) void k_lists_slots(const int32_t* __restrict__ padded,
-                                                     const int64_t* __restrict__ base, int G,
-                                                     int gpw, int32_t* __restrict__ start,
-                                                     int32_t* __restrict__ ngroups) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= G) return;
-  const int q = k / gpw;
-  start[k] = (int32_t)(base[q] / kListStartUnit);      // gpw * padded is a multiple of 16 * 16
-  ngroups[k] = padded[q] / kListPad;                   // half-steps of 16 entries
 }
 
 // Spec S6, entry order.  Class of a position = position mod C; within a class positions are
@@ -315,7 +269,10 @@ __global__ __launch_bounds__(256) void k_lists_seglen(const uint4* __restrict__ 
     seglen[(int64_t)sgm * G + g] = n;
   }
 }
-// thread = wave group: padded sub-list length per segment = the group's longest, rounded up
+// ---- plan: padded lengths, group bases and slot starts, for any N -------------------------------
+// An item is a (wave group, segment) pair; nseg = 1 (N <= 20479) has the whole row as its one segment
+// and the gene lengths as the segment lengths.
+// thread = wave group: padded sub-list length per segment = the group's longest, rounded up to kListPad
 __global__ __launch_bounds__(256) void k_lists_segpad(const int32_t* __restrict__ seglen,
                                                       const int32_t* __restrict__ order, int G,
                                                       int gpw, int64_t nwg, int nseg,
@@ -331,45 +288,18 @@ __global__ __launch_bounds__(256) void k_lists_segpad(const int32_t* __restrict_
     padded[q * nseg + sgm] = (m + kListPad - 1) / kListPad * kListPad;
   }
 }
-// base[i] = entries before item i (item = (wave group, segment), padded[i] * gpw entries each),
-// base[n] = all entries: exclusive prefix sum, one block
-__global__ __launch_bounds__(1024) void k_lists_base(const int32_t* __restrict__ padded, int64_t n,
-                                                     int gpw, int64_t* __restrict__ base) {
-  __shared__ int64_t wsum[16];
-  __shared__ int64_t carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (int64_t i0 = 0; i0 < n; i0 += 1024) {
-    const int64_t i = i0 + tid;
-    const int64_t x = i < n ? (int64_t)padded[i] * gpw : 0;
-    int64_t s = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int64_t y = __shfl_up(s, off);
-      if (lane >= off) s += y;
-    }
-    if (lane == 63) wsum[wave] = s;
-    __syncthreads();
-    int64_t wo = 0;
-    for (int w = 0; w < wave; ++w) wo += wsum[w];
-    const int64_t carry = carry_s;
-    if (i < n) base[i] = carry + wo + s - x;
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + wo + s;
-    __syncthreads();
-  }
-  if (tid == 0) base[n] = carry_s;
-}
+// base[i] = entries before item i (k_scan_excl of padded[i] * gpw); start = base in units of
+// 2^unit_shift entries (kListStartUnit * 4 bytes); ngroups = half steps of kListPad entries
 __global__ __launch_bounds__(256) void k_lists_segslots(const int32_t* __restrict__ padded,
                                                         const int64_t* __restrict__ base, int G,
-                                                        int gpw, int nseg, int32_t* __restrict__ start,
+                                                        int gpw, int nseg, int unit_shift,
+                                                        int32_t* __restrict__ start,
                                                         int32_t* __restrict__ ngroups) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= G) return;
   const int64_t q = k / gpw;
   for (int sgm = 0; sgm < nseg; ++sgm) {
-    start[(int64_t)sgm * G + k] = (int32_t)(base[q * nseg + sgm] / (2 * kListStartUnit));   // 16-bit entries: 128 bytes = 64
+    start[(int64_t)sgm * G + k] = (int32_t)(base[q * nseg + sgm] >> unit_shift);   // gpw * padded is a multiple of 16 * 16
     ngroups[(int64_t)sgm * G + k] = padded[q * nseg + sgm] / kListPad;
   }
 }
@@ -530,32 +460,36 @@ int scoary_lists_plan(scoary_handle h, const uint32_t* d_tiled, int64_t G, int64
     int32_t* out = p == passes - 1 ? d_order : ord[p & 1];
     hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)L.nblk), dim3(64), 0, s, in, len, (int)G, kmax,
                        8 * p, (int)L.nblk, hist);
-    hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, s, hist, (int64_t)256 * L.nblk);
+    hipLaunchKernelGGL((k_scan_excl<int32_t, int32_t>), dim3(1), dim3(1024), 0, s, hist, (int64_t)256 * L.nblk,
+                       1, hist, nullptr);
     hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)L.nblk), dim3(64), 0, s, in, len, (int)G,
                        kmax, 8 * p, (int)L.nblk, hist, out);
   }
-  if (L.nseg > 1) {           // N > 20479: sub-lists per segment, d_start / d_ngroups are [nseg][G]
-    int32_t* seglen = reinterpret_cast<int32_t*>(sc + L.seglen);
+  // d_start / d_ngroups are [nseg][G]; entries are 32-bit LDS byte offsets of a tile row, or 16-bit
+  // row indices inside the segment when there are segments (N > 20479)
+  const int entry_bytes = L.nseg > 1 ? 2 : 4;
+  const int start_shift = __builtin_ctz(kListStartUnit * 4 / entry_bytes);
+  const int32_t* seglen = len;
+  if (L.nseg > 1) {
+    int32_t* sl = reinterpret_cast<int32_t*>(sc + L.seglen);
     hipLaunchKernelGGL(k_lists_seglen, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s,
                        reinterpret_cast<const uint4*>(d_tiled), Gp, (int)G, (int)N, (int)L.nseg,
-                       d_flipped, seglen);
-    hipLaunchKernelGGL(k_lists_segpad, dim3((unsigned)((L.nwg + 255) / 256)), dim3(256), 0, s, seglen,
-                       d_order, (int)G, gpw, L.nwg, (int)L.nseg, padded);
-    hipLaunchKernelGGL(k_lists_base, dim3(1), dim3(1024), 0, s, padded, L.nwg * L.nseg, gpw, base);
-    hipLaunchKernelGGL(k_lists_segslots, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, padded,
-                       base, (int)G, gpw, (int)L.nseg, d_start, d_ngroups);
-  } else {
-    hipLaunchKernelGGL(k_lists_plan, dim3(1), dim3(1024), 0, s, len, d_order, (int)G, gpw, L.nwg,
-                       padded, base);
-    hipLaunchKernelGGL(k_lists_slots, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, padded, base,
-                       (int)G, gpw, d_start, d_ngroups);
+                       d_flipped, sl);
+    seglen = sl;
   }
+  const int64_t items = L.nwg * L.nseg;
+  hipLaunchKernelGGL(k_lists_segpad, dim3((unsigned)((L.nwg + 255) / 256)), dim3(256), 0, s, seglen,
+                     d_order, (int)G, gpw, L.nwg, (int)L.nseg, padded);
+  hipLaunchKernelGGL((k_scan_excl<int32_t, int64_t>), dim3(1), dim3(1024), 0, s, padded, items, (int64_t)gpw,
+                     base, base + items);
+  hipLaunchKernelGGL(k_lists_segslots, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, padded, base,
+                     (int)G, gpw, (int)L.nseg, start_shift, d_start, d_ngroups);
   HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(entries_out, base + L.nwg * L.nseg, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipMemcpyAsync(entries_out, base + items, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipStreamSynchronize(s));
-  // entries_out counts 32-bit words of index array; the segmented sub-lists hold two 16-bit
-  // entries per word (every sub-list is a multiple of 64 x 16 entries: the total is even)
-  if (L.nseg > 1) *entries_out /= 2;
+  // entries_out counts 32-bit words of index array (every sub-list is a multiple of 64 x 16
+  // entries: the 16-bit total is even)
+  *entries_out = *entries_out * entry_bytes / 4;
   return SCOARY_OK;
 }
 

@@ -159,6 +159,52 @@ __device__ __forceinline__ int fresh_lane() {
   return l;
 }
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// Interleaved lists: a wave group's 64 lanes read 64 consecutive 16-byte index vectors per piece; lane l
+// reads vector piece*64 + l of its group.
+struct alignas(16) Ent { uint32_t e[4]; };
+// A wave group's list: its length in half-steps of 16 entries (lists are padded to 16: a last
+// half step costs half a step, where padding to 32 made the average list 3 % longer), its last
+// vector, and a buffer resource on it -- group base in the descriptor (SGPRs), vector offset in
+// the scalar offset, lane offset in one VGPR: no per-load 64-bit VALU address arithmetic.
+// num_records = the bytes from the group's base to the end of the index array: a read past
+// the end (groups without entries still issue their prologue loads) returns 0.
+struct Group { int nhalf, last; __amdgpu_buffer_rsrc_t rsrc; };
+// slot = the group's first list slot in lstart / lngroups; vph = index vectors per lane and half step
+__device__ __forceinline__ Group open_group(const uint32_t* lidx, const int32_t* lstart,
+                                           const int32_t* lngroups, int64_t slot, int vph,
+                                           int64_t lidx_bytes) {
+  const int64_t start = (int64_t)__builtin_amdgcn_readfirstlane(lstart[slot]);
+  const int nh = __builtin_amdgcn_readfirstlane(lngroups[slot]);
+  const int64_t gbytes = lidx_bytes - start * 128;
+  return Group{nh, max(nh * vph - 1, 0),
+               __builtin_amdgcn_make_buffer_rsrc(
+                   const_cast<Ent*>(reinterpret_cast<const Ent*>(lidx) + start * 8), 0,
+                   (int)min(gbytes, (int64_t)0x7fffffff), 0x00020000)};
+}
+// index vector p of the group for this lane (lane_off = 16 * lane); vectors past the last re-read it
+__device__ __forceinline__ Ent load_from(const Group& gr, uint32_t lane_off, int p) {
+  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
+      gr.rsrc, lane_off, min(p, gr.last) * (kWave * (int)sizeof(Ent)), 0);
+  return Ent{{v.x, v.y, v.z, v.w}};
+}
+
+// One 16-byte vector per lane, src4 + lane -> LDS address lds + 16 * lane, by LDS-DMA
+// (global_load_lds_dwordx4): a wavefront moves 64 x 16 B per instruction straight into LDS
+// (destination = M0 + 16*lane), no VGPR round trip and no ds_write pass.  Address = wave-uniform
+// base (SGPR pair) + 32-bit lane offset: the saddr form (inline asm: the builtin only takes a
+// per-lane 64-bit address).  lane_off = 16 * lane.
+__device__ __forceinline__ void lds_dma16(uint32_t lds, uint32_t lane_off, const uint4* src4) {
+  uint32_t m0_saved;     // M0 is handed back as it was: nothing else may be assumed about it
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
+               : "=&s"(m0_saved)
+               : "s"(lds), "v"(lane_off), "s"(src4)
+               : "memory");
+}
+
 // 128 permutations per lane: LPG = TW/4 lanes per gene read the tile rows with
 // ds_read_b128, 64/LPG genes per wavefront; one address add serves four words.
 // ds_read_b128 is served in the lane groups {0-3,12-15,20-27}, ... over the full
@@ -176,8 +222,6 @@ struct Rows4 { uint32_t w0[4], w1[4], w2[4], w3[4]; };   // 4 tile rows x 4 perm
       "v_add_u32_dpp %3, %7, %8 " QP " row_mask:0xf bank_mask:0xf"                       \
       : "=&v"(a[0]), "=&v"(a[1]), "=&v"(a[2]), "=&v"(a[3])                               \
       : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(colb))
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 template <int LPG, int H, int NW>
 __device__ __forceinline__ void read4x4(Rows4& x, const uint32_t (&e)[4], uint32_t colb) {
   uint32_t a[4];
@@ -278,56 +322,23 @@ __global__ __launch_bounds__(1024) void k_permute_lists(const uint32_t* __restri
   // over the tiles by k_lists_reduce (one device-scope atomicAdd per (gene, tile) cost a
   // 32-byte memory-side write each: 316 MB for a 2 MB result at the headline config)
   uint16_t* out = partial + (int64_t)blockIdx.x * ((int64_t)ngroups * GPW);
-
-  // interleaved lists (piece = TW entries): the wavefront's 64 lanes read 64 consecutive
-  // 16-byte index vectors per piece; lane l reads vector piece*64 + l of its group
-  struct alignas(16) Ent { uint32_t e[4]; };
-  // A wave group's list: its length in half-steps of 16 entries (lists are padded to 16: a last
-  // half step costs half a step, where padding to 32 made the average list 3 % longer), its last
-  // piece, and a buffer resource on it -- group base in the descriptor (SGPRs), piece offset in
-  // the scalar offset, lane offset in one VGPR: no per-load 64-bit VALU address arithmetic.
-  // num_records = the bytes from the group's base to the end of the index array: a read past
-  // the end (groups without entries still issue their prologue loads) returns 0.
-  struct Group { int nhalf, last; __amdgpu_buffer_rsrc_t rsrc; };
-  auto open_group = [&](int qq) -> Group {
-    const int64_t start = (int64_t)__builtin_amdgcn_readfirstlane(lstart[qq * GPW]);
-    const int nh = __builtin_amdgcn_readfirstlane(lngroups[qq * GPW]);
-    const int64_t gbytes = lidx_bytes - start * 128;
-    return Group{nh, max(nh * (4 / LPG) - 1, 0),
-                 __builtin_amdgcn_make_buffer_rsrc(
-                     const_cast<Ent*>(reinterpret_cast<const Ent*>(lidx) + start * 8), 0,
-                     (int)min(gbytes, (int64_t)0x7fffffff), 0x00020000)};
-  };
-  auto load_from = [&](const Group& gr, int p) -> Ent {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
-        gr.rsrc, lane_off, min(p, gr.last) * (kWave * (int)sizeof(Ent)), 0);
-    return Ent{{v.x, v.y, v.z, v.w}};
-  };
+  // wave group qq's list (piece = TW entries, a half step = 4 / LPG vectors per lane)
+  auto group_at = [&](int qq) { return open_group(lidx, lstart, lngroups, qq * GPW, 4 / LPG, lidx_bytes); };
   // The first four index vectors of a group are requested one group AHEAD: at the start of the
   // previous group's epilogue (region test, ~0.3 us of VALU work in which the ring registers
   // are dead) -- and for the wavefront's first group here, before the label tile is waited
   // for -- so a group does not open with an exposed L2 round trip.
   int q = q_lo + wave;
-  Group cur = open_group(min(q, ngroups - 1));
-  Ent ring[4] = {load_from(cur, 0), load_from(cur, 1), load_from(cur, 2), load_from(cur, 3)};
-  const uint32_t* src = tiles + (int64_t)blockIdx.x * list_tile_dwords(N, TW);
+  Group cur = group_at(min(q, ngroups - 1));
+  Ent ring[4] = {load_from(cur, lane_off, 0), load_from(cur, lane_off, 1), load_from(cur, lane_off, 2),
+                 load_from(cur, lane_off, 3)};
   {
-    // tile -> LDS by LDS-DMA (global_load_lds_dwordx4): a wavefront moves 64 x 16 B
-    // per instruction straight into LDS (destination = M0 + 16*lane), no VGPR round trip
-    // and no ds_write pass.  Address = wave-uniform base (SGPR pair) + 32-bit lane offset:
-    // the saddr form (inline asm: the builtin only takes a per-lane 64-bit address).
-    const uint4* src4 = reinterpret_cast<const uint4*>(src);
+    // tile -> LDS (lds_dma16)
+    const uint4* src4 = reinterpret_cast<const uint4*>(tiles + (int64_t)blockIdx.x * list_tile_dwords(N, TW));
     const int n4 = (int)(list_tile_dwords(N, TW) / 4);   // HBM tiles are padded to 16 bytes
     const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t*)tile_lds;
     for (int i = wave * kWave; i < n4; i += nwaves * kWave)
-      if (i + lane < n4) {
-        uint32_t m0_saved;     // M0 is handed back as it was: nothing else may be assumed about it
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-                     : "=&s"(m0_saved)
-                     : "s"(lds0 + (uint32_t)i * 16u), "v"(lane_off), "s"(src4 + i)
-                     : "memory");
-      }
+      if (i + lane < n4) lds_dma16(lds0 + (uint32_t)i * 16u, lane_off, src4 + i);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
@@ -351,11 +362,11 @@ __global__ __launch_bounds__(1024) void k_permute_lists(const uint32_t* __restri
 #undef SCOARY_READ4
     // next group of this wavefront: open it and request its first index vectors now
     if (q + nwaves < q_hi) {
-      cur = open_group(q + nwaves);
-      ring[0] = load_from(cur, 0);
-      ring[1] = load_from(cur, 1);
-      ring[2] = load_from(cur, 2);
-      ring[3] = load_from(cur, 3);
+      cur = group_at(q + nwaves);
+      ring[0] = load_from(cur, lane_off, 0);
+      ring[1] = load_from(cur, lane_off, 1);
+      ring[2] = load_from(cur, lane_off, 2);
+      ring[3] = load_from(cur, lane_off, 3);
     }
     // the lane's gene within the group, recomputed here (volatile asm: not hoisted) rather
     // than held in a register across the list walk -- the walk uses every VGPR there is
@@ -421,24 +432,6 @@ __global__ __launch_bounds__(1024) void k_permute_seglists(const uint32_t* __res
   const int q_hi = min(ngroups, q_lo + groups_per_block);
   const uint32_t lane_off = (uint32_t)lane * 16u;
   uint16_t* out = partial + (int64_t)blockIdx.x * ((int64_t)ngroups * GPW);
-  struct alignas(16) Ent { uint32_t e[4]; };
-  struct Group { int nhalf, last; __amdgpu_buffer_rsrc_t rsrc; };
-  auto open_group = [&](int qq, int sgm) -> Group {
-    const int64_t slot = (int64_t)sgm * G + (int64_t)qq * GPW;
-    const int64_t start = (int64_t)__builtin_amdgcn_readfirstlane(lstart[slot]);
-    const int nh = __builtin_amdgcn_readfirstlane(lngroups[slot]);
-    const int64_t gbytes = lidx_bytes - start * 128;
-    // a half step (16 entries of 16 bits) is two 16-byte vectors per lane
-    return Group{nh, max(nh * 2 - 1, 0),
-                 __builtin_amdgcn_make_buffer_rsrc(
-                     const_cast<Ent*>(reinterpret_cast<const Ent*>(lidx) + start * 8), 0,
-                     (int)min(gbytes, (int64_t)0x7fffffff), 0x00020000)};
-  };
-  auto load_from = [&](const Group& gr, int p) -> Ent {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
-        gr.rsrc, lane_off, min(p, gr.last) * (kWave * (int)sizeof(Ent)), 0);
-    return Ent{{v.x, v.y, v.z, v.w}};
-  };
   const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t*)tile_lds;
   const uint32_t three = 3u;                             // SDWA shift amount (an SGPR operand)
   const uint32_t* src = tiles + (int64_t)blockIdx.x * ((int64_t)nseg * kSegStride);
@@ -455,21 +448,17 @@ __global__ __launch_bounds__(1024) void k_permute_seglists(const uint32_t* __res
       // the sub-list's first four index vectors are requested before the tile segment is
       // (re)loaded, so the walk does not open with an exposed L2 round trip (inactive
       // wavefronts read the block's last group: harmless)
-      const Group cur = open_group(min(q, q_hi - 1), sgm);
-      Ent ring[4] = {load_from(cur, 0), load_from(cur, 1), load_from(cur, 2), load_from(cur, 3)};
+      // a half step (16 entries of 16 bits) is two 16-byte vectors per lane
+      const int64_t qg = (int64_t)min(q, q_hi - 1) * GPW;
+      const Group cur = open_group(lidx, lstart, lngroups, (int64_t)sgm * G + qg, 2, lidx_bytes);
+      Ent ring[4] = {load_from(cur, lane_off, 0), load_from(cur, lane_off, 1), load_from(cur, lane_off, 2),
+                     load_from(cur, lane_off, 3)};
       __syncthreads();                       // the previous segment has been walked by everyone
       {
         const uint4* src4 = reinterpret_cast<const uint4*>(src + (int64_t)sgm * kSegStride);
         constexpr int n4 = kSegStride / 4;
         for (int i = wave * kWave; i < n4; i += nwaves * kWave)
-          if (i + lane < n4) {
-            uint32_t m0_saved;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                         "global_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-                         : "=&s"(m0_saved)
-                         : "s"(lds0 + (uint32_t)i * 16u), "v"(lane_off), "s"(src4 + i)
-                         : "memory");
-          }
+          if (i + lane < n4) lds_dma16(lds0 + (uint32_t)i * 16u, lane_off, src4 + i);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       __syncthreads();
@@ -588,14 +577,16 @@ static ListGeom list_geom(int num_cu, int64_t G, int64_t T, int64_t N, int64_t P
   return g;
 }
 
-template <int TW, int KC>
-static int launch_permute_lists(scoary_handle h, hipStream_t s, const uint32_t* d_tiles,
-                                const uint32_t* d_lidx, int64_t entries, const int32_t* d_lstart,
-                                const int32_t* d_lngroups, const int32_t* d_lorder,
-                                const uint8_t* d_lflipped, const uint32_t* d_crit,
-                                const uint32_t* d_lcrit_in, const int32_t* d_margins,
-                                uint32_t* d_scratch, int64_t G, int64_t T, int64_t N, int64_t P,
-                                uint32_t* d_r, int accumulate) {
+// One list launch: regions into slot order (unless given), the list kernel `kernel` against the label
+// tiles (`name` its timer, `lds` its dynamic LDS bytes, `optin` its bit in h->lists_lds_optin, `extra` its
+// arguments before `partial`), the sum over the tiles.  Both kernels share the scratch layout and geometry.
+template <typename Kernel, typename... Extra>
+static int launch_lists(scoary_handle h, hipStream_t s, Kernel kernel, const char* name, size_t lds, int optin,
+                        const uint32_t* d_tiles, const uint32_t* d_lidx, int64_t entries,
+                        const int32_t* d_lstart, const int32_t* d_lngroups, const int32_t* d_lorder,
+                        const uint8_t* d_lflipped, const uint32_t* d_crit, const uint32_t* d_lcrit_in,
+                        const int32_t* d_margins, uint32_t* d_scratch, int64_t G, int64_t T, int64_t N,
+                        int64_t P, uint32_t* d_r, int accumulate, Extra... extra) {
   uint32_t* d_lcrit_sc = d_scratch;                    // [T][G][2]
   uint16_t* d_partial = reinterpret_cast<uint16_t*>(d_scratch + 2 * T * G);   // [T][ntiles][gs]
   const uint32_t* d_lcrit = d_lcrit_in ? d_lcrit_in : d_lcrit_sc;
@@ -608,75 +599,24 @@ static int launch_permute_lists(scoary_handle h, hipStream_t s, const uint32_t* 
   const ListGeom g = list_geom(h->num_cu, G, T, N, P, entries);
   if (T * g.ntiles > 0x7fffffffLL || g.chunks > 65535)
     return fail(h, SCOARY_ERR_SIZE, "scoary_permute_lists: grid too large");
-  const size_t lds = (size_t)list_tile_dwords(N, TW) * sizeof(uint32_t);
-  const void* fn = reinterpret_cast<const void*>(&k_permute_lists<list_lpg(TW), list_nw(TW), KC>);
-  if (!(h->lists_lds_optin & TW)) {   // once per handle (= per device) and tile width
+  if (!(h->lists_lds_optin & optin)) {   // once per handle (= per device) and kernel
     // list entries of the one-lane-per-gene kernels are absolute LDS addresses: the label
     // tile must be the kernel's only LDS object (dynamic LDS then starts at address 0)
+    const void* fn = reinterpret_cast<const void*>(kernel);
     hipFuncAttributes attr;
     HIP_TRY(h, hipFuncGetAttributes(&attr, fn));
     if (attr.sharedSizeBytes != 0)
-      return fail(h, SCOARY_ERR_SIZE, "scoary_permute_lists: k_permute_lists has static LDS; the "
-                                      "label tile would not sit at LDS address 0");
+      return fail(h, SCOARY_ERR_SIZE, std::string("scoary_permute_lists: ") + name +
+                                          " has static LDS; the label tile would not sit at LDS address 0");
     HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    h->lists_lds_optin |= TW;
+    h->lists_lds_optin |= optin;
   }
   {
-    KernelTimer kt(h, s, "k_permute_lists");
-    hipLaunchKernelGGL((k_permute_lists<list_lpg(TW), list_nw(TW), KC>),
-                       dim3((unsigned)(T * g.ntiles), (unsigned)g.chunks), dim3(1024), lds, s, d_tiles,
+    KernelTimer kt(h, s, name);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(T * g.ntiles), (unsigned)g.chunks), dim3(1024), lds, s, d_tiles,
                        d_lidx, d_lstart, d_lngroups, reinterpret_cast<const uint2*>(d_lcrit), (int)G,
                        (int)N, P, (int)g.ntiles, (int)g.gpb,
-                       (entries + kListSlack) * (int64_t)sizeof(uint32_t), d_partial);
-  }
-  {
-    KernelTimer kt(h, s, "k_lists_reduce");
-    hipLaunchKernelGGL(k_lists_reduce, dim3((unsigned)((G + kWave - 1) / kWave), (unsigned)T), dim3(256), 0, s,
-                       d_partial, (int)g.ntiles, g.gs, (int)G, d_lorder, accumulate, d_r);
-  }
-  HIP_TRY(h, hipGetLastError());
-  return SCOARY_OK;
-}
-// N > 20479: the segmented kernel (k_permute_seglists), same scratch layout and geometry
-static int launch_permute_seglists(scoary_handle h, hipStream_t s, const uint32_t* d_tiles,
-                                   const uint32_t* d_lidx, int64_t entries, const int32_t* d_lstart,
-                                   const int32_t* d_lngroups, const int32_t* d_lorder,
-                                   const uint8_t* d_lflipped, const uint32_t* d_crit,
-                                   const uint32_t* d_lcrit_in, const int32_t* d_margins,
-                                   uint32_t* d_scratch, int64_t G, int64_t T, int64_t N, int64_t P,
-                                   uint32_t* d_r, int accumulate) {
-  constexpr int KC = 16;
-  uint32_t* d_lcrit_sc = d_scratch;
-  uint16_t* d_partial = reinterpret_cast<uint16_t*>(d_scratch + 2 * T * G);
-  const uint32_t* d_lcrit = d_lcrit_in ? d_lcrit_in : d_lcrit_sc;
-  if (!d_lcrit_in) {
-    KernelTimer kt(h, s, "k_lists_crit");
-    hipLaunchKernelGGL(k_lists_crit, dim3((unsigned)((G + 255) / 256), (unsigned)T), dim3(256), 0, s,
-                       reinterpret_cast<const uint2*>(d_crit), d_margins, d_lorder, d_lflipped,
-                       (int)G, reinterpret_cast<uint2*>(d_lcrit_sc));
-  }
-  const ListGeom g = list_geom(h->num_cu, G, T, N, P, entries);
-  if (T * g.ntiles > 0x7fffffffLL || g.chunks > 65535)
-    return fail(h, SCOARY_ERR_SIZE, "scoary_permute_lists: grid too large");
-  const size_t lds = (size_t)kSegStride * sizeof(uint32_t);
-  const void* fn = reinterpret_cast<const void*>(&k_permute_seglists<KC>);
-  constexpr int kOptinBit = 32;                         // next to the tile widths 16 / 8 / 4 / 2
-  if (!(h->lists_lds_optin & kOptinBit)) {
-    hipFuncAttributes attr;
-    HIP_TRY(h, hipFuncGetAttributes(&attr, fn));
-    if (attr.sharedSizeBytes != 0)
-      return fail(h, SCOARY_ERR_SIZE, "scoary_permute_lists: k_permute_seglists has static LDS; the "
-                                      "label tile would not sit at LDS address 0");
-    HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    h->lists_lds_optin |= kOptinBit;
-  }
-  {
-    KernelTimer kt(h, s, "k_permute_seglists");
-    hipLaunchKernelGGL((k_permute_seglists<KC>), dim3((unsigned)(T * g.ntiles), (unsigned)g.chunks),
-                       dim3(1024), lds, s, d_tiles, d_lidx, d_lstart, d_lngroups,
-                       reinterpret_cast<const uint2*>(d_lcrit), (int)G, (int)N, P, (int)g.ntiles,
-                       (int)g.gpb, (entries + kListSlack) * (int64_t)sizeof(uint32_t),
-                       list_segments(N), d_partial);
+                       (entries + kListSlack) * (int64_t)sizeof(uint32_t), extra..., d_partial);
   }
   {
     KernelTimer kt(h, s, "k_lists_reduce");
@@ -712,15 +652,18 @@ int scoary_permute_lists(scoary_handle h, const uint32_t* d_tiles, const uint32_
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   uint32_t* sc = static_cast<uint32_t*>(d_scratch);
+  // N > 20479: the segmented kernel, one 2-dword tile segment in LDS at a time; its opt-in bit sits
+  // next to the tile widths 16 / 8 / 4 / 2
   if (list_segments(N) > 1)
-    return launch_permute_seglists(h, s, d_tiles, d_lidx, entries, d_lstart, d_lngroups, d_lorder,
-                                   d_lflipped, d_crit, d_lcrit, d_margins, sc, G, T, N, P, d_r,
-                                   accumulate);
+    return launch_lists(h, s, &k_permute_seglists<16>, "k_permute_seglists", (size_t)kSegStride * sizeof(uint32_t),
+                        32, d_tiles, d_lidx, entries, d_lstart, d_lngroups, d_lorder, d_lflipped, d_crit, d_lcrit,
+                        d_margins, sc, G, T, N, P, d_r, accumulate, list_segments(N));
   // counter planes KC: lists hold <= N/2 entries, N/2 < 2^KC (and N + 1 < 2^(KC+1))
-#define LAUNCH(TWV, KCV)                                                                        \
-  return launch_permute_lists<TWV, KCV>(h, s, d_tiles, d_lidx, entries, d_lstart, d_lngroups,   \
-                                        d_lorder, d_lflipped, d_crit, d_lcrit, d_margins, sc, G, \
-                                        T, N, P, d_r, accumulate)
+#define LAUNCH(TWV, KCV)                                                                             \
+  return launch_lists(h, s, &k_permute_lists<list_lpg(TWV), list_nw(TWV), KCV>, "k_permute_lists",  \
+                      (size_t)list_tile_dwords(N, TWV) * sizeof(uint32_t), TWV, d_tiles, d_lidx,     \
+                      entries, d_lstart, d_lngroups, d_lorder, d_lflipped, d_crit, d_lcrit, d_margins, \
+                      sc, G, T, N, P, d_r, accumulate)
   if (TW == 16) LAUNCH(16, 11);
   if (TW == 8) LAUNCH(8, 12);
   if (TW == 4) LAUNCH(4, 13);

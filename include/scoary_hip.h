@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define SCOARY_ABI_VERSION 9
+#define SCOARY_ABI_VERSION 10
 
 /* error codes */
 #define SCOARY_OK 0
@@ -274,6 +274,48 @@ int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_
                          const int32_t *d_margins, void *d_scratch,
                          int64_t G, int64_t T, int64_t N, int64_t P, uint32_t *d_r,
                          int accumulate, scoary_stream_t stream);
+
+/* ---- matrix-core kernel for the long-list slots (N <= scoary_mfma_max_isolates() = 2048) ----
+ * The list count is a 0/1 GEMM whose cost does not depend on the list length, so the slots with
+ * the longest lists -- slots [0, k_split), the slot order is by descending length -- can take
+ * v_mfma_scale_f32_32x32x64_f8f6f4 (E2M1 operands, exact in fp32) instead of the list walk; d_r
+ * stays bit-identical.
+ *   scoary_mfma_panels_build : once per data set, after scoary_lists_plan: d_panels =
+ *       scoary_mfma_panels_bytes(G, N) bytes, the minority rows of all list slots as A fragments
+ *   scoary_mfma_bfrag_bytes  : the per-step B-operand buffer d_bfrag (caller-owned, like d_scratch)
+ *   scoary_mfma_breakeven_entries : padded list length (d_lngroups * 16) at which the two kernels
+ *       cost the same, from the two measured rates in scoary_mfma.hip
+ *   scoary_set_mfma_route    : NONE / ALL / AUTO (the default) for this handle
+ *   scoary_mfma_route        : host only -- the k_split scoary_permute_hybrid will accept: 0 (NONE,
+ *       N > 2048, or fewer than one round of blocks over the CUs), G (ALL), or (AUTO) the whole
+ *       number of 256-slot blocks that the two measured rates make cheapest -- the break-even
+ *       length, moved to a block count that fills whole rounds over the CUs.  block_start: HOST
+ *       int64 [ceil(G/256) + 1] = index entries in front of every 256-slot block
+ *       (32 * d_lstart[256 b]) and the entry count last
+ *   scoary_permute_hybrid    : scoary_permute_lists with the slots [0, k_split) on the matrix cores;
+ *       routed_entries = index entries in front of slot k_split (32 * d_lstart[k_split]; sizes the
+ *       list kernel's chunks).  k_split = 0 is scoary_permute_lists (d_panels / d_bfrag unused). */
+#define SCOARY_MFMA_ROUTE_NONE 0
+#define SCOARY_MFMA_ROUTE_ALL 1
+#define SCOARY_MFMA_ROUTE_AUTO 2
+int64_t scoary_mfma_max_isolates(void);
+int64_t scoary_mfma_panels_bytes(int64_t G, int64_t N);
+int64_t scoary_mfma_bfrag_bytes(int64_t N, int64_t P, int64_t T);
+int64_t scoary_mfma_breakeven_entries(void);
+int scoary_mfma_panels_build(scoary_handle h, const uint32_t *d_tiled, int64_t G, int64_t N,
+                             const int32_t *d_order, const uint8_t *d_flipped, void *d_panels,
+                             scoary_stream_t stream);
+int scoary_set_mfma_route(scoary_handle h, int mode);
+int64_t scoary_mfma_route(scoary_handle h, const int64_t *block_start, int64_t G, int64_t T,
+                          int64_t N, int64_t P);
+int scoary_permute_hybrid(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
+                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,
+                          const int32_t *d_lorder, const uint8_t *d_lflipped,
+                          const uint32_t *d_crit, const uint32_t *d_lcrit,
+                          const int32_t *d_margins, void *d_scratch,
+                          int64_t G, int64_t T, int64_t N, int64_t P, uint32_t *d_r,
+                          int accumulate, const void *d_panels, void *d_bfrag, int64_t k_split,
+                          int64_t routed_entries, scoary_stream_t stream);
 
 /* ---- index lists of the list-driven kernel, built on the device -----------------
  * From the tiled gene matrix already in HBM (no host pass, no PCIe copy of the

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SCOARY_HIP_LIB") or os.path.join(_HERE, "csrc", "libscoary_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "scoary_hip.h")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _i64, _u64, _i32, _vp, _cp = (ctypes.c_int64, ctypes.c_uint64, ctypes.c_int,
                               ctypes.c_void_p, ctypes.c_char_p)
@@ -54,6 +54,15 @@ SIGNATURES = {
     "scoary_permute_lists_scratch_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "scoary_permute_lists": (_i32, [_vp, _vp, _vp, _i64] + [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp,
                                                                        _i32, _vp]),
+    "scoary_mfma_max_isolates": (_i64, []),
+    "scoary_mfma_panels_bytes": (_i64, [_i64, _i64]),
+    "scoary_mfma_bfrag_bytes": (_i64, [_i64, _i64, _i64]),
+    "scoary_mfma_breakeven_entries": (_i64, []),
+    "scoary_mfma_panels_build": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "scoary_set_mfma_route": (_i32, [_vp, _i32]),
+    "scoary_mfma_route": (_i64, [_vp, _vp, _i64, _i64, _i64, _i64]),
+    "scoary_permute_hybrid": (_i32, [_vp, _vp, _vp, _i64] + [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp,
+                                                                        _i32, _vp, _vp, _i64, _i64, _vp]),
     "scoary_lists_scratch_bytes": (_i64, [_i64, _i64]),
     "scoary_lists_slack_entries": (_i64, []),
     "scoary_lists_plan": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp,

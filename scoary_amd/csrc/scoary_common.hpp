@@ -5,6 +5,7 @@
 #define SCOARY_COMMON_HPP
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -22,6 +23,8 @@ struct scoary_ctx {
   bool timing = false;
   int lists_lds_optin = 0;   // k_permute_lists instances (by tile width) with the 160 KB LDS opt-in done
   int labels_lds_optin = 0;  // k_labels instances with it
+  int mfma_lds_optin = 0;    // k_permute_mfma with it
+  int mfma_route = SCOARY_MFMA_ROUTE_AUTO;   // scoary_set_mfma_route: which list slots take the matrix-core kernel
   uint32_t* scipy_primes = nullptr;  // scoary_fisher_scipy's prime table and reciprocals (device,
   float* scipy_inv = nullptr;        // built on the handle's first call, freed by scoary_destroy)
   int scipy_nprimes = 0;
@@ -31,6 +34,17 @@ struct scoary_ctx {
   };
   std::vector<Timed> timed;
 };
+
+// scoary_mfma.hip: the matrix-core kernel of the slots [0, k_split) of a list launch (scoary_lists.hip calls it
+// between the region conversion and the list kernel); geometry = stages of 64 permutations, ranges per trait
+// (rp) of `per` stages each, 256-slot gene blocks, blocks in all
+struct MfmaGeom {
+  int64_t stages, rp, per, gene_blocks, blocks;
+};
+MfmaGeom scoary_mfma_geom(int num_cu, int64_t k_split, int64_t T, int64_t P, int64_t ntiles);
+int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, const void* d_panels, void* d_bfrag,
+                       const uint32_t* d_lcrit, uint16_t* d_partial, int64_t k_split, int64_t G, int64_t T,
+                       int64_t N, int64_t P, int64_t ntiles, int64_t gs);
 
 namespace {
 

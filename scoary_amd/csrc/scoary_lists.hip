@@ -297,7 +297,7 @@ __global__ __launch_bounds__(1024) void k_permute_lists(const uint32_t* __restri
                                                         const uint2* __restrict__ lcrit, int G,
                                                         int N, int64_t P, int ntiles,
                                                         int groups_per_block, int64_t lidx_bytes,
-                                                        uint16_t* __restrict__ partial) {
+                                                        int q_first, uint16_t* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) uint32_t tile_lds[];
   scoary_bank_defs();                // assembler symbols for the operand-ordering .if blocks
   constexpr int TW = NW * LPG;       // tile row, dwords
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(1024) void k_permute_lists(const uint32_t* __restri
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: loops over groups stay scalar
   const int col = lane % LPG;
   const int ngroups = (G + GPW - 1) / GPW;         // wave groups of GPW genes
-  const int q_lo = blockIdx.y * groups_per_block;
+  const int q_lo = q_first + blockIdx.y * groups_per_block;   // groups below q_first: the matrix-core kernel's
   const int q_hi = min(ngroups, q_lo + groups_per_block);
   const uint32_t lane_off = (uint32_t)lane * 16u;   // 16-byte vectors: tile loads and index loads
   // per-(trait, tile) exceedance counts of every list slot: plain 16-bit stores, summed
@@ -555,7 +555,10 @@ static int64_t list_chunk_bytes(int TW) {
 struct ListGeom {
   int64_t ntiles, ngroups, gs, gpb, chunks;
 };
-static ListGeom list_geom(int num_cu, int64_t G, int64_t T, int64_t N, int64_t P, int64_t entries) {
+// `first` = the first wave group the list kernel walks (the groups below it are routed to k_permute_mfma),
+// `entries` = the index entries of the groups it does walk
+static ListGeom list_geom(int num_cu, int64_t G, int64_t T, int64_t N, int64_t P, int64_t entries,
+                          int64_t first = 0) {
   ListGeom g{};
   const int TW = list_tw(N), GPW = kWave / list_lpg(TW);
   const int64_t tile_perms = TW * 32;
@@ -571,22 +574,25 @@ static ListGeom list_geom(int num_cu, int64_t G, int64_t T, int64_t N, int64_t P
   if (chunks < by_l2) chunks = by_l2;
   if (chunks > 65535) chunks = 65535;
   if (chunks < 1) chunks = 1;
-  g.gpb = (g.ngroups + chunks - 1) / chunks;
+  const int64_t walked = g.ngroups - first;
+  g.gpb = (walked + chunks - 1) / chunks;
   g.gpb = (g.gpb + 15) / 16 * 16;
-  g.chunks = (g.ngroups + g.gpb - 1) / g.gpb;
+  g.chunks = g.gpb ? (walked + g.gpb - 1) / g.gpb : 0;
   return g;
 }
 
 // One list launch: regions into slot order (unless given), the list kernel `kernel` against the label
 // tiles (`name` its timer, `lds` its dynamic LDS bytes, `optin` its bit in h->lists_lds_optin, `extra` its
-// arguments before `partial`), the sum over the tiles.  Both kernels share the scratch layout and geometry.
+// arguments before `partial`: the first wave group it walks, or the segment count), the sum over the tiles.
+// Both kernels share the scratch layout and geometry.
 template <typename Kernel, typename... Extra>
 static int launch_lists(scoary_handle h, hipStream_t s, Kernel kernel, const char* name, size_t lds, int optin,
                         const uint32_t* d_tiles, const uint32_t* d_lidx, int64_t entries,
                         const int32_t* d_lstart, const int32_t* d_lngroups, const int32_t* d_lorder,
                         const uint8_t* d_lflipped, const uint32_t* d_crit, const uint32_t* d_lcrit_in,
                         const int32_t* d_margins, uint32_t* d_scratch, int64_t G, int64_t T, int64_t N,
-                        int64_t P, uint32_t* d_r, int accumulate, Extra... extra) {
+                        int64_t P, uint32_t* d_r, int accumulate, const void* d_panels, void* d_bfrag,
+                        int64_t k_split, int64_t routed_entries, Extra... extra) {
   uint32_t* d_lcrit_sc = d_scratch;                    // [T][G][2]
   uint16_t* d_partial = reinterpret_cast<uint16_t*>(d_scratch + 2 * T * G);   // [T][ntiles][gs]
   const uint32_t* d_lcrit = d_lcrit_in ? d_lcrit_in : d_lcrit_sc;
@@ -596,7 +602,16 @@ static int launch_lists(scoary_handle h, hipStream_t s, Kernel kernel, const cha
                        reinterpret_cast<const uint2*>(d_crit), d_margins, d_lorder, d_lflipped,
                        (int)G, reinterpret_cast<uint2*>(d_lcrit_sc));
   }
-  const ListGeom g = list_geom(h->num_cu, G, T, N, P, entries);
+  // slots [0, k_split): k_permute_mfma, into the same partial counts; the list kernel starts at the
+  // wave group behind them (k_split is a multiple of 256 slots, or G: nothing left to walk)
+  const int64_t gpw = kWave / list_lpg(list_tw(N));
+  const int64_t q_first = (k_split + gpw - 1) / gpw;
+  const ListGeom g = list_geom(h->num_cu, G, T, N, P, entries - routed_entries, q_first);
+  if (k_split > 0) {
+    const int rc = scoary_mfma_launch(h, s, d_tiles, d_panels, d_bfrag, d_lcrit, d_partial, k_split, G, T, N, P,
+                                      g.ntiles, g.gs);
+    if (rc != SCOARY_OK) return rc;
+  }
   if (T * g.ntiles > 0x7fffffffLL || g.chunks > 65535)
     return fail(h, SCOARY_ERR_SIZE, "scoary_permute_lists: grid too large");
   if (!(h->lists_lds_optin & optin)) {   // once per handle (= per device) and kernel
@@ -611,7 +626,7 @@ static int launch_lists(scoary_handle h, hipStream_t s, Kernel kernel, const cha
     HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     h->lists_lds_optin |= optin;
   }
-  {
+  if (g.chunks > 0) {
     KernelTimer kt(h, s, name);
     hipLaunchKernelGGL(kernel, dim3((unsigned)(T * g.ntiles), (unsigned)g.chunks), dim3(1024), lds, s, d_tiles,
                        d_lidx, d_lstart, d_lngroups, reinterpret_cast<const uint2*>(d_lcrit), (int)G,
@@ -640,7 +655,23 @@ int scoary_permute_lists(scoary_handle h, const uint32_t* d_tiles, const uint32_
                          const uint32_t* d_crit, const uint32_t* d_lcrit, const int32_t* d_margins,
                          void* d_scratch, int64_t G, int64_t T, int64_t N, int64_t P,
                          uint32_t* d_r, int accumulate, scoary_stream_t stream) {
+  return scoary_permute_hybrid(h, d_tiles, d_lidx, entries, d_lstart, d_lngroups, d_lorder, d_lflipped, d_crit,
+                               d_lcrit, d_margins, d_scratch, G, T, N, P, d_r, accumulate, nullptr, nullptr, 0, 0,
+                               stream);
+}
+
+int scoary_permute_hybrid(scoary_handle h, const uint32_t* d_tiles, const uint32_t* d_lidx,
+                          int64_t entries, const int32_t* d_lstart, const int32_t* d_lngroups,
+                          const int32_t* d_lorder, const uint8_t* d_lflipped,
+                          const uint32_t* d_crit, const uint32_t* d_lcrit, const int32_t* d_margins,
+                          void* d_scratch, int64_t G, int64_t T, int64_t N, int64_t P,
+                          uint32_t* d_r, int accumulate, const void* d_panels, void* d_bfrag,
+                          int64_t k_split, int64_t routed_entries, scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
+  if (k_split < 0 || k_split > G || routed_entries < 0 || routed_entries > entries ||
+      (k_split > 0 && (!d_panels || !d_bfrag || N > scoary_mfma_max_isolates() ||
+                       (k_split % 256 != 0 && k_split != G))))
+    return fail(h, SCOARY_ERR_ARG, "scoary_permute_hybrid: bad k_split (scoary_mfma_route gives a valid one)");
   if (!d_tiles || !d_lidx || !d_lstart || !d_lngroups || !d_lorder || !d_lflipped ||
       (!d_crit && !d_lcrit) || (!d_lcrit && !d_margins) || !d_scratch || !d_r || G < 1 || T < 1 ||
       N < 1 || P < 1 || entries < 0)
@@ -657,13 +688,14 @@ int scoary_permute_lists(scoary_handle h, const uint32_t* d_tiles, const uint32_
   if (list_segments(N) > 1)
     return launch_lists(h, s, &k_permute_seglists<16>, "k_permute_seglists", (size_t)kSegStride * sizeof(uint32_t),
                         32, d_tiles, d_lidx, entries, d_lstart, d_lngroups, d_lorder, d_lflipped, d_crit, d_lcrit,
-                        d_margins, sc, G, T, N, P, d_r, accumulate, list_segments(N));
+                        d_margins, sc, G, T, N, P, d_r, accumulate, nullptr, nullptr, 0, 0, list_segments(N));
   // counter planes KC: lists hold <= N/2 entries, N/2 < 2^KC (and N + 1 < 2^(KC+1))
 #define LAUNCH(TWV, KCV)                                                                             \
   return launch_lists(h, s, &k_permute_lists<list_lpg(TWV), list_nw(TWV), KCV>, "k_permute_lists",  \
                       (size_t)list_tile_dwords(N, TWV) * sizeof(uint32_t), TWV, d_tiles, d_lidx,     \
                       entries, d_lstart, d_lngroups, d_lorder, d_lflipped, d_crit, d_lcrit, d_margins, \
-                      sc, G, T, N, P, d_r, accumulate)
+                      sc, G, T, N, P, d_r, accumulate, d_panels, d_bfrag, k_split, routed_entries,       \
+                      (int)((k_split + kWave / list_lpg(TWV) - 1) / (kWave / list_lpg(TWV))))
   if (TW == 16) LAUNCH(16, 11);
   if (TW == 8) LAUNCH(8, 12);
   if (TW == 4) LAUNCH(4, 13);

@@ -1,0 +1,394 @@
+// scoary_mfma.hip -- the matrix-core permutation path for long-list genes (N <= 2048).
+//
+// The list count of the list-driven kernel is a 0/1 GEMM,
+//     u[slot][pi] = sum_i minority[slot][i] * label[i][pi],
+// exact in fp32, whose cost does not depend on the list length.  k_permute_lists pays 2 LUT ops
+// per listed isolate and 32 permutations, so beyond a break-even list length (kMfmaNsPerGene /
+// kListNsPerEntry below) the matrix cores are cheaper; scoary_permute_hybrid routes the slots
+// [0, k_split) -- the long-list end of the slot order -- here and leaves the rest to the lists.
+//
+//   k_mfma_panels  (once per data set)  minority rows of the list slots as E2M1 (0 = 0x0, 1.0 = 0x2)
+//                                       A fragments of v_mfma_scale_f32_32x32x64_f8f6f4, 1 KB per slot
+//   k_mfma_bfrag   (per label batch)    the label tiles of k_labels as E2M1 B fragments, 64 KB per
+//                                       (trait, 64 permutations): the SAME draws the list kernel reads
+//   k_permute_mfma                      gene operand stationary in registers (256 per lane), B streamed
+//                                       through a four-slot LDS ring by LDS-DMA, region test on the
+//                                       accumulators, 16-bit counts into the list path's `partial`
+#include "scoary_common.hpp"
+
+// The two measured rates the routing is decided by (scoary_mfma_route): a routed gene costs kMfmaNsPerGene
+// whatever its list holds, a listed gene kListNsPerEntry per padded list entry -- break-even list length
+// = their ratio (scoary_mfma_breakeven_entries).  Both per 100 000 tests of the gene (cfg3: 10 traits x
+// 10 000 permutations), chip-wide, on MI355X: k_permute_mfma + k_mfma_bfrag with every cfg3 gene routed,
+// the parent's k_permute_lists with none (profiles/r09_mfma_hybrid.txt).
+const double kMfmaNsPerGene = 80.0;
+const double kListNsPerEntry = 0.177;
+const double kMfmaPanelLoadStages = 6.0;   // a block's A panel (256 KB from HBM), in stages of its loop
+
+namespace {
+
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+constexpr int kKSteps = 32;                       // K-steps of 64 isolates: N <= 2048
+constexpr int kBlockGenes = 256;                  // four wavefronts x 64 list slots
+constexpr int kFragBytes = 1024;                  // one operand fragment: 64 lanes x 16 bytes (32 E2M1 values)
+constexpr int kStageBytes = 2 * kKSteps * kFragBytes;   // B of (trait, 64 permutations): [K-step][column tile][lane]
+constexpr int kHalfBytes = kStageBytes / 2;       // the unit of the LDS ring: 16 K-steps
+constexpr int kRingBytes = 4 * kHalfBytes;        // 128 KB
+constexpr int kDmaPerHalf = kHalfBytes / 4 / kFragBytes;   // LDS-DMA instructions per wavefront and half stage
+constexpr int kMfmaLds = kRingBytes + kBlockGenes * 8;     // + (-centre, half width) of the block's 256 slots
+
+// 8 presence bits -> 8 E2M1 nibbles (bit i -> nibble i = 0b0010 = 1.0): pairs of bits select a byte
+// of the pool {0x00, 0x02, 0x20, 0x22} through v_perm_b32
+__device__ __forceinline__ uint32_t fp4_of_bits8(uint32_t b) {
+  uint32_t y = b | (b << 12);
+  y = (y | (y << 6)) & 0x03030303u;
+  return __builtin_amdgcn_perm(0u, 0x22200200u, y);
+}
+__device__ __forceinline__ v4i fp4_of_bits32(uint32_t w) {
+  return v4i{(int)fp4_of_bits8(w & 0xffu), (int)fp4_of_bits8((w >> 8) & 0xffu),
+             (int)fp4_of_bits8((w >> 16) & 0xffu), (int)fp4_of_bits8(w >> 24)};
+}
+
+// A panels: [wave panel of 64 slots][row tile i][K-step k][lane] x 16 bytes.  Lane l of fragment (i, k)
+// holds slot 64 * panel + 32 i + (l & 31), isolates 64 k + 32 (l >> 5) .. + 31: one 32-bit word of the
+// gene's tiled row, XOR `flipped` (the MINORITY indicator: the accumulator is the list count u),
+// isolates >= N and slots >= G zero.
+__global__ __launch_bounds__(256) void k_mfma_panels(const uint32_t* __restrict__ tiled, int64_t Gp, int G, int N,
+                                                     const int32_t* __restrict__ order,
+                                                     const uint8_t* __restrict__ flipped, int64_t total,
+                                                     v4i* __restrict__ panels) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int lane = (int)(idx & 63);
+  const int64_t f = idx >> 6;
+  const int k = (int)(f & 31), i = (int)((f >> 5) & 1);
+  const int64_t slot = (f >> 6) * 64 + i * 32 + (lane & 31);
+  const int w = 2 * k + (lane >> 5);              // word of the row: isolates 32 w .. 32 w + 31
+  uint32_t bits = 0u;
+  if (slot < G && 32 * w < N) {
+    const int g = order[slot];
+    bits = tiled[((int64_t)(w >> 2) * Gp + g) * 4 + (w & 3)];
+    if (flipped[g]) bits = ~bits;
+    if (32 * w + 32 > N) bits &= (1u << (N - 32 * w)) - 1u;
+  }
+  panels[idx] = fp4_of_bits32(bits);
+}
+
+// B fragments from the label tiles (tiles[t][tile][row 0..N][16 dwords], dword j of a row = permutations
+// 512 tile + 32 j .. + 31): bfrag[t][stage s][K-step k][column tile j][lane] x 16 bytes, lane l = permutation
+// 64 s + 32 j + (l & 31), isolates 64 k + 32 (l >> 5) .. + 31.  A wavefront reads dword 2 (s % 8) + j of
+// 64 rows (lane = isolate) and transposes 64 x 32 bits with one ballot per permutation.  Rows >= N are
+// zero; permutations >= P hold whatever the tile holds and are masked by the kernel.
+__global__ __launch_bounds__(256) void k_mfma_bfrag(const uint32_t* __restrict__ tiles, int N, int ntiles,
+                                                    int64_t tile_dwords, int S, v4i* __restrict__ bfrag) {
+  const int s = blockIdx.x, t = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t* tile = tiles + ((int64_t)t * ntiles + (s >> 3)) * tile_dwords + 2 * (s & 7);
+  v4i* out = bfrag + ((int64_t)t * S + s) * (kStageBytes / 16);
+  for (int k = wave; k < kKSteps; k += 4) {
+    const int row = k * 64 + lane;
+    uint2 w = make_uint2(0u, 0u);
+    if (row < N) w = *reinterpret_cast<const uint2*>(tile + (int64_t)row * 16);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const uint32_t x = j ? w.y : w.x;
+      uint32_t mine = 0u;
+#pragma unroll
+      for (int c = 0; c < 32; ++c) {
+        const uint64_t bal = __ballot((x >> c) & 1u);
+        const uint32_t v = (lane >> 5) ? (uint32_t)(bal >> 32) : (uint32_t)bal;
+        if ((lane & 31) == c) mine = v;
+      }
+      out[(k * 2 + j) * 64 + lane] = fp4_of_bits32(mine);
+    }
+  }
+}
+
+// One 16-byte vector per lane, src + 16 * lane -> LDS address lds + 16 * lane, by LDS-DMA: wave-uniform
+// base in an SGPR pair, the lane offset in one VGPR, the LDS destination in M0 (handed back as it was).
+__device__ __forceinline__ void mfma_dma16(uint32_t lds, uint32_t lane_off, const unsigned char* src) {
+  uint32_t m0_saved;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
+               : "=&s"(m0_saved)
+               : "s"(lds), "v"(lane_off), "s"(src)
+               : "memory");
+}
+
+// Bijective XCD remap: consecutive work items land on ONE XCD (blocks are dealt to the eight XCDs
+// round-robin), so the blocks resident on an XCD at one time share their (trait, permutation range)
+// and stream the same B stages out of that XCD's L2.
+__device__ __forceinline__ int xcd_item(int orig, int n) {
+  const int q = n >> 3, r = n & 7, x = orig & 7;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (orig >> 3);
+}
+
+// Block = 256 list slots (four wavefronts x 64, one wavefront per SIMD) x one trait x `per` stages of 64
+// permutations.  A: 2 row tiles x 32 K-steps x 4 registers per lane, loaded once.  B: half stages of 32 KB
+// move HBM/L2 -> LDS by LDS-DMA three ahead of their use through a four-slot ring; the wait that retires
+// half n is the counted vmcnt(2 halves) in front of the barrier that precedes its first ds_read, and slot
+// (n + 3) % 4 is refilled behind that same barrier -- every wavefront has consumed half n - 1 by then.
+// There is no ordinary global load inside the loop (the compiler would wait vmcnt(0) for it and drain the ring).
+// The accumulators start at minus the centre of the acceptance interval [lo, hi1) of the list count, so
+// "u outside the interval" is one compare, |acc| > half width; the two column tiles of a row share one
+// per-lane counter that lives across the stages, the 32 lanes of a row meet once, at the end.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void k_permute_mfma(const v4i* __restrict__ panels, const unsigned char* __restrict__ bfrag,
+                    const uint2* __restrict__ lcrit, int G, int64_t P, int S, int per, int rp, int nblk_genes,
+                    int ntiles, int64_t gs, uint16_t* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const int item = xcd_item(blockIdx.x, gridDim.x);
+  const int gb = item % nblk_genes, rng = item / nblk_genes;
+  const int t = rng / rp, jr = rng % rp;
+  const int s0 = jr * per, ns = min(per, S - s0);
+  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  float2* thr = reinterpret_cast<float2*>(lds + kRingBytes);
+  {
+    const int64_t slot = (int64_t)gb * kBlockGenes + tid;
+    float2 c = make_float2(0.f, 1e30f);            // slots >= G: never counted
+    if (slot < G) {
+      const uint2 cr = lcrit[(int64_t)t * G + slot];
+      c = make_float2(-0.5f * (float)((int)cr.x + (int)cr.y - 1), 0.5f * (float)((int)cr.y - 1 - (int)cr.x));
+    }
+    thr[tid] = c;
+  }
+  v4i a[2][kKSteps];
+  {
+    const v4i* ap = panels + ((int64_t)gb * 4 + wave) * (2 * kKSteps * 64) + lane;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int k = 0; k < kKSteps; ++k) a[i][k] = ap[(i * kKSteps + k) * 64];
+    // every A load retired here, before the first LDS-DMA is issued: no compiler-placed wait in the loop
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int k = 0; k < kKSteps; ++k) asm volatile("" : "+v"(a[i][k]));
+  }
+  __syncthreads();
+
+  const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)lds;
+  const uint32_t lane_off = (uint32_t)lane * 16u;
+  const unsigned char* bsrc = bfrag + ((int64_t)t * S + s0) * kStageBytes + wave * (kHalfBytes / 4);
+  const int nh = 2 * ns;
+  // half n of the block's range -> ring slot n % 4; halves past the end re-read the last one into a slot
+  // nobody reads any more, so the vmcnt counts stay the same to the end
+  auto issue_half = [&](int n) {
+    const unsigned char* src = bsrc + (int64_t)min(n, nh - 1) * kHalfBytes;
+    const uint32_t dst = lds0 + (uint32_t)(n & 3) * kHalfBytes + (uint32_t)wave * (kHalfBytes / 4);
+#pragma unroll
+    for (int p = 0; p < kDmaPerHalf; ++p) mfma_dma16(dst + p * kFragBytes, lane_off, src + p * kFragBytes);
+  };
+  issue_half(0);
+  issue_half(1);
+  issue_half(2);
+
+  uint32_t ex[2][16];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ex[i][r] = 0u;
+  const float2* my_thr = thr + wave * 64 + 4 * half;     // row of (i, r): 32 i + (r & 3) + 8 (r >> 2) + 4 half
+  const int64_t last_valid = P - (int64_t)s0 * 64;        // permutations of this range that exist
+
+  for (int st = 0; st < ns; ++st) {
+    v16f acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float c = my_thr[i * 32 + (r & 3) + 8 * (r >> 2)].x;
+        acc[i][0][r] = c;
+        acc[i][1][r] = c;
+      }
+    const unsigned char* bbuf = lds + (st & 1) * kStageBytes + lane * 16;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      static_assert(kDmaPerHalf == 8, "vmcnt(16) below = two half stages of 8 LDS-DMA instructions in flight");
+      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      issue_half(2 * st + h + 3);
+      // B fragments are read two K-steps (eight MFMAs) ahead of their use through a three-deep register
+      // ring: with one wavefront per SIMD nothing else hides the ds_read latency.  The scheduling barriers
+      // keep the reads where they are written (left alone, the compiler reads each fragment right before its MFMAs).
+      v4i bq[3][2];
+      auto read_b = [&](int kk) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          bq[kk % 3][j] = *reinterpret_cast<const v4i*>(bbuf + ((h * (kKSteps / 2) + kk) * 2 + j) * kFragBytes);
+      };
+      read_b(0);
+      read_b(1);
+#pragma unroll
+      for (int kk = 0; kk < kKSteps / 2; ++kk) {
+        const int k = h * (kKSteps / 2) + kk;
+        if (kk + 2 < kKSteps / 2) read_b(kk + 2);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const v8i aa = v8i{a[i][k].x, a[i][k].y, a[i][k].z, a[i][k].w, 0, 0, 0, 0};
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const v4i x = bq[kk % 3][j];
+            acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aa, v8i{x.x, x.y, x.z, x.w, 0, 0, 0, 0},
+                                                                        acc[i][j], 4, 4, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    const int64_t nvalid = last_valid - (int64_t)st * 64;
+    if (nvalid >= 64) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float hw = my_thr[i * 32 + (r & 3) + 8 * (r >> 2)].y;
+          ex[i][r] += (uint32_t)(__builtin_fabsf(acc[i][0][r]) > hw) + (uint32_t)(__builtin_fabsf(acc[i][1][r]) > hw);
+        }
+    } else {                                        // ragged last stage: columns >= P do not count
+      const bool v0 = l31 < nvalid, v1 = l31 + 32 < nvalid;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float hw = my_thr[i * 32 + (r & 3) + 8 * (r >> 2)].y;
+          ex[i][r] += (uint32_t)(v0 && __builtin_fabsf(acc[i][0][r]) > hw) +
+                      (uint32_t)(v1 && __builtin_fabsf(acc[i][1][r]) > hw);
+        }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last (redundant) transfers land before the LDS is given up
+
+  // partial[t][tile][slot]: the range's count goes to tile jr, zeros to the tiles jr + rp, jr + 2 rp, ...
+  // (k_lists_reduce sums every tile of every slot)
+  uint16_t* out = partial + ((int64_t)t * ntiles + jr) * gs + (int64_t)gb * kBlockGenes + wave * 64 + 4 * half;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      uint32_t v = ex[i][r];
+#pragma unroll
+      for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
+      const int row = i * 32 + (r & 3) + 8 * (r >> 2);
+      if (l31 == 0 && (int64_t)gb * kBlockGenes + wave * 64 + 4 * half + row < G) {
+        out[row] = (uint16_t)v;
+        for (int tile = jr + rp; tile < ntiles; tile += rp) out[(int64_t)(tile - jr) * gs + row] = 0;
+      }
+    }
+}
+
+}  // namespace
+
+// Stages of 64 permutations per block (`per`) and ranges per trait (`rp`): the fewest rounds of blocks
+// over the CUs, a block long enough to pay for loading its A panel (~6 stages' worth), a range's count
+// within 16 bits and one range per partial tile at most.
+MfmaGeom scoary_mfma_geom(int num_cu, int64_t k_split, int64_t T, int64_t P, int64_t ntiles) {
+  MfmaGeom g{};
+  g.stages = (P + 63) / 64;
+  g.gene_blocks = (k_split + kBlockGenes - 1) / kBlockGenes;
+  const int64_t rp_min = (g.stages + 1022) / 1023, rp_max = std::min<int64_t>(std::min(ntiles, g.stages), 64);
+  double best = 0.0;
+  for (int64_t rp = rp_min; rp <= std::max(rp_min, rp_max); ++rp) {
+    const int64_t per = (g.stages + rp - 1) / rp, ranges = (g.stages + per - 1) / per;
+    const int64_t blocks = g.gene_blocks * T * ranges;
+    const double cost = (double)((blocks + num_cu - 1) / num_cu) * ((double)per + kMfmaPanelLoadStages);
+    if (g.rp == 0 || cost < best) best = cost, g.rp = ranges, g.per = per, g.blocks = blocks;
+  }
+  return g;
+}
+
+int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, const void* d_panels, void* d_bfrag,
+                       const uint32_t* d_lcrit, uint16_t* d_partial, int64_t k_split, int64_t G, int64_t T,
+                       int64_t N, int64_t P, int64_t ntiles, int64_t gs) {
+  const MfmaGeom g = scoary_mfma_geom(h->num_cu, k_split, T, P, ntiles);
+  if (g.blocks > 0x7fffffffLL || g.stages > 0x7fffffffLL / 64)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_permute_hybrid: grid too large");
+  if (!h->mfma_lds_optin) {
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_permute_mfma),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    h->mfma_lds_optin = 1;
+  }
+  {
+    KernelTimer kt(h, s, "k_mfma_bfrag");
+    hipLaunchKernelGGL(k_mfma_bfrag, dim3((unsigned)g.stages, (unsigned)T), dim3(256), 0, s, d_tiles, (int)N,
+                       (int)ntiles, list_tile_dwords(N, 16), (int)g.stages, static_cast<v4i*>(d_bfrag));
+  }
+  {
+    KernelTimer kt(h, s, "k_permute_mfma");
+    hipLaunchKernelGGL(k_permute_mfma, dim3((unsigned)g.blocks), dim3(256), kMfmaLds, s,
+                       static_cast<const v4i*>(d_panels), static_cast<const unsigned char*>(d_bfrag),
+                       reinterpret_cast<const uint2*>(d_lcrit), (int)G, P, (int)g.stages, (int)g.per, (int)g.rp,
+                       (int)g.gene_blocks, (int)ntiles, gs, d_partial);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+
+extern "C" {
+
+int64_t scoary_mfma_max_isolates(void) { return kKSteps * 64; }
+int64_t scoary_mfma_panels_bytes(int64_t G, int64_t N) {
+  if (G < 1 || N < 1 || N > kKSteps * 64) return 0;
+  return round_up(G, kBlockGenes) * (2 * kKSteps * 16);
+}
+int64_t scoary_mfma_bfrag_bytes(int64_t N, int64_t P, int64_t T) {
+  if (N < 1 || N > kKSteps * 64 || P < 1 || T < 1) return 0;
+  return T * ((P + 63) / 64) * kStageBytes;
+}
+int64_t scoary_mfma_breakeven_entries(void) { return (int64_t)std::ceil(kMfmaNsPerGene / kListNsPerEntry); }
+
+int scoary_mfma_panels_build(scoary_handle h, const uint32_t* d_tiled, int64_t G, int64_t N, const int32_t* d_order,
+                             const uint8_t* d_flipped, void* d_panels, scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (!d_tiled || !d_order || !d_flipped || !d_panels || G < 1 || N < 1)
+    return fail(h, SCOARY_ERR_ARG, "scoary_mfma_panels_build: bad argument");
+  if (N > kKSteps * 64 || G > 0x7fffffffLL - kBlockGenes)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_mfma_panels_build: N > 2048 or G >= 2^31");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t total = scoary_mfma_panels_bytes(G, N) / 16;
+  KernelTimer kt(h, s, "k_mfma_panels");
+  hipLaunchKernelGGL(k_mfma_panels, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_tiled,
+                     scoary_tiled_genes(G), (int)G, (int)N, d_order, d_flipped, total, static_cast<v4i*>(d_panels));
+  HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+
+int scoary_set_mfma_route(scoary_handle h, int mode) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (mode < SCOARY_MFMA_ROUTE_NONE || mode > SCOARY_MFMA_ROUTE_AUTO)
+    return fail(h, SCOARY_ERR_ARG, "scoary_set_mfma_route: mode is 0 (none), 1 (all) or 2 (auto)");
+  h->mfma_route = mode;
+  return SCOARY_OK;
+}
+
+// AUTO: the whole number of 256-slot blocks that makes (rounds of MFMA blocks over the CUs) x (stages + panel
+// load) x (time of a stage) + (entries left to the lists) x kListNsPerEntry smallest.  Where a round of blocks
+// is short against the whole this is the break-even length; the rounds term keeps the split off block counts
+// that are a fraction over a multiple of the CU count (cfg3: 106 gene blocks x 10 traits = 4.1 rounds).
+int64_t scoary_mfma_route(scoary_handle h, const int64_t* block_start, int64_t G, int64_t T, int64_t N, int64_t P) {
+  if (!h || G < 1 || T < 1 || P < 1 || N < 1 || N > kKSteps * 64 || h->mfma_route == SCOARY_MFMA_ROUTE_NONE)
+    return 0;
+  if (h->mfma_route == SCOARY_MFMA_ROUTE_ALL) return G;
+  if (!block_start) return 0;
+  const int64_t nb = G / kBlockGenes, total = block_start[(G + kBlockGenes - 1) / kBlockGenes];
+  const double tests = (double)T * (double)P / 1e5;
+  const double stage_ns = kMfmaNsPerGene * h->num_cu * kBlockGenes * 64 / 1e5;   // one block, one stage
+  double best = kListNsPerEntry * (double)total * tests;
+  int64_t best_nb = 0;
+  for (int64_t b = 1; b <= nb; ++b) {
+    const MfmaGeom g = scoary_mfma_geom(h->num_cu, b * kBlockGenes, T, P, (P + 511) / 512);
+    if (g.blocks < h->num_cu) continue;            // less than one round of blocks over the CUs: lists
+    const double cost = (double)((g.blocks + h->num_cu - 1) / h->num_cu) * ((double)g.per + kMfmaPanelLoadStages) * stage_ns +
+                        kListNsPerEntry * (double)(total - block_start[b]) * tests;
+    if (cost < best) best = cost, best_nb = b;
+  }
+  return best_nb * kBlockGenes;
+}
+
+}  // extern "C"

@@ -45,11 +45,15 @@ class ListMemoryError(_abi.ScoaryHipError):
 
 class GeneLists:
     """Minority index lists of a gene matrix on the device (scoary_lists_plan / _fill).
-    start / ngroups: int32 [G] per list slot, or [segments, G] for N > 20479."""
+    start / ngroups: int32 [G] per list slot, or [segments, G] for N > 20479.
+    panels: the slots' minority rows as matrix-core operands (scoary_mfma_panels_build; N <= 2048), or
+    None; block_start: host int64 array, index entries in front of every 256-slot block (and the
+    total last); routes: k_split per (routing mode, T, P), a host-side cache."""
 
     def __init__(self, idx, start, ngroups, order, flipped, entries):
         self.idx, self.start, self.ngroups = idx, start, ngroups
         self.order, self.flipped, self.entries = order, flipped, entries
+        self.panels, self.block_start, self.routes = None, None, {}
 
 
 class TraitPlan:
@@ -90,7 +94,7 @@ class Workspace:
         self.odds = eng._empty((T, G), torch.float64)
         self.crit = eng._empty((T, G, 2), torch.int32) if permutations > 0 else None
         self.r = eng._empty((T, G), torch.int32) if permutations > 0 else None
-        self.tiles = self.scratch = self.perms = self.lcrit = None
+        self.tiles = self.scratch = self.perms = self.lcrit = self.bfrag = None
         self.label_shards = None
         self.auto = None        # engine.associate's cached hipGraph of a launch-bound step
         self.batch = 0
@@ -104,6 +108,9 @@ class Workspace:
             self.label_shards = eng.label_shards
             self.scratch = eng.permute_lists_scratch(G, T, N, nb0)
             self.lcrit = eng._empty((T, G, 2), torch.int32)
+            # B operand of the matrix-core kernel, one label batch
+            if genes.lists is not None and genes.lists.panels is not None:
+                self.bfrag = eng._empty((int(eng.lib.scoary_mfma_bfrag_bytes(N, nb0, T)) // 4,), torch.int32)
         elif permutations > 0:
             if perm_buffer is not None:
                 self.perms = perm_buffer
@@ -307,7 +314,44 @@ class AssociationEngine:
             self.h, self._ptr(genes.tiled), G, N, self._ptr(scratch), self._ptr(order),
             self._ptr(flipped), total, self._ptr(idx), self._stream()), "scoary_lists_fill")
         genes.lists = GeneLists(idx, start, ngroups, order, flipped, total)
+        self._build_panels(genes, budget_bytes - need)
         return genes.lists
+
+    def _build_panels(self, genes, budget_bytes):
+        """The matrix-core operands of the list slots (N <= 2048, 1 KB per slot; skipped when they do
+        not fit the budget: the lists then take every gene) and what the routing needs on the host."""
+        torch = _torch()
+        L, G, N = genes.lists, genes.G, genes.N
+        nbytes = int(self.lib.scoary_mfma_panels_bytes(G, N))
+        if nbytes == 0 or nbytes > budget_bytes:
+            return
+        panels = self._empty((nbytes // 4,), torch.int32)
+        self._check(self.lib.scoary_mfma_panels_build(
+            self.h, self._ptr(genes.tiled), G, N, self._ptr(L.order), self._ptr(L.flipped),
+            self._ptr(panels), self._stream()), "scoary_mfma_panels_build")
+        starts = L.start[::256].to(torch.int64).cpu().numpy() * 32    # d_lstart counts units of 32 entries
+        L.block_start = np.ascontiguousarray(np.append(starts, np.int64(L.entries)), dtype=np.int64)
+        L.panels = panels
+
+    def mfma_split(self, genes, T, P):
+        """Slots [0, k_split) of a (T, P) launch go to the matrix-core kernel: scoary_mfma_route (the
+        handle's routing mode, the two measured rates, the launch shape), cached per data set."""
+        L = genes.lists
+        if L is None or L.panels is None:
+            return 0
+        key = (getattr(self, "_mfma_mode", "auto"), int(T), int(P))
+        k = L.routes.get(key)
+        if k is None:
+            k = L.routes[key] = int(self.lib.scoary_mfma_route(
+                self.h, ctypes.c_void_p(L.block_start.ctypes.data), genes.G, int(T), genes.N, int(P)))
+        return k
+
+    def set_mfma_route(self, mode):
+        """Which list slots the matrix-core kernel takes: "none", "all" or "auto" (the default: the slots
+        above the measured break-even list length) -- scoary_set_mfma_route."""
+        self._check(self.lib.scoary_set_mfma_route(self.h, {"none": 0, "all": 1, "auto": 2}[mode]),
+                    "scoary_set_mfma_route")
+        self._mfma_mode = mode
 
     def list_params(self, N):
         """(tile row dwords, row stride bytes, genes per wavefront, classes,
@@ -352,7 +396,7 @@ class AssociationEngine:
         return self._empty(((nbytes + 3) // 4,), torch.int32)
 
     def permute_lists(self, genes, tiles, crit, margins, P, r, scratch=None, lcrit=None,
-                      accumulate=True):
+                      accumulate=True, bfrag=None):
         """r (+)= exceedance counts of P permutations (label tiles ``tiles``).  The regions
         come in gene order (``crit`` from fisher) or, one launch cheaper, in slot order
         (``lcrit`` from fisher(..., lists=...)); accumulate=False overwrites r."""
@@ -360,13 +404,23 @@ class AssociationEngine:
         T = (lcrit if lcrit is not None else crit).shape[0]
         if scratch is None:
             scratch = self.permute_lists_scratch(genes.G, T, genes.N, P)
-        self._check(self.lib.scoary_permute_lists(
+        # the long-list slots [0, k_split) go to the matrix-core kernel (a host-side decision: the
+        # handle's routing mode, the data set's break-even count and the launch shape)
+        routed = 0
+        k_split = self.mfma_split(genes, T, P)
+        if k_split > 0:
+            if bfrag is None:
+                bfrag = self._empty((int(self.lib.scoary_mfma_bfrag_bytes(genes.N, P, T)) // 4,), _torch().int32)
+            routed = int(L.block_start[-1 if k_split >= genes.G else k_split // 256])
+        self._check(self.lib.scoary_permute_hybrid(
             self.h, self._ptr(tiles), self._ptr(L.idx), L.entries, self._ptr(L.start),
             self._ptr(L.ngroups), self._ptr(L.order), self._ptr(L.flipped),
             self._ptr(crit) if lcrit is None else None,
             self._ptr(lcrit) if lcrit is not None else None,
             self._ptr(margins), self._ptr(scratch), genes.G, T, genes.N, P, self._ptr(r),
-            1 if accumulate else 0, self._stream()), "scoary_permute_lists")
+            1 if accumulate else 0, self._ptr(L.panels) if k_split > 0 else None,
+            self._ptr(bfrag) if k_split > 0 else None, k_split, routed, self._stream()),
+            "scoary_permute_hybrid")
         return r
 
     # -- a3: counts -----------------------------------------------------------
@@ -547,8 +601,10 @@ class AssociationEngine:
         # and kept alive by `refs`, so their memory cannot be recycled under the graph), their
         # versions (in-place edits through torch since the recording) and the scalars.
         refs = (genes.tiled, traits, masks, plan, plan.margins, plan.mask_class, plan.buf) + \
-            ((L.idx, L.start, L.ngroups, L.order, L.flipped) if L is not None else ())
+            ((L.idx, L.start, L.ngroups, L.order, L.flipped) if L is not None else ()) + \
+            ((L.panels,) if L is not None and L.panels is not None else ())
         scalars = (genes.G, genes.N, int(traits.shape[0]), int(permutations), int(seed), bool(use_lists),
+                   getattr(self, "_mfma_mode", "auto"),
                    tuple(getattr(x, "_version", 0) for x in refs))
         st = ws.auto
         same = st is not None and st["scalars"] == scalars and len(st["refs"]) == len(refs) and \
@@ -649,7 +705,7 @@ class AssociationEngine:
                 if done > 0:
                     self._label_tiles(ws, masks, margins, genes.N, nb, done, seed)
                 self.permute_lists(genes, ws.tiles, None, margins, nb, ws.r, scratch=ws.scratch,
-                                   lcrit=lcrit, accumulate=done > 0)
+                                   lcrit=lcrit, accumulate=done > 0, bfrag=ws.bfrag)
                 done += nb
             return {"counts": counts, "margins": margins, "p": p, "odds": odds, "crit": crit,
                     "r": ws.r}

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define SCOARY_ABI_VERSION 10
+#define SCOARY_ABI_VERSION 11
 
 /* error codes */
 #define SCOARY_OK 0
@@ -215,6 +215,39 @@ int scoary_permute_seq(scoary_handle h, const uint32_t *d_tiled, const uint32_t 
                        const uint32_t *d_crit, const uint32_t *d_thr, int64_t G, int64_t T,
                        int64_t N, int64_t P, int64_t perm_base, uint32_t *d_r,
                        uint32_t *d_nstop, scoary_stream_t stream);
+
+/* ---- Westfall-Young single-step minP (ABI 11; spec S7 of DESIGN.md) -------------------
+ * No counterpart in the reference (its only corrections are Bonferroni and Benjamini-Hochberg,
+ * scoary/methods.py:903-925): for every permuted labelling the SMALLEST raw Fisher p over all genes,
+ *   d_minp[t][pi] = min(d_minp[t][pi], min over g of p_tg(popcount(gene_g & perm_{t,pi}))),
+ * p_tg(a) = what scoary_fisher returns, bit for bit, for the table (a, npos - a, gm - a,
+ * nval - npos - gm + a) with the margins of d_counts[t][g].  The family-wise adjusted p of gene g is
+ * (#{pi : minp[t][pi] <= p[t][g]} + 1) / (P + 1), counted by the caller from scoary_fisher's own p.
+ *   scoary_minp_plan : per (trait, gene) the support [lo, hi] = [max(0, npos + gm - nval), min(npos, gm)]
+ *       of the overlap count: d_lo int32 [T][G] = lo, d_off int64 [T * G + 1] = the exclusive prefix sum
+ *       of the support sizes hi - lo + 1 (CSR offsets; the total last), *entries_out (HOST) = that
+ *       total.  Synchronises `stream` (the caller needs the count to allocate d_tab), like
+ *       scoary_lists_plan.
+ *   scoary_minp_fill : d_tab double [entries]: d_tab[d_off[t G + g] + a - lo] = p_tg(a).  The entries
+ *       are produced by scoary_fisher's own kernel over the enumerated tables, a chunk at a time;
+ *       d_scratch = scoary_minp_fill_scratch_bytes(entries) bytes (the table list of one chunk).
+ *   scoary_permute_minp : d_perms = vecrows [T][P][Wp] as scoary_perm_generate writes them (the
+ *       permutations perm_base .. perm_base + P - 1 of these T traits); d_minp = double
+ *       [T][minp_stride], the batch lands at columns perm_base .. perm_base + P - 1.  The CALLER
+ *       initialises d_minp to 1.0 (the identity of the minimum); the call accumulates by min (a 64-bit
+ *       atomic on the bit pattern of the non-negative double), so batches of permutations, gene
+ *       shards (each with the plan / tables of its own genes) and trait groups (pointers moved to
+ *       the group's first trait) compose.  Any N scoary_permute takes. */
+int64_t scoary_minp_fill_scratch_bytes(int64_t entries);
+int scoary_minp_plan(scoary_handle h, const int32_t *d_counts, int64_t T, int64_t G, int64_t *d_off,
+                     int32_t *d_lo, int64_t *entries_out, scoary_stream_t stream);
+int scoary_minp_fill(scoary_handle h, const int32_t *d_counts, const int64_t *d_off,
+                     const int32_t *d_lo, int64_t T, int64_t G, int64_t entries, void *d_scratch,
+                     double *d_tab, scoary_stream_t stream);
+int scoary_permute_minp(scoary_handle h, const uint32_t *d_tiled, const uint32_t *d_perms,
+                        const int64_t *d_off, const int32_t *d_lo, const double *d_tab, int64_t G,
+                        int64_t T, int64_t N, int64_t P, int64_t perm_base, int64_t minp_stride,
+                        double *d_minp, scoary_stream_t stream);
 
 /* ---- a7/a8, list-driven variant -------------------------------------------
  * Same result as scoary_perm_generate + scoary_permute (d_r is bit-identical),

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SCOARY_HIP_LIB") or os.path.join(_HERE, "csrc", "libscoary_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "scoary_hip.h")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _i64, _u64, _i32, _vp, _cp = (ctypes.c_int64, ctypes.c_uint64, ctypes.c_int,
                               ctypes.c_void_p, ctypes.c_char_p)
@@ -41,6 +41,10 @@ SIGNATURES = {
     "scoary_permute": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "scoary_permute_seq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp,
                                   _vp]),
+    "scoary_minp_fill_scratch_bytes": (_i64, [_i64]),
+    "scoary_minp_plan": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, ctypes.POINTER(_i64), _vp]),
+    "scoary_minp_fill": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "scoary_permute_minp": (_i32, [_vp] * 6 + [_i64] * 6 + [_vp, _vp]),
     "scoary_list_tiles_words": (_i64, [_i64, _i64, _i64]),
     "scoary_list_tile_words": (_i64, [_i64]),
     "scoary_list_params": (_i32, [_i64, _vp]),

@@ -234,6 +234,22 @@ def gather_genes(rec_local, G, dst=0, group=None, async_op=False, recv=None, par
     return work, finish
 
 
+def all_reduce_min(t, group=None):
+    """Element-wise minimum of ``t`` over the ranks, in place, on every rank: the one exchange of the
+    Westfall-Young minima (spec S7) -- each rank's [T, P] minima over its own genes.  No-op for a single
+    process; gloo moves host memory, so device tensors are staged through the host for it."""
+    if not is_distributed():
+        return t
+    import torch.distributed as dist
+    if dist.get_backend(group) != "nccl" and t.device.type == "cuda":
+        host = t.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.MIN, group=group)
+        t.copy_(host)
+    else:
+        dist.all_reduce(t, op=dist.ReduceOp.MIN, group=group)
+    return t
+
+
 class LabelShards:
     """Permutation shards of the label tiles (engine.label_shards): every rank generates one
     contiguous share of a batch's flat (trait, tile) array and ONE all_gather_into_tensor over

@@ -36,6 +36,7 @@ class GeneMatrix:
         self.G = int(G)
         self.N = int(N)
         self.lists = None       # GeneLists, for the list-driven permutation kernel
+        self.minp_cache = None  # the p tables of the last minp(..., plan=...) on this matrix (engine.minp)
 
 
 class ListMemoryError(_abi.ScoaryHipError):
@@ -54,6 +55,15 @@ class GeneLists:
         self.idx, self.start, self.ngroups = idx, start, ngroups
         self.order, self.flipped, self.entries = order, flipped, entries
         self.panels, self.block_start, self.routes = None, None, {}
+
+
+class MinpTables:
+    """The p tables of a group of traits (scoary_minp_plan / _fill, spec S7): tab float64 [entries] holds
+    p_tg(a) for every overlap count a of the support of (trait, gene), CSR-style: off int64 [T * G + 1], lo
+    int32 [T, G] = the smallest a of the support; tab[off[t G + g] + a - lo[t, g]] = p_tg(a)."""
+
+    def __init__(self, off, lo, tab, entries):
+        self.off, self.lo, self.tab, self.entries = off, lo, tab, int(entries)
 
 
 class TraitPlan:
@@ -551,6 +561,114 @@ class AssociationEngine:
             done += nb
         return r, nstop
 
+    # -- Westfall-Young minP (spec S7) ------------------------------------------
+    def minp_tables(self, counts):
+        """The p tables of the traits of ``counts`` (int32 device tensor [T, G, 4], contiguous): every entry is
+        k_fisher's own double for the enumerated table.  One 8-byte read-back (the entry count)."""
+        torch = _torch()
+        counts = counts.contiguous()
+        T, G = int(counts.shape[0]), int(counts.shape[1])
+        off = self._empty((T * G + 1,), torch.int64)
+        lo = self._empty((T, G), torch.int32)
+        entries = ctypes.c_int64()
+        self._check(self.lib.scoary_minp_plan(self.h, self._ptr(counts), T, G, self._ptr(off), self._ptr(lo),
+                                              ctypes.byref(entries), self._stream()), "scoary_minp_plan")
+        total = int(entries.value)
+        tab = self._empty((total,), torch.float64)
+        scratch = self._empty((int(self.lib.scoary_minp_fill_scratch_bytes(total)) // 8,), torch.int64)
+        self._check(self.lib.scoary_minp_fill(self.h, self._ptr(counts), self._ptr(off), self._ptr(lo), T, G,
+                                              total, self._ptr(scratch), self._ptr(tab), self._stream()),
+                    "scoary_minp_fill")
+        return MinpTables(off, lo, tab, total)
+
+    def permute_minp(self, genes, perms, tables, minp, P=None, perm_base=0):
+        """minp[t, perm_base + i] = min(itself, min over the genes of p_tg(popcount(gene & perms[t, i]))) for the
+        label rows ``perms`` (int32 [T, P, Wp], perm_generate's layout).  ``minp``: float64 [T, >= perm_base + P],
+        rows contiguous, initialised to 1.0 by the caller."""
+        T = int(perms.shape[0])
+        if P is None:
+            P = int(perms.shape[1])
+        if minp.stride(1) != 1 or (T > 1 and minp.stride(0) != minp.shape[1]) or not perms.is_contiguous():
+            raise ValueError("permute_minp: minp rows and the label rows must be contiguous")
+        self._check(self.lib.scoary_permute_minp(
+            self.h, self._ptr(genes.tiled), self._ptr(perms), self._ptr(tables.off), self._ptr(tables.lo),
+            self._ptr(tables.tab), genes.G, T, genes.N, int(P), int(perm_base), int(minp.shape[1]),
+            self._ptr(minp), self._stream()), "scoary_permute_minp")
+        return minp
+
+    def minp_trait_groups(self, counts, table_budget_bytes):
+        """Consecutive traits whose p tables together stay under ``table_budget_bytes`` (a trait that is larger on
+        its own is a group of one): list of (first, end).  Reads T entry counts back."""
+        torch = _torch()
+        c = counts.to(torch.int64)
+        npos, gm, nval = c[..., 0] + c[..., 1], c[..., 0] + c[..., 2], c.sum(dim=-1)
+        size = torch.minimum(npos, gm) - torch.clamp(npos + gm - nval, min=0) + 1
+        per_trait = (size.sum(dim=1) * 8).cpu().tolist()
+        groups, first, used = [], 0, 0
+        for t, b in enumerate(per_trait):
+            if t > first and used + b > table_budget_bytes:
+                groups.append((first, t))
+                first, used = t, 0
+            used += b
+        groups.append((first, len(per_trait)))
+        return groups
+
+    def minp(self, genes, traits, masks, permutations, seed=0, res=None, out=None, perm_range=None,
+             table_budget_bytes=8 << 30, label_budget_bytes=8 << 30, plan=None):
+        """Westfall-Young minP (spec S7): float64 device tensor [T, permutations], minp[t, pi] = the smallest raw
+        Fisher p over the genes of ``genes`` under the S4 labels of (seed, t, pi).  ``res``: an associate() result of
+        the same genes and traits (its counts and margins are used; without one they are counted here).
+        ``out``: a [T, permutations] tensor to min into (1.0 where nothing has been accumulated yet) -- gene shards and permutation ranges (``perm_range`` = (first, end)) compose by
+        min.  The tables of a trait group stay under ``table_budget_bytes`` and the label rows of a batch under
+        ``label_budget_bytes``; the result depends on neither.  ``plan``: the TraitPlan of these traits; with
+        one, and when all traits fit one group, the tables stay attached to ``genes`` (genes.minp_cache, as the
+        index lists do) and later calls with the same plan reuse them: the tables depend on the gene matrix and
+        the traits alone, and building them is most of a step (cfg3: 119 of 150 ms)."""
+        torch = _torch()
+        if plan is not None and not plan.fits(traits, masks):
+            raise ValueError("the trait plan was built from other trait / mask tensors")
+        if res is not None:
+            counts, margins = res["counts"], res["margins"]
+        else:
+            counts, margins = self.counts(genes, traits, masks, plan=plan)
+        T, N, P = int(counts.shape[0]), genes.N, int(permutations)
+        if out is None:
+            out = torch.ones((T, P), dtype=torch.float64, device=self.device)
+        p0, p1 = (0, P) if perm_range is None else (int(perm_range[0]), int(perm_range[1]))
+        if p1 <= p0:
+            return out
+        Wp = self.row_words(N)
+        buf = None
+        cached = genes.minp_cache if plan is not None else None
+        if cached is not None and (cached["plan"] is not plan or cached["budget"] != table_budget_bytes):
+            cached = genes.minp_cache = None
+        groups = cached["groups"] if cached else self.minp_trait_groups(counts, table_budget_bytes)
+        for t0, t1 in groups:
+            Tg = t1 - t0
+            tables = cached["tables"] if cached else self.minp_tables(counts[t0:t1])
+            if plan is not None and cached is None and len(groups) == 1:
+                genes.minp_cache = {"plan": plan, "budget": table_budget_bytes, "groups": groups, "tables": tables}
+            batch = self.perm_batch(Tg, N, p1 - p0, budget_bytes=label_budget_bytes)
+            if buf is None or buf.numel() < Tg * batch * Wp:
+                buf = self._empty((Tg * batch * Wp,), torch.int32)
+            done = p0
+            while done < p1:
+                nb = min(batch, p1 - done)
+                perms = buf[:Tg * nb * Wp].view(Tg, nb, Wp)
+                self.perm_generate(masks[t0:t1], margins[t0:t1], N, nb, done, seed, out=perms, trait_base=t0)
+                self.permute_minp(genes, perms, tables, out[t0:t1], P=nb, perm_base=done)
+                done += nb
+            del tables
+        return out
+
+    @staticmethod
+    def r_fwer(minp, p):
+        """r_fwer[t, g] = #{pi : minp[t, pi] <= p[t, g]} (int32 [T, G]): a sort of every trait's minima and a
+        search for every gene's p.  ``p`` must be the association step's own bits (before fisher_scipy)."""
+        torch = _torch()
+        srt = torch.sort(minp, dim=1).values.contiguous()
+        return torch.searchsorted(srt, p.contiguous(), right=True).to(torch.int32)
+
     def perm_batch(self, T, N, P, budget_bytes=8 << 30):
         """Permutations per generate/permute round so the label buffer stays
         under budget_bytes."""
@@ -637,7 +755,8 @@ class AssociationEngine:
         sh.all_gather(ws.tiles, nflat, tile_words)
 
     def associate(self, genes, traits, masks, permutations=0, seed=0, perm_buffer=None,
-                  use_lists=None, workspace=None, plan=None, graph=None, records=None):
+                  use_lists=None, workspace=None, plan=None, graph=None, records=None, fwer=False,
+                  table_budget_bytes=8 << 30):
         """counts -> Fisher -> (optional) permutation exceedance counts.
         Returns dict of device tensors: counts [T,G,4], margins [T,2],
         p / odds [T,G], r [T,G] (uint32 bit pattern in int32) or None.  With
@@ -647,9 +766,20 @@ class AssociationEngine:
         workspace AND a plan, a launch-bound step (auto_graph_eligible) is recorded into a
         hipGraph on its second call and replayed afterwards; ``graph=False`` keeps it eager.
         ``records``: an int32 [T, G, 10] device tensor -- the result is also packed into it
-        (pack_records) and returned as res["records"]."""
+        (pack_records) and returned as res["records"].  ``fwer=True`` (needs permutations): also the
+        Westfall-Young minima res["minp"] float64 [T, P] (minp()) and res["r_fwer"] int32 [T, G] = the number of
+        permutations whose minimum is <= the gene's own p; the p tables of a trait group stay under
+        ``table_budget_bytes`` and, with a ``plan``, are built once per (gene matrix, plan) and reused (minp()).
+        Such a step is never replayed from a graph (it reads sizes back)."""
+        if fwer and permutations <= 0:
+            raise ValueError("fwer=True needs permutations > 0")
         res = self._associate(genes, traits, masks, permutations, seed, perm_buffer, use_lists,
-                              workspace, plan, graph if records is None else False)
+                              workspace, plan, graph if records is None and not fwer else False)
+        if fwer:
+            res = dict(res)
+            res["minp"] = self.minp(genes, traits, masks, permutations, seed, res=res,
+                                    table_budget_bytes=table_budget_bytes, plan=plan)
+            res["r_fwer"] = self.r_fwer(res["minp"], res["p"])
         if records is not None:
             # the exchange records of the step, packed as its last kernel (inside a captured step:
             # one launch less per replay for a gene-sharded rank)

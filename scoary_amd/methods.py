@@ -769,14 +769,18 @@ def _pattern_groups(table, maskrow, idx, hashes):
     return inv.reshape(-1)
 
 
-def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False):
+def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, fwer=False):
     """Whole hot path for all traits; under torchrun (world > 1) every rank
     takes a stride gene shard (dist.GenePartition: the reference's domains,
     scoary/methods.py:1076-1078) and the per-gene records are all-gathered
     over RCCL and woven back into file order, so every rank returns the full arrays.
     ``early_abort``: the reference's sequential estimator (scoary/methods.py:1360-1363)
     on the Fisher statistic instead of the fixed-P count: out["nstop"] then holds the
-    permutation count every gene stopped at (0 = ran to the end)."""
+    permutation count every gene stopped at (0 = ran to the end).
+    ``fwer``: also the Westfall-Young minima (spec S7): out["minp"] [T, P] and out["r_fwer"] [T, G] = the
+    number of permutations whose smallest p over ALL genes is <= the gene's own p.  Under gene sharding
+    every rank takes the minima over its own genes, one all_reduce(MIN) of the [T, P] doubles follows, and
+    r_fwer travels in the record's nstop word (the feature excludes early abort)."""
     import torch
     from . import dist
     eng = get_engine()
@@ -807,6 +811,9 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         a = sel.start
         whole = sel == slice(0, G, 1)
         if len(range(*sel.indices(G))) == 0:
+            if fwer:            # a rank without genes still takes part in the reduction of the minima
+                minp_all.append(dist.all_reduce_min(torch.ones((T, permutations), dtype=torch.float64,
+                                                               device=eng.device)))
             return torch.zeros((T, 0, dist.REC_WORDS), dtype=torch.int32, device=eng.device)
         with _stage("device setup (H2D, tiling, trait plan)"):
             gm = table.on_device(eng) if whole else eng.tile_rows(table.rows64[sel], N)
@@ -841,12 +848,21 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         with _stage("kernels (counts, Fisher, permutations)"):
             res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan)
             torch.cuda.synchronize(eng.device)
+        r_fwer = None
+        if fwer:
+            with _stage("Westfall-Young minP (p tables, k_permute_minp)"):
+                minp = dist.all_reduce_min(eng.minp(gm, trv, mkv, permutations, seed, res=res))
+                # counted on k_fisher's own bits, before the SciPy-digits pass rewrites the last ulp of p
+                r_fwer = eng.r_fwer(minp, res["p"])
+                minp_all.append(minp)
+                torch.cuda.synchronize(eng.device)
         scipy_digits(res)
         with _stage("kernels (counts, Fisher, permutations)"):
-            rec = eng.pack_records(res)
+            rec = eng.pack_records(res, nstop=r_fwer)
             torch.cuda.synchronize(eng.device)
         return rec
 
+    minp_all = []
     rec = dist.associate_sharded(local, G)
     with _stage("results D2H"):
         # the stable p order for BH: numpy does 200 000 doubles in 25-40 ms, which beats the
@@ -858,6 +874,9 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         out["p_order"] = p_order
     if permutations <= 0:
         out["r"] = None
+    if fwer:
+        out["r_fwer"], out["nstop"] = out["nstop"], np.zeros_like(out["nstop"])
+        out["minp"] = minp_all[0].cpu().numpy()
     return out
 
 
@@ -915,14 +934,17 @@ def _usable_cpus():
 
 
 def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEED,
-                  early_abort=False):
+                  early_abort=False, fwer=False):
     """Counts, Fisher's exact test and B/BH correction for every trait x gene
     (methods.py:757-928).  ``permutations`` >= 10 additionally attaches the
     Fisher-statistic ``Empirical_p`` (= (r+1)/(P+1), methods.py:1365) to every
-    row -- the north_star's replacement for the tree-statistic Permute loop."""
+    row -- the north_star's replacement for the tree-statistic Permute loop.  ``fwer`` (with
+    permutations): also ``Westfall_Young_p`` = (r_fwer+1)/(P+1), the single-step minP adjusted p."""
+    if fwer and (permutations < 10 or early_abort):
+        raise ValueError("fwer needs permutations >= 10 and excludes early_abort")
     table = _as_table(genedic)
     names, tarr = _trait_arrays(traitsdic, table.strains)
-    dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort)
+    dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, fwer)
     collapse_hashes = None
     if collapse:
         eng = get_engine()
@@ -949,6 +971,9 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
             # permutations gets (r+1)/(n+1) = the reference's (r+1.0)/(i+2.0), :1362
             n_used = np.where(dev["nstop"][t] > 0, dev["nstop"][t], permutations).astype(np.float64)
             emp = (dev["r"][t].astype(np.float64) + 1.0) / (n_used + 1.0)
+        wy = None
+        if fwer:
+            wy = (dev["r_fwer"][t].astype(np.float64) + 1.0) / (permutations + 1.0)
 
         if not collapse:
             # names stay in the GeneTable: the result rows are (table, idx) -- nothing per
@@ -1009,6 +1034,8 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
                 "B_p": B, "BH_p": BH}
         if emp is not None:
             cols["Empirical_p"] = emp[rows_idx]
+        if wy is not None:
+            cols["Westfall_Young_p"] = wy[rows_idx]
         if collapse:
             tr = TraitResults(names_out, nugn, ann, cols, number_of_tests, members)
         else:
@@ -1352,10 +1379,13 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
     with_emp = permutations >= 10
     if with_emp:
         columns.append("Empirical_p")
-    columns += list(extracolstoprint)
-    table = _as_table(genedic) if extracolstoprint else None
     if not isinstance(Trait, TraitResults):
         Trait = _trait_results_from_dict(Trait)
+    with_wy = no_pairwise and with_emp and "Westfall_Young_p" in Trait.cols      # --permute-fwer
+    if with_wy:
+        columns.append("Westfall_Young_p")
+    columns += list(extracolstoprint)
+    table = _as_table(genedic) if extracolstoprint else None
 
     n = len(Trait)
     # (-m 0 or a negative -m: no rows, as the reference's xrange(num_results), :1024 / :1143)
@@ -1381,6 +1411,9 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
         if with_emp:
             colget["Empirical_p"] = np.asarray(Trait.column("Empirical_p"))
             fields.append("Empirical_p")
+        if with_wy:
+            colget["Westfall_Young_p"] = np.asarray(Trait.column("Westfall_Young_p"))
+            fields.append("Westfall_Young_p")
         keyed = {CUT_FIELD[m]: colget[CUT_FIELD[m]] for m in cutoffs}
         sel = cand[np.all([keyed[CUT_FIELD[m]][cand] <= c for m, c in cutoffs.items()], axis=0)] \
             if cutoffs else cand
@@ -1440,7 +1473,7 @@ def _trait_results_from_dict(rows):
     """Plain {gene: row dict} (the reference's Results[trait]) -> TraitResults."""
     genes = list(rows.keys())
     cols = {}
-    for k in TraitResults.FIELDS + ("Empirical_p",):
+    for k in TraitResults.FIELDS + ("Empirical_p", "Westfall_Young_p"):
         if genes and k in rows[genes[0]]:
             cols[k] = np.array([rows[g][k] for g in genes])
     return TraitResults(genes, [rows[g]["NUGN"] for g in genes],
@@ -1545,6 +1578,10 @@ def ScoaryArgumentParser(argv=None):
                    "with early abort for the Fisher-statistic permutations -- a gene stops after "
                    "i >= 30 permutations once 1 - binom.cdf(r, i, 0.1) < 0.05 and gets "
                    "(r+1)/(i+2) (large empirical p-values become coarse, like the reference's)")
+    a.add_argument("--permute-fwer", dest="permute_fwer", action="store_true", default=False,
+                   help="With --no_pairwise --permute: add the column Westfall_Young_p, the single-step "
+                   "minP family-wise adjusted p -- (1 + number of permutations whose smallest Fisher p "
+                   "over all genes is <= the gene's own p) / (permutations + 1) (scoary_amd extension)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1702,7 +1739,8 @@ def main(**kwargs):
         # in the pairwise stage like the reference does.
         res = Setup_results(genedic, traitsdic, args.collapse,
                             permutations=args.permute if args.no_pairwise else 0, seed=seed,
-                            early_abort=getattr(args, "permute_early_abort", False))
+                            early_abort=getattr(args, "permute_early_abort", False),
+                            fwer=getattr(args, "permute_fwer", False))
         t_stats = _time.time()
         if args.upgma_tree and rank == 0:
             # (with --no_pairwise there is no tree and the reference writes str(None) + ";", :277-280, :741-751)
@@ -1779,6 +1817,16 @@ def _validate(args, cutoffs):
                  "exactly as many as the number of correction methods and in corresponding "
                  "sequence. e.g. -c I EPW -p 0.1 0.05 will apply an individual p-value cutoff "
                  "of 0.1 AND a pairwise comparisons p-value cutoff of 0.05.")
+    if getattr(args, "permute_fwer", False):
+        if not args.no_pairwise:
+            sys.exit("Cannot use --permute-fwer without --no_pairwise. The Westfall-Young minima are taken "
+                     "over the Fisher statistic of every gene")
+        if args.permute < 10:
+            sys.exit("Cannot use --permute-fwer without performing permutations. Use '--permute X' where X "
+                     "is a number equal to or larger than 10")
+        if getattr(args, "permute_early_abort", False):
+            sys.exit("Cannot use --permute-fwer together with --permute-early-abort. Every gene has to see "
+                     "every permutation")
     if "P" in cutoffs and args.permute == 0:
         sys.exit("Cannot use empirical p-values in filtration without performing "
                  "permutations. Use '--permute X' where X is a number equal to or larger than 10")

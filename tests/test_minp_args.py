@@ -1,0 +1,64 @@
+"""--permute-fwer: the argument checks (host only -- they exit before the engine is touched) and the
+declarations of the ABI 11 entry points."""
+import os
+import re
+import sys
+
+import pytest
+
+
+def _run(argv, exampledir, tmp_path, monkeypatch):
+    from scoary_amd import methods as m
+
+    def no_engine():
+        raise AssertionError("the engine was started before the arguments were refused")
+    monkeypatch.setattr(m, "get_engine", no_engine)
+    monkeypatch.setenv("SCOARY_OVERLAP_STARTUP", "0")
+    monkeypatch.setattr(sys, "argv", ["scoary", "-g", os.path.join(exampledir, "Gene_presence_absence.csv"),
+                                      "-t", os.path.join(exampledir, "Tetracycline_resistance.csv"),
+                                      "-o", str(tmp_path), "--no-time"] + argv)
+    with pytest.raises(SystemExit) as e:
+        m.main()
+    return e.value.code
+
+
+@pytest.mark.parametrize("argv,message", [
+    (["--permute-fwer", "-e", "100"], "Cannot use --permute-fwer without --no_pairwise"),
+    (["--permute-fwer", "--no_pairwise"], "Cannot use --permute-fwer without performing permutations"),
+    (["--permute-fwer", "--no_pairwise", "-e", "5"], "Cannot use --permute-fwer without performing permutations"),
+    (["--permute-fwer", "--no_pairwise", "-e", "100", "--permute-early-abort"],
+     "Cannot use --permute-fwer together with --permute-early-abort"),
+])
+def test_permute_fwer_refusals(exampledir, tmp_path, monkeypatch, argv, message):
+    code = _run(argv, exampledir, tmp_path, monkeypatch)
+    assert isinstance(code, str) and code.startswith(message), code
+    assert not [f for f in os.listdir(tmp_path) if f.endswith(".results.csv")]
+
+
+def test_flag_is_off_by_default():
+    from scoary_amd import methods as m
+    args, _cut = m.ScoaryArgumentParser(["-g", "g.csv", "-t", "t.csv"])
+    assert args.permute_fwer is False
+    args, _cut = m.ScoaryArgumentParser(["-g", "g.csv", "-t", "t.csv", "--permute-fwer"])
+    assert args.permute_fwer is True
+
+
+def test_setup_results_refuses_fwer_without_permutations():
+    from scoary_amd import methods as m
+    with pytest.raises(ValueError):
+        m.Setup_results({}, {}, False, permutations=0, fwer=True)
+    with pytest.raises(ValueError):
+        m.Setup_results({}, {}, False, permutations=100, early_abort=True, fwer=True)
+
+
+def test_minp_entry_points_are_declared():
+    from scoary_amd import _abi
+    assert _abi.ABI_VERSION == 11
+    header = open(_abi.HEADER_PATH).read()
+    assert re.search(r"#define SCOARY_ABI_VERSION 11\b", header)
+    for name in ("scoary_minp_fill_scratch_bytes", "scoary_minp_plan", "scoary_minp_fill", "scoary_permute_minp"):
+        assert name in _abi.SIGNATURES
+        m = re.search(r"\b%s\(([^;]*)\);" % name, header)
+        assert m, name
+        nargs = len([a for a in m.group(1).split(",") if a.strip()])
+        assert nargs == len(_abi.SIGNATURES[name][1]), name

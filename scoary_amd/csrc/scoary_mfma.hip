@@ -11,19 +11,20 @@
 //                                       A fragments of v_mfma_scale_f32_32x32x64_f8f6f4, 1 KB per slot
 //   k_mfma_bfrag   (per label batch)    the label tiles of k_labels as E2M1 B fragments, 64 KB per
 //                                       (trait, 64 permutations): the SAME draws the list kernel reads
-//   k_permute_mfma                      gene operand stationary in registers (256 per lane), B streamed
-//                                       through a four-slot LDS ring by LDS-DMA, region test on the
-//                                       accumulators, 16-bit counts into the list path's `partial`
+//   k_permute_mfma                      gene operand stationary in registers (128 per lane), two wavefronts
+//                                       per SIMD half a stage apart, B streamed through a four-slot LDS
+//                                       ring by LDS-DMA, region test on the accumulators, 16-bit counts
+//                                       into the list path's `partial`
 #include "scoary_common.hpp"
 
 // The two measured rates the routing is decided by (scoary_mfma_route): a routed gene costs kMfmaNsPerGene
 // whatever its list holds, a listed gene kListNsPerEntry per padded list entry -- break-even list length
 // = their ratio (scoary_mfma_breakeven_entries).  Both per 100 000 tests of the gene (cfg3: 10 traits x
 // 10 000 permutations), chip-wide, on MI355X: k_permute_mfma + k_mfma_bfrag with every cfg3 gene routed,
-// the parent's k_permute_lists with none (profiles/r09_mfma_hybrid.txt).
-const double kMfmaNsPerGene = 80.0;
+// k_permute_lists with none (profiles/r11_mfma_two_wave.txt).
+const double kMfmaNsPerGene = 62.0;
 const double kListNsPerEntry = 0.177;
-const double kMfmaPanelLoadStages = 6.0;   // a block's A panel (256 KB from HBM), in stages of its loop
+const double kMfmaPanelLoadStages = 10.0;  // a block's start (A panel: 256 KB from HBM) and end, in stages of its loop
 
 namespace {
 
@@ -32,13 +33,18 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 
 constexpr int kKSteps = 32;                       // K-steps of 64 isolates: N <= 2048
-constexpr int kBlockGenes = 256;                  // four wavefronts x 64 list slots
+constexpr int kBlockGenes = 256;                  // list slots of a block: eight wavefronts x 32
+constexpr int kBlockWaves = 8;                    // two per SIMD
 constexpr int kFragBytes = 1024;                  // one operand fragment: 64 lanes x 16 bytes (32 E2M1 values)
 constexpr int kStageBytes = 2 * kKSteps * kFragBytes;   // B of (trait, 64 permutations): [K-step][column tile][lane]
 constexpr int kHalfBytes = kStageBytes / 2;       // the unit of the LDS ring: 16 K-steps
-constexpr int kRingBytes = 4 * kHalfBytes;        // 128 KB
-constexpr int kDmaPerHalf = kHalfBytes / 4 / kFragBytes;   // LDS-DMA instructions per wavefront and half stage
-constexpr int kMfmaLds = kRingBytes + kBlockGenes * 8;     // + (-centre, half width) of the block's 256 slots
+constexpr int kRingSlots = 4;                     // 128 KB
+constexpr int kAhead = kRingSlots - 2;            // a half stage is issued this many ticks before its first read
+constexpr int kRingBytes = kRingSlots * kHalfBytes;
+constexpr int kDmaPerHalf = kHalfBytes / kBlockWaves / kFragBytes;   // LDS-DMA instructions per wavefront and half stage
+constexpr int kMfmaLds = kRingBytes;
+static_assert(kRingSlots >= 4 && kMfmaLds <= 160 * 1024 && (kAhead - 1) * kDmaPerHalf < 64,
+              "a half stage is issued at least two ticks ahead, within the LDS of a CU and the vmcnt field");
 
 // 8 presence bits -> 8 E2M1 nibbles (bit i -> nibble i = 0b0010 = 1.0): pairs of bits select a byte
 // of the pool {0x00, 0x02, 0x20, 0x22} through v_perm_b32
@@ -126,16 +132,37 @@ __device__ __forceinline__ int xcd_item(int orig, int n) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (orig >> 3);
 }
 
-// Block = 256 list slots (four wavefronts x 64, one wavefront per SIMD) x one trait x `per` stages of 64
-// permutations.  A: 2 row tiles x 32 K-steps x 4 registers per lane, loaded once.  B: half stages of 32 KB
-// move HBM/L2 -> LDS by LDS-DMA three ahead of their use through a four-slot ring; the wait that retires
-// half n is the counted vmcnt(2 halves) in front of the barrier that precedes its first ds_read, and slot
-// (n + 3) % 4 is refilled behind that same barrier -- every wavefront has consumed half n - 1 by then.
-// There is no ordinary global load inside the loop (the compiler would wait vmcnt(0) for it and drain the ring).
-// The accumulators start at minus the centre of the acceptance interval [lo, hi1) of the list count, so
-// "u outside the interval" is one compare, |acc| > half width; the two column tiles of a row share one
-// per-lane counter that lives across the stages, the 32 lanes of a row meet once, at the end.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+// Block = 256 list slots x one trait x `per` stages of 64 permutations; eight wavefronts, two per SIMD.
+// Wavefront w owns 32 slots, row tile w & 1 of wave panel w >> 1: its A fragments of all 32 K-steps stay in
+// 128 registers, next to two column tiles of accumulators, minus the interval centre and the half width of
+// its 16 rows and 16 counters (no LDS beside the ring, at most 256 registers: two wavefronts per SIMD).
+// The accumulators start at minus the centre of the acceptance interval [lo, hi1) of the list count -- the C
+// operand of a stage's first K-step -- so "u outside the interval" is one compare, |acc| > half width; the two
+// column tiles of a row share one per-lane counter that lives across the stages, the 32 lanes of a row meet
+// once, at the end.
+//
+// Stagger.  Wavefronts 4..7, the SIMD partners of 0..3, run half a stage behind them: in tick n (one barrier
+// per tick, nh + 1 ticks for nh half stages) the early wavefronts read half n, the late ones half n - 1, so
+// one partner's region test, LDS-DMA issue and first fragment reads fall beside the other's MFMAs.  The region
+// test of a stage waits for the barrier that follows the stage (the partner is in mid-stage behind it, and
+// would only wait at that barrier for a test in front of it); the range's last one follows the loop.
+// Measured and not built in, each within the kernel's run-to-run spread (profiles/r11_mfma_two_wave.txt):
+// s_setprio 1 for the late wavefronts; a fifth ring slot (issue three ticks ahead, 160 KB); with it, reading
+// the next half's first fragments in front of the barrier.
+//
+// Ring.  B moves HBM/L2 -> LDS by LDS-DMA in half stages of 32 KB (16 K-steps), half n into slot
+// n % kRingSlots, every wavefront 4 KB of it.  Invariant, for every tick n:
+//   * before the barrier of tick n a wavefront has issued halves 0 .. n + kAhead - 1 and waits with the
+//     counted vmcnt(kAhead - 1 halves) until its pieces of half n have landed; behind the barrier half n is
+//     whole (and half n - 1 has been since the barrier before);
+//   * behind that barrier it issues half n + kAhead into slot (n + kAhead) % kRingSlots = (n - 2) % kRingSlots:
+//     half n - 2 was last read in tick n - 1, by the late wavefronts, and every wavefront has passed a barrier
+//     since; the slots of the halves n - 1 and n, which are being read, are other slots (kRingSlots >= 3).
+// Halves past the end re-read the last one into such a slot, which nobody reads any more, so the counts stay
+// the same to the end; ns = 1 and the late wavefronts' last half (tick nh, no early work beside it) need no
+// case of their own.  There is no ordinary global load inside the loop (the compiler would wait vmcnt(0) for
+// it and drain the ring).
+__global__ __launch_bounds__(kBlockWaves * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_permute_mfma(const v4i* __restrict__ panels, const unsigned char* __restrict__ bfrag,
                     const uint2* __restrict__ lcrit, int G, int64_t P, int S, int per, int rp, int nblk_genes,
                     int ntiles, int64_t gs, uint16_t* __restrict__ partial) {
@@ -146,146 +173,137 @@ void k_permute_mfma(const v4i* __restrict__ panels, const unsigned char* __restr
   const int s0 = jr * per, ns = min(per, S - s0);
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float2* thr = reinterpret_cast<float2*>(lds + kRingBytes);
-  {
-    const int64_t slot = (int64_t)gb * kBlockGenes + tid;
-    float2 c = make_float2(0.f, 1e30f);            // slots >= G: never counted
-    if (slot < G) {
-      const uint2 cr = lcrit[(int64_t)t * G + slot];
-      c = make_float2(-0.5f * (float)((int)cr.x + (int)cr.y - 1), 0.5f * (float)((int)cr.y - 1 - (int)cr.x));
-    }
-    thr[tid] = c;
+  const bool late = wave >= kBlockWaves / 2;
+  // accumulator register r of a lane is row (r & 3) + 8 (r >> 2) + 4 half of the wavefront's 32 slots
+  const int64_t row0 = (int64_t)gb * kBlockGenes + wave * 32 + 4 * half;
+  v16f negc;
+  float hw[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t slot = row0 + (r & 3) + 8 * (r >> 2);
+    const uint2 cr = lcrit[(int64_t)t * G + min(slot, (int64_t)G - 1)];
+    negc[r] = -0.5f * (float)((int)cr.x + (int)cr.y - 1);
+    hw[r] = slot < G ? 0.5f * (float)((int)cr.y - 1 - (int)cr.x) : 1e30f;   // slots >= G: never counted
   }
-  v4i a[2][kKSteps];
+  v4i a[kKSteps];
   {
-    const v4i* ap = panels + ((int64_t)gb * 4 + wave) * (2 * kKSteps * 64) + lane;
+    const v4i* ap = panels + ((int64_t)gb * kBlockWaves + wave) * (kKSteps * 64) + lane;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int k = 0; k < kKSteps; ++k) a[k] = ap[k * 64];
+    // every global load retired here, before the first LDS-DMA is issued: no compiler-placed wait in the loop
 #pragma unroll
-      for (int k = 0; k < kKSteps; ++k) a[i][k] = ap[(i * kKSteps + k) * 64];
-    // every A load retired here, before the first LDS-DMA is issued: no compiler-placed wait in the loop
+    for (int k = 0; k < kKSteps; ++k) asm volatile("" : "+v"(a[k]));
+    asm volatile("" : "+v"(negc));
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int k = 0; k < kKSteps; ++k) asm volatile("" : "+v"(a[i][k]));
+    for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(hw[r]));
   }
-  __syncthreads();
 
   const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)lds;
   const uint32_t lane_off = (uint32_t)lane * 16u;
-  const unsigned char* bsrc = bfrag + ((int64_t)t * S + s0) * kStageBytes + wave * (kHalfBytes / 4);
+  const unsigned char* bsrc = bfrag + ((int64_t)t * S + s0) * kStageBytes + wave * (kHalfBytes / kBlockWaves);
   const int nh = 2 * ns;
-  // half n of the block's range -> ring slot n % 4; halves past the end re-read the last one into a slot
-  // nobody reads any more, so the vmcnt counts stay the same to the end
   auto issue_half = [&](int n) {
     const unsigned char* src = bsrc + (int64_t)min(n, nh - 1) * kHalfBytes;
-    const uint32_t dst = lds0 + (uint32_t)(n & 3) * kHalfBytes + (uint32_t)wave * (kHalfBytes / 4);
+    const uint32_t dst = lds0 + (uint32_t)(n % kRingSlots) * kHalfBytes + (uint32_t)wave * (kHalfBytes / kBlockWaves);
 #pragma unroll
     for (int p = 0; p < kDmaPerHalf; ++p) mfma_dma16(dst + p * kFragBytes, lane_off, src + p * kFragBytes);
   };
-  issue_half(0);
-  issue_half(1);
-  issue_half(2);
+#pragma unroll
+  for (int n = 0; n < kAhead; ++n) issue_half(n);
+  int tick = 0;
+  auto next_tick = [&]() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kAhead - 1) * kDmaPerHalf) : "memory");
+    __builtin_amdgcn_s_barrier();
+    issue_half(tick + kAhead);
+    ++tick;
+  };
 
-  uint32_t ex[2][16];
+  uint32_t ex[16];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ex[i][r] = 0u;
-  const float2* my_thr = thr + wave * 64 + 4 * half;     // row of (i, r): 32 i + (r & 3) + 8 (r >> 2) + 4 half
+  for (int r = 0; r < 16; ++r) ex[r] = 0u;
   const int64_t last_valid = P - (int64_t)s0 * 64;        // permutations of this range that exist
 
+  v16f acc[2];
+  auto region_test = [&](int64_t nvalid) {
+    if (nvalid >= 64) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        ex[r] += (uint32_t)(__builtin_fabsf(acc[0][r]) > hw[r]) + (uint32_t)(__builtin_fabsf(acc[1][r]) > hw[r]);
+    } else {                                        // ragged last stage: columns >= P do not count
+      const bool v0 = l31 < nvalid, v1 = l31 + 32 < nvalid;
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        ex[r] += (uint32_t)(v0 && __builtin_fabsf(acc[0][r]) > hw[r]) +
+                 (uint32_t)(v1 && __builtin_fabsf(acc[1][r]) > hw[r]);
+    }
+  };
+  if (late) next_tick();                            // tick 0: the early wavefronts' first half
+  int rslot = 0;                                    // ring slot of the half this wavefront reads next
   for (int st = 0; st < ns; ++st) {
-    v16f acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float c = my_thr[i * 32 + (r & 3) + 8 * (r >> 2)].x;
-        acc[i][0][r] = c;
-        acc[i][1][r] = c;
-      }
-    const unsigned char* bbuf = lds + (st & 1) * kStageBytes + lane * 16;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      static_assert(kDmaPerHalf == 8, "vmcnt(16) below = two half stages of 8 LDS-DMA instructions in flight");
-      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      issue_half(2 * st + h + 3);
-      // B fragments are read two K-steps (eight MFMAs) ahead of their use through a three-deep register
-      // ring: with one wavefront per SIMD nothing else hides the ds_read latency.  The scheduling barriers
-      // keep the reads where they are written (left alone, the compiler reads each fragment right before its MFMAs).
+      next_tick();
+      const unsigned char* bbuf = lds + rslot * kHalfBytes + lane * 16;
+      rslot = rslot == kRingSlots - 1 ? 0 : rslot + 1;
+      // B fragments are read two K-steps (four MFMAs) ahead of their use through a three-deep register ring.
+      // The scheduling barriers keep the reads where they are written (left alone, the compiler reads each
+      // fragment right before its MFMAs).
       v4i bq[3][2];
       auto read_b = [&](int kk) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          bq[kk % 3][j] = *reinterpret_cast<const v4i*>(bbuf + ((h * (kKSteps / 2) + kk) * 2 + j) * kFragBytes);
+          bq[kk % 3][j] = *reinterpret_cast<const v4i*>(bbuf + (kk * 2 + j) * kFragBytes);
       };
       read_b(0);
       read_b(1);
+      if (h == 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (st > 0) region_test(64);                // stage st - 1, never the range's last: all 64 columns exist
+        __builtin_amdgcn_sched_barrier(0);
+      }
 #pragma unroll
       for (int kk = 0; kk < kKSteps / 2; ++kk) {
         const int k = h * (kKSteps / 2) + kk;
         if (kk + 2 < kKSteps / 2) read_b(kk + 2);
         __builtin_amdgcn_sched_barrier(0);
+        const v8i aa = v8i{a[k].x, a[k].y, a[k].z, a[k].w, 0, 0, 0, 0};
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const v8i aa = v8i{a[i][k].x, a[i][k].y, a[i][k].z, a[i][k].w, 0, 0, 0, 0};
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const v4i x = bq[kk % 3][j];
-            acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aa, v8i{x.x, x.y, x.z, x.w, 0, 0, 0, 0},
-                                                                        acc[i][j], 4, 4, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-          }
+        for (int j = 0; j < 2; ++j) {
+          const v4i x = bq[kk % 3][j];
+          // the stage's first K-step takes minus the centre as C: no accumulator set-up
+          acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aa, v8i{x.x, x.y, x.z, x.w, 0, 0, 0, 0},
+                                                                   k == 0 ? negc : acc[j], 4, 4, 0, 0x7f7f7f7f, 0,
+                                                                   0x7f7f7f7f);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    const int64_t nvalid = last_valid - (int64_t)st * 64;
-    if (nvalid >= 64) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float hw = my_thr[i * 32 + (r & 3) + 8 * (r >> 2)].y;
-          ex[i][r] += (uint32_t)(__builtin_fabsf(acc[i][0][r]) > hw) + (uint32_t)(__builtin_fabsf(acc[i][1][r]) > hw);
-        }
-    } else {                                        // ragged last stage: columns >= P do not count
-      const bool v0 = l31 < nvalid, v1 = l31 + 32 < nvalid;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float hw = my_thr[i * 32 + (r & 3) + 8 * (r >> 2)].y;
-          ex[i][r] += (uint32_t)(v0 && __builtin_fabsf(acc[i][0][r]) > hw) +
-                      (uint32_t)(v1 && __builtin_fabsf(acc[i][1][r]) > hw);
-        }
-    }
   }
+  if (!late) next_tick();                           // tick nh: the late wavefronts' last half
+  region_test(last_valid - (int64_t)(ns - 1) * 64);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last (redundant) transfers land before the LDS is given up
 
   // partial[t][tile][slot]: the range's count goes to tile jr, zeros to the tiles jr + rp, jr + 2 rp, ...
   // (k_lists_reduce sums every tile of every slot)
-  uint16_t* out = partial + ((int64_t)t * ntiles + jr) * gs + (int64_t)gb * kBlockGenes + wave * 64 + 4 * half;
+  uint16_t* out = partial + ((int64_t)t * ntiles + jr) * gs + row0;
+  const int nrows = (int)min((int64_t)32, (int64_t)G - ((int64_t)gb * kBlockGenes + wave * 32));   // of the wavefront's slots, < G
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int r = 0; r < 16; ++r) {
+    uint32_t v = ex[r];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      uint32_t v = ex[i][r];
-#pragma unroll
-      for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
-      const int row = i * 32 + (r & 3) + 8 * (r >> 2);
-      if (l31 == 0 && (int64_t)gb * kBlockGenes + wave * 64 + 4 * half + row < G) {
-        out[row] = (uint16_t)v;
-        for (int tile = jr + rp; tile < ntiles; tile += rp) out[(int64_t)(tile - jr) * gs + row] = 0;
-      }
+    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    const int row = (r & 3) + 8 * (r >> 2);
+    if (l31 == 0 && 4 * half + row < nrows) {
+      out[row] = (uint16_t)v;
+      for (int tile = jr + rp; tile < ntiles; tile += rp) out[(int64_t)(tile - jr) * gs + row] = 0;
     }
+  }
 }
 
 }  // namespace
 
 // Stages of 64 permutations per block (`per`) and ranges per trait (`rp`): the fewest rounds of blocks
-// over the CUs, a block long enough to pay for loading its A panel (~6 stages' worth), a range's count
+// over the CUs, a block long enough to pay for loading its A panel (~10 stages' worth), a range's count
 // within 16 bits and one range per partial tile at most.
 MfmaGeom scoary_mfma_geom(int num_cu, int64_t k_split, int64_t T, int64_t P, int64_t ntiles) {
   MfmaGeom g{};
@@ -320,7 +338,7 @@ int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, 
   }
   {
     KernelTimer kt(h, s, "k_permute_mfma");
-    hipLaunchKernelGGL(k_permute_mfma, dim3((unsigned)g.blocks), dim3(256), kMfmaLds, s,
+    hipLaunchKernelGGL(k_permute_mfma, dim3((unsigned)g.blocks), dim3(kBlockWaves * 64), kMfmaLds, s,
                        static_cast<const v4i*>(d_panels), static_cast<const unsigned char*>(d_bfrag),
                        reinterpret_cast<const uint2*>(d_lcrit), (int)G, P, (int)g.stages, (int)g.per, (int)g.rp,
                        (int)g.gene_blocks, (int)ntiles, gs, d_partial);

@@ -249,6 +249,33 @@ int scoary_permute_minp(scoary_handle h, const uint32_t *d_tiled, const uint32_t
                         int64_t T, int64_t N, int64_t P, int64_t perm_base, int64_t minp_stride,
                         double *d_minp, scoary_stream_t stream);
 
+/* ---- Westfall-Young step-down minP (spec S8 of DESIGN.md) ------------------------------
+ * Added after ABI 11 without a version change: three new entry points, nothing existing changes its
+ * meaning, so a caller built against ABI 11 keeps working (backward compatible).
+ * Per trait the genes are ranked ascending by (p, gene index): d_order int32 [T][G] = the gene at rank k,
+ * d_psorted double [T][G] = its p (scoary_fisher's own double).  With the p tables of scoary_minp_plan /
+ * _fill, for every label row b of the batch
+ *   q_b[k] = min over j >= k of p_{t,order[j]}(popcount(gene_order[j] & perm_{t,b})),
+ *   d_c[t][k] += #{ b : q_b[k] <= d_psorted[t][k] }          (uint32, BY RANK POSITION, doubles compared exactly),
+ *   d_minp[t][perm_base + b] = min(itself, q_b[0])           (scoary_permute_minp's value, bit for bit; NULL: not kept).
+ * The CALLER zeroes d_c before the first batch of permutations (batches add) and initialises d_minp to 1.0.
+ * Ties, the running maximum over the ranks and the scatter back to gene order (S8 steps 4-6) are the caller's.
+ * The rank order is walked in chunks and two passes: chunk minima first, then every chunk starts from the
+ * minimum of the later chunks and counts -- no block waits for another.  scoary_stepdown_chunks = the number
+ * of chunks for this (G, T, P) on this handle's device (host only, the launch shape's own value).
+ * A chunk is ceil(G / chunks) positions rounded up to a multiple of 64.
+ * scoary_stepdown_scratch_bytes = the size of d_scratch: the rank-ordered position arrays, every trait's gene
+ * rows copied into rank order (one tiled matrix per trait, which is why it takes N), the chunk minima and one
+ * count byte per trait, group of 64 permutations and position.  Nothing in it has to survive the call.  Asynchronous on `stream`, allocates nothing.  Any N scoary_permute_minp takes, the same size
+ * refusals. */
+int64_t scoary_stepdown_chunks(scoary_handle h, int64_t G, int64_t T, int64_t P);
+int64_t scoary_stepdown_scratch_bytes(scoary_handle h, int64_t G, int64_t T, int64_t N, int64_t P);
+int scoary_permute_stepdown(scoary_handle h, const uint32_t *d_tiled, const uint32_t *d_perms,
+                            const int64_t *d_off, const int32_t *d_lo, const double *d_tab,
+                            const int32_t *d_order, const double *d_psorted, int64_t G, int64_t T,
+                            int64_t N, int64_t P, int64_t perm_base, int64_t minp_stride,
+                            double *d_minp, uint32_t *d_c, void *d_scratch, scoary_stream_t stream);
+
 /* ---- a7/a8, list-driven variant -------------------------------------------
  * Same result as scoary_perm_generate + scoary_permute (d_r is bit-identical),
  * different data flow: genes as lists of the isolates that carry their

@@ -45,6 +45,9 @@ SIGNATURES = {
     "scoary_minp_plan": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, ctypes.POINTER(_i64), _vp]),
     "scoary_minp_fill": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "scoary_permute_minp": (_i32, [_vp] * 6 + [_i64] * 6 + [_vp, _vp]),
+    "scoary_stepdown_chunks": (_i64, [_vp, _i64, _i64, _i64]),
+    "scoary_stepdown_scratch_bytes": (_i64, [_vp, _i64, _i64, _i64, _i64]),
+    "scoary_permute_stepdown": (_i32, [_vp] * 8 + [_i64] * 6 + [_vp] * 4),
     "scoary_list_tiles_words": (_i64, [_i64, _i64, _i64]),
     "scoary_list_tile_words": (_i64, [_i64]),
     "scoary_list_params": (_i32, [_i64, _vp]),

@@ -625,18 +625,36 @@ class AssociationEngine:
         index lists do) and later calls with the same plan reuse them: the tables depend on the gene matrix and
         the traits alone, and building them is most of a step (cfg3: 119 of 150 ms)."""
         torch = _torch()
-        if plan is not None and not plan.fits(traits, masks):
-            raise ValueError("the trait plan was built from other trait / mask tensors")
-        if res is not None:
-            counts, margins = res["counts"], res["margins"]
-        else:
-            counts, margins = self.counts(genes, traits, masks, plan=plan)
-        T, N, P = int(counts.shape[0]), genes.N, int(permutations)
+        counts, margins = self._minp_inputs(genes, traits, masks, res, plan)
+        T, P = int(counts.shape[0]), int(permutations)
         if out is None:
             out = torch.ones((T, P), dtype=torch.float64, device=self.device)
         p0, p1 = (0, P) if perm_range is None else (int(perm_range[0]), int(perm_range[1]))
+
+        def launch(t0, t1, tables, perms, nb, done):
+            self.permute_minp(genes, perms, tables, out[t0:t1], P=nb, perm_base=done)
+        self._minp_batches(genes, masks, counts, margins, p0, p1, seed, table_budget_bytes, label_budget_bytes, plan,
+                           launch)
+        return out
+
+    def _minp_inputs(self, genes, traits, masks, res, plan):
+        """(counts, margins) of minp() / minp_stepdown(): an associate() result's, or counted here."""
+        if plan is not None and not plan.fits(traits, masks):
+            raise ValueError("the trait plan was built from other trait / mask tensors")
+        if res is not None:
+            return res["counts"], res["margins"]
+        return self.counts(genes, traits, masks, plan=plan)
+
+    def _minp_batches(self, genes, masks, counts, margins, p0, p1, seed, table_budget_bytes, label_budget_bytes, plan,
+                      launch):
+        """The loop minp() and minp_stepdown() share: trait groups under the table budget (their p tables built, or
+        taken from / left in genes.minp_cache when there is a plan), label batches under the label budget, and per
+        batch ``launch(t0, t1, tables, perms, nb, done)`` -- the traits [t0, t1) with their tables and the label rows
+        ``perms`` [t1 - t0, nb, Wp] of the permutations done .. done + nb - 1."""
+        torch = _torch()
         if p1 <= p0:
-            return out
+            return
+        N = genes.N
         Wp = self.row_words(N)
         buf = None
         cached = genes.minp_cache if plan is not None else None
@@ -656,10 +674,9 @@ class AssociationEngine:
                 nb = min(batch, p1 - done)
                 perms = buf[:Tg * nb * Wp].view(Tg, nb, Wp)
                 self.perm_generate(masks[t0:t1], margins[t0:t1], N, nb, done, seed, out=perms, trait_base=t0)
-                self.permute_minp(genes, perms, tables, out[t0:t1], P=nb, perm_base=done)
+                launch(t0, t1, tables, perms, nb, done)
                 done += nb
             del tables
-        return out
 
     @staticmethod
     def r_fwer(minp, p):
@@ -668,6 +685,82 @@ class AssociationEngine:
         torch = _torch()
         srt = torch.sort(minp, dim=1).values.contiguous()
         return torch.searchsorted(srt, p.contiguous(), right=True).to(torch.int32)
+
+    # -- Westfall-Young step-down minP (spec S8) ----------------------------------
+    def stepdown_chunks(self, G, T, P):
+        """Chunks the rank order of G genes is walked in for T traits and P permutations per call
+        (scoary_stepdown_chunks: the launch shape's own value)."""
+        return int(self.lib.scoary_stepdown_chunks(self.h, int(G), int(T), int(P)))
+
+    def permute_stepdown(self, genes, perms, tables, order, p_sorted, c, minp=None, P=None, perm_base=0):
+        """c[t, k] += #{i : min over j >= k of p_{t,order[t,j]}(popcount(gene & perms[t, i])) <= p_sorted[t, k]}: the raw
+        step-down counts BY RANK POSITION (spec S8 steps 2-3) of the label rows ``perms`` (int32 [T, P, Wp]).
+        ``order`` int32 [T, G] = the gene at every rank, ``p_sorted`` float64 [T, G] = its p, ``c`` int32 [T, G]
+        (uint32 bit pattern), zeroed by the caller before the first batch.  ``minp`` (optional): float64
+        [T, >= perm_base + P] initialised to 1.0; column perm_base + i takes the minimum over all genes, as
+        permute_minp writes it.  Returns c."""
+        torch = _torch()
+        T = int(perms.shape[0])
+        if P is None:
+            P = int(perms.shape[1])
+        G = genes.G
+        if not (perms.is_contiguous() and order.is_contiguous() and p_sorted.is_contiguous() and c.is_contiguous()):
+            raise ValueError("permute_stepdown: label rows, order, p_sorted and c must be contiguous")
+        if tuple(order.shape) != (T, G) or tuple(p_sorted.shape) != (T, G) or tuple(c.shape) != (T, G) or \
+                order.dtype != torch.int32 or p_sorted.dtype != torch.float64 or c.dtype != torch.int32:
+            raise ValueError("permute_stepdown: order int32, p_sorted float64 and c int32 must be [T, G]")
+        stride = 0
+        if minp is not None:
+            if minp.stride(1) != 1 or (T > 1 and minp.stride(0) != minp.shape[1]):
+                raise ValueError("permute_stepdown: minp rows must be contiguous")
+            stride = int(minp.shape[1])
+        need = int(self.lib.scoary_stepdown_scratch_bytes(self.h, G, T, genes.N, int(P)))
+        scratch = self._empty(((need + 7) // 8,), torch.int64)
+        self._check(self.lib.scoary_permute_stepdown(
+            self.h, self._ptr(genes.tiled), self._ptr(perms), self._ptr(tables.off), self._ptr(tables.lo),
+            self._ptr(tables.tab), self._ptr(order), self._ptr(p_sorted), G, T, genes.N, int(P), int(perm_base),
+            stride, self._ptr(minp) if minp is not None else None, self._ptr(c), self._ptr(scratch),
+            self._stream()), "scoary_permute_stepdown")
+        return c
+
+    def minp_stepdown(self, genes, traits, masks, permutations, seed=0, res=None, table_budget_bytes=8 << 30,
+                      label_budget_bytes=8 << 30, plan=None):
+        """Westfall-Young step-down minP (spec S8): (r_sd int32 [T, G], minp float64 [T, permutations]).  Per
+        trait the genes are ranked by (p, gene index) -- one stable device sort of the association step's own p --
+        and the gene at rank k is compared, per permuted labelling, with the smallest permuted p over the genes at
+        rank k and behind; r_sd[t, g] = the number of labellings where that minimum is <= the gene's own p, tied
+        genes taking the count of the first of their group and the counts made monotone along the ranks;
+        (r_sd + 1) / (P + 1) is the adjusted p, never above the single-step one.  ``minp`` is minp()'s result, bit
+        for bit (the same pass produces it).  ``res``, the budgets and ``plan`` as in minp(): the same trait groups,
+        label batches and genes.minp_cache; the result depends on none of them.
+        On a GENE SHARD this is the step-down within that shard; shards do NOT compose (the successive minimum at
+        a global rank mixes the genes of all shards): run it on the whole matrix."""
+        torch = _torch()
+        counts, margins = self._minp_inputs(genes, traits, masks, res, plan)
+        if res is not None:
+            p = res["p"]
+        else:
+            p = self.fisher(counts.reshape(-1, 4), want_crit=False)[0].view(counts.shape[0], counts.shape[1])
+        T, G, P = int(counts.shape[0]), genes.G, int(permutations)
+        ps, order = torch.sort(p.contiguous(), dim=1, stable=True)          # ascending (p, gene index)
+        ps, order32 = ps.contiguous(), order.to(torch.int32).contiguous()
+        c = torch.zeros((T, G), dtype=torch.int32, device=self.device)
+        minp = torch.ones((T, P), dtype=torch.float64, device=self.device)
+
+        def launch(t0, t1, tables, perms, nb, done):
+            self.permute_stepdown(genes, perms, tables, order32[t0:t1], ps[t0:t1], c[t0:t1], minp=minp[t0:t1], P=nb,
+                                  perm_base=done)
+        self._minp_batches(genes, masks, counts, margins, 0, P, seed, table_budget_bytes, label_budget_bytes, plan,
+                           launch)
+        # steps 4 and 5: every tie group takes the count of its first position, then the running maximum
+        pos = torch.arange(G, device=self.device).expand(T, G)
+        first = torch.ones((T, G), dtype=torch.bool, device=self.device)
+        first[:, 1:] = ps[:, 1:] != ps[:, :-1]
+        head = torch.cummax(torch.where(first, pos, torch.zeros_like(pos)), dim=1).values
+        r_rank = torch.cummax(c.gather(1, head), dim=1).values
+        r_sd = torch.empty_like(c)
+        r_sd.scatter_(1, order, r_rank)
+        return r_sd, minp
 
     def perm_batch(self, T, N, P, budget_bytes=8 << 30):
         """Permutations per generate/permute round so the label buffer stays
@@ -756,7 +849,7 @@ class AssociationEngine:
 
     def associate(self, genes, traits, masks, permutations=0, seed=0, perm_buffer=None,
                   use_lists=None, workspace=None, plan=None, graph=None, records=None, fwer=False,
-                  table_budget_bytes=8 << 30):
+                  table_budget_bytes=8 << 30, stepdown=False):
         """counts -> Fisher -> (optional) permutation exceedance counts.
         Returns dict of device tensors: counts [T,G,4], margins [T,2],
         p / odds [T,G], r [T,G] (uint32 bit pattern in int32) or None.  With
@@ -770,12 +863,20 @@ class AssociationEngine:
         Westfall-Young minima res["minp"] float64 [T, P] (minp()) and res["r_fwer"] int32 [T, G] = the number of
         permutations whose minimum is <= the gene's own p; the p tables of a trait group stay under
         ``table_budget_bytes`` and, with a ``plan``, are built once per (gene matrix, plan) and reused (minp()).
-        Such a step is never replayed from a graph (it reads sizes back)."""
-        if fwer and permutations <= 0:
-            raise ValueError("fwer=True needs permutations > 0")
+        Such a step is never replayed from a graph (it reads sizes back).  ``stepdown=True`` (needs permutations):
+        the step-down counts res["r_fwer_sd"] int32 [T, G] and res["minp"] (minp_stepdown(), spec S8); together with
+        ``fwer`` res["r_fwer"] comes from those same minima, k_permute_minp is not launched."""
+        if (fwer or stepdown) and permutations <= 0:
+            raise ValueError("fwer=True / stepdown=True need permutations > 0")
         res = self._associate(genes, traits, masks, permutations, seed, perm_buffer, use_lists,
-                              workspace, plan, graph if records is None and not fwer else False)
-        if fwer:
+                              workspace, plan, graph if records is None and not (fwer or stepdown) else False)
+        if stepdown:
+            res = dict(res)
+            res["r_fwer_sd"], res["minp"] = self.minp_stepdown(genes, traits, masks, permutations, seed, res=res,
+                                                               table_budget_bytes=table_budget_bytes, plan=plan)
+            if fwer:
+                res["r_fwer"] = self.r_fwer(res["minp"], res["p"])
+        elif fwer:
             res = dict(res)
             res["minp"] = self.minp(genes, traits, masks, permutations, seed, res=res,
                                     table_budget_bytes=table_budget_bytes, plan=plan)

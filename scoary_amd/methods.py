@@ -769,7 +769,8 @@ def _pattern_groups(table, maskrow, idx, hashes):
     return inv.reshape(-1)
 
 
-def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, fwer=False):
+def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, fwer=False,
+               fwer_stepdown=False):
     """Whole hot path for all traits; under torchrun (world > 1) every rank
     takes a stride gene shard (dist.GenePartition: the reference's domains,
     scoary/methods.py:1076-1078) and the per-gene records are all-gathered
@@ -780,7 +781,10 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
     ``fwer``: also the Westfall-Young minima (spec S7): out["minp"] [T, P] and out["r_fwer"] [T, G] = the
     number of permutations whose smallest p over ALL genes is <= the gene's own p.  Under gene sharding
     every rank takes the minima over its own genes, one all_reduce(MIN) of the [T, P] doubles follows, and
-    r_fwer travels in the record's nstop word (the feature excludes early abort)."""
+    r_fwer travels in the record's nstop word (the feature excludes early abort).
+    ``fwer_stepdown``: the step-down counts (spec S8) out["r_fwer_sd"] [T, G], single process only -- the
+    successive minima run over all genes in one order, gene shards do not compose; they reach the host beside the
+    records, as the minima do.  With ``fwer`` as well, r_fwer is counted from the same pass's minima."""
     import torch
     from . import dist
     eng = get_engine()
@@ -849,7 +853,16 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
             res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan)
             torch.cuda.synchronize(eng.device)
         r_fwer = None
-        if fwer:
+        if fwer_stepdown:
+            with _stage("Westfall-Young step-down minP (p tables, k_stepdown_minp)"):
+                # ranked on k_fisher's own bits, before the SciPy-digits pass rewrites the last ulp of p
+                r_sd, minp = eng.minp_stepdown(gm, trv, mkv, permutations, seed, res=res)
+                sd_all.append(r_sd)
+                if fwer:
+                    r_fwer = eng.r_fwer(minp, res["p"])
+                minp_all.append(minp)
+                torch.cuda.synchronize(eng.device)
+        elif fwer:
             with _stage("Westfall-Young minP (p tables, k_permute_minp)"):
                 minp = dist.all_reduce_min(eng.minp(gm, trv, mkv, permutations, seed, res=res))
                 # counted on k_fisher's own bits, before the SciPy-digits pass rewrites the last ulp of p
@@ -862,7 +875,7 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
             torch.cuda.synchronize(eng.device)
         return rec
 
-    minp_all = []
+    minp_all, sd_all = [], []
     rec = dist.associate_sharded(local, G)
     with _stage("results D2H"):
         # the stable p order for BH: numpy does 200 000 doubles in 25-40 ms, which beats the
@@ -876,7 +889,10 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         out["r"] = None
     if fwer:
         out["r_fwer"], out["nstop"] = out["nstop"], np.zeros_like(out["nstop"])
+    if fwer or fwer_stepdown:
         out["minp"] = minp_all[0].cpu().numpy()
+    if fwer_stepdown:
+        out["r_fwer_sd"] = sd_all[0].cpu().numpy() if sd_all else np.zeros((T, 0), dtype=np.int32)
     return out
 
 
@@ -934,17 +950,31 @@ def _usable_cpus():
 
 
 def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEED,
-                  early_abort=False, fwer=False):
+                  early_abort=False, fwer=False, fwer_stepdown=False):
     """Counts, Fisher's exact test and B/BH correction for every trait x gene
     (methods.py:757-928).  ``permutations`` >= 10 additionally attaches the
     Fisher-statistic ``Empirical_p`` (= (r+1)/(P+1), methods.py:1365) to every
     row -- the north_star's replacement for the tree-statistic Permute loop.  ``fwer`` (with
-    permutations): also ``Westfall_Young_p`` = (r_fwer+1)/(P+1), the single-step minP adjusted p."""
+    permutations): also ``Westfall_Young_p`` = (r_fwer+1)/(P+1), the single-step minP adjusted p.
+    ``fwer_stepdown`` (with permutations, one process): also ``Westfall_Young_stepdown_p`` = (r_sd+1)/(P+1), the
+    step-down minP adjusted p (spec S8)."""
     if fwer and (permutations < 10 or early_abort):
         raise ValueError("fwer needs permutations >= 10 and excludes early_abort")
+    if fwer_stepdown:
+        # (permutations are 0 here whenever the run is not --no_pairwise)
+        if permutations <= 0:
+            raise ValueError("fwer_stepdown needs the Fisher-statistic permutations of --no_pairwise")
+        if permutations < 10:
+            raise ValueError("fwer_stepdown needs permutations >= 10")
+        if early_abort:
+            raise ValueError("fwer_stepdown excludes early_abort")
+        from . import dist
+        if dist.world_rank()[0] > 1:
+            raise ValueError("fwer_stepdown needs a single process: the successive minima run over all genes in "
+                             "one order; gene shards do not compose")
     table = _as_table(genedic)
     names, tarr = _trait_arrays(traitsdic, table.strains)
-    dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, fwer)
+    dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, fwer, fwer_stepdown)
     collapse_hashes = None
     if collapse:
         eng = get_engine()
@@ -974,6 +1004,9 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
         wy = None
         if fwer:
             wy = (dev["r_fwer"][t].astype(np.float64) + 1.0) / (permutations + 1.0)
+        wy_sd = None
+        if fwer_stepdown:
+            wy_sd = (dev["r_fwer_sd"][t].astype(np.float64) + 1.0) / (permutations + 1.0)
 
         if not collapse:
             # names stay in the GeneTable: the result rows are (table, idx) -- nothing per
@@ -1036,6 +1069,8 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
             cols["Empirical_p"] = emp[rows_idx]
         if wy is not None:
             cols["Westfall_Young_p"] = wy[rows_idx]
+        if wy_sd is not None:
+            cols["Westfall_Young_stepdown_p"] = wy_sd[rows_idx]
         if collapse:
             tr = TraitResults(names_out, nugn, ann, cols, number_of_tests, members)
         else:
@@ -1384,6 +1419,9 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
     with_wy = no_pairwise and with_emp and "Westfall_Young_p" in Trait.cols      # --permute-fwer
     if with_wy:
         columns.append("Westfall_Young_p")
+    with_wy_sd = no_pairwise and with_emp and "Westfall_Young_stepdown_p" in Trait.cols      # --permute-fwer-stepdown
+    if with_wy_sd:
+        columns.append("Westfall_Young_stepdown_p")
     columns += list(extracolstoprint)
     table = _as_table(genedic) if extracolstoprint else None
 
@@ -1414,6 +1452,9 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
         if with_wy:
             colget["Westfall_Young_p"] = np.asarray(Trait.column("Westfall_Young_p"))
             fields.append("Westfall_Young_p")
+        if with_wy_sd:
+            colget["Westfall_Young_stepdown_p"] = np.asarray(Trait.column("Westfall_Young_stepdown_p"))
+            fields.append("Westfall_Young_stepdown_p")
         keyed = {CUT_FIELD[m]: colget[CUT_FIELD[m]] for m in cutoffs}
         sel = cand[np.all([keyed[CUT_FIELD[m]][cand] <= c for m, c in cutoffs.items()], axis=0)] \
             if cutoffs else cand
@@ -1473,7 +1514,7 @@ def _trait_results_from_dict(rows):
     """Plain {gene: row dict} (the reference's Results[trait]) -> TraitResults."""
     genes = list(rows.keys())
     cols = {}
-    for k in TraitResults.FIELDS + ("Empirical_p", "Westfall_Young_p"):
+    for k in TraitResults.FIELDS + ("Empirical_p", "Westfall_Young_p", "Westfall_Young_stepdown_p"):
         if genes and k in rows[genes[0]]:
             cols[k] = np.array([rows[g][k] for g in genes])
     return TraitResults(genes, [rows[g]["NUGN"] for g in genes],
@@ -1582,6 +1623,11 @@ def ScoaryArgumentParser(argv=None):
                    help="With --no_pairwise --permute: add the column Westfall_Young_p, the single-step "
                    "minP family-wise adjusted p -- (1 + number of permutations whose smallest Fisher p "
                    "over all genes is <= the gene's own p) / (permutations + 1) (scoary_amd extension)")
+    a.add_argument("--permute-fwer-stepdown", dest="permute_fwer_stepdown", action="store_true", default=False,
+                   help="With --no_pairwise --permute: add the column Westfall_Young_stepdown_p, the step-down "
+                   "minP family-wise adjusted p -- every gene is compared, per permutation, with the smallest "
+                   "Fisher p over the genes ranked at or behind it only; never above Westfall_Young_p, same "
+                   "family-wise error (single process; scoary_amd extension)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1740,7 +1786,8 @@ def main(**kwargs):
         res = Setup_results(genedic, traitsdic, args.collapse,
                             permutations=args.permute if args.no_pairwise else 0, seed=seed,
                             early_abort=getattr(args, "permute_early_abort", False),
-                            fwer=getattr(args, "permute_fwer", False))
+                            fwer=getattr(args, "permute_fwer", False),
+                            fwer_stepdown=getattr(args, "permute_fwer_stepdown", False))
         t_stats = _time.time()
         if args.upgma_tree and rank == 0:
             # (with --no_pairwise there is no tree and the reference writes str(None) + ";", :277-280, :741-751)
@@ -1827,6 +1874,20 @@ def _validate(args, cutoffs):
         if getattr(args, "permute_early_abort", False):
             sys.exit("Cannot use --permute-fwer together with --permute-early-abort. Every gene has to see "
                      "every permutation")
+    if getattr(args, "permute_fwer_stepdown", False):
+        if not args.no_pairwise:
+            sys.exit("Cannot use --permute-fwer-stepdown without --no_pairwise. The Westfall-Young minima are "
+                     "taken over the Fisher statistic of every gene")
+        if args.permute < 10:
+            sys.exit("Cannot use --permute-fwer-stepdown without performing permutations. Use '--permute X' "
+                     "where X is a number equal to or larger than 10")
+        if getattr(args, "permute_early_abort", False):
+            sys.exit("Cannot use --permute-fwer-stepdown together with --permute-early-abort. Every gene has to "
+                     "see every permutation")
+        from . import dist
+        if dist.world_rank()[0] > 1:
+            sys.exit("Cannot use --permute-fwer-stepdown under more than one rank: the successive minima run over "
+                     "all genes in one order; gene shards do not compose")
     if "P" in cutoffs and args.permute == 0:
         sys.exit("Cannot use empirical p-values in filtration without performing "
                  "permutations. Use '--permute X' where X is a number equal to or larger than 10")

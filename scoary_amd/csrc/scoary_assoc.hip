@@ -728,10 +728,7 @@ __global__ __launch_bounds__(64) void k_permute_chunked(const uint4* __restrict_
 #pragma unroll
         for (int q = 0; q < CQ; ++q) {
           const uint4 s = pr[q];  // wave-uniform -> s_load
-          bcnt_acc(acc[j], gw[q].x & s.x);
-          bcnt_acc(acc[j], gw[q].y & s.y);
-          bcnt_acc(acc[j], gw[q].z & s.z);
-          bcnt_acc(acc[j], gw[q].w & s.w);
+          and_popc(acc[j], gw[q], s);
         }
       }
     }
@@ -786,10 +783,7 @@ __global__ __launch_bounds__(64) void k_permute_seq(const uint4* __restrict__ ti
 #pragma unroll
         for (int q = 0; q < CQ; ++q) {
           const uint4 s = pr[q];  // wave-uniform -> s_load
-          bcnt_acc(acc[j], gw[q].x & s.x);
-          bcnt_acc(acc[j], gw[q].y & s.y);
-          bcnt_acc(acc[j], gw[q].z & s.z);
-          bcnt_acc(acc[j], gw[q].w & s.w);
+          and_popc(acc[j], gw[q], s);
         }
       }
     }
@@ -806,14 +800,6 @@ __global__ __launch_bounds__(64) void k_permute_seq(const uint4* __restrict__ ti
     r[(int64_t)t * G + g] = run;
     nstop[(int64_t)t * G + g] = stop;
   }
-}
-
-template <int RQ, int GL>
-void launch_permute_reg(dim3 grid, hipStream_t s, const uint32_t* tiled, const uint32_t* perms,
-                        const uint32_t* crit, int G, int Gp, int64_t P, int pchunk, uint32_t* r) {
-  hipLaunchKernelGGL((k_permute_reg<RQ, GL>), grid, dim3(kWave), 0, s,
-                     reinterpret_cast<const uint4*>(tiled), perms,
-                     reinterpret_cast<const uint2*>(crit), G, Gp, P, pchunk, r);
 }
 
 }  // namespace
@@ -1016,27 +1002,17 @@ int scoary_permute(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d_p
   nch = (P + pchunk - 1) / pchunk;
   dim3 grid((unsigned)gene_waves, (unsigned)nch, (unsigned)T);
 
-  // tiled rows are a kRegQuads size up to kMaxRegQuads quads, multiples of kChunkQuads beyond
-  if (Qp > kMaxRegQuads && Qp % kChunkQuads != 0)
-    return fail(h, SCOARY_ERR_SIZE, "scoary_permute: unsupported tiled row size");
+  if (!tiled_quads_ok(Qp)) return fail(h, SCOARY_ERR_SIZE, "scoary_permute: unsupported tiled row size");
+  const uint4* t4 = reinterpret_cast<const uint4*>(d_tiled);
+  const uint2* c2 = reinterpret_cast<const uint2*>(d_crit);
   KernelTimer kt(h, s, "k_permute");
-  if (Qp <= kMaxRegQuads) {
-    switch (Qp) {
-#define CASE_RQ(RQ)                                                                          \
-  case RQ:                                                                                   \
-    launch_permute_reg<RQ, 1>(grid, s, d_tiled, d_perms, d_crit, (int)G, (int)Gp, P, pchunk, d_r); \
-    break;
-      CASE_RQ(1) CASE_RQ(2) CASE_RQ(4) CASE_RQ(6) CASE_RQ(8) CASE_RQ(12) CASE_RQ(16) CASE_RQ(20)
-      CASE_RQ(24)
-#undef CASE_RQ
-      default:
-        return fail(h, SCOARY_ERR_SIZE, "scoary_permute: unsupported tiled row size");
-    }
-  } else {
-    hipLaunchKernelGGL((k_permute_chunked<kChunkQuads, 8>), grid, dim3(kWave), 0, s,
-                       reinterpret_cast<const uint4*>(d_tiled), d_perms,
-                       reinterpret_cast<const uint2*>(d_crit), (int)G, (int)Gp, (int)Qp, P, pchunk, d_r);
-  }
+  const bool reg = with_reg_quads(Qp, [&](auto rq) {
+    hipLaunchKernelGGL((k_permute_reg<decltype(rq)::value, GL>), grid, dim3(kWave), 0, s, t4, d_perms, c2, (int)G,
+                       (int)Gp, P, pchunk, d_r);
+  });
+  if (!reg)
+    hipLaunchKernelGGL((k_permute_chunked<kChunkQuads, 8>), grid, dim3(kWave), 0, s, t4, d_perms, c2, (int)G,
+                       (int)Gp, (int)Qp, P, pchunk, d_r);
   HIP_TRY(h, hipGetLastError());
   return SCOARY_OK;
 }
@@ -1058,20 +1034,12 @@ int scoary_permute_seq(scoary_handle h, const uint32_t* d_tiled, const uint32_t*
   const dim3 grid((unsigned)(Gp / kWave), (unsigned)T);
   const uint4* t4 = reinterpret_cast<const uint4*>(d_tiled);
   const uint2* c2 = reinterpret_cast<const uint2*>(d_crit);
-  // tiled rows come in the register sizes of kRegQuads (any of 1, 2, 4, 6 ... quads) or in
-  // multiples of kChunkQuads: chunk = the largest of 8 / 4 / 2 / 1 quads that divides Qp
-  if (Qp % 8 == 0)
-    hipLaunchKernelGGL((k_permute_seq<8, 8>), grid, dim3(kWave), 0, s, t4, d_perms, c2, d_thr, (int)G,
-                       (int)Gp, (int)Qp, P, perm_base, d_r, d_nstop);
-  else if (Qp % 4 == 0)
-    hipLaunchKernelGGL((k_permute_seq<4, 8>), grid, dim3(kWave), 0, s, t4, d_perms, c2, d_thr, (int)G,
-                       (int)Gp, (int)Qp, P, perm_base, d_r, d_nstop);
-  else if (Qp % 2 == 0)
-    hipLaunchKernelGGL((k_permute_seq<2, 8>), grid, dim3(kWave), 0, s, t4, d_perms, c2, d_thr, (int)G,
-                       (int)Gp, (int)Qp, P, perm_base, d_r, d_nstop);
-  else
-    hipLaunchKernelGGL((k_permute_seq<1, 8>), grid, dim3(kWave), 0, s, t4, d_perms, c2, d_thr, (int)G,
-                       (int)Gp, (int)Qp, P, perm_base, d_r, d_nstop);
+  // tiled rows come in the register sizes of RegQuads (any of 1, 2, 4, 6 ... quads) or in multiples of
+  // kChunkQuads: chunk = the largest of 8 / 4 / 2 / 1 quads that divides Qp = its lowest set bit, 8 at the most
+  with_quads(std::integer_sequence<int, 8, 4, 2, 1>{}, std::min<int64_t>(Qp & -Qp, 8), [&](auto cq) {
+    hipLaunchKernelGGL((k_permute_seq<decltype(cq)::value, 8>), grid, dim3(kWave), 0, s, t4, d_perms, c2, d_thr,
+                       (int)G, (int)Gp, (int)Qp, P, perm_base, d_r, d_nstop);
+  });
   HIP_TRY(h, hipGetLastError());
   return SCOARY_OK;
 }

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "scoary_hip.h"
@@ -51,21 +52,50 @@ namespace {
 constexpr int kWave = 64;
 constexpr int kGeneAlign = 256;
 
-// Row sizes (in quads of four 32-bit words) for which a gene row is held
-// entirely in VGPRs by k_permute_reg.
+// Row sizes (in quads of four 32-bit words) for which a row is held entirely in VGPRs: the gene row by
+// k_permute_reg, a lane's label row by k_permute_minp / k_stepdown_minp.  THE list: the instances, the padding
+// of tiled_quads() and every dispatcher follow from it.
 // Longer rows go to k_permute_chunked (measured 1.39x faster than registers at N=5000).
-constexpr int kRegQuads[] = {1, 2, 4, 6, 8, 12, 16, 20, 24};
-constexpr int kMaxRegQuads = 24;
+using RegQuads = std::integer_sequence<int, 1, 2, 4, 6, 8, 12, 16, 20, 24>;
 constexpr int kChunkQuads = 8;  // k_permute_chunked: quads per register chunk
+
+// the smallest size of the list that is >= q; 0 when there is none
+template <int... Q>
+constexpr int quads_at_least(std::integer_sequence<int, Q...>, int64_t q) {
+  int r = 0;
+  ((r = (Q >= q && (r == 0 || Q < r)) ? Q : r), ...);
+  return r;
+}
+template <int... Q>
+constexpr int quads_max(std::integer_sequence<int, Q...>) {
+  int r = 0;
+  ((r = Q > r ? Q : r), ...);
+  return r;
+}
+constexpr int kMaxRegQuads = quads_max(RegQuads{});
+
+// f(std::integral_constant<int, Q>{}) for the size Q of the list that equals Qp; false when Qp is none of them
+template <int... Q, class F>
+inline bool with_quads(std::integer_sequence<int, Q...>, int64_t Qp, F&& f) {
+  return ((Qp == Q && (f(std::integral_constant<int, Q>{}), true)) || ...);
+}
+template <class F>
+inline bool with_reg_quads(int64_t Qp, F&& f) {
+  return with_quads(RegQuads{}, Qp, f);
+}
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 inline int64_t tiled_quads(int64_t N) {
   int64_t q = (((N + 31) / 32) + 3) / 4;
   if (q < 1) q = 1;
-  for (int r : kRegQuads)
-    if (r >= q) return r;
-  return round_up(q, kChunkQuads);
+  const int r = quads_at_least(RegQuads{}, q);
+  return r ? r : round_up(q, kChunkQuads);
+}
+
+// the row sizes tiled_quads() produces: a RegQuads size up to kMaxRegQuads quads, multiples of kChunkQuads beyond
+inline bool tiled_quads_ok(int64_t Qp) {
+  return Qp > kMaxRegQuads ? Qp % kChunkQuads == 0 : with_reg_quads(Qp, [](auto) {});
 }
 
 // ---- list-driven permutation path: layout constants shared by scoary_lists.hip
@@ -186,6 +216,14 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 // ~15 % more VALU work in the permutation inner loop.
 __device__ __forceinline__ void bcnt_acc(uint32_t& acc, uint32_t x) {
   asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc) : "v"(x));
+}
+
+// acc += popcount(a & b) over the four words of a quad: one accumulator, one dependent chain
+__device__ __forceinline__ void and_popc(uint32_t& acc, const uint4 a, const uint4 b) {
+  bcnt_acc(acc, a.x & b.x);
+  bcnt_acc(acc, a.y & b.y);
+  bcnt_acc(acc, a.z & b.z);
+  bcnt_acc(acc, a.w & b.w);
 }
 
 }  // namespace

@@ -763,8 +763,14 @@ def test_launch_bound_steps_replay_a_graph_by_themselves(eng, orc, use_lists, mo
 
 
 # ------------------------------ opt-in early abort on the Fisher statistic -----
+# tiled row size (quads) of the early-abort cases: k_permute_seq walks a row in chunks of the largest of 8 / 4 / 2 / 1
+# quads that divides it.  The (70, N, 2, 64) cases are one small shape per chunk width: 8, 4, 2 and 1
+SEQ_ROW_QUADS = {90: 1, 100: 1, 400: 4, 700: 6, 900: 8, 1000: 8, 2100: 20, 7000: 56}
+
+
 @pytest.mark.parametrize("G,N,T,P", [(120, 90, 2, 200), (70, 700, 1, 333), (40, 2100, 2, 130), (64, 1000, 1, 120),
-                                     (30, 7000, 1, 70)])
+                                     (30, 7000, 1, 70)]
+                         + [(70, N, 2, 64) for N in (900, 400, 700, 100)])
 def test_permute_sequential_early_abort_vs_oracle(eng, orc, G, N, T, P):
     """--permute-early-abort (scoary_permute_seq): the reference's sequential estimator
     (scoary/methods.py:1348-1365) applied to the Fisher statistic.  The oracle leg states
@@ -773,6 +779,7 @@ def test_permute_sequential_early_abort_vs_oracle(eng, orc, G, N, T, P):
     calls binom.cdf per step like the reference).  r, the stopping point and the estimate
     agree for every (gene, trait); batching the permutations changes nothing."""
     from scoary_amd import tree as T_
+    assert eng.quads(N) == SEQ_ROW_QUADS[N]             # which chunk width the shape reaches
     rng = np.random.default_rng(G + N + P)
     genes, traits = _random_case(rng, G, N, T)
     genes[3] = (rng.random(N) < 0.5).astype(np.uint8)

@@ -326,11 +326,18 @@ def test_list_variants_edges_and_random(eng, orc, cache, N, P, tw, segments):
 
 
 # ------------------------------------------------------------------ 4. dense k_permute ------
-@pytest.mark.parametrize("G,N,P", [(300, 65, 129), (513, 1000, 193), (60, 3300, 70)])
+# tiled row size (quads) of the dense cases: every k_permute_reg instance (1, 2, 4, 6, 8, 12, 16, 20, 24 quads) and
+# k_permute_chunked (> 24)
+DENSE_ROW_QUADS = {65: 1, 200: 2, 400: 4, 700: 6, 1000: 8, 1300: 12, 1800: 16, 2300: 20, 2600: 24, 3300: 32}
+
+
+@pytest.mark.parametrize("G,N,P", [(300, 65, 129), (513, 1000, 193), (60, 3300, 70)]
+                         + [(60, N, 70) for N in (200, 400, 700, 1300, 1800, 2300, 2600)])
 def test_dense_edges_and_random(eng, orc, cache, G, N, P):
-    """scoary_permute with the gene-order form of the same intervals: register rows (N <= 3072) and the
+    """scoary_permute with the gene-order form of the same intervals: every register row size (N <= 3072) and the
     chunked variant (N = 3300)."""
     import torch
+    assert eng.quads(N) == DENSE_ROW_QUADS[N]           # which instance the shape reaches
     p = _probe_problem(eng, cache, G, N)
     lb = _labels(eng, orc, cache, (G, N), p, P, rows=True)
     for name, lo, hi1 in _families(p):

@@ -138,15 +138,23 @@ def test_stepdown_equals_the_oracle(eng, G, N, T, P, seed):
 
 
 # ---- 2. the kernel alone over synthetic tables: every position informative ---------------------------------------
-@pytest.mark.parametrize("G,N,T,P", [(1100, 100, 2, 70), (1100, 131, 2, 33), (130, 2600, 1, 40), (130, 3300, 1, 40)])
+# tiled row size (quads) of every N used below: which k_stepdown_minp instance the case reaches -- every register row
+# size (1, 2, 4, 6, 8, 12, 16, 20, 24 quads) and the chunked kernel (> 24)
+ROW_QUADS = {100: 1, 131: 2, 200: 2, 400: 4, 700: 6, 900: 8, 1300: 12, 1800: 16, 2300: 20, 2600: 24, 3300: 32}
+
+
+@pytest.mark.parametrize("G,N,T,P", [(1100, 100, 2, 70), (1100, 131, 2, 33), (130, 2600, 1, 40), (130, 3300, 1, 40)]
+                         + [(130, N, 1, 40) for N in (200, 400, 700, 900, 1300, 1800, 2300)])
 def test_raw_counts_over_synthetic_tables(eng, G, N, T, P):
     """The real CSR layout of the p tables filled with random doubles, random label rows (they may leave a gene's
     support: the clamp of the gather is part of the contract), a random rank order and p_sorted drawn from the
     successive minima themselves: counts in mid-range at most positions, exact equalities, a tie run of 40.
     G = 1100 is walked in >= 3 chunks with a ragged last one (both passes); N = 131 / P = 33 are ragged at the quad
-    and the lane; N = 2600 and N = 3300 are the largest register-resident row and the chunked instance."""
+    and the lane; N = 2600 and N = 3300 are the largest register-resident row and the chunked instance; the other
+    (130, N, 1, 40) cases walk the remaining register row sizes, both passes' instances of each."""
     import torch
     from scoary_amd.engine import MinpTables, pack_bits_rows
+    assert eng.quads(N) == ROW_QUADS[N]                 # which instance the shape reaches
     assert (eng.quads(N) > 24) == (N > 3072)
     rng = np.random.default_rng(7000 + N)
     genes, traits = make_sd_data(G, N, T, 5)
@@ -155,25 +163,30 @@ def test_raw_counts_over_synthetic_tables(eng, G, N, T, P):
     real = eng.minp_tables(counts)
     off = real.off.cpu().numpy()
     lo = real.lo.cpu().numpy()
-    tab = rng.random(real.entries)
+    for _draw in range(3):
+        # a draw can come out flat: a one-entry table (the absent or the core gene) with a small p late in the rank
+        # order is the minimum of every position before it.  Then the same stream is drawn from again
+        tab = rng.random(real.entries)
+        labels = (rng.random((T, P, N)) < rng.uniform(0.2, 0.8, (T, P, 1))).astype(np.uint8)
+        order = np.stack([rng.permutation(G) for _ in range(T)]).astype(np.int32)
+        ps = np.empty((T, G))
+        q = []
+        for t in range(T):
+            a = labels[t].astype(np.int64) @ genes.T.astype(np.int64)                       # [P, G]
+            size = np.diff(off)[t * G:(t + 1) * G]
+            idx = np.clip(a - lo[t][None, :], 0, size[None, :] - 1)
+            pperm = tab[off[t * G:(t + 1) * G][None, :] + idx]
+            q.append(np.minimum.accumulate(pperm[:, order[t]][:, ::-1], axis=1)[:, ::-1])
+            ps[t] = np.sort(q[t][rng.integers(0, P, G), np.arange(G)])                     # entries of tab, ascending
+            a0 = 500 if G > 600 else 50
+            ps[t, a0:a0 + 40] = ps[t, a0]                                                  # a run of 40 equal values
+            assert (np.diff(ps[t]) >= 0).all()
+        want_c = np.stack([(q[t] <= ps[t][None, :]).sum(axis=0) for t in range(T)])
+        want_minp = np.stack([q[t][:, 0] for t in range(T)])
+        if ((want_c > 0) & (want_c < P)).mean() > 0.5:
+            break
     tables = MinpTables(real.off, real.lo, torch.from_numpy(tab).to(eng.device), real.entries)
-    labels = (rng.random((T, P, N)) < rng.uniform(0.2, 0.8, (T, P, 1))).astype(np.uint8)
     perms = torch.stack([eng.vecrows(pack_bits_rows(labels[t]), N) for t in range(T)]).contiguous()
-    order = np.stack([rng.permutation(G) for _ in range(T)]).astype(np.int32)
-    ps = np.empty((T, G))
-    q = []
-    for t in range(T):
-        a = labels[t].astype(np.int64) @ genes.T.astype(np.int64)                       # [P, G]
-        size = np.diff(off)[t * G:(t + 1) * G]
-        idx = np.clip(a - lo[t][None, :], 0, size[None, :] - 1)
-        pperm = tab[off[t * G:(t + 1) * G][None, :] + idx]
-        q.append(np.minimum.accumulate(pperm[:, order[t]][:, ::-1], axis=1)[:, ::-1])
-        ps[t] = np.sort(q[t][rng.integers(0, P, G), np.arange(G)])                     # entries of tab, ascending
-        a0 = 500 if G > 600 else 50
-        ps[t, a0:a0 + 40] = ps[t, a0]                                                  # a run of 40 equal values
-        assert (np.diff(ps[t]) >= 0).all()
-    want_c = np.stack([(q[t] <= ps[t][None, :]).sum(axis=0) for t in range(T)])
-    want_minp = np.stack([q[t][:, 0] for t in range(T)])
     # informative: most positions strictly between 0 and P, and the exact-equality case occurs
     assert ((want_c > 0) & (want_c < P)).mean() > 0.5
     assert sum(int((q[t] == ps[t][None, :]).sum()) for t in range(T)) >= 10

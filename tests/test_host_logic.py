@@ -754,6 +754,60 @@ def test_build_refuses_a_list_kernel_that_spills_or_grew_static_lds():
             ge.check_kernel_resources(json.load(f))
 
 
+def test_build_rules_cover_minp_stepdown_and_mfma():
+    """The one rule table of the build (RESOURCE_RULES) on synthetic compiler reports: every family beside the lists
+    -- k_permute_minp, k_stepdown_minp, k_permute_mfma -- fails the build on a missing instance, on scratch or a
+    spill, and on its register cap (128 VGPRs register-resident, VGPRs + AGPRs <= 256 for the matrix-core kernel);
+    the chunked instances carry no cap; the message names the kernel and the figure."""
+    import __graft_entry__ as ge
+    rq = (1, 2, 4, 6, 8, 12, 16, 20, 24)
+    minp = ["14k_permute_minpILi%dE" % q for q in rq]
+    sd = ["15k_stepdown_minpILi%dELb%dE" % (q, c) for q in rq for c in (0, 1)]
+    minp_chunked = ["22k_permute_minp_chunkedILi8ELi8E"]
+    sd_chunked = ["23k_stepdown_minp_chunkedILi8ELi8ELb%dE" % c for c in (0, 1)]
+    mfma = ["14k_permute_mfma"]
+    lists = ["15k_permute_listsILi4ELi4ELi%dE" % (11 + i) for i in range(4)] + ["18k_permute_seglistsILi16E"]
+    remarks = _REMARKS.replace("VGPRs: %(vgprs)d", "VGPRs: %(vgprs)d [-Rpass-analysis=kernel-resource-usage]\n"
+                               "x.hip:1:1: remark:     AGPRs: %(agprs)d", 1)
+
+    def report(changed=(), drop=(), **kw):
+        text = ""
+        for name in lists + minp + minp_chunked + sd + sd_chunked + mfma + ["8k_fisher"]:
+            if name in drop:
+                continue
+            vals = dict(vgprs=128, agprs=128 if name in mfma else 0, scratch=64 if name == "8k_fisher" else 0,
+                        spill=0, lds=0)
+            if name in changed:
+                vals.update(kw)
+            text += remarks.replace("15k_permute_listsILi4ELi4ELi11E", name) % vals
+        return ge.parse_resource_usage(text)
+
+    ok = report()
+    assert len(ok) == 5 + 9 + 1 + 18 + 2 + 1 + 1 and all("AGPRs" in v for v in ok.values())
+    ge.check_kernel_resources(ok, ge.RESOURCE_RULES)      # 128 VGPRs, 128 + 128 registers, scratch in k_fisher: fine
+    for family in (minp, sd, mfma, minp_chunked, sd_chunked):
+        one = family[-1]
+        with pytest.raises(RuntimeError, match="expected %d " % len(family)):
+            ge.check_kernel_resources(report(drop=[one]), ge.RESOURCE_RULES)
+        for bad, word in ((dict(scratch=16), "scratch 16"), (dict(spill=3), "VGPR spills 3")):
+            with pytest.raises(RuntimeError, match="%s.*%s" % (one, word)):
+                ge.check_kernel_resources(report([one], **bad), ge.RESOURCE_RULES)
+    for one in (minp[3], sd[0], sd[17]):                  # register-resident: the cap holds for every instance
+        with pytest.raises(RuntimeError, match=one + ".*129 VGPRs > 128"):
+            ge.check_kernel_resources(report([one], vgprs=129), ge.RESOURCE_RULES)
+    with pytest.raises(RuntimeError, match=r"k_permute_mfma.*129 VGPRs \+ 128 AGPRs > 256"):
+        ge.check_kernel_resources(report(mfma, vgprs=129), ge.RESOURCE_RULES)
+    with pytest.raises(RuntimeError, match=r"k_permute_mfma.*128 VGPRs \+ 129 AGPRs > 256"):
+        ge.check_kernel_resources(report(mfma, agprs=129), ge.RESOURCE_RULES)
+    ge.check_kernel_resources(report(minp_chunked + sd_chunked, vgprs=129), ge.RESOURCE_RULES)   # no cap there
+    with pytest.raises(RuntimeError, match="k_permute_minpILi2E.* uses 8 bytes of scratch"):       # the global rule
+        ge.check_kernel_resources(report([minp[1]], scratch=8), ())
+    # the library that is actually in the tree passed the whole table when it was built
+    if os.path.exists(ge.HIP_RESOURCES):
+        with open(ge.HIP_RESOURCES) as f:
+            ge.check_kernel_resources(json.load(f), ge.RESOURCE_RULES)
+
+
 def test_bench_refuses_counters_of_other_kernel_sources(tmp_path, monkeypatch):
     """roofline counters come from a profiles/ file that records the hash
     of the kernel sources it was collected from; a summary of other sources is refused

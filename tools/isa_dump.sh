@@ -20,9 +20,10 @@ for line in open(out + "/unit.dis"):
         name, body = m.group(1), []
         continue
     if name:
-        # drop addresses and encodings: mnemonic + operands only
+        # drop addresses and encodings: mnemonic + operands only; "..." is objdump's elision of the zero
+        # padding after s_endpgm, not an instruction
         t = line.split("//")[0].strip()
-        if t: body.append(re.sub(r"\s+", " ", t))
+        if t and t != "...": body.append(re.sub(r"\s+", " ", t))
 if name: res[name] = body
 for k, b in sorted(res.items()):
     print("%s  %6d instr  %s" % (hashlib.sha256("\n".join(b).encode()).hexdigest()[:16], len(b), k))

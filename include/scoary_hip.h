@@ -326,6 +326,43 @@ int scoary_perm_generate_tiles_range(scoary_handle h, const uint32_t *d_masks,
                                      int64_t perm_base, int64_t trait_base, uint64_t seed,
                                      int64_t first_tile, int64_t n_tiles, uint32_t *d_tiles,
                                      scoary_stream_t stream);
+/* ---- labels shuffled within strata (spec S9 of DESIGN.md; additive, ABI 11) --------------
+ * Restricted exchangeability: d_strata[i] in [0, S) names the stratum (lineage, cluster, ...) of isolate i,
+ * the same for all traits.  Independently for every stratum the trait's npos_ts positives among the
+ * stratum's members lie on a uniformly random subset of its nval_ts valid members: S4's plan per
+ * (trait, stratum), S4's round 0 with the stratum's q, and the fix-up per (permutation, stratum) over the
+ * stratum's members (Philox counter ((s << 20) | (draw >> 2), pi, trait, "SCOD")).  With S = 1 the labels
+ * are scoary_perm_generate's bit for bit.  npos and nval of the trait are unchanged, so margins, crit and
+ * the p tables of the unstratified path stay valid and every consumer of label rows / tiles takes these.
+ *   d_strata   : uint16 [N]
+ *   d_members  : int32 [N], the isolates ordered by (stratum, index)
+ *   d_offsets  : int32 [S + 1], members of stratum s = d_members[d_offsets[s] .. d_offsets[s + 1]);
+ *                d_offsets[0] = 0 and d_offsets[S] = N.  A DEVICE array: that it partitions [0, N) is
+ *                checked by the caller on its host copy (scoary_amd/engine.py: strata_plan); the kernel
+ *                clamps every index it derives, so a bad table gives wrong labels, not a wild access
+ *   d_smargins : int32 [T][S][2] = (npos_ts, nval_ts), written by scoary_strata_margins from the label rows
+ *                d_labels and validity rows d_masks (vecrows [T][Wp])
+ * S <= scoary_perm_max_strata(), N <= scoary_perm_strata_max_isolates() (unsegmented label tiles),
+ * T <= 65535, permutation indices < 2^32: SCOARY_ERR_SIZE otherwise.  Rows: vecrows [T][P][Wp]; tiles: the
+ * layout and the (first_tile, n_tiles) range of scoary_perm_generate_tiles_range, perm_base a multiple
+ * of 32. */
+int scoary_perm_max_strata(void);
+int64_t scoary_perm_strata_max_isolates(void);
+int scoary_strata_margins(scoary_handle h, const uint32_t *d_labels, const uint32_t *d_masks,
+                          const uint16_t *d_strata, int64_t T, int64_t N, int64_t S,
+                          int32_t *d_smargins, scoary_stream_t stream);
+int scoary_perm_generate_strata(scoary_handle h, const uint32_t *d_masks, const uint16_t *d_strata,
+                                const int32_t *d_members, const int32_t *d_offsets,
+                                const int32_t *d_smargins, int64_t T, int64_t N, int64_t S, int64_t P,
+                                int64_t perm_base, int64_t trait_base, uint64_t seed,
+                                uint32_t *d_perms, scoary_stream_t stream);
+int scoary_perm_generate_tiles_strata_range(scoary_handle h, const uint32_t *d_masks,
+                                            const uint16_t *d_strata, const int32_t *d_members,
+                                            const int32_t *d_offsets, const int32_t *d_smargins,
+                                            int64_t T, int64_t N, int64_t S, int64_t P,
+                                            int64_t perm_base, int64_t trait_base, uint64_t seed,
+                                            int64_t first_tile, int64_t n_tiles, uint32_t *d_tiles,
+                                            scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

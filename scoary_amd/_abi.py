@@ -12,6 +12,10 @@ LIB_PATH = os.environ.get("SCOARY_HIP_LIB") or os.path.join(_HERE, "csrc", "libs
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "scoary_hip.h")
 
 ABI_VERSION = 11
+# scoary_perm_max_strata() / scoary_perm_strata_max_isolates(): what the stratified label generator takes, known
+# here so that the command line can refuse a strata file before the library is loaded (load() compares)
+PERM_MAX_STRATA = 1024
+PERM_STRATA_MAX_ISOLATES = 20479
 
 _i64, _u64, _i32, _vp, _cp = (ctypes.c_int64, ctypes.c_uint64, ctypes.c_int,
                               ctypes.c_void_p, ctypes.c_char_p)
@@ -58,6 +62,11 @@ SIGNATURES = {
     "scoary_perm_generate_tiles_range": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _u64, _i64,
                                                 _i64, _vp, _vp]),
     "scoary_perm_max_isolates": (_i64, []),
+    "scoary_perm_max_strata": (_i32, []),
+    "scoary_perm_strata_max_isolates": (_i64, []),
+    "scoary_strata_margins": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "scoary_perm_generate_strata": (_i32, [_vp] * 6 + [_i64] * 6 + [_u64, _vp, _vp]),
+    "scoary_perm_generate_tiles_strata_range": (_i32, [_vp] * 6 + [_i64] * 6 + [_u64, _i64, _i64, _vp, _vp]),
     "scoary_permute_lists_scratch_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "scoary_permute_lists": (_i32, [_vp, _vp, _vp, _i64] + [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp,
                                                                        _i32, _vp]),
@@ -122,5 +131,8 @@ def load():
     got = lib.scoary_abi_version()
     if got != ABI_VERSION:
         raise ScoaryHipError("ABI version mismatch: library %d, binding %d" % (got, ABI_VERSION))
+    if (lib.scoary_perm_max_strata(), lib.scoary_perm_strata_max_isolates()) != \
+            (PERM_MAX_STRATA, PERM_STRATA_MAX_ISOLATES):
+        raise ScoaryHipError("the library's strata limits differ from the binding's")
     _lib = lib
     return lib

@@ -25,6 +25,9 @@
 // done: N * NB * 4 bytes (NB = 1 or 2 by how many blocks the launch has).  Beyond N = 40 000 a
 // row keeps only 16 / 8 / ... 1 of the 32 permutations of a dword (more Philox work per label,
 // still parallel in N).
+//
+// k_labels_strata (spec S9, further down) shuffles within strata: the same block shape, round 0 and output code,
+// the plan and the fix-up per stratum.
 #include "scoary_common.hpp"
 
 namespace {
@@ -99,6 +102,123 @@ struct LabelArgs {
   uint32_t* out;
 };
 
+// What a block of k_labels_strata produces: (trait, NB dword columns of 32 permutations).  The block map of
+// k_labels with all 32 permutations of a column in one block (k_labels keeps its own inline copy, sub-dword
+// rows included: it is tuned, and its register allocation stays where it is).
+template <int NB>
+struct LabelBlock {
+  int t;
+  uint32_t Bglob;            // Philox block of column 0
+  uint32_t* tile_base;       // tiles: row 0, column `col` of the block's tile
+  uint32_t live[NB];         // permutations of column w that exist, as a mask over the 32 bits of the Philox block
+};
+// false: the block has nothing to do (the padding of a tile launch)
+template <int NB, int OUT>
+__device__ __forceinline__ bool label_block(const LabelArgs& a, LabelBlock<NB>& b) {
+  int64_t lc0 = 0;                                   // tiles: dword column among this launch's permutations
+  b.tile_base = nullptr;
+  if constexpr (OUT == 0) {
+    // the units of one tile get block ids that are equal mod 8 (one XCD, one L2), as in k_labels
+    const int units = a.TW / NB;
+    const int64_t id = blockIdx.x;
+    const int64_t qd = id >> 3;
+    const int col = (int)(qd % units) * NB;
+    const int64_t fl = (qd / units) * 8 + (id & 7);
+    if (fl >= a.nflat) return false;
+    const int64_t f = a.first_flat + fl;
+    b.t = (int)(f / a.ntiles);
+    lc0 = (f % a.ntiles) * a.TW + col;
+    b.Bglob = (uint32_t)((a.perm_base >> 5) + lc0);
+    b.tile_base = a.out + f * list_tile_dwords(a.N, a.TW) + col;
+  } else {
+    b.t = blockIdx.y;
+    b.Bglob = (uint32_t)((a.perm_base >> 5) + blockIdx.x);
+  }
+#pragma unroll
+  for (int w = 0; w < NB; ++w) {
+    int64_t lo, hi;                                  // bits [lo, hi) of the block exist
+    if constexpr (OUT == 0) {
+      lo = 0;
+      hi = a.P - (lc0 + w) * 32;
+    } else {
+      const int64_t first = (int64_t)(b.Bglob + w) * 32;
+      lo = a.perm_base - first;
+      hi = a.perm_base + a.P - first;
+    }
+    lo = lo < 0 ? 0 : (lo > 32 ? 32 : lo);
+    hi = hi < 0 ? 0 : (hi > 32 ? 32 : hi);
+    const uint32_t below_hi = hi >= 32 ? 0xffffffffu : ((1u << hi) - 1u);
+    const uint32_t below_lo = lo >= 32 ? 0xffffffffu : ((1u << lo) - 1u);
+    b.live[w] = hi > lo ? (below_hi & ~below_lo) : 0u;
+  }
+  return true;
+}
+
+// Output of a block whose rows are final: row_field(row, w) = the labels of isolate `row`, column w
+template <int NB, int OUT, class RowField>
+__device__ __forceinline__ void emit_labels(const LabelArgs& a, int t, int bit0, uint32_t Bglob, uint32_t* tile_base,
+                                            const uint32_t (&live)[NB], RowField row_field) {
+  const int tid = threadIdx.x, lane = tid & 63, tpb = blockDim.x, nwaves = tpb >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int N = a.N, elt = 1 << a.elt_log2;
+  if constexpr (OUT == 0) {
+    const bool seg = a.TW == kSegTW;                  // two-dword tiles: segmented above N = 20479
+    auto row_off = [&](int64_t row) -> int64_t { return seg ? list_row_dword(N, row) : row * a.TW; };
+    if (elt == 32) {
+      for (int row = tid; row < N; row += tpb) {
+        uint32_t* dst = tile_base + row_off(row);
+        if constexpr (NB == 2) {
+          *reinterpret_cast<uint2*>(dst) = make_uint2(row_field(row, 0), row_field(row, 1));
+        } else {
+          dst[0] = row_field(row, 0);
+        }
+      }
+    } else {                                          // 16 / 8 permutations of the dword: narrow stores
+      for (int row = tid; row < N; row += tpb) {
+        uint8_t* dst = reinterpret_cast<uint8_t*>(tile_base + row_off(row)) + (bit0 >> 3);
+        const uint32_t f = row_field(row, 0);
+        if (elt == 16) *reinterpret_cast<uint16_t*>(dst) = (uint16_t)f;
+        else *dst = (uint8_t)f;
+      }
+    }
+    // the all-zero row(s) list padding points at: one per segment
+    const int nseg = seg ? list_segments(N) : 1;
+    if (tid < nseg) {
+      const int64_t z = nseg > 1 ? (int64_t)tid * kSegStride + list_seg_rows(N, tid) * kSegTW : row_off(N);
+      if (elt == 32) {
+#pragma unroll
+        for (int w = 0; w < NB; ++w) tile_base[z + w] = 0u;
+      } else {
+        uint8_t* dst = reinterpret_cast<uint8_t*>(tile_base + z) + (bit0 >> 3);
+        if (elt == 16) *reinterpret_cast<uint16_t*>(dst) = 0;
+        else *dst = 0;
+      }
+    }
+  } else {
+    static_assert(OUT == 0 || NB == 1, "bit rows: one dword column per block");
+    // permutation-major rows: 64 isolates per wavefront step, one ballot per permutation
+    const int nchunks = (N + 63) >> 6;
+    const int64_t pl = (int64_t)Bglob * 32 + bit0 + lane - a.perm_base;   // lane < elt: its permutation
+    const bool mine = lane < elt && ((live[0] >> (bit0 + (lane & 31))) & 1u);
+    uint32_t* prow = a.out + ((int64_t)t * a.P + (mine ? pl : 0)) * a.Wp;
+    for (int c = wave; c < nchunks; c += nwaves) {
+      const int row = c * 64 + lane;
+      const uint32_t f = row < N ? row_field(row, 0) : 0u;
+      uint32_t lo = 0u, hi = 0u;
+      for (int j = 0; j < elt; ++j) {
+        const uint64_t m64 = __ballot((f >> j) & 1u);
+        if (lane == j) {
+          lo = (uint32_t)m64;
+          hi = (uint32_t)(m64 >> 32);
+        }
+      }
+      if (mine) *reinterpret_cast<uint2*>(prow + 2 * c) = make_uint2(lo, hi);
+    }
+    if (mine)
+      for (int k = 2 * nchunks + wave; k < a.Wp; k += nwaves) prow[k] = 0u;
+  }
+}
+
 // NB dword columns per block (NB > 1 only with all 32 permutations per dword); OUT 0: tiles, 1: rows
 template <int NB, int OUT>   // NB = 1, 2
 __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
@@ -109,6 +229,8 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
   const int elt = 1 << a.elt_log2;                  // permutation bits a row keeps per column
   const int subs = 32 >> a.elt_log2;                // blocks that share one dword column
   // ---- which (trait, dword column(s), bits) this block produces ----
+  // (label_block() above is a second copy of this map and of the live masks, for k_labels_strata: a change of
+  // the XCD mapping or of the tile layout has to be made in both)
   int t, bit0;
   uint32_t Bglob;                                    // Philox block of column 0
   int64_t lc0 = 0;                                   // tiles: dword column among this launch's permutations
@@ -362,62 +484,224 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
     }
     return f;
   };
-  if constexpr (OUT == 0) {
-    const bool seg = a.TW == kSegTW;                  // two-dword tiles: segmented above N = 20479
-    auto row_off = [&](int64_t row) -> int64_t { return seg ? list_row_dword(N, row) : row * a.TW; };
-    if (elt == 32) {
-      for (int row = tid; row < N; row += tpb) {
-        uint32_t* dst = tile_base + row_off(row);
-        if constexpr (NB == 2) {
-          *reinterpret_cast<uint2*>(dst) = make_uint2(row_field(row, 0), row_field(row, 1));
-        } else {
-          dst[0] = row_field(row, 0);
-        }
-      }
-    } else {                                          // 16 / 8 permutations of the dword: narrow stores
-      for (int row = tid; row < N; row += tpb) {
-        uint8_t* dst = reinterpret_cast<uint8_t*>(tile_base + row_off(row)) + (bit0 >> 3);
-        const uint32_t f = row_field(row, 0);
-        if (elt == 16) *reinterpret_cast<uint16_t*>(dst) = (uint16_t)f;
-        else *dst = (uint8_t)f;
-      }
-    }
-    // the all-zero row(s) list padding points at: one per segment
-    const int nseg = seg ? list_segments(N) : 1;
-    if (tid < nseg) {
-      const int64_t z = nseg > 1 ? (int64_t)tid * kSegStride + list_seg_rows(N, tid) * kSegTW : row_off(N);
-      if (elt == 32) {
+  emit_labels<NB, OUT>(a, t, bit0, Bglob, tile_base, live, row_field);
+}
+
+// ---- spec S9: labels shuffled within strata ------------------------------------------------------
+// Restricted exchangeability: every stratum s (isolates mem_s[0..n_s), any partition of the isolates the caller
+// supplies) keeps its own npos_ts positives, placed uniformly on its nval_ts valid members; the strata are
+// independent.  The plan (m, flip, q) is S4's per (trait, stratum), round 0 is S4's bern_word with the
+// stratum's q, and the fix-up runs per (permutation, stratum) over the stratum's members with the stratum in
+// the Philox counter -- with one stratum this is S4 bit for bit.
+constexpr int kMaxStrata = 1024;                // the per-stratum table of a block: 16 bytes each in LDS
+constexpr int kStrataMaxIsolates = 20479;       // unsegmented tiles; members are 16-bit in LDS
+
+struct StrataArgs {
+  const uint16_t* strata;    // [N] stratum of every isolate
+  const int32_t* members;    // [N] isolates by (stratum, index)
+  const int32_t* offsets;    // [S + 1] first member of every stratum; offsets[S] = N
+  const int32_t* smargins;   // [T][S][2] = (npos_ts, nval_ts)
+  int S;
+};
+
+// NB dword columns of 32 permutations per block; OUT 0: tiles, 1: rows.  The block shape of k_labels.
+template <int NB, int OUT>   // NB = 1, 2
+__global__ __launch_bounds__(1024) void k_labels_strata(const LabelArgs a, const StrataArgs sa) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  const int tid = threadIdx.x, lane = tid & 63, tpb = blockDim.x;
+  const int N = a.N, S = sa.S;
+  LabelBlock<NB> blk;
+  if (!label_block<NB, OUT>(a, blk)) return;
+  const int t = blk.t;
+  const uint32_t Bglob = blk.Bglob;
+  uint32_t live[NB];
 #pragma unroll
-        for (int w = 0; w < NB; ++w) tile_base[z + w] = 0u;
-      } else {
-        uint8_t* dst = reinterpret_cast<uint8_t*>(tile_base + z) + (bit0 >> 3);
-        if (elt == 16) *reinterpret_cast<uint16_t*>(dst) = 0;
-        else *dst = 0;
-      }
+  for (int w = 0; w < NB; ++w) live[w] = blk.live[w];
+  const uint32_t tglob = (uint32_t)(a.trait_base + t);
+  const uint32_t* mrow = a.masks + (int64_t)t * a.Wp;
+
+  // ---- LDS: rows (NB dwords per isolate), validity words, the stratum table, the members ----
+  const int nmw = (N + 31) >> 5;
+  uint32_t* xs = lds;
+  uint32_t* vm = xs + (((int64_t)N * NB + 3) & ~3);
+  uint4* tab = reinterpret_cast<uint4*>(vm + ((nmw + 3) & ~3));    // (m, n_s, 2^32 mod n_s, offset | q << 16 | flip << 24)
+  uint16_t* mem = reinterpret_cast<uint16_t*>(tab + S);
+  for (int k = tid; k < nmw; k += tpb) vm[k] = mrow[k];
+  for (int s = tid; s < S; s += tpb) {
+    // (a table that does not partition [0, N) is refused on the host; the clamps keep every index inside)
+    const int off = min(max(sa.offsets[s], 0), N);
+    const int n = min(max(sa.offsets[s + 1] - off, 0), N - off);
+    const int32_t* mg = sa.smargins + ((int64_t)t * S + s) * 2;
+    const LabelPlan plan = label_plan(mg[0], mg[1]);
+    const uint32_t rej = n > 0 ? (0u - (uint32_t)n) % (uint32_t)n : 0u;        // 2^32 mod n_s
+    tab[s] = make_uint4(plan.m, (uint32_t)n, rej, (uint32_t)off | (plan.q << 16) | ((plan.flip ? 1u : 0u) << 24));
+  }
+  for (int k = tid; k < N; k += tpb) mem[k] = (uint16_t)min(max(sa.members[k], 0), N - 1);
+  __syncthreads();
+  auto stratum_of = [&](int row) -> uint32_t { return tab[min((int)sa.strata[row], S - 1)].w; };
+
+  // ---- round 0: lane = isolate, q by the isolate's stratum ----
+  for (int row = tid; row < N; row += tpb) {
+    const bool valid = (vm[row >> 5] >> (row & 31)) & 1u;
+    uint32_t x[NB];
+#pragma unroll
+    for (int w = 0; w < NB; ++w) x[w] = 0u;
+    if (valid) {
+      const uint32_t q = (stratum_of(row) >> 16) & 0xffu;
+#pragma unroll
+      for (int w = 0; w < NB; ++w)
+        x[w] = bern_word((uint32_t)row, Bglob + (uint32_t)w, tglob, q, a.k0, a.k1) & live[w];
     }
-  } else {
-    static_assert(OUT == 0 || NB == 1, "bit rows: one dword column per block");
-    // permutation-major rows: 64 isolates per wavefront step, one ballot per permutation
-    const int nchunks = (N + 63) >> 6;
-    const int64_t pl = (int64_t)Bglob * 32 + bit0 + lane - a.perm_base;   // lane < elt: its permutation
-    const bool mine = lane < elt && ((live[0] >> (bit0 + (lane & 31))) & 1u);
-    uint32_t* prow = a.out + ((int64_t)t * a.P + (mine ? pl : 0)) * a.Wp;
-    for (int c = wave; c < nchunks; c += nwaves) {
-      const int row = c * 64 + lane;
-      const uint32_t f = row < N ? row_field(row, 0) : 0u;
-      uint32_t lo = 0u, hi = 0u;
-      for (int j = 0; j < elt; ++j) {
-        const uint64_t m64 = __ballot((f >> j) & 1u);
-        if (lane == j) {
-          lo = (uint32_t)m64;
-          hi = (uint32_t)(m64 >> 32);
+    if constexpr (NB == 2) {
+      *reinterpret_cast<uint2*>(xs + (int64_t)row * 2) = make_uint2(x[0], x[1]);
+    } else {
+      xs[row] = x[0];
+    }
+  }
+  __syncthreads();
+
+  // ---- fix-up: the group of L lanes of a permutation walks the strata ----
+  // Per stratum: K = the permutation's marks among the members (marks sit on valid isolates only), then
+  // k_labels' fix-up against mem_s.  While at least four marks per call are missing, lane l takes Philox call
+  // base + l (any order gives the sequential result).  The last < 4 marks have to go draw by draw -- one lane's
+  // work -- but strata are independent (their members are disjoint), so the group walks L strata, leaves the
+  // tail of stratum s0 + l to lane l, and the L tails run side by side: at eight isolates per stratum nearly
+  // every stratum is all tail, and one active lane per group would cost a Philox call per stratum and wavefront.
+  // The loops over the strata are uniform for the block, the batched rounds for the group.
+  {
+    const int nperm = 32 * NB;
+    const int L = min(kWave, tpb / nperm);               // a power of two, >= 2
+    const int pidx = tid / L, l = tid & (L - 1);
+    const bool in_group = pidx < nperm;                  // tpb > 64 * nperm: the last wavefronts idle
+    const int w = pidx >> 5, j = pidx & 31;
+    const bool alive = in_group && (((w ? live[NB - 1] : live[0]) >> j) & 1u);
+    const uint32_t pi = (Bglob + (uint32_t)w) * 32u + (uint32_t)j;
+    const uint32_t bitj = 1u << j;
+    const uint64_t gmask = (L == 64 ? ~(uint64_t)0 : (((uint64_t)1 << L) - 1)) << (lane & ~(L - 1));
+    // one draw against stratum (n, reject_below, off): Lemire rejection, then the member at the position;
+    // returns 1 if the bit changed (k_labels: draw1)
+    auto draw1 = [&](uint32_t rnd, bool add, uint32_t n, uint32_t reject_below, uint32_t off) -> int {
+      const uint64_t prod = (uint64_t)rnd * (uint64_t)n;
+      if ((uint32_t)prod < reject_below) return 0;
+      const uint32_t pos = mem[off + (uint32_t)(prod >> 32)];
+      uint32_t* x = &xs[pos * NB + w];
+      if (add) {
+        if (!((vm[pos >> 5] >> (pos & 31u)) & 1u)) return 0;
+        return (__hip_atomic_fetch_or(x, bitj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & bitj) ? 0 : 1;
+      }
+      return (__hip_atomic_fetch_and(x, ~bitj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & bitj) ? 1 : 0;
+    };
+    for (int s0 = 0; s0 < S; s0 += L) {
+      int my_d = 0;                                      // stratum s0 + l: marks its tail has to add (> 0) / remove
+      uint32_t my_base = 0;                              // ... and its next Philox call
+      const int s1 = min(S, s0 + L);
+      for (int s = s0; s < s1; ++s) {
+        const uint4 e = tab[s];
+        const uint32_t n = e.y, reject_below = e.z, off = e.w & 0xffffu;
+        if (n == 0u) continue;
+        int K = 0;
+        if (alive)
+          for (uint32_t k = (uint32_t)l; k < n; k += (uint32_t)L) K += (xs[(uint32_t)mem[off + k] * NB + w] >> j) & 1u;
+        for (int o = 1; o < L; o <<= 1) K += __shfl_xor(K, o);
+        int d = alive ? (int)e.x - K : 0;                // > 0: add marks, < 0: remove
+        // four draws of one Philox call; the toggles are LDS atomics whose returned old word says whether THIS
+        // lane changed the bit (k_labels: draws4)
+        auto draws4 = [&](const uint32_t (&rnd)[4], bool add) -> int {
+          uint32_t idx[4];
+          bool ok[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const uint64_t prod = (uint64_t)rnd[u] * (uint64_t)n;
+            const uint32_t pos = mem[off + (uint32_t)(prod >> 32)];
+            idx[u] = pos * NB + w;
+            ok[u] = (uint32_t)prod >= reject_below;
+            if (add) ok[u] = ok[u] && ((vm[pos >> 5] >> (pos & 31u)) & 1u);
+          }
+          uint32_t old[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            old[u] = add ? bitj : 0u;
+            if (ok[u])
+              old[u] = add ? __hip_atomic_fetch_or(&xs[idx[u]], bitj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+                           : __hip_atomic_fetch_and(&xs[idx[u]], ~bitj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
+          int won = 0;
+#pragma unroll
+          for (int u = 0; u < 4; ++u) won += add ? ((old[u] & bitj) ? 0 : 1) : ((old[u] & bitj) ? 1 : 0);
+          return won;
+        };
+        const uint32_t cs = (uint32_t)s << 20;           // the stratum in the counter: calls stay below 2^20
+        uint32_t base = 0;                               // next Philox call of this (permutation, stratum)
+        while ((d >= 4 || d <= -4) && base < kFixMaxCalls) {   // group-uniform: rounds that cannot overshoot
+          const bool add = d > 0;
+          const int need = add ? d : -d;
+          const int k = min(min(L, need >> 2), (int)(kFixMaxCalls - base));
+          uint32_t r[4];
+          int won = 0;
+          if (l < k) {
+            philox4x32_10(cs | (base + (uint32_t)l), pi, tglob, kDomFix, a.k0, a.k1, r);
+            won = draws4(r, add);
+          }
+          int got = 0;
+#pragma unroll
+          for (int bitn = 0; bitn < 3; ++bitn)
+            got += __popcll(__ballot((won >> bitn) & 1) & gmask) << bitn;
+          d = add ? d - got : d + got;
+          base += (uint32_t)k;
+        }
+        if (l == s - s0) my_d = d, my_base = base;       // |d| < 4 (or the safety stop): the tail
+      }
+      // the tails of the L strata, lane l in the draw order of stratum s0 + l
+      if (my_d != 0) {
+        const uint4 e = tab[s0 + l];
+        const uint32_t cs = (uint32_t)(s0 + l) << 20;
+        const bool add = my_d > 0;
+        int left = add ? my_d : -my_d;
+        while (left > 0 && my_base < kFixMaxCalls) {
+          uint32_t r[4];
+          philox4x32_10(cs | my_base, pi, tglob, kDomFix, a.k0, a.k1, r);
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (left > 0) left -= draw1(r[u], add, e.y, e.z, e.w & 0xffffu);
+          ++my_base;
         }
       }
-      if (mine) *reinterpret_cast<uint2*>(prow + 2 * c) = make_uint2(lo, hi);
     }
-    if (mine)
-      for (int k = 2 * nchunks + wave; k < a.Wp; k += nwaves) prow[k] = 0u;
   }
+  __syncthreads();
+
+  // ---- output: marks, or per stratum their complement among the valid isolates ----
+  auto row_field = [&](int row, int w) -> uint32_t {
+    uint32_t f = xs[(int64_t)row * NB + w];
+    if ((stratum_of(row) >> 24) & 1u) {
+      const bool valid = (vm[row >> 5] >> (row & 31)) & 1u;
+      f = valid ? (~f & live[w]) : 0u;
+    }
+    return f;
+  };
+  emit_labels<NB, OUT>(a, t, 0, Bglob, blk.tile_base, live, row_field);
+}
+
+// (npos_ts, nval_ts) of every (trait, stratum): one block per trait, a histogram over the strata in LDS
+__global__ __launch_bounds__(256) void k_strata_margins(const uint32_t* __restrict__ labels,
+                                                        const uint32_t* __restrict__ masks,
+                                                        const uint16_t* __restrict__ strata, int N, int Wp, int S,
+                                                        int32_t* __restrict__ out) {
+  __shared__ int hist[2 * kMaxStrata];
+  const int t = blockIdx.x, tid = threadIdx.x;
+  for (int k = tid; k < 2 * S; k += blockDim.x) hist[k] = 0;
+  __syncthreads();
+  const uint32_t* lrow = labels + (int64_t)t * Wp;
+  const uint32_t* mrow = masks + (int64_t)t * Wp;
+  for (int row = tid; row < N; row += blockDim.x) {
+    const uint32_t valid = (mrow[row >> 5] >> (row & 31)) & 1u;
+    if (!valid) continue;
+    const int s = min((int)strata[row], S - 1);
+    if ((lrow[row >> 5] >> (row & 31)) & 1u) atomicAdd(&hist[2 * s], 1);
+    atomicAdd(&hist[2 * s + 1], 1);
+  }
+  __syncthreads();
+  for (int k = tid; k < 2 * S; k += blockDim.x) out[(int64_t)t * 2 * S + k] = hist[k];
 }
 
 // ---- launch geometry --------------------------------------------------------------------------
@@ -462,6 +746,38 @@ int launch_labels(scoary_handle h, hipStream_t s, const LabelArgs& a, dim3 grid,
   }
   hipLaunchKernelGGL((k_labels<NB, OUT>), grid, dim3((unsigned)tpb), lds, s, a);
   HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+
+// ---- stratified launches ------------------------------------------------------------------------
+int64_t strata_lds_bytes(int64_t N, int NB, int64_t S) {
+  const int64_t xs = (N * NB + 3) / 4 * 4, vm = ((N + 31) / 32 + 3) / 4 * 4;
+  return (xs + vm + 4 * S + (N + 1) / 2) * 4;
+}
+template <int NB, int OUT>
+int launch_labels_strata(scoary_handle h, hipStream_t s, const LabelArgs& a, const StrataArgs& sa, dim3 grid, int tpb) {
+  const size_t lds = (size_t)strata_lds_bytes(a.N, NB, sa.S);
+  if (tpb < 64 || tpb > 1024 || (tpb & (tpb - 1)) || lds > (size_t)kLabelsMaxLds)
+    return fail(h, SCOARY_ERR_SIZE, "k_labels_strata: rows, members and the stratum table do not fit LDS (or a block "
+                                    "size that is no power of two in 64..1024)");
+  const void* fn = reinterpret_cast<const void*>(&k_labels_strata<NB, OUT>);
+  const int bit = 1 << (16 + NB + 8 * OUT);
+  if (lds > 64 * 1024 && !(h->labels_lds_optin & bit)) {
+    HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLabelsMaxLds));
+    h->labels_lds_optin |= bit;
+  }
+  hipLaunchKernelGGL((k_labels_strata<NB, OUT>), grid, dim3((unsigned)tpb), lds, s, a, sa);
+  HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+// the argument checks the three stratified entry points share; `what` names the entry point
+int strata_check(scoary_handle h, const char* what, bool pointers, int64_t T, int64_t N, int64_t S) {
+  if (!pointers || T < 1 || N < 1 || S < 1)
+    return fail(h, SCOARY_ERR_ARG, std::string(what) + ": bad argument");
+  if (T > 65535) return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": T > 65535");
+  if (S > kMaxStrata) return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more strata than scoary_perm_max_strata()");
+  if (N > kStrataMaxIsolates)
+    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more isolates than scoary_perm_strata_max_isolates()");
   return SCOARY_OK;
 }
 
@@ -559,6 +875,93 @@ int scoary_perm_generate_tiles(scoary_handle h, const uint32_t* d_masks, const i
   const int64_t ntiles = TW && P > 0 ? (P + TW * 32 - 1) / (TW * 32) : 0;
   return scoary_perm_generate_tiles_range(h, d_masks, d_margins, T, N, P, perm_base, trait_base, seed,
                                           0, T * ntiles, d_tiles, stream);
+}
+
+
+// ---- spec S9: within-stratum shuffles ---------------------------------------------------------------
+int scoary_perm_max_strata(void) { return kMaxStrata; }
+int64_t scoary_perm_strata_max_isolates(void) { return kStrataMaxIsolates; }
+
+int scoary_strata_margins(scoary_handle h, const uint32_t* d_labels, const uint32_t* d_masks,
+                          const uint16_t* d_strata, int64_t T, int64_t N, int64_t S, int32_t* d_smargins,
+                          scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (int rc = strata_check(h, "scoary_strata_margins", d_labels && d_masks && d_strata && d_smargins, T, N, S))
+    return rc;
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  KernelTimer kt(h, s, "k_strata_margins");
+  hipLaunchKernelGGL(k_strata_margins, dim3((unsigned)T), dim3(256), 0, s, d_labels, d_masks, d_strata, (int)N,
+                     (int)scoary_row_words(N), (int)S, d_smargins);
+  HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+
+int scoary_perm_generate_strata(scoary_handle h, const uint32_t* d_masks, const uint16_t* d_strata,
+                                const int32_t* d_members, const int32_t* d_offsets, const int32_t* d_smargins,
+                                int64_t T, int64_t N, int64_t S, int64_t P, int64_t perm_base, int64_t trait_base,
+                                uint64_t seed, uint32_t* d_perms, scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (int rc = strata_check(h, "scoary_perm_generate_strata",
+                            d_masks && d_strata && d_members && d_offsets && d_smargins && d_perms && P >= 1 &&
+                                perm_base >= 0 && trait_base >= 0, T, N, S))
+    return rc;
+  if (trait_base + T > 0x7fffffffLL || perm_base + P > 0xffffffffLL)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_strata: permutation index >= 2^32");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  LabelArgs a{};
+  a.masks = d_masks, a.N = (int)N, a.Wp = (int)scoary_row_words(N);
+  a.P = P, a.perm_base = perm_base, a.trait_base = (int)trait_base;
+  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.elt_log2 = 5, a.out = d_perms;
+  const StrataArgs sa{d_strata, d_members, d_offsets, d_smargins, (int)S};
+  const int64_t gx = ((perm_base + P - 1) >> 5) - (perm_base >> 5) + 1;       // Philox blocks touched
+  if (gx > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_strata: grid too large");
+  KernelTimer kt(h, s, "k_perm_generate_strata");
+  return launch_labels_strata<1, 1>(h, s, a, sa, dim3((unsigned)gx, (unsigned)T),
+                                    labels_threads(gx * T, N, h->num_cu));
+}
+
+int scoary_perm_generate_tiles_strata_range(scoary_handle h, const uint32_t* d_masks, const uint16_t* d_strata,
+                                            const int32_t* d_members, const int32_t* d_offsets,
+                                            const int32_t* d_smargins, int64_t T, int64_t N, int64_t S, int64_t P,
+                                            int64_t perm_base, int64_t trait_base, uint64_t seed,
+                                            int64_t first_tile, int64_t n_tiles, uint32_t* d_tiles,
+                                            scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (int rc = strata_check(h, "scoary_perm_generate_tiles_strata_range",
+                            d_masks && d_strata && d_members && d_offsets && d_smargins && d_tiles && P >= 1 &&
+                                perm_base >= 0 && trait_base >= 0 && first_tile >= 0 && n_tiles >= 0, T, N, S))
+    return rc;
+  if (perm_base & 31)
+    return fail(h, SCOARY_ERR_ARG, "scoary_perm_generate_tiles_strata_range: perm_base must be a multiple of 32");
+  if (trait_base + T > 0x7fffffffLL || perm_base + P > 0xffffffffLL)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles_strata_range: permutation index >= 2^32");
+  const int TW = list_tw(N);
+  const int64_t tile_perms = TW * 32;
+  const int64_t ntiles = (P + tile_perms - 1) / tile_perms;
+  if (first_tile + n_tiles > T * ntiles)
+    return fail(h, SCOARY_ERR_ARG, "scoary_perm_generate_tiles_strata_range: tile range past the last (trait, tile)");
+  if (n_tiles == 0) return SCOARY_OK;
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  LabelArgs a{};
+  a.masks = d_masks, a.N = (int)N, a.Wp = (int)scoary_row_words(N);
+  a.P = P, a.perm_base = perm_base, a.trait_base = (int)trait_base;
+  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.elt_log2 = 5;
+  a.ntiles = (int)ntiles, a.TW = TW, a.first_flat = first_tile, a.nflat = n_tiles, a.out = d_tiles;
+  const StrataArgs sa{d_strata, d_members, d_offsets, d_smargins, (int)S};
+  // two dword columns per block by k_labels' rule: >= 2 blocks per CU in the launch and in a CU's LDS
+  const int NB = (2 <= TW && n_tiles * (TW / 2) >= 2 * (int64_t)h->num_cu &&
+                  strata_lds_bytes(N, 2, S) <= kLabelsMaxLds / 2) ? 2 : 1;
+  const int64_t units = TW / NB;
+  const int64_t gx = (n_tiles + 7) / 8 * 8 * units;
+  if (gx > 0x7fffffffLL)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles_strata_range: grid too large");
+  const int tpb = labels_threads(n_tiles * units, N, h->num_cu);
+  KernelTimer kt(h, s, "k_perm_generate_tiles_strata");
+  if (NB == 2) return launch_labels_strata<2, 0>(h, s, a, sa, dim3((unsigned)gx), tpb);
+  return launch_labels_strata<1, 0>(h, s, a, sa, dim3((unsigned)gx), tpb);
 }
 
 }  // extern "C"

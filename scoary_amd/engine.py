@@ -86,6 +86,35 @@ class TraitPlan:
                 and self.versions == (traits._version, masks._version))
 
 
+class StrataPlan:
+    """Strata for within-stratum label shuffles (spec S9; engine.strata_plan): strata int16 [N] (uint16 bit
+    pattern) = the stratum of every isolate, members int32 [N] = the isolates by (stratum, index), offsets int32
+    [S + 1] = the first member of every stratum, smargins int32 [T, S, 2] = (positives, valid isolates) of every
+    (trait, stratum) -- device tensors -- and S, N, T; sizes = the host array of the S stratum sizes.  Valid for
+    exactly the trait / mask rows it was built from."""
+
+    def __init__(self, strata, members, offsets, smargins, S, N, sizes, checked=False):
+        self.strata, self.members, self.offsets, self.smargins = strata, members, offsets, smargins
+        self.S, self.N, self.T, self.sizes = int(S), int(N), int(smargins.shape[0]), sizes
+        if not checked:
+            # the library takes members and offsets as device arrays and cannot look at them: one host copy, here,
+            # whoever built the plan -- the offsets run from 0 to N and the members are the isolates, each once
+            off = offsets.cpu().numpy().astype(np.int64)
+            mem = members.cpu().numpy().astype(np.int64)
+            if off.shape != (self.S + 1,) or off[0] != 0 or off[-1] != self.N or (np.diff(off) < 0).any():
+                raise ValueError("StrataPlan: the stratum offsets must rise from 0 to N = %d in S + 1 = %d entries"
+                                 % (self.N, self.S + 1))
+            if mem.shape != (self.N,) or not np.array_equal(np.sort(mem), np.arange(self.N)):
+                raise ValueError("StrataPlan: members must hold every isolate 0 .. N - 1 exactly once")
+
+    def rows(self, t0, t1):
+        """The plan of the traits [t0, t1) alone (a view: the trait groups of minp())."""
+        if t0 == 0 and t1 == self.T:
+            return self
+        return StrataPlan(self.strata, self.members, self.offsets, self.smargins[t0:t1], self.S, self.N, self.sizes,
+                          checked=True)
+
+
 class Workspace:
     """Device buffers of one associate() step (engine.workspace)."""
 
@@ -374,16 +403,26 @@ class AssociationEngine:
         return int(N) <= int(self.lib.scoary_list_max_isolates())
 
     def perm_generate_tiles(self, masks, margins, N, P, perm_base, seed, out=None, trait_base=0,
-                            tile_range=None):
+                            tile_range=None, strata=None):
         """Label tiles of permutations perm_base .. perm_base + P - 1 (perm_base a multiple of
         32).  ``tile_range`` = (first, count): only these flat (trait, tile) indices of the
         [T][tiles] array are written (scoary_perm_generate_tiles_range) -- one rank's share of a
-        run that all-gathers the rest (dist.LabelShards)."""
+        run that all-gathers the rest (dist.LabelShards).  ``strata``: a StrataPlan of these traits --
+        the labels are shuffled within its strata (spec S9)."""
         torch = _torch()
         T = masks.shape[0]
         if out is None:
             out = self._empty((int(self.lib.scoary_list_tiles_words(N, P, T)),), torch.int32)
-        if tile_range is None:
+        if strata is not None:
+            self._strata_fits(strata, T, N)
+            if tile_range is None:
+                tile_range = (0, self.tiles_per_batch(N, P, T)[0])
+            self._check(self.lib.scoary_perm_generate_tiles_strata_range(
+                self.h, self._ptr(masks), self._ptr(strata.strata), self._ptr(strata.members),
+                self._ptr(strata.offsets), self._ptr(strata.smargins), T, N, strata.S, P, perm_base, trait_base,
+                ctypes.c_uint64(seed), int(tile_range[0]), int(tile_range[1]), self._ptr(out), self._stream()),
+                "scoary_perm_generate_tiles_strata_range")
+        elif tile_range is None:
             self._check(self.lib.scoary_perm_generate_tiles(
                 self.h, self._ptr(masks), self._ptr(margins), T, N, P, perm_base, trait_base,
                 ctypes.c_uint64(seed), self._ptr(out), self._stream()), "scoary_perm_generate_tiles")
@@ -515,12 +554,63 @@ class AssociationEngine:
         return int(self.lib.scoary_fisher_scipy_max_isolates())
 
     # -- a8 / a7: permutations -------------------------------------------------
-    def perm_generate(self, masks, margins, N, P, perm_base, seed, out=None, trait_base=0):
+    def strata_max(self):
+        """(most strata, most isolates) the stratified label generator takes."""
+        return int(self.lib.scoary_perm_max_strata()), int(self.lib.scoary_perm_strata_max_isolates())
+
+    def strata_plan(self, strata_host, trait_rows, mask_rows, N, S=None):
+        """The StrataPlan of ``strata_host`` (N integers in [0, S); S = the largest + 1 unless given) for the
+        label rows ``trait_rows`` and validity rows ``mask_rows`` (vecrows [T, Wp], as trait_plan takes them).
+        Members and offsets are built on the host (StrataPlan checks a host copy of them, also for a plan put
+        together by hand: the library takes them as device arrays), the per-stratum margins by k_strata_margins."""
+        torch = _torch()
+        N = int(N)
+        st = np.asarray(strata_host)
+        if st.ndim != 1 or st.shape[0] != N or N < 1 or not np.issubdtype(st.dtype, np.integer):
+            raise ValueError("strata_plan: strata must be %d integers, one per isolate" % N)
+        st = st.astype(np.int64)
+        S = int(st.max()) + 1 if S is None else int(S)
+        max_s, max_n = self.strata_max()
+        if st.min() < 0 or st.max() >= S:
+            raise ValueError("strata_plan: stratum indices must lie in [0, S)")
+        if S > max_s:
+            raise ValueError("strata_plan: %d strata, the generator takes %d (scoary_perm_max_strata)" % (S, max_s))
+        if N > max_n:
+            raise ValueError("strata_plan: %d isolates, the stratified generator takes %d "
+                             "(scoary_perm_strata_max_isolates)" % (N, max_n))
+        sizes = np.bincount(st, minlength=S)
+        members = np.argsort(st, kind="stable").astype(np.int32)
+        offsets = np.concatenate(([0], np.cumsum(sizes))).astype(np.int32)
+        T = int(trait_rows.shape[0])
+        dev = [torch.from_numpy(x).to(self.device) for x in
+               (st.astype(np.uint16).view(np.int16), members, offsets)]
+        smargins = self._empty((T, S, 2), torch.int32)
+        self._check(self.lib.scoary_strata_margins(self.h, self._ptr(trait_rows), self._ptr(mask_rows),
+                                                   self._ptr(dev[0]), T, N, S, self._ptr(smargins),
+                                                   self._stream()), "scoary_strata_margins")
+        return StrataPlan(dev[0], dev[1], dev[2], smargins, S, N, sizes)
+
+    @staticmethod
+    def _strata_fits(strata, T, N):
+        if strata.T != int(T) or strata.N != int(N) or not strata.smargins.is_contiguous():
+            raise ValueError("the strata plan was built for other traits (%d traits, %d isolates)"
+                             % (strata.T, strata.N))
+
+    def perm_generate(self, masks, margins, N, P, perm_base, seed, out=None, trait_base=0, strata=None):
+        """Label rows [T, P, Wp] of the permutations perm_base .. perm_base + P - 1 (spec S4); with ``strata``
+        (a StrataPlan of these traits) shuffled within its strata (spec S9)."""
         torch = _torch()
         T = masks.shape[0]
         Wp = self.row_words(N)
         if out is None:
             out = self._empty((T, P, Wp), torch.int32)
+        if strata is not None:
+            self._strata_fits(strata, T, N)
+            self._check(self.lib.scoary_perm_generate_strata(
+                self.h, self._ptr(masks), self._ptr(strata.strata), self._ptr(strata.members),
+                self._ptr(strata.offsets), self._ptr(strata.smargins), T, N, strata.S, P, perm_base, trait_base,
+                ctypes.c_uint64(seed), self._ptr(out), self._stream()), "scoary_perm_generate_strata")
+            return out
         self._check(self.lib.scoary_perm_generate(self.h, self._ptr(masks), self._ptr(margins), T,
                                                   N, P, perm_base, trait_base,
                                                   ctypes.c_uint64(seed),
@@ -537,11 +627,11 @@ class AssociationEngine:
                                             self._ptr(r), self._stream()), "scoary_permute")
         return r
 
-    def permute_sequential(self, genes, masks, margins, crit, permutations, seed, thr):
+    def permute_sequential(self, genes, masks, margins, crit, permutations, seed, thr, strata=None):
         """The reference's sequential estimator with early abort on the Fisher statistic
         (scoary_permute_seq): returns (r, nstop) int32 device tensors [T, G]; Empirical_p =
         (r + 1) / ((nstop or P) + 1).  ``thr``: host array of abort thresholds per
-        permutation index (tree._abort_thresholds)."""
+        permutation index (tree._abort_thresholds).  ``strata``: a StrataPlan (labels of spec S9)."""
         torch = _torch()
         T = masks.shape[0]
         r = torch.zeros((T, genes.G), dtype=torch.int32, device=self.device)
@@ -553,7 +643,7 @@ class AssociationEngine:
         done = 0
         while done < permutations:
             nb = min(batch, permutations - done)
-            self.perm_generate(masks, margins, genes.N, nb, done, seed, out=buf)
+            self.perm_generate(masks, margins, genes.N, nb, done, seed, out=buf, strata=strata)
             self._check(self.lib.scoary_permute_seq(
                 self.h, self._ptr(genes.tiled), self._ptr(buf), self._ptr(crit), self._ptr(d_thr),
                 genes.G, T, genes.N, nb, done, self._ptr(r), self._ptr(nstop), self._stream()),
@@ -614,7 +704,7 @@ class AssociationEngine:
         return groups
 
     def minp(self, genes, traits, masks, permutations, seed=0, res=None, out=None, perm_range=None,
-             table_budget_bytes=8 << 30, label_budget_bytes=8 << 30, plan=None):
+             table_budget_bytes=8 << 30, label_budget_bytes=8 << 30, plan=None, strata=None):
         """Westfall-Young minP (spec S7): float64 device tensor [T, permutations], minp[t, pi] = the smallest raw
         Fisher p over the genes of ``genes`` under the S4 labels of (seed, t, pi).  ``res``: an associate() result of
         the same genes and traits (its counts and margins are used; without one they are counted here).
@@ -623,7 +713,8 @@ class AssociationEngine:
         ``label_budget_bytes``; the result depends on neither.  ``plan``: the TraitPlan of these traits; with
         one, and when all traits fit one group, the tables stay attached to ``genes`` (genes.minp_cache, as the
         index lists do) and later calls with the same plan reuse them: the tables depend on the gene matrix and
-        the traits alone, and building them is most of a step (cfg3: 119 of 150 ms)."""
+        the traits alone, and building them is most of a step (cfg3: 119 of 150 ms).  ``strata``: a StrataPlan
+        of these traits -- the labels are those of spec S9 (the tables do not depend on it)."""
         torch = _torch()
         counts, margins = self._minp_inputs(genes, traits, masks, res, plan)
         T, P = int(counts.shape[0]), int(permutations)
@@ -634,7 +725,7 @@ class AssociationEngine:
         def launch(t0, t1, tables, perms, nb, done):
             self.permute_minp(genes, perms, tables, out[t0:t1], P=nb, perm_base=done)
         self._minp_batches(genes, masks, counts, margins, p0, p1, seed, table_budget_bytes, label_budget_bytes, plan,
-                           launch)
+                           launch, strata=strata)
         return out
 
     def _minp_inputs(self, genes, traits, masks, res, plan):
@@ -646,7 +737,7 @@ class AssociationEngine:
         return self.counts(genes, traits, masks, plan=plan)
 
     def _minp_batches(self, genes, masks, counts, margins, p0, p1, seed, table_budget_bytes, label_budget_bytes, plan,
-                      launch):
+                      launch, strata=None):
         """The loop minp() and minp_stepdown() share: trait groups under the table budget (their p tables built, or
         taken from / left in genes.minp_cache when there is a plan), label batches under the label budget, and per
         batch ``launch(t0, t1, tables, perms, nb, done)`` -- the traits [t0, t1) with their tables and the label rows
@@ -673,7 +764,8 @@ class AssociationEngine:
             while done < p1:
                 nb = min(batch, p1 - done)
                 perms = buf[:Tg * nb * Wp].view(Tg, nb, Wp)
-                self.perm_generate(masks[t0:t1], margins[t0:t1], N, nb, done, seed, out=perms, trait_base=t0)
+                self.perm_generate(masks[t0:t1], margins[t0:t1], N, nb, done, seed, out=perms, trait_base=t0,
+                                   strata=strata.rows(t0, t1) if strata is not None else None)
                 launch(t0, t1, tables, perms, nb, done)
                 done += nb
             del tables
@@ -724,7 +816,7 @@ class AssociationEngine:
         return c
 
     def minp_stepdown(self, genes, traits, masks, permutations, seed=0, res=None, table_budget_bytes=8 << 30,
-                      label_budget_bytes=8 << 30, plan=None):
+                      label_budget_bytes=8 << 30, plan=None, strata=None):
         """Westfall-Young step-down minP (spec S8): (r_sd int32 [T, G], minp float64 [T, permutations]).  Per
         trait the genes are ranked by (p, gene index) -- one stable device sort of the association step's own p --
         and the gene at rank k is compared, per permuted labelling, with the smallest permuted p over the genes at
@@ -734,7 +826,7 @@ class AssociationEngine:
         for bit (the same pass produces it).  ``res``, the budgets and ``plan`` as in minp(): the same trait groups,
         label batches and genes.minp_cache; the result depends on none of them.
         On a GENE SHARD this is the step-down within that shard; shards do NOT compose (the successive minimum at
-        a global rank mixes the genes of all shards): run it on the whole matrix."""
+        a global rank mixes the genes of all shards): run it on the whole matrix.  ``strata`` as in minp()."""
         torch = _torch()
         counts, margins = self._minp_inputs(genes, traits, masks, res, plan)
         if res is not None:
@@ -751,7 +843,7 @@ class AssociationEngine:
             self.permute_stepdown(genes, perms, tables, order32[t0:t1], ps[t0:t1], c[t0:t1], minp=minp[t0:t1], P=nb,
                                   perm_base=done)
         self._minp_batches(genes, masks, counts, margins, 0, P, seed, table_budget_bytes, label_budget_bytes, plan,
-                           launch)
+                           launch, strata=strata)
         # steps 4 and 5: every tie group takes the count of its first position, then the running maximum
         pos = torch.arange(G, device=self.device).expand(T, G)
         first = torch.ones((T, G), dtype=torch.bool, device=self.device)
@@ -802,7 +894,7 @@ class AssociationEngine:
             return False
         return float(genes.G) * int(T) * max(int(permutations), 1) <= self.AUTO_GRAPH_MAX_TESTS
 
-    def _auto_graph(self, genes, traits, masks, permutations, seed, use_lists, ws, plan):
+    def _auto_graph(self, genes, traits, masks, permutations, seed, use_lists, ws, plan, strata=None):
         """The cached-graph path of associate(): returns the result dict, or None for 'run eagerly'."""
         torch = _torch()
         if getattr(self, "_timing", False) or torch.cuda.is_current_stream_capturing():
@@ -813,9 +905,12 @@ class AssociationEngine:
         # versions (in-place edits through torch since the recording) and the scalars.
         refs = (genes.tiled, traits, masks, plan, plan.margins, plan.mask_class, plan.buf) + \
             ((L.idx, L.start, L.ngroups, L.order, L.flipped) if L is not None else ()) + \
-            ((L.panels,) if L is not None and L.panels is not None else ())
+            ((L.panels,) if L is not None and L.panels is not None else ()) + \
+            ((strata, strata.strata, strata.members, strata.offsets, strata.smargins) if strata is not None else ())
+        # (a graph recorded without strata is never replayed for a step with strata, or the reverse: the strata
+        # plan and its tensors are among the references, and the flag among the scalars)
         scalars = (genes.G, genes.N, int(traits.shape[0]), int(permutations), int(seed), bool(use_lists),
-                   getattr(self, "_mfma_mode", "auto"),
+                   getattr(self, "_mfma_mode", "auto"), strata is not None,
                    tuple(getattr(x, "_version", 0) for x in refs))
         st = ws.auto
         same = st is not None and st["scalars"] == scalars and len(st["refs"]) == len(refs) and \
@@ -827,29 +922,29 @@ class AssociationEngine:
             return None                                   # first call with these buffers: eager
         if st["graph"] is None:                           # second call: record (runs the step as well)
             st["graph"], st["res"] = self.capture(genes, traits, masks, permutations, seed, ws,
-                                                  use_lists=use_lists, plan=plan)
+                                                  use_lists=use_lists, plan=plan, strata=strata)
             # the capture ran on its own stream: order the caller's stream behind it
             torch.cuda.current_stream(self.device).wait_stream(st["graph"].stream)
             return st["res"]
         st["graph"].launch()
         return st["res"]
 
-    def _label_tiles(self, ws, masks, margins, N, nb, base, seed):
+    def _label_tiles(self, ws, masks, margins, N, nb, base, seed, strata=None):
         """One batch of label tiles into ws.tiles: all of them, or -- with label shards -- this
         rank's share followed by the all-gather of the others'."""
         sh = ws.label_shards
         if sh is None or sh.world == 1:
-            self.perm_generate_tiles(masks, margins, N, nb, base, seed, out=ws.tiles)
+            self.perm_generate_tiles(masks, margins, N, nb, base, seed, out=ws.tiles, strata=strata)
             return
         nflat, tile_words = self.tiles_per_batch(N, nb, masks.shape[0])
         _per, first, count = sh.share(nflat)
         self.perm_generate_tiles(masks, margins, N, nb, base, seed, out=ws.tiles,
-                                 tile_range=(first, count))
+                                 tile_range=(first, count), strata=strata)
         sh.all_gather(ws.tiles, nflat, tile_words)
 
     def associate(self, genes, traits, masks, permutations=0, seed=0, perm_buffer=None,
                   use_lists=None, workspace=None, plan=None, graph=None, records=None, fwer=False,
-                  table_budget_bytes=8 << 30, stepdown=False):
+                  table_budget_bytes=8 << 30, stepdown=False, strata=None):
         """counts -> Fisher -> (optional) permutation exceedance counts.
         Returns dict of device tensors: counts [T,G,4], margins [T,2],
         p / odds [T,G], r [T,G] (uint32 bit pattern in int32) or None.  With
@@ -865,21 +960,29 @@ class AssociationEngine:
         ``table_budget_bytes`` and, with a ``plan``, are built once per (gene matrix, plan) and reused (minp()).
         Such a step is never replayed from a graph (it reads sizes back).  ``stepdown=True`` (needs permutations):
         the step-down counts res["r_fwer_sd"] int32 [T, G] and res["minp"] (minp_stepdown(), spec S8); together with
-        ``fwer`` res["r_fwer"] comes from those same minima, k_permute_minp is not launched."""
+        ``fwer`` res["r_fwer"] comes from those same minima, k_permute_minp is not launched.  ``strata``: a
+        StrataPlan of these traits (strata_plan) -- every permutation shuffles the labels within its strata only
+        (spec S9): r, minp, r_fwer and r_fwer_sd are then counted under that null; None: the code as it was."""
         if (fwer or stepdown) and permutations <= 0:
             raise ValueError("fwer=True / stepdown=True need permutations > 0")
+        if strata is not None and permutations > 0:
+            self._strata_fits(strata, traits.shape[0], genes.N)
+        elif permutations <= 0:
+            strata = None
         res = self._associate(genes, traits, masks, permutations, seed, perm_buffer, use_lists,
-                              workspace, plan, graph if records is None and not (fwer or stepdown) else False)
+                              workspace, plan, graph if records is None and not (fwer or stepdown) else False,
+                              strata=strata)
         if stepdown:
             res = dict(res)
             res["r_fwer_sd"], res["minp"] = self.minp_stepdown(genes, traits, masks, permutations, seed, res=res,
-                                                               table_budget_bytes=table_budget_bytes, plan=plan)
+                                                               table_budget_bytes=table_budget_bytes, plan=plan,
+                                                               strata=strata)
             if fwer:
                 res["r_fwer"] = self.r_fwer(res["minp"], res["p"])
         elif fwer:
             res = dict(res)
             res["minp"] = self.minp(genes, traits, masks, permutations, seed, res=res,
-                                    table_budget_bytes=table_budget_bytes, plan=plan)
+                                    table_budget_bytes=table_budget_bytes, plan=plan, strata=strata)
             res["r_fwer"] = self.r_fwer(res["minp"], res["p"])
         if records is not None:
             # the exchange records of the step, packed as its last kernel (inside a captured step:
@@ -889,7 +992,7 @@ class AssociationEngine:
         return res
 
     def _associate(self, genes, traits, masks, permutations, seed, perm_buffer, use_lists, workspace,
-                   plan, graph):
+                   plan, graph, strata=None):
         """The step behind associate() (its docstring)."""
         torch = _torch()
         T = traits.shape[0]
@@ -907,7 +1010,7 @@ class AssociationEngine:
         # (graph=None: automatic; False: never -- capture() itself, per-kernel timing)
         if graph is None and workspace is not None and plan is not None and perm_buffer is None \
                 and ws.label_shards is None and self.auto_graph_eligible(genes, T, permutations):
-            res = self._auto_graph(genes, traits, masks, permutations, seed, use_lists, ws, plan)
+            res = self._auto_graph(genes, traits, masks, permutations, seed, use_lists, ws, plan, strata)
             if res is not None:
                 return res
         counts, margins = self.counts(genes, traits, masks,
@@ -926,7 +1029,7 @@ class AssociationEngine:
             side = self._side_stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                self._label_tiles(ws, masks, margins, genes.N, nb0, 0, seed)
+                self._label_tiles(ws, masks, margins, genes.N, nb0, 0, seed, strata)
             p, odds, crit, lcrit = self.fisher(counts, out=(ws.p, ws.odds, ws.crit),
                                                lists=genes.lists, lcrit=ws.lcrit)
             main.wait_stream(side)
@@ -934,7 +1037,7 @@ class AssociationEngine:
             while done < permutations:
                 nb = min(ws.batch, permutations - done)
                 if done > 0:
-                    self._label_tiles(ws, masks, margins, genes.N, nb, done, seed)
+                    self._label_tiles(ws, masks, margins, genes.N, nb, done, seed, strata)
                 self.permute_lists(genes, ws.tiles, None, margins, nb, ws.r, scratch=ws.scratch,
                                    lcrit=lcrit, accumulate=done > 0, bfrag=ws.bfrag)
                 done += nb
@@ -949,13 +1052,13 @@ class AssociationEngine:
             done = 0
             while done < permutations:
                 nb = min(batch, permutations - done)
-                self.perm_generate(masks, margins, genes.N, nb, done, seed, out=ws.perms)
+                self.perm_generate(masks, margins, genes.N, nb, done, seed, out=ws.perms, strata=strata)
                 self.permute(genes, ws.perms[:, :nb] if nb == batch else ws.perms, crit, r, P=nb)
                 done += nb
         return {"counts": counts, "margins": margins, "p": p, "odds": odds, "crit": crit, "r": r}
 
     def capture(self, genes, traits, masks, permutations, seed, workspace, use_lists=None, plan=None,
-                records=None):
+                records=None, strata=None):
         """Record one associate() step into a hipGraph (scoary_graph_*): returns
         (StepGraph, result dict).  The results live in ``workspace``; ``launch()``
         recomputes them with a single graph launch.  The step is run once eagerly
@@ -970,7 +1073,8 @@ class AssociationEngine:
             raise _abi.ScoaryHipError("capture(): label shards are active -- their all-gather is a collective "
                                       "and cannot be recorded into a hipGraph")
         self.associate(genes, traits, masks, permutations=permutations, seed=seed,
-                       use_lists=use_lists, workspace=workspace, plan=plan, graph=False, records=records)
+                       use_lists=use_lists, workspace=workspace, plan=plan, graph=False, records=records,
+                       strata=strata)
         torch.cuda.synchronize(self.device)
         stream = torch.cuda.Stream(device=self.device)      # a fresh stream: never mid-capture
         with torch.cuda.stream(stream):
@@ -979,7 +1083,7 @@ class AssociationEngine:
             try:
                 res = self.associate(genes, traits, masks, permutations=permutations, seed=seed,
                                      use_lists=use_lists, workspace=workspace, plan=plan, graph=False,
-                                     records=records)
+                                     records=records, strata=strata)
                 failed = False
             finally:
                 # the capture must be ended either way; a graph that came out of a failed step

@@ -770,7 +770,7 @@ def _pattern_groups(table, maskrow, idx, hashes):
 
 
 def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, fwer=False,
-               fwer_stepdown=False):
+               fwer_stepdown=False, strata=None):
     """Whole hot path for all traits; under torchrun (world > 1) every rank
     takes a stride gene shard (dist.GenePartition: the reference's domains,
     scoary/methods.py:1076-1078) and the per-gene records are all-gathered
@@ -784,7 +784,9 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
     r_fwer travels in the record's nstop word (the feature excludes early abort).
     ``fwer_stepdown``: the step-down counts (spec S8) out["r_fwer_sd"] [T, G], single process only -- the
     successive minima run over all genes in one order, gene shards do not compose; they reach the host beside the
-    records, as the minima do.  With ``fwer`` as well, r_fwer is counted from the same pass's minima."""
+    records, as the minima do.  With ``fwer`` as well, r_fwer is counted from the same pass's minima.
+    ``strata``: the stratum index of every isolate of the table (--permute-strata): every permutation shuffles
+    the labels within the strata only (spec S9); every rank generates the same labels."""
     import torch
     from . import dist
     eng = get_engine()
@@ -793,6 +795,7 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         trv = eng.vecrows(pack_bits_rows(tarr == 1), N)
         mkv = eng.vecrows(pack_bits_rows(tarr != 2), N)
         plan = eng.trait_plan(trv, mkv, N)            # margins + mask classes: once per trait set
+        sp = eng.strata_plan(strata, trv, mkv, N) if strata is not None and permutations > 0 else None
 
     def scipy_digits(res):
         # Up to 170 isolates k_fisher's p IS scipy.stats.fisher_exact's double; above, it is the exact value of SciPy's
@@ -846,17 +849,17 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
             crit = eng.fisher(res["counts"], want_crit=True)[2]
             scipy_digits(res)
             r, nstop = eng.permute_sequential(gm, mkv, res["margins"], crit, permutations, seed,
-                                              T_._abort_thresholds(permutations))
+                                              T_._abort_thresholds(permutations), strata=sp)
             res["r"] = r
             return eng.pack_records(res, nstop=nstop)
         with _stage("kernels (counts, Fisher, permutations)"):
-            res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan)
+            res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan, strata=sp)
             torch.cuda.synchronize(eng.device)
         r_fwer = None
         if fwer_stepdown:
             with _stage("Westfall-Young step-down minP (p tables, k_stepdown_minp)"):
                 # ranked on k_fisher's own bits, before the SciPy-digits pass rewrites the last ulp of p
-                r_sd, minp = eng.minp_stepdown(gm, trv, mkv, permutations, seed, res=res)
+                r_sd, minp = eng.minp_stepdown(gm, trv, mkv, permutations, seed, res=res, strata=sp)
                 sd_all.append(r_sd)
                 if fwer:
                     r_fwer = eng.r_fwer(minp, res["p"])
@@ -864,7 +867,7 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
                 torch.cuda.synchronize(eng.device)
         elif fwer:
             with _stage("Westfall-Young minP (p tables, k_permute_minp)"):
-                minp = dist.all_reduce_min(eng.minp(gm, trv, mkv, permutations, seed, res=res))
+                minp = dist.all_reduce_min(eng.minp(gm, trv, mkv, permutations, seed, res=res, strata=sp))
                 # counted on k_fisher's own bits, before the SciPy-digits pass rewrites the last ulp of p
                 r_fwer = eng.r_fwer(minp, res["p"])
                 minp_all.append(minp)
@@ -950,14 +953,18 @@ def _usable_cpus():
 
 
 def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEED,
-                  early_abort=False, fwer=False, fwer_stepdown=False):
+                  early_abort=False, fwer=False, fwer_stepdown=False, strata=None):
     """Counts, Fisher's exact test and B/BH correction for every trait x gene
     (methods.py:757-928).  ``permutations`` >= 10 additionally attaches the
     Fisher-statistic ``Empirical_p`` (= (r+1)/(P+1), methods.py:1365) to every
     row -- the north_star's replacement for the tree-statistic Permute loop.  ``fwer`` (with
     permutations): also ``Westfall_Young_p`` = (r_fwer+1)/(P+1), the single-step minP adjusted p.
     ``fwer_stepdown`` (with permutations, one process): also ``Westfall_Young_stepdown_p`` = (r_sd+1)/(P+1), the
-    step-down minP adjusted p (spec S8)."""
+    step-down minP adjusted p (spec S8).  ``strata`` (with permutations): one stratum index per isolate, in
+    the table's strain order -- the permutations shuffle the labels within the strata only (spec S9), which
+    changes the values of Empirical_p and of the Westfall-Young columns and nothing else."""
+    if strata is not None and permutations < 10:
+        raise ValueError("strata need the Fisher-statistic permutations of --no_pairwise (permutations >= 10)")
     if fwer and (permutations < 10 or early_abort):
         raise ValueError("fwer needs permutations >= 10 and excludes early_abort")
     if fwer_stepdown:
@@ -974,7 +981,10 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
                              "one order; gene shards do not compose")
     table = _as_table(genedic)
     names, tarr = _trait_arrays(traitsdic, table.strains)
-    dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, fwer, fwer_stepdown)
+    if strata is not None and len(strata) != len(table.strains):
+        raise ValueError("strata: one stratum index per isolate of the gene table")
+    dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, fwer, fwer_stepdown,
+                     strata=strata)
     collapse_hashes = None
     if collapse:
         eng = get_engine()
@@ -1628,6 +1638,12 @@ def ScoaryArgumentParser(argv=None):
                    "minP family-wise adjusted p -- every gene is compared, per permutation, with the smallest "
                    "Fisher p over the genes ranked at or behind it only; never above Westfall_Young_p, same "
                    "family-wise error (single process; scoary_amd extension)")
+    a.add_argument("--permute-strata", dest="permute_strata", metavar="FILE", default=None,
+                   help="With --no_pairwise --permute: shuffle the trait labels only within strata (lineage, "
+                   "BAPS / PopPUNK cluster, sequence type, country ...), the permutation null for a structured "
+                   "population. FILE is a CSV with a header row (read with --delimiter): column 1 the isolate "
+                   "name, column 2 its stratum label; further columns are ignored. Changes Empirical_p and the "
+                   "Westfall-Young columns (scoary_amd extension)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1783,11 +1799,19 @@ def main(**kwargs):
         # --no_pairwise: Fisher-statistic permutations for every gene (north_star);
         # default mode: tree-statistic permutations of the surviving genes, done
         # in the pairwise stage like the reference does.
+        strata = None
+        if getattr(args, "permute_strata", None):
+            # the authoritative call, on the strains the reader kept (_validate's early one reads the header on its
+            # own: should the two ever disagree, the same exit message appears here, after the engine has started)
+            strata, labels = strata_indices(args.strata_map, strains)
+            sizes = np.bincount(strata, minlength=len(labels))
+            log.info("Permuting trait labels within %d strata of %d to %d isolates (%s)"
+                     % (len(labels), int(sizes.min()), int(sizes.max()), args.permute_strata))
         res = Setup_results(genedic, traitsdic, args.collapse,
                             permutations=args.permute if args.no_pairwise else 0, seed=seed,
                             early_abort=getattr(args, "permute_early_abort", False),
                             fwer=getattr(args, "permute_fwer", False),
-                            fwer_stepdown=getattr(args, "permute_fwer_stepdown", False))
+                            fwer_stepdown=getattr(args, "permute_fwer_stepdown", False), strata=strata)
         t_stats = _time.time()
         if args.upgma_tree and rank == 0:
             # (with --no_pairwise there is no tree and the reference writes str(None) + ";", :277-280, :741-751)
@@ -1842,6 +1866,54 @@ class _LevelCounter(logging.Handler):
         self.n[record.levelname] = self.n.get(record.levelname, 0) + 1
 
 
+def read_strata_file(path, delimiter=","):
+    """--permute-strata FILE: a CSV with a header row; column 1 = isolate name, column 2 = stratum label (any
+    non-empty string), further columns ignored.  Returns {isolate: label} in file order."""
+    out = {}
+    with open(path, "r", newline=None) as f:
+        rows = csv.reader(f, skipinitialspace=True, delimiter=delimiter)
+        next(rows, None)                                   # the header row
+        for line, row in enumerate(rows, start=2):
+            if not row or all(c.strip() == "" for c in row):
+                continue
+            name = row[0].strip()
+            label = row[1].strip() if len(row) > 1 else ""
+            if label == "":
+                sys.exit("The strata file %s has an empty stratum label for isolate %s (line %d)"
+                         % (path, name, line))
+            if name in out:
+                sys.exit("The strata file %s names isolate %s more than once (line %d)" % (path, name, line))
+            out[name] = label
+    return out
+
+
+def strata_indices(strata_map, strains):
+    """(int64 array: the stratum index of every isolate of ``strains``, the list of stratum labels): labels are
+    numbered 0 ... S-1 in order of first appearance along ``strains``; isolates of the file that are not analysed
+    are ignored."""
+    missing = [s for s in strains if s not in strata_map]
+    if missing:
+        sys.exit("The strata file does not name a stratum for %d of the analysed isolates, e.g. %s"
+                 % (len(missing), ", ".join(missing[:5])))
+    index, out = {}, np.zeros(len(strains), dtype=np.int64)
+    for i, s in enumerate(strains):
+        out[i] = index.setdefault(strata_map[s], len(index))
+    return out, list(index)
+
+
+def _analysed_isolates(args):
+    """The isolate columns of the gene table that the run analyses: its header from column -s on, restricted to
+    the isolates of -r -- what Csv_to_dic_Roary keeps, read from the first line alone."""
+    with open(args.genes, "r", newline=None) as f:
+        header = next(csv.reader(f, skipinitialspace=True, delimiter=args.delimiter), [])
+    strains = header[int(args.start_col) - 1:]
+    if args.restrict_to is not None and os.path.isfile(args.restrict_to):
+        with open(args.restrict_to, "r") as f:
+            allowed = {iso for line in f for iso in line.rstrip().split(",")}
+        strains = [s for s in strains if s in allowed]
+    return strains
+
+
 def _validate(args, cutoffs):
     """Argument checks of methods.py:126-181 (same conditions, same exits)."""
     if args.traits is None or args.genes is None:
@@ -1888,6 +1960,26 @@ def _validate(args, cutoffs):
         if dist.world_rank()[0] > 1:
             sys.exit("Cannot use --permute-fwer-stepdown under more than one rank: the successive minima run over "
                      "all genes in one order; gene shards do not compose")
+    if getattr(args, "permute_strata", None):
+        if not args.no_pairwise:
+            sys.exit("Cannot use --permute-strata without --no_pairwise. The strata restrict the permutations of "
+                     "the Fisher statistic")
+        if args.permute < 10:
+            sys.exit("Cannot use --permute-strata without performing permutations. Use '--permute X' where X "
+                     "is a number equal to or larger than 10")
+        if not os.path.isfile(args.permute_strata):
+            sys.exit("Could not find the strata file: %s" % args.permute_strata)
+        args.strata_map = read_strata_file(args.permute_strata, args.delimiter)
+        # the isolates of the analysis are the header of the gene table (after -s and -r): checked here, before the
+        # engine starts and the table is read
+        strata, labels = strata_indices(args.strata_map, _analysed_isolates(args))
+        from . import _abi
+        if len(labels) > _abi.PERM_MAX_STRATA:
+            sys.exit("The strata file %s names %d strata for the analysed isolates; --permute-strata takes at "
+                     "most %d" % (args.permute_strata, len(labels), _abi.PERM_MAX_STRATA))
+        if len(strata) > _abi.PERM_STRATA_MAX_ISOLATES:
+            sys.exit("--permute-strata takes at most %d isolates; this analysis has %d"
+                     % (_abi.PERM_STRATA_MAX_ISOLATES, len(strata)))
     if "P" in cutoffs and args.permute == 0:
         sys.exit("Cannot use empirical p-values in filtration without performing "
                  "permutations. Use '--permute X' where X is a number equal to or larger than 10")

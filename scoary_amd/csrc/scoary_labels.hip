@@ -26,8 +26,15 @@
 // row keeps only 16 / 8 / ... 1 of the 32 permutations of a dword (more Philox work per label,
 // still parallel in N).
 //
-// k_labels_strata (spec S9, further down) shuffles within strata: the same block shape, round 0 and output code,
-// the plan and the fix-up per stratum.
+// One generator, two fix-up drivers.  The block map (label_block), the LDS carve-up (lds_map), round 0
+// (bern_word, store_row0), the fix-up pieces (fix_group, toggle4, toggle1, fix_rounds, fix_tail), the output
+// (emit_labels) and the host side (launch_block behind launch_labels / launch_labels_strata, which pick the
+// instance and carry each kernel's own limit; label_args, tile_shape) exist once.  What the two kernels
+// own is how a permutation's surplus |m - K| is found and who places it:
+//   k_labels         (spec S4) one plan per trait, K from bit-sliced counters kept during round 0, the fix-up
+//                    over all N isolates; rows of fewer than 32 permutations per dword for large N;
+//   k_labels_strata  (spec S9) a plan per (trait, stratum), K from a count over the stratum's members, the
+//                    fix-up per stratum over its member list, the tails of L strata side by side.
 #include "scoary_common.hpp"
 
 namespace {
@@ -102,37 +109,47 @@ struct LabelArgs {
   uint32_t* out;
 };
 
-// What a block of k_labels_strata produces: (trait, NB dword columns of 32 permutations).  The block map of
-// k_labels with all 32 permutations of a column in one block (k_labels keeps its own inline copy, sub-dword
-// rows included: it is tuned, and its register allocation stays where it is).
+// What a block produces: (trait, NB dword columns of 32 permutations), or with sub-dword rows the bits
+// [bit0, bit0 + elt) of one column
 template <int NB>
 struct LabelBlock {
-  int t;
+  int t, bit0;
   uint32_t Bglob;            // Philox block of column 0
   uint32_t* tile_base;       // tiles: row 0, column `col` of the block's tile
   uint32_t live[NB];         // permutations of column w that exist, as a mask over the 32 bits of the Philox block
 };
-// false: the block has nothing to do (the padding of a tile launch)
-template <int NB, int OUT>
+// The block map of both kernels.  SUB: rows may keep fewer than 32 permutations of a dword (a.elt_log2 < 5;
+// only k_labels has such rows).  false: the block has nothing to do (the padding of a tile launch)
+template <int NB, int OUT, bool SUB>
 __device__ __forceinline__ bool label_block(const LabelArgs& a, LabelBlock<NB>& b) {
+  const int elt_log2 = SUB ? a.elt_log2 : 5;
+  const int elt = 1 << elt_log2;                     // permutation bits a row keeps per column
+  const int subs = 32 >> elt_log2;                   // blocks that share one dword column
   int64_t lc0 = 0;                                   // tiles: dword column among this launch's permutations
   b.tile_base = nullptr;
   if constexpr (OUT == 0) {
-    // the units of one tile get block ids that are equal mod 8 (one XCD, one L2), as in k_labels
-    const int units = a.TW / NB;
+    // block id -> (flat tile, unit): the units of one tile get ids that are equal mod 8, i.e. run
+    // on one XCD (observed placement: block b on XCD b % 8), so the 4 * NB-byte pieces they
+    // write into the same tile rows meet in one L2 and leave it as whole lines
+    const int units = a.TW * subs / NB;
     const int64_t id = blockIdx.x;
     const int64_t qd = id >> 3;
-    const int col = (int)(qd % units) * NB;
+    const int unit = (int)(qd % units);
     const int64_t fl = (qd / units) * 8 + (id & 7);
     if (fl >= a.nflat) return false;
     const int64_t f = a.first_flat + fl;
     b.t = (int)(f / a.ntiles);
-    lc0 = (f % a.ntiles) * a.TW + col;
+    const int tile = (int)(f % a.ntiles);
+    const int col = unit / subs * NB;
+    b.bit0 = (unit % subs) * elt;
+    lc0 = (int64_t)tile * a.TW + col;
     b.Bglob = (uint32_t)((a.perm_base >> 5) + lc0);
-    b.tile_base = a.out + f * list_tile_dwords(a.N, a.TW) + col;
+    // (more than one segment means N > 20479, hence TW == kSegTW; below that this is list_tile_dwords)
+    b.tile_base = a.out + f * list_tile_dwords_seg(a.N, a.TW) + col;
   } else {
     b.t = blockIdx.y;
-    b.Bglob = (uint32_t)((a.perm_base >> 5) + blockIdx.x);
+    b.Bglob = (uint32_t)((a.perm_base >> 5) + blockIdx.x / subs);
+    b.bit0 = (int)(blockIdx.x % subs) * elt;
   }
 #pragma unroll
   for (int w = 0; w < NB; ++w) {
@@ -154,13 +171,176 @@ __device__ __forceinline__ bool label_block(const LabelArgs& a, LabelBlock<NB>& 
   return true;
 }
 
+// The LDS of a block as dword offsets, read by the kernel and by the host code that sizes its launch: the rows
+// xs at 0 (stride_bits per isolate), the validity words vm, then what the kernel keeps besides (own).
+// I: int64_t on the host, which sizes the launch for any N a caller may pass; int in the kernels, where a
+// launch that fits kLabelsMaxLds keeps N * stride_bits below 2^21
+template <class I>
+struct LdsMap {
+  I vm, own, end;
+  __host__ __device__ I bytes() const { return end * 4; }
+};
+template <class I>
+__host__ __device__ inline LdsMap<I> lds_map(I N, int stride_bits, I own_dwords) {
+  LdsMap<I> m;
+  m.vm = (((N * stride_bits + 31) >> 5) + 3) & ~(I)3;
+  m.own = m.vm + ((((N + 31) >> 5) + 3) & ~(I)3);
+  m.end = m.own + own_dwords;
+  return m;
+}
+// k_labels keeps the mark counts of its 32 * NB permutations; k_labels_strata the stratum table (16 bytes each)
+// and the 16-bit member list
+template <class I>
+__host__ __device__ inline LdsMap<I> labels_lds(I N, int elt, int NB) { return lds_map<I>(N, elt * NB, 32 * NB); }
+template <class I>
+__host__ __device__ inline LdsMap<I> strata_lds(I N, int NB, I S) {
+  return lds_map<I>(N, 32 * NB, 4 * S + (N + 1) / 2);
+}
+
+// Round 0 leaves the marks of isolate `row` in xs: whole dwords, or (sub-dword rows, xs zeroed) OR-ed into place
+template <int NB>
+__device__ __forceinline__ void store_row0(uint32_t* xs, int row, const uint32_t (&x)[NB], int elt_log2) {
+  if (elt_log2 == 5) {
+    if constexpr (NB == 2) {
+      *reinterpret_cast<uint2*>(xs + (int64_t)row * 2) = make_uint2(x[0], x[1]);
+    } else {
+      xs[row] = x[0];
+    }
+  } else if (x[0]) {
+    const uint32_t bp = (uint32_t)row << elt_log2;
+    atomicOr(&xs[bp >> 5], x[0] << (bp & 31u));
+  }
+}
+
+// ---- the fix-up: a group of L lanes per permutation ----
+// The spec consumes the position draws c = 0, 1, 2, ... of a permutation one after the other; but as long as at
+// least as many marks are missing as a batch has draws, EVERY distinct candidate the batch hits is toggled,
+// whatever the order -- so lane l of the group takes Philox call base + l (four draws) and the group toggles
+// with LDS atomics (the returned old bit says who was first at a position).  A round uses k = min(L, |d| / 4)
+// calls, so it can never overshoot; the last < 4 marks are placed by ONE lane, draw by draw (fix_tail).
+// A draw is a position in [0, n), exactly uniform by Lemire rejection (reject_below = 2^32 mod n); iso(position)
+// is the isolate there, and its bit of this permutation is bit bp = isolate * stride_bits + pidx of xs.
+struct FixGroup {
+  uint32_t* xs;              // the rows
+  const uint32_t* vm;        // the validity words
+  uint32_t stride_bits;      // bits of xs per isolate = permutations of the block
+  int L, l, pidx;            // lanes per permutation (a power of two), this lane among them, their permutation
+  bool in_group, alive;      // tpb > 64 * nperm: the last wavefronts idle; alive: the permutation exists
+  uint32_t pi;               // the permutation's global index (Philox counter word 1)
+  uint64_t gmask;            // the group's lanes within the wavefront
+  uint32_t tglob, k0, k1;    // Philox counter word 2 and key
+};
+template <int NB>
+__device__ __forceinline__ FixGroup fix_group(const LabelArgs& a, const LabelBlock<NB>& b, uint32_t* xs,
+                                              const uint32_t* vm, int nperm) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  FixGroup g;
+  g.xs = xs, g.vm = vm, g.stride_bits = (uint32_t)nperm;
+  g.L = min(kWave, (int)blockDim.x / nperm);
+  g.pidx = tid / g.L, g.l = tid & (g.L - 1);
+  g.in_group = g.pidx < nperm;
+  const int w = g.pidx >> 5, j = g.pidx & 31;
+  g.alive = g.in_group && ((((w & (NB - 1)) ? b.live[NB - 1] : b.live[0]) >> (b.bit0 + j)) & 1u);
+  g.pi = (b.Bglob + (uint32_t)w) * 32u + (uint32_t)(b.bit0 + j);
+  g.gmask = (g.L == 64 ? ~(uint64_t)0 : (((uint64_t)1 << g.L) - 1)) << (lane & ~(g.L - 1));
+  g.tglob = (uint32_t)(a.trait_base + b.t), g.k0 = a.k0, g.k1 = a.k1;
+  return g;
+}
+// Four draws of one Philox call: positions, then the toggles as LDS atomics -- an OR on a marked isolate / an
+// AND on an unmarked one changes nothing, so only invalid isolates have to be kept away (add mode), and the
+// returned old word says whether THIS lane changed the bit.  The four atomics are independent: issued back to
+// back, one wait.  Returns how many bits this lane changed.
+template <class Iso>
+__device__ __forceinline__ int toggle4(const FixGroup& g, const uint32_t (&rnd)[4], bool add, uint32_t n,
+                                       uint32_t reject_below, Iso iso) {
+  uint32_t idx[4], bit[4];
+  bool ok[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const uint64_t prod = (uint64_t)rnd[u] * (uint64_t)n;
+    const uint32_t pos = iso((uint32_t)(prod >> 32));
+    const uint32_t bp = pos * g.stride_bits + (uint32_t)g.pidx;
+    idx[u] = bp >> 5;
+    bit[u] = 1u << (bp & 31u);
+    ok[u] = (uint32_t)prod >= reject_below;            // Lemire rejection: no draw otherwise
+    if (add) ok[u] = ok[u] && ((g.vm[pos >> 5] >> (pos & 31u)) & 1u);
+  }
+  uint32_t old[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    old[u] = add ? bit[u] : 0u;                        // "no change" for the draws that are none
+    if (ok[u])
+      old[u] = add ? __hip_atomic_fetch_or(&g.xs[idx[u]], bit[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+                   : __hip_atomic_fetch_and(&g.xs[idx[u]], ~bit[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  int won = 0;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) won += add ? ((old[u] & bit[u]) ? 0 : 1) : ((old[u] & bit[u]) ? 1 : 0);
+  return won;
+}
+// one draw at a time (the last < 4 marks): returns 1 if the bit changed
+template <class Iso>
+__device__ __forceinline__ int toggle1(const FixGroup& g, uint32_t rnd, bool add, uint32_t n, uint32_t reject_below,
+                                       Iso iso) {
+  const uint64_t prod = (uint64_t)rnd * (uint64_t)n;
+  if ((uint32_t)prod < reject_below) return 0;
+  const uint32_t pos = iso((uint32_t)(prod >> 32));
+  const uint32_t bp = pos * g.stride_bits + (uint32_t)g.pidx, b1 = 1u << (bp & 31u);
+  if (add) {
+    if (!((g.vm[pos >> 5] >> (pos & 31u)) & 1u)) return 0;
+    return (__hip_atomic_fetch_or(&g.xs[bp >> 5], b1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & b1) ? 0 : 1;
+  }
+  return (__hip_atomic_fetch_and(&g.xs[bp >> 5], ~b1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & b1) ? 1 : 0;
+}
+// The batched rounds, group-uniform, while |d| >= 4 (d > 0: marks to add, < 0: to remove); `base` is the next
+// Philox call, `ctr_hi` what is OR-ed into the call counter (the stratum, from bit 20).  The safety stop
+// kFixMaxCalls ends the loop; CLAMP also keeps a round's calls below it, which the stratified kernel needs
+// because the stratum sits right above (the stop is unreachable on consistent input).
+template <bool CLAMP, class Iso>
+__device__ __forceinline__ void fix_rounds(const FixGroup& g, int& d, uint32_t& base, uint32_t ctr_hi, uint32_t n,
+                                           uint32_t reject_below, Iso iso) {
+  while ((d >= 4 || d <= -4) && base < kFixMaxCalls) {
+    const bool add = d > 0;
+    const int need = add ? d : -d;
+    int k = min(g.L, need >> 2);
+    if constexpr (CLAMP) k = min(k, (int)(kFixMaxCalls - base));
+    uint32_t r[4];
+    int won = 0;
+    if (g.l < k) {
+      philox4x32_10(ctr_hi | (base + (uint32_t)g.l), g.pi, g.tglob, kDomFix, g.k0, g.k1, r);
+      won = toggle4(g, r, add, n, reject_below, iso);
+    }
+    // marks toggled by the group in this round
+    int got = 0;
+#pragma unroll
+    for (int bitn = 0; bitn < 3; ++bitn) got += __popcll(__ballot((won >> bitn) & 1) & g.gmask) << bitn;
+    d = add ? d - got : d + got;
+    base += (uint32_t)k;
+  }
+}
+// The last |d| < 4 marks, in draw order: the work of one lane (the caller says which)
+template <class Iso>
+__device__ __forceinline__ void fix_tail(const FixGroup& g, int d, uint32_t base, uint32_t ctr_hi, uint32_t n,
+                                         uint32_t reject_below, Iso iso) {
+  const bool add = d > 0;
+  int left = add ? d : -d;
+  while (left > 0 && base < kFixMaxCalls) {
+    uint32_t r[4];
+    philox4x32_10(ctr_hi | base, g.pi, g.tglob, kDomFix, g.k0, g.k1, r);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (left > 0) left -= toggle1(g, r[u], add, n, reject_below, iso);
+    ++base;
+  }
+}
+
 // Output of a block whose rows are final: row_field(row, w) = the labels of isolate `row`, column w
 template <int NB, int OUT, class RowField>
-__device__ __forceinline__ void emit_labels(const LabelArgs& a, int t, int bit0, uint32_t Bglob, uint32_t* tile_base,
-                                            const uint32_t (&live)[NB], RowField row_field) {
+__device__ __forceinline__ void emit_labels(const LabelArgs& a, const LabelBlock<NB>& b, RowField row_field) {
   const int tid = threadIdx.x, lane = tid & 63, tpb = blockDim.x, nwaves = tpb >> 6;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int N = a.N, elt = 1 << a.elt_log2;
+  const int N = a.N, elt = 1 << a.elt_log2, bit0 = b.bit0;
+  uint32_t* tile_base = b.tile_base;
   if constexpr (OUT == 0) {
     const bool seg = a.TW == kSegTW;                  // two-dword tiles: segmented above N = 20479
     auto row_off = [&](int64_t row) -> int64_t { return seg ? list_row_dword(N, row) : row * a.TW; };
@@ -198,9 +378,9 @@ __device__ __forceinline__ void emit_labels(const LabelArgs& a, int t, int bit0,
     static_assert(OUT == 0 || NB == 1, "bit rows: one dword column per block");
     // permutation-major rows: 64 isolates per wavefront step, one ballot per permutation
     const int nchunks = (N + 63) >> 6;
-    const int64_t pl = (int64_t)Bglob * 32 + bit0 + lane - a.perm_base;   // lane < elt: its permutation
-    const bool mine = lane < elt && ((live[0] >> (bit0 + (lane & 31))) & 1u);
-    uint32_t* prow = a.out + ((int64_t)t * a.P + (mine ? pl : 0)) * a.Wp;
+    const int64_t pl = (int64_t)b.Bglob * 32 + bit0 + lane - a.perm_base;   // lane < elt: its permutation
+    const bool mine = lane < elt && ((b.live[0] >> (bit0 + (lane & 31))) & 1u);
+    uint32_t* prow = a.out + ((int64_t)b.t * a.P + (mine ? pl : 0)) * a.Wp;
     for (int c = wave; c < nchunks; c += nwaves) {
       const int row = c * 64 + lane;
       const uint32_t f = row < N ? row_field(row, 0) : 0u;
@@ -223,78 +403,30 @@ __device__ __forceinline__ void emit_labels(const LabelArgs& a, int t, int bit0,
 template <int NB, int OUT>   // NB = 1, 2
 __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  const int tid = threadIdx.x, lane = tid & 63, tpb = blockDim.x, nwaves = tpb >> 6;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tid = threadIdx.x, lane = tid & 63, tpb = blockDim.x;
   const int N = a.N;
   const int elt = 1 << a.elt_log2;                  // permutation bits a row keeps per column
-  const int subs = 32 >> a.elt_log2;                // blocks that share one dword column
-  // ---- which (trait, dword column(s), bits) this block produces ----
-  // (label_block() above is a second copy of this map and of the live masks, for k_labels_strata: a change of
-  // the XCD mapping or of the tile layout has to be made in both)
-  int t, bit0;
-  uint32_t Bglob;                                    // Philox block of column 0
-  int64_t lc0 = 0;                                   // tiles: dword column among this launch's permutations
-  uint32_t* tile_base = nullptr;                     // tiles: row 0, column `col` of the block's tile
-  if constexpr (OUT == 0) {
-    // block id -> (flat tile, unit): the units of one tile get ids that are equal mod 8, i.e. run
-    // on one XCD (observed placement: block b on XCD b % 8), so the 4 * NB-byte pieces they
-    // write into the same tile rows meet in one L2 and leave it as whole lines
-    const int units = a.TW * subs / NB;
-    const int64_t id = blockIdx.x;
-    const int64_t qd = id >> 3;
-    const int unit = (int)(qd % units);
-    const int64_t fl = (qd / units) * 8 + (id & 7);
-    if (fl >= a.nflat) return;
-    const int64_t f = a.first_flat + fl;
-    t = (int)(f / a.ntiles);
-    const int tile = (int)(f % a.ntiles);
-    const int col = unit / subs * NB;
-    bit0 = (unit % subs) * elt;
-    lc0 = (int64_t)tile * a.TW + col;
-    Bglob = (uint32_t)((a.perm_base >> 5) + lc0);
-    const int64_t tile_dw = a.TW == kSegTW ? list_tile_dwords_seg(N, a.TW) : list_tile_dwords(N, a.TW);
-    tile_base = a.out + f * tile_dw + col;
-  } else {
-    t = blockIdx.y;
-    Bglob = (uint32_t)((a.perm_base >> 5) + blockIdx.x / subs);
-    bit0 = (int)(blockIdx.x % subs) * elt;
-  }
-  // permutations of column w that exist, as a mask over the 32 bits of the Philox block
-  uint32_t live[NB];
-#pragma unroll
-  for (int w = 0; w < NB; ++w) {
-    int64_t lo, hi;                                  // bits [lo, hi) of the block exist
-    if constexpr (OUT == 0) {
-      lo = 0;
-      hi = a.P - (lc0 + w) * 32;
-    } else {
-      const int64_t first = (int64_t)(Bglob + w) * 32;
-      lo = a.perm_base - first;
-      hi = a.perm_base + a.P - first;
-    }
-    lo = lo < 0 ? 0 : (lo > 32 ? 32 : lo);
-    hi = hi < 0 ? 0 : (hi > 32 ? 32 : hi);
-    const uint32_t below_hi = hi >= 32 ? 0xffffffffu : ((1u << hi) - 1u);
-    const uint32_t below_lo = lo >= 32 ? 0xffffffffu : ((1u << lo) - 1u);
-    live[w] = hi > lo ? (below_hi & ~below_lo) : 0u;
-  }
+  LabelBlock<NB> blk;
+  if (!label_block<NB, OUT, true>(a, blk)) return;
+  const int t = blk.t, bit0 = blk.bit0;
+  const uint32_t Bglob = blk.Bglob;
+  const uint32_t (&live)[NB] = blk.live;
   const uint32_t fieldmask = elt == 32 ? 0xffffffffu : ((1u << elt) - 1u);
   const uint32_t tglob = (uint32_t)(a.trait_base + t);
   const LabelPlan plan = label_plan(__builtin_amdgcn_readfirstlane(a.margins[2 * t]),
                                     __builtin_amdgcn_readfirstlane(a.margins[2 * t + 1]));
   const uint32_t* mrow = a.masks + (int64_t)t * a.Wp;
 
-  // ---- LDS: rows (stride_bits per isolate), validity words, mark counts ----
-  const int stride_bits = elt * NB;
-  const int xs_dwords = (int)(((int64_t)N * stride_bits + 31) >> 5);
+  // ---- LDS: rows (elt * NB bits per isolate), validity words, mark counts ----
+  const LdsMap<int> lm = labels_lds(N, elt, NB);
   uint32_t* xs = lds;
-  uint32_t* vm = lds + ((xs_dwords + 3) & ~3);
+  uint32_t* vm = lds + lm.vm;
+  int* kc = reinterpret_cast<int*>(lds + lm.own);
   const int nmw = (N + 31) >> 5;
-  int* kc = reinterpret_cast<int*>(vm + ((nmw + 3) & ~3));
   for (int k = tid; k < nmw; k += tpb) vm[k] = mrow[k];
   if (tid < 32 * NB) kc[tid] = 0;
   if (elt != 32) {                                   // sub-dword rows are OR-ed into place
-    for (int k = tid; k < xs_dwords; k += tpb) xs[k] = 0u;
+    for (int k = tid; k < lm.vm; k += tpb) xs[k] = 0u;   // (with the up to 3 dwords of padding before vm)
     __syncthreads();
   }
 
@@ -324,16 +456,7 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
           carry = nc;
         }
     }
-    if (elt == 32) {
-      if constexpr (NB == 2) {
-        *reinterpret_cast<uint2*>(xs + (int64_t)row * 2) = make_uint2(x[0], x[1]);
-      } else {
-        xs[row] = x[0];
-      }
-    } else if (x[0]) {
-      const uint32_t bp = (uint32_t)row << a.elt_log2;
-      atomicOr(&xs[bp >> 5], x[0] << (bp & 31u));
-    }
+    store_row0<NB>(xs, row, x, a.elt_log2);
   }
   // ---- marks per permutation: butterfly over the wavefront, then one LDS atomic per wavefront ----
 #pragma unroll
@@ -369,102 +492,15 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
   }
   __syncthreads();
 
-  // ---- fix-up: a group of L lanes per permutation ----
-  // Spec S4 consumes the position draws c = 0, 1, 2, ... one after the other; but as long as at
-  // least as many marks are missing as a batch has draws, EVERY distinct candidate the batch hits
-  // is toggled, whatever the order -- so lane l of the group takes Philox call base + l (four
-  // draws) and the group toggles with LDS atomics (the returned old bit says who was first at a
-  // position).  A round uses k = min(L, |d| / 4) calls, so it can never overshoot; the last
-  // < 4 marks are placed by the group's first lane, draw by draw.
+  // ---- fix-up over all N isolates: the batched rounds, then the group's first lane places the last marks ----
   {
-    const int nperm = stride_bits;                       // permutations of this block
-    const int L = min(kWave, tpb / nperm);               // a power of two, >= 2
-    const int pidx = tid / L, l = tid & (L - 1);
-    const bool in_group = pidx < nperm;                  // tpb > 64 * nperm: the last wavefronts idle
-    const int w = pidx >> 5, j = pidx & 31;
-    const bool alive = in_group && ((live[NB == 1 ? 0 : (w & (NB - 1))] >> (bit0 + j)) & 1u);
-    const uint32_t pi = (Bglob + (uint32_t)w) * 32u + (uint32_t)(bit0 + j);
-    int d = alive ? (int)plan.m - kc[in_group ? pidx : 0] : 0;   // > 0: add marks, < 0: remove
+    const FixGroup g = fix_group<NB>(a, blk, xs, vm, elt * NB);
+    int d = g.alive ? (int)plan.m - kc[g.in_group ? g.pidx : 0] : 0;   // > 0: add marks, < 0: remove
     const uint32_t reject_below = (uint32_t)(((uint64_t)1 << 32) % (uint64_t)N);
-    const uint64_t gmask = (L == 64 ? ~(uint64_t)0 : (((uint64_t)1 << L) - 1)) << (lane & ~(L - 1));
-    const int leader = lane & ~(L - 1);
-    // one draw: position from a Philox word, toggled if it is a candidate; returns 1 if this lane
-    // changed the bit
-    // Four draws of one Philox call: positions, then the toggles as LDS atomics -- an OR on a
-    // marked isolate / an AND on an unmarked one changes nothing, so only invalid isolates have
-    // to be kept away (add mode), and the returned old word says whether THIS lane changed the
-    // bit.  The four atomics are independent: issued back to back, one wait.  `upto`: stop after
-    // that many changes (the sequential tail; 4 = no limit).
-    auto draws4 = [&](const uint32_t (&rnd)[4], bool add) -> int {
-      uint32_t idx[4], bit[4];
-      bool ok[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint64_t prod = (uint64_t)rnd[u] * (uint64_t)(uint32_t)N;
-        const uint32_t pos = (uint32_t)(prod >> 32);
-        const uint32_t bp = pos * (uint32_t)stride_bits + (uint32_t)pidx;
-        idx[u] = bp >> 5;
-        bit[u] = 1u << (bp & 31u);
-        ok[u] = (uint32_t)prod >= reject_below;          // Lemire rejection: no draw otherwise
-        if (add) ok[u] = ok[u] && ((vm[pos >> 5] >> (pos & 31u)) & 1u);
-      }
-      uint32_t old[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        old[u] = add ? bit[u] : 0u;                      // "no change" for the draws that are none
-        if (ok[u])
-          old[u] = add ? __hip_atomic_fetch_or(&xs[idx[u]], bit[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-                       : __hip_atomic_fetch_and(&xs[idx[u]], ~bit[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-      int won = 0;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) won += add ? ((old[u] & bit[u]) ? 0 : 1) : ((old[u] & bit[u]) ? 1 : 0);
-      return won;
-    };
-    // one draw at a time (the last < 4 marks): returns 1 if the bit changed
-    auto draw1 = [&](uint32_t rnd, bool add) -> int {
-      const uint64_t prod = (uint64_t)rnd * (uint64_t)(uint32_t)N;
-      if ((uint32_t)prod < reject_below) return 0;
-      const uint32_t pos = (uint32_t)(prod >> 32);
-      const uint32_t bp = pos * (uint32_t)stride_bits + (uint32_t)pidx, b1 = 1u << (bp & 31u);
-      if (add) {
-        if (!((vm[pos >> 5] >> (pos & 31u)) & 1u)) return 0;
-        return (__hip_atomic_fetch_or(&xs[bp >> 5], b1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & b1) ? 0 : 1;
-      }
-      return (__hip_atomic_fetch_and(&xs[bp >> 5], ~b1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & b1) ? 1 : 0;
-    };
+    const auto isolate = [](uint32_t pos) { return pos; };
     uint32_t base = 0;                                   // next Philox call of this permutation
-    while (d != 0 && base < kFixMaxCalls) {              // group-uniform
-      const bool add = d > 0;
-      const int need = add ? d : -d;
-      const int k = min(L, need >> 2);
-      uint32_t r[4];
-      if (k == 0) {                                      // the last marks: in draw order
-        int left = need;
-        if (l == 0) {
-          philox4x32_10(base, pi, tglob, kDomFix, a.k0, a.k1, r);
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            if (left > 0) left -= draw1(r[u], add);
-        }
-        left = __shfl(left, leader);
-        d = add ? left : -left;
-        base += 1u;
-      } else {
-        int won = 0;
-        if (l < k) {
-          philox4x32_10(base + (uint32_t)l, pi, tglob, kDomFix, a.k0, a.k1, r);
-          won = draws4(r, add);
-        }
-        // marks toggled by the group in this round
-        int got = 0;
-#pragma unroll
-        for (int bitn = 0; bitn < 3; ++bitn)
-          got += __popcll(__ballot((won >> bitn) & 1) & gmask) << bitn;
-        d = add ? d - got : d + got;
-        base += (uint32_t)k;
-      }
-    }
+    fix_rounds<false>(g, d, base, 0u, (uint32_t)N, reject_below, isolate);
+    if (g.l == 0) fix_tail(g, d, base, 0u, (uint32_t)N, reject_below, isolate);
   }
   __syncthreads();
 
@@ -484,7 +520,7 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
     }
     return f;
   };
-  emit_labels<NB, OUT>(a, t, bit0, Bglob, tile_base, live, row_field);
+  emit_labels<NB, OUT>(a, blk, row_field);
 }
 
 // ---- spec S9: labels shuffled within strata ------------------------------------------------------
@@ -508,23 +544,22 @@ struct StrataArgs {
 template <int NB, int OUT>   // NB = 1, 2
 __global__ __launch_bounds__(1024) void k_labels_strata(const LabelArgs a, const StrataArgs sa) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  const int tid = threadIdx.x, lane = tid & 63, tpb = blockDim.x;
+  const int tid = threadIdx.x, tpb = blockDim.x;
   const int N = a.N, S = sa.S;
   LabelBlock<NB> blk;
-  if (!label_block<NB, OUT>(a, blk)) return;
+  if (!label_block<NB, OUT, false>(a, blk)) return;
   const int t = blk.t;
   const uint32_t Bglob = blk.Bglob;
-  uint32_t live[NB];
-#pragma unroll
-  for (int w = 0; w < NB; ++w) live[w] = blk.live[w];
+  const uint32_t (&live)[NB] = blk.live;
   const uint32_t tglob = (uint32_t)(a.trait_base + t);
   const uint32_t* mrow = a.masks + (int64_t)t * a.Wp;
 
   // ---- LDS: rows (NB dwords per isolate), validity words, the stratum table, the members ----
+  const LdsMap<int> lm = strata_lds(N, NB, S);
   const int nmw = (N + 31) >> 5;
   uint32_t* xs = lds;
-  uint32_t* vm = xs + (((int64_t)N * NB + 3) & ~3);
-  uint4* tab = reinterpret_cast<uint4*>(vm + ((nmw + 3) & ~3));    // (m, n_s, 2^32 mod n_s, offset | q << 16 | flip << 24)
+  uint32_t* vm = lds + lm.vm;
+  uint4* tab = reinterpret_cast<uint4*>(lds + lm.own);    // (m, n_s, 2^32 mod n_s, offset | q << 16 | flip << 24)
   uint16_t* mem = reinterpret_cast<uint16_t*>(tab + S);
   for (int k = tid; k < nmw; k += tpb) vm[k] = mrow[k];
   for (int s = tid; s < S; s += tpb) {
@@ -552,44 +587,24 @@ __global__ __launch_bounds__(1024) void k_labels_strata(const LabelArgs a, const
       for (int w = 0; w < NB; ++w)
         x[w] = bern_word((uint32_t)row, Bglob + (uint32_t)w, tglob, q, a.k0, a.k1) & live[w];
     }
-    if constexpr (NB == 2) {
-      *reinterpret_cast<uint2*>(xs + (int64_t)row * 2) = make_uint2(x[0], x[1]);
-    } else {
-      xs[row] = x[0];
-    }
+    store_row0<NB>(xs, row, x, 5);
   }
   __syncthreads();
 
   // ---- fix-up: the group of L lanes of a permutation walks the strata ----
-  // Per stratum: K = the permutation's marks among the members (marks sit on valid isolates only), then
-  // k_labels' fix-up against mem_s.  While at least four marks per call are missing, lane l takes Philox call
-  // base + l (any order gives the sequential result).  The last < 4 marks have to go draw by draw -- one lane's
-  // work -- but strata are independent (their members are disjoint), so the group walks L strata, leaves the
+  // Per stratum: K = the permutation's marks among the members (marks sit on valid isolates only), then the
+  // batched rounds against mem_s.  The last < 4 marks have to go draw by draw -- one lane's work -- but strata
+  // are independent (their members are disjoint), so the group walks L strata, leaves the
   // tail of stratum s0 + l to lane l, and the L tails run side by side: at eight isolates per stratum nearly
   // every stratum is all tail, and one active lane per group would cost a Philox call per stratum and wavefront.
   // The loops over the strata are uniform for the block, the batched rounds for the group.
   {
-    const int nperm = 32 * NB;
-    const int L = min(kWave, tpb / nperm);               // a power of two, >= 2
-    const int pidx = tid / L, l = tid & (L - 1);
-    const bool in_group = pidx < nperm;                  // tpb > 64 * nperm: the last wavefronts idle
-    const int w = pidx >> 5, j = pidx & 31;
-    const bool alive = in_group && (((w ? live[NB - 1] : live[0]) >> j) & 1u);
-    const uint32_t pi = (Bglob + (uint32_t)w) * 32u + (uint32_t)j;
-    const uint32_t bitj = 1u << j;
-    const uint64_t gmask = (L == 64 ? ~(uint64_t)0 : (((uint64_t)1 << L) - 1)) << (lane & ~(L - 1));
-    // one draw against stratum (n, reject_below, off): Lemire rejection, then the member at the position;
-    // returns 1 if the bit changed (k_labels: draw1)
-    auto draw1 = [&](uint32_t rnd, bool add, uint32_t n, uint32_t reject_below, uint32_t off) -> int {
-      const uint64_t prod = (uint64_t)rnd * (uint64_t)n;
-      if ((uint32_t)prod < reject_below) return 0;
-      const uint32_t pos = mem[off + (uint32_t)(prod >> 32)];
-      uint32_t* x = &xs[pos * NB + w];
-      if (add) {
-        if (!((vm[pos >> 5] >> (pos & 31u)) & 1u)) return 0;
-        return (__hip_atomic_fetch_or(x, bitj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & bitj) ? 0 : 1;
-      }
-      return (__hip_atomic_fetch_and(x, ~bitj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & bitj) ? 1 : 0;
+    const FixGroup g = fix_group<NB>(a, blk, xs, vm, 32 * NB);
+    const int L = g.L, l = g.l, j = g.pidx & 31;
+    const uint32_t* xw = xs + (g.pidx >> 5);             // the permutation's dword column of the rows
+    // position -> isolate of the stratum whose members start at `off`
+    const auto member_at = [mem](uint32_t off) {
+      return [mem, off](uint32_t pos) -> uint32_t { return mem[off + pos]; };
     };
     for (int s0 = 0; s0 < S; s0 += L) {
       int my_d = 0;                                      // stratum s0 + l: marks its tail has to add (> 0) / remove
@@ -597,74 +612,22 @@ __global__ __launch_bounds__(1024) void k_labels_strata(const LabelArgs a, const
       const int s1 = min(S, s0 + L);
       for (int s = s0; s < s1; ++s) {
         const uint4 e = tab[s];
-        const uint32_t n = e.y, reject_below = e.z, off = e.w & 0xffffu;
+        const uint32_t n = e.y, off = e.w & 0xffffu;
         if (n == 0u) continue;
         int K = 0;
-        if (alive)
-          for (uint32_t k = (uint32_t)l; k < n; k += (uint32_t)L) K += (xs[(uint32_t)mem[off + k] * NB + w] >> j) & 1u;
+        if (g.alive)                                     // bit bp = member * 32 * NB + pidx, by dword and bit
+          for (uint32_t k = (uint32_t)l; k < n; k += (uint32_t)L) K += (xw[(uint32_t)mem[off + k] * NB] >> j) & 1u;
         for (int o = 1; o < L; o <<= 1) K += __shfl_xor(K, o);
-        int d = alive ? (int)e.x - K : 0;                // > 0: add marks, < 0: remove
-        // four draws of one Philox call; the toggles are LDS atomics whose returned old word says whether THIS
-        // lane changed the bit (k_labels: draws4)
-        auto draws4 = [&](const uint32_t (&rnd)[4], bool add) -> int {
-          uint32_t idx[4];
-          bool ok[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const uint64_t prod = (uint64_t)rnd[u] * (uint64_t)n;
-            const uint32_t pos = mem[off + (uint32_t)(prod >> 32)];
-            idx[u] = pos * NB + w;
-            ok[u] = (uint32_t)prod >= reject_below;
-            if (add) ok[u] = ok[u] && ((vm[pos >> 5] >> (pos & 31u)) & 1u);
-          }
-          uint32_t old[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            old[u] = add ? bitj : 0u;
-            if (ok[u])
-              old[u] = add ? __hip_atomic_fetch_or(&xs[idx[u]], bitj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-                           : __hip_atomic_fetch_and(&xs[idx[u]], ~bitj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          }
-          int won = 0;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) won += add ? ((old[u] & bitj) ? 0 : 1) : ((old[u] & bitj) ? 1 : 0);
-          return won;
-        };
-        const uint32_t cs = (uint32_t)s << 20;           // the stratum in the counter: calls stay below 2^20
+        int d = g.alive ? (int)e.x - K : 0;              // > 0: add marks, < 0: remove
         uint32_t base = 0;                               // next Philox call of this (permutation, stratum)
-        while ((d >= 4 || d <= -4) && base < kFixMaxCalls) {   // group-uniform: rounds that cannot overshoot
-          const bool add = d > 0;
-          const int need = add ? d : -d;
-          const int k = min(min(L, need >> 2), (int)(kFixMaxCalls - base));
-          uint32_t r[4];
-          int won = 0;
-          if (l < k) {
-            philox4x32_10(cs | (base + (uint32_t)l), pi, tglob, kDomFix, a.k0, a.k1, r);
-            won = draws4(r, add);
-          }
-          int got = 0;
-#pragma unroll
-          for (int bitn = 0; bitn < 3; ++bitn)
-            got += __popcll(__ballot((won >> bitn) & 1) & gmask) << bitn;
-          d = add ? d - got : d + got;
-          base += (uint32_t)k;
-        }
+        // the stratum in the counter: calls stay below 2^20
+        fix_rounds<true>(g, d, base, (uint32_t)s << 20, n, e.z, member_at(off));
         if (l == s - s0) my_d = d, my_base = base;       // |d| < 4 (or the safety stop): the tail
       }
       // the tails of the L strata, lane l in the draw order of stratum s0 + l
       if (my_d != 0) {
         const uint4 e = tab[s0 + l];
-        const uint32_t cs = (uint32_t)(s0 + l) << 20;
-        const bool add = my_d > 0;
-        int left = add ? my_d : -my_d;
-        while (left > 0 && my_base < kFixMaxCalls) {
-          uint32_t r[4];
-          philox4x32_10(cs | my_base, pi, tglob, kDomFix, a.k0, a.k1, r);
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            if (left > 0) left -= draw1(r[u], add, e.y, e.z, e.w & 0xffffu);
-          ++my_base;
-        }
+        fix_tail(g, my_d, my_base, (uint32_t)(s0 + l) << 20, e.y, e.z, member_at(e.w & 0xffffu));
       }
     }
   }
@@ -679,7 +642,7 @@ __global__ __launch_bounds__(1024) void k_labels_strata(const LabelArgs a, const
     }
     return f;
   };
-  emit_labels<NB, OUT>(a, t, 0, Bglob, blk.tile_base, live, row_field);
+  emit_labels<NB, OUT>(a, blk, row_field);
 }
 
 // (npos_ts, nval_ts) of every (trait, stratum): one block per trait, a histogram over the strata in LDS
@@ -705,15 +668,11 @@ __global__ __launch_bounds__(256) void k_strata_margins(const uint32_t* __restri
 }
 
 // ---- launch geometry --------------------------------------------------------------------------
-int64_t labels_lds_bytes(int64_t N, int elt, int NB) {
-  const int64_t xs = ((N * elt * NB + 31) / 32 + 3) / 4 * 4, vm = ((N + 31) / 32 + 3) / 4 * 4;
-  return (xs + vm + 32 * NB) * 4;
-}
 // permutations of a dword column a block keeps: 32 while its rows fit LDS, else 16, 8 (tiles),
 // ... 1 (bit rows); 0: N too large
 int labels_elt(int64_t N, int min_elt) {
   for (int elt = 32; elt >= min_elt; elt >>= 1)
-    if (labels_lds_bytes(N, elt, 1) <= kLabelsMaxLds) return elt;
+    if (labels_lds(N, elt, 1).bytes() <= kLabelsMaxLds) return elt;
   return 0;
 }
 int ilog2(int v) {
@@ -731,54 +690,107 @@ int labels_threads(int64_t blocks, int64_t N, int num_cu) {
   while (tpb < 1024 && (N + tpb - 1) / tpb > kMaxRowsPerThread) tpb *= 2;
   return tpb;
 }
-template <int NB, int OUT>
-int launch_labels(scoary_handle h, hipStream_t s, const LabelArgs& a, dim3 grid, int tpb, int elt) {
-  const size_t lds = (size_t)labels_lds_bytes(a.N, elt, NB);
-  // the per-lane mark counters would wrap (labels_threads never picks such a geometry)
-  if (tpb < 64 || tpb > 1024 || (tpb & (tpb - 1)) || (a.N + tpb - 1) / tpb > kMaxRowsPerThread)
-    return fail(h, SCOARY_ERR_SIZE, "k_labels: more than 1023 isolates per thread (or a block size that is no "
-                                    "power of two in 64..1024)");
-  const void* fn = reinterpret_cast<const void*>(&k_labels<NB, OUT>);
-  const int bit = 1 << (NB + 8 * OUT);             // 2, 4, 16 | 512
-  if (lds > 64 * 1024 && !(h->labels_lds_optin & bit)) {
+// The one launch path of the generator kernels.  optin_bit: the kernel's bit in the handle's record of who may
+// use more than 64 KB of LDS; fits / why: the kernel's own limit, and what to say when it or the block size is off
+template <class... Args>
+int launch_block(scoary_handle h, hipStream_t s, void (*kernel)(Args...), int optin_bit, int64_t lds_bytes,
+                 bool fits, const char* why, dim3 grid, int tpb, const Args&... args) {
+  if (tpb < 64 || tpb > 1024 || (tpb & (tpb - 1)) || !fits) return fail(h, SCOARY_ERR_SIZE, why);
+  const void* fn = reinterpret_cast<const void*>(kernel);
+  if (lds_bytes > 64 * 1024 && !(h->labels_lds_optin & optin_bit)) {
     HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLabelsMaxLds));
-    h->labels_lds_optin |= bit;
+    h->labels_lds_optin |= optin_bit;
   }
-  hipLaunchKernelGGL((k_labels<NB, OUT>), grid, dim3((unsigned)tpb), lds, s, a);
+  hipLaunchKernelGGL(kernel, grid, dim3((unsigned)tpb), (size_t)lds_bytes, s, args...);
   HIP_TRY(h, hipGetLastError());
   return SCOARY_OK;
+}
+int launch_labels(scoary_handle h, hipStream_t s, const LabelArgs& a, int NB, int OUT, dim3 grid, int tpb) {
+  // the per-lane mark counters would wrap (labels_threads never picks such a geometry)
+  const bool fits = (int64_t)tpb * kMaxRowsPerThread >= a.N;
+  return launch_block(h, s, OUT ? k_labels<1, 1> : (NB == 2 ? k_labels<2, 0> : k_labels<1, 0>),
+                      1 << (NB + 8 * OUT) /* 2, 4 | 512 */, labels_lds<int64_t>(a.N, 1 << a.elt_log2, NB).bytes(), fits,
+                      "k_labels: more than 1023 isolates per thread (or a block size that is no power of two in "
+                      "64..1024)", grid, tpb, a);
+}
+int launch_labels_strata(scoary_handle h, hipStream_t s, const LabelArgs& a, const StrataArgs& sa, int NB, int OUT,
+                         dim3 grid, int tpb) {
+  const int64_t lds_bytes = strata_lds<int64_t>(a.N, NB, sa.S).bytes();
+  return launch_block(h, s, OUT ? k_labels_strata<1, 1> : (NB == 2 ? k_labels_strata<2, 0> : k_labels_strata<1, 0>),
+                      1 << (16 + NB + 8 * OUT), lds_bytes, lds_bytes <= kLabelsMaxLds,
+                      "k_labels_strata: rows, members and the stratum table do not fit LDS (or a block size that is "
+                      "no power of two in 64..1024)", grid, tpb, a, sa);
 }
 
-// ---- stratified launches ------------------------------------------------------------------------
-int64_t strata_lds_bytes(int64_t N, int NB, int64_t S) {
-  const int64_t xs = (N * NB + 3) / 4 * 4, vm = ((N + 31) / 32 + 3) / 4 * 4;
-  return (xs + vm + 4 * S + (N + 1) / 2) * 4;
+// What every launch fills of LabelArgs (bit rows are complete with it; tiles add their range from a TileShape)
+LabelArgs label_args(const uint32_t* d_masks, const int32_t* d_margins, int64_t N, int64_t P, int64_t perm_base,
+                     int64_t trait_base, uint64_t seed, int elt, uint32_t* d_out) {
+  LabelArgs a{};
+  a.masks = d_masks, a.margins = d_margins, a.N = (int)N, a.Wp = (int)scoary_row_words(N);
+  a.P = P, a.perm_base = perm_base, a.trait_base = (int)trait_base;
+  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.elt_log2 = ilog2(elt), a.out = d_out;
+  return a;
 }
-template <int NB, int OUT>
-int launch_labels_strata(scoary_handle h, hipStream_t s, const LabelArgs& a, const StrataArgs& sa, dim3 grid, int tpb) {
-  const size_t lds = (size_t)strata_lds_bytes(a.N, NB, sa.S);
-  if (tpb < 64 || tpb > 1024 || (tpb & (tpb - 1)) || lds > (size_t)kLabelsMaxLds)
-    return fail(h, SCOARY_ERR_SIZE, "k_labels_strata: rows, members and the stratum table do not fit LDS (or a block "
-                                    "size that is no power of two in 64..1024)");
-  const void* fn = reinterpret_cast<const void*>(&k_labels_strata<NB, OUT>);
-  const int bit = 1 << (16 + NB + 8 * OUT);
-  if (lds > 64 * 1024 && !(h->labels_lds_optin & bit)) {
-    HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLabelsMaxLds));
-    h->labels_lds_optin |= bit;
-  }
-  hipLaunchKernelGGL((k_labels_strata<NB, OUT>), grid, dim3((unsigned)tpb), lds, s, a, sa);
-  HIP_TRY(h, hipGetLastError());
-  return SCOARY_OK;
+
+// ---- the checks the entry points share; `what` names the entry point in the message -------------
+int check_args(scoary_handle h, const char* what, bool ok) {
+  return ok ? SCOARY_OK : fail(h, SCOARY_ERR_ARG, std::string(what) + ": bad argument");
 }
-// the argument checks the three stratified entry points share; `what` names the entry point
-int strata_check(scoary_handle h, const char* what, bool pointers, int64_t T, int64_t N, int64_t S) {
-  if (!pointers || T < 1 || N < 1 || S < 1)
-    return fail(h, SCOARY_ERR_ARG, std::string(what) + ": bad argument");
+int check_tile_base(scoary_handle h, const char* what, int64_t perm_base) {
+  return (perm_base & 31) ? fail(h, SCOARY_ERR_ARG, std::string(what) + ": perm_base must be a multiple of 32")
+                          : SCOARY_OK;
+}
+int check_grid(scoary_handle h, const char* what, int64_t gx) {
+  return gx > 0x7fffffffLL ? fail(h, SCOARY_ERR_SIZE, std::string(what) + ": grid too large") : SCOARY_OK;
+}
+// the stratified entry points: arguments, then the limits of the per-stratum tables
+int strata_check(scoary_handle h, const char* what, bool ok, int64_t T, int64_t N, int64_t S) {
+  if (int rc = check_args(h, what, ok && T >= 1 && N >= 1 && S >= 1)) return rc;
   if (T > 65535) return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": T > 65535");
-  if (S > kMaxStrata) return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more strata than scoary_perm_max_strata()");
+  if (S > kMaxStrata)
+    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more strata than scoary_perm_max_strata()");
   if (N > kStrataMaxIsolates)
     return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more isolates than scoary_perm_strata_max_isolates()");
   return SCOARY_OK;
+}
+
+// bit rows: one block per (Philox block touched, sub-dword piece)
+int64_t row_blocks(int64_t perm_base, int64_t P, int elt) {
+  return (((perm_base + P - 1) >> 5) - (perm_base >> 5) + 1) * (32 / elt);
+}
+
+// The launch shape of a tile range.  gx = 0: the range is empty, nothing to launch
+struct TileShape {
+  int TW, NB, tpb;
+  int64_t ntiles, gx;
+};
+// elt: permutations of a dword a block keeps (0: N too large for the generator); lds(NB): the kernel's LDS map
+template <class Lds>
+int tile_shape(scoary_handle h, const char* what, int64_t T, int64_t N, int64_t P, int64_t first_tile,
+               int64_t n_tiles, int elt, Lds lds, TileShape& ts) {
+  ts = TileShape{};
+  ts.TW = list_tw(N);
+  if (!ts.TW) return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": N too large for LDS tiles");
+  const int64_t tile_perms = ts.TW * 32;
+  ts.ntiles = (P + tile_perms - 1) / tile_perms;
+  if (first_tile + n_tiles > T * ts.ntiles)
+    return fail(h, SCOARY_ERR_ARG, std::string(what) + ": tile range past the last (trait, tile)");
+  if (n_tiles == 0) return SCOARY_OK;
+  if (!elt) return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": N too large for the label generator");
+  // dword columns per block: two if that keeps >= 2 blocks per CU in the launch and >= 2 blocks
+  // of LDS per CU (wider pieces per tile row, fewer count reductions)
+  // (four columns per block were measured too: the fix-up then has two lanes per permutation and
+  // k_labels is slower at the headline shape, 0.086 against 0.077 ms)
+  ts.NB = (elt == 32 && 2 <= ts.TW && n_tiles * (ts.TW / 2) >= 2 * (int64_t)h->num_cu &&
+           lds(2).bytes() <= kLabelsMaxLds / 2) ? 2 : 1;
+  const int64_t units = (int64_t)ts.TW * (32 / elt) / ts.NB;
+  ts.gx = (n_tiles + 7) / 8 * 8 * units;
+  if (int rc = check_grid(h, what, ts.gx)) return rc;
+  ts.tpb = labels_threads(n_tiles * units, N, h->num_cu);
+  return SCOARY_OK;
+}
+void tile_args(LabelArgs& a, const TileShape& ts, int64_t first_tile, int64_t n_tiles) {
+  a.ntiles = (int)ts.ntiles, a.TW = ts.TW, a.first_flat = first_tile, a.nflat = n_tiles;
 }
 
 }  // namespace
@@ -797,74 +809,48 @@ int64_t scoary_perm_max_isolates(void) {
 int scoary_perm_generate(scoary_handle h, const uint32_t* d_masks, const int32_t* d_margins,
                          int64_t T, int64_t N, int64_t P, int64_t perm_base, int64_t trait_base,
                          uint64_t seed, uint32_t* d_perms, scoary_stream_t stream) {
+  const char* what = "scoary_perm_generate";
   if (!h) return SCOARY_ERR_ARG;
-  if (!d_masks || !d_margins || !d_perms || T < 1 || N < 1 || P < 1 || perm_base < 0 || trait_base < 0)
-    return fail(h, SCOARY_ERR_ARG, "scoary_perm_generate: bad argument");
+  if (int rc = check_args(h, what, d_masks && d_margins && d_perms && T >= 1 && N >= 1 && P >= 1 && perm_base >= 0 &&
+                                       trait_base >= 0))
+    return rc;
   if (T > 65535 || trait_base + T > 0x7fffffffLL || perm_base + P > 0xffffffffLL)
     return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate: T > 65535 or permutation index >= 2^32");
   const int elt = labels_elt(N, 1);
   if (!elt) return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate: more isolates than scoary_perm_max_isolates()");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  LabelArgs a{};
-  a.masks = d_masks, a.margins = d_margins, a.N = (int)N, a.Wp = (int)scoary_row_words(N);
-  a.P = P, a.perm_base = perm_base, a.trait_base = (int)trait_base;
-  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.elt_log2 = ilog2(elt), a.out = d_perms;
-  const int64_t nblk32 = ((perm_base + P - 1) >> 5) - (perm_base >> 5) + 1;   // Philox blocks touched
-  const int64_t gx = nblk32 * (32 / elt);
-  if (gx > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate: grid too large");
+  const LabelArgs a = label_args(d_masks, d_margins, N, P, perm_base, trait_base, seed, elt, d_perms);
+  const int64_t gx = row_blocks(perm_base, P, elt);
+  if (int rc = check_grid(h, what, gx)) return rc;
   KernelTimer kt(h, s, "k_perm_generate");
-  return launch_labels<1, 1>(h, s, a, dim3((unsigned)gx, (unsigned)T),
-                             labels_threads(gx * T, N, h->num_cu), elt);
+  return launch_labels(h, s, a, 1, 1, dim3((unsigned)gx, (unsigned)T), labels_threads(gx * T, N, h->num_cu));
 }
 
 int scoary_perm_generate_tiles_range(scoary_handle h, const uint32_t* d_masks, const int32_t* d_margins,
                                      int64_t T, int64_t N, int64_t P, int64_t perm_base,
                                      int64_t trait_base, uint64_t seed, int64_t first_tile,
                                      int64_t n_tiles, uint32_t* d_tiles, scoary_stream_t stream) {
+  const char* what = "scoary_perm_generate_tiles";
   if (!h) return SCOARY_ERR_ARG;
-  if (!d_masks || !d_margins || !d_tiles || T < 1 || N < 1 || P < 1 || perm_base < 0 || trait_base < 0 ||
-      first_tile < 0 || n_tiles < 0)
-    return fail(h, SCOARY_ERR_ARG, "scoary_perm_generate_tiles: bad argument");
-  if (perm_base & 31)
-    return fail(h, SCOARY_ERR_ARG, "scoary_perm_generate_tiles: perm_base must be a multiple of 32");
+  if (int rc = check_args(h, what, d_masks && d_margins && d_tiles && T >= 1 && N >= 1 && P >= 1 && perm_base >= 0 &&
+                                       trait_base >= 0 && first_tile >= 0 && n_tiles >= 0))
+    return rc;
+  if (int rc = check_tile_base(h, what, perm_base)) return rc;
   if (T > 65535 || perm_base + P > 0xffffffffLL)
     return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles: T > 65535 or permutation index >= 2^32");
-  const int TW = list_tw(N);
-  if (!TW) return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles: N too large for LDS tiles");
-  const int64_t tile_perms = TW * 32;
-  const int64_t ntiles = (P + tile_perms - 1) / tile_perms;
-  if (first_tile + n_tiles > T * ntiles)
-    return fail(h, SCOARY_ERR_ARG, "scoary_perm_generate_tiles: tile range past the last (trait, tile)");
-  if (n_tiles == 0) return SCOARY_OK;
   const int elt = labels_elt(N, 8);
-  if (!elt) return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles: N too large for the label generator");
+  TileShape ts;
+  if (int rc = tile_shape(h, what, T, N, P, first_tile, n_tiles, elt,
+                          [&](int nb) { return labels_lds(N, 32, nb); }, ts))
+    return rc;
+  if (ts.gx == 0) return SCOARY_OK;
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  LabelArgs a{};
-  a.masks = d_masks, a.margins = d_margins, a.N = (int)N, a.Wp = (int)scoary_row_words(N);
-  a.P = P, a.perm_base = perm_base, a.trait_base = (int)trait_base;
-  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.elt_log2 = ilog2(elt);
-  a.ntiles = (int)ntiles, a.TW = TW, a.first_flat = first_tile, a.nflat = n_tiles, a.out = d_tiles;
-  // dword columns per block: as many as keep >= 2 blocks per CU in the launch and >= 2 blocks
-  // of LDS per CU (wider pieces per tile row, fewer count reductions)
-  // (four columns per block were measured too: the fix-up then has two lanes per permutation and
-  // the kernel is slower at the headline shape, 0.086 against 0.077 ms)
-  int NB = 1;
-  if (elt == 32)
-    for (int nb = 2; nb > 1; nb >>= 1)
-      if (nb <= TW && n_tiles * (TW / nb) >= 2 * (int64_t)h->num_cu &&
-          labels_lds_bytes(N, 32, nb) <= kLabelsMaxLds / 2) {
-        NB = nb;
-        break;
-      }
-  const int64_t units = (int64_t)TW * (32 / elt) / NB;
-  const int64_t gx = (n_tiles + 7) / 8 * 8 * units;
-  if (gx > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles: grid too large");
-  const int tpb = labels_threads(n_tiles * units, N, h->num_cu);
+  LabelArgs a = label_args(d_masks, d_margins, N, P, perm_base, trait_base, seed, elt, d_tiles);
+  tile_args(a, ts, first_tile, n_tiles);
   KernelTimer kt(h, s, "k_perm_generate_tiles");
-  if (NB == 2) return launch_labels<2, 0>(h, s, a, dim3((unsigned)gx), tpb, elt);
-  return launch_labels<1, 0>(h, s, a, dim3((unsigned)gx), tpb, elt);
+  return launch_labels(h, s, a, ts.NB, 0, dim3((unsigned)ts.gx), ts.tpb);
 }
 
 int scoary_perm_generate_tiles(scoary_handle h, const uint32_t* d_masks, const int32_t* d_margins,
@@ -901,25 +887,22 @@ int scoary_perm_generate_strata(scoary_handle h, const uint32_t* d_masks, const 
                                 const int32_t* d_members, const int32_t* d_offsets, const int32_t* d_smargins,
                                 int64_t T, int64_t N, int64_t S, int64_t P, int64_t perm_base, int64_t trait_base,
                                 uint64_t seed, uint32_t* d_perms, scoary_stream_t stream) {
+  const char* what = "scoary_perm_generate_strata";
   if (!h) return SCOARY_ERR_ARG;
-  if (int rc = strata_check(h, "scoary_perm_generate_strata",
-                            d_masks && d_strata && d_members && d_offsets && d_smargins && d_perms && P >= 1 &&
-                                perm_base >= 0 && trait_base >= 0, T, N, S))
+  if (int rc = strata_check(h, what, d_masks && d_strata && d_members && d_offsets && d_smargins && d_perms &&
+                                         P >= 1 && perm_base >= 0 && trait_base >= 0, T, N, S))
     return rc;
   if (trait_base + T > 0x7fffffffLL || perm_base + P > 0xffffffffLL)
     return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_strata: permutation index >= 2^32");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  LabelArgs a{};
-  a.masks = d_masks, a.N = (int)N, a.Wp = (int)scoary_row_words(N);
-  a.P = P, a.perm_base = perm_base, a.trait_base = (int)trait_base;
-  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.elt_log2 = 5, a.out = d_perms;
+  const LabelArgs a = label_args(d_masks, nullptr, N, P, perm_base, trait_base, seed, 32, d_perms);
   const StrataArgs sa{d_strata, d_members, d_offsets, d_smargins, (int)S};
-  const int64_t gx = ((perm_base + P - 1) >> 5) - (perm_base >> 5) + 1;       // Philox blocks touched
-  if (gx > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_strata: grid too large");
+  const int64_t gx = row_blocks(perm_base, P, 32);
+  if (int rc = check_grid(h, what, gx)) return rc;
   KernelTimer kt(h, s, "k_perm_generate_strata");
-  return launch_labels_strata<1, 1>(h, s, a, sa, dim3((unsigned)gx, (unsigned)T),
-                                    labels_threads(gx * T, N, h->num_cu));
+  return launch_labels_strata(h, s, a, sa, 1, 1, dim3((unsigned)gx, (unsigned)T),
+                              labels_threads(gx * T, N, h->num_cu));
 }
 
 int scoary_perm_generate_tiles_strata_range(scoary_handle h, const uint32_t* d_masks, const uint16_t* d_strata,
@@ -928,40 +911,27 @@ int scoary_perm_generate_tiles_strata_range(scoary_handle h, const uint32_t* d_m
                                             int64_t perm_base, int64_t trait_base, uint64_t seed,
                                             int64_t first_tile, int64_t n_tiles, uint32_t* d_tiles,
                                             scoary_stream_t stream) {
+  const char* what = "scoary_perm_generate_tiles_strata_range";
   if (!h) return SCOARY_ERR_ARG;
-  if (int rc = strata_check(h, "scoary_perm_generate_tiles_strata_range",
-                            d_masks && d_strata && d_members && d_offsets && d_smargins && d_tiles && P >= 1 &&
-                                perm_base >= 0 && trait_base >= 0 && first_tile >= 0 && n_tiles >= 0, T, N, S))
+  if (int rc = strata_check(h, what, d_masks && d_strata && d_members && d_offsets && d_smargins && d_tiles &&
+                                         P >= 1 && perm_base >= 0 && trait_base >= 0 && first_tile >= 0 &&
+                                         n_tiles >= 0, T, N, S))
     return rc;
-  if (perm_base & 31)
-    return fail(h, SCOARY_ERR_ARG, "scoary_perm_generate_tiles_strata_range: perm_base must be a multiple of 32");
+  if (int rc = check_tile_base(h, what, perm_base)) return rc;
   if (trait_base + T > 0x7fffffffLL || perm_base + P > 0xffffffffLL)
     return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles_strata_range: permutation index >= 2^32");
-  const int TW = list_tw(N);
-  const int64_t tile_perms = TW * 32;
-  const int64_t ntiles = (P + tile_perms - 1) / tile_perms;
-  if (first_tile + n_tiles > T * ntiles)
-    return fail(h, SCOARY_ERR_ARG, "scoary_perm_generate_tiles_strata_range: tile range past the last (trait, tile)");
-  if (n_tiles == 0) return SCOARY_OK;
+  TileShape ts;
+  if (int rc = tile_shape(h, what, T, N, P, first_tile, n_tiles, 32,
+                          [&](int nb) { return strata_lds(N, nb, S); }, ts))
+    return rc;
+  if (ts.gx == 0) return SCOARY_OK;
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  LabelArgs a{};
-  a.masks = d_masks, a.N = (int)N, a.Wp = (int)scoary_row_words(N);
-  a.P = P, a.perm_base = perm_base, a.trait_base = (int)trait_base;
-  a.k0 = (uint32_t)seed, a.k1 = (uint32_t)(seed >> 32), a.elt_log2 = 5;
-  a.ntiles = (int)ntiles, a.TW = TW, a.first_flat = first_tile, a.nflat = n_tiles, a.out = d_tiles;
+  LabelArgs a = label_args(d_masks, nullptr, N, P, perm_base, trait_base, seed, 32, d_tiles);
+  tile_args(a, ts, first_tile, n_tiles);
   const StrataArgs sa{d_strata, d_members, d_offsets, d_smargins, (int)S};
-  // two dword columns per block by k_labels' rule: >= 2 blocks per CU in the launch and in a CU's LDS
-  const int NB = (2 <= TW && n_tiles * (TW / 2) >= 2 * (int64_t)h->num_cu &&
-                  strata_lds_bytes(N, 2, S) <= kLabelsMaxLds / 2) ? 2 : 1;
-  const int64_t units = TW / NB;
-  const int64_t gx = (n_tiles + 7) / 8 * 8 * units;
-  if (gx > 0x7fffffffLL)
-    return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles_strata_range: grid too large");
-  const int tpb = labels_threads(n_tiles * units, N, h->num_cu);
   KernelTimer kt(h, s, "k_perm_generate_tiles_strata");
-  if (NB == 2) return launch_labels_strata<2, 0>(h, s, a, sa, dim3((unsigned)gx), tpb);
-  return launch_labels_strata<1, 0>(h, s, a, sa, dim3((unsigned)gx), tpb);
+  return launch_labels_strata(h, s, a, sa, ts.NB, 0, dim3((unsigned)ts.gx), ts.tpb);
 }
 
 }  // extern "C"

@@ -418,8 +418,7 @@ class AssociationEngine:
             if tile_range is None:
                 tile_range = (0, self.tiles_per_batch(N, P, T)[0])
             self._check(self.lib.scoary_perm_generate_tiles_strata_range(
-                self.h, self._ptr(masks), self._ptr(strata.strata), self._ptr(strata.members),
-                self._ptr(strata.offsets), self._ptr(strata.smargins), T, N, strata.S, P, perm_base, trait_base,
+                self.h, self._ptr(masks), *self._strata_ptrs(strata), T, N, strata.S, P, perm_base, trait_base,
                 ctypes.c_uint64(seed), int(tile_range[0]), int(tile_range[1]), self._ptr(out), self._stream()),
                 "scoary_perm_generate_tiles_strata_range")
         elif tile_range is None:
@@ -596,6 +595,10 @@ class AssociationEngine:
             raise ValueError("the strata plan was built for other traits (%d traits, %d isolates)"
                              % (strata.T, strata.N))
 
+    def _strata_ptrs(self, strata):
+        """The four device arrays of a StrataPlan, in the order the stratified generators take them."""
+        return tuple(self._ptr(x) for x in (strata.strata, strata.members, strata.offsets, strata.smargins))
+
     def perm_generate(self, masks, margins, N, P, perm_base, seed, out=None, trait_base=0, strata=None):
         """Label rows [T, P, Wp] of the permutations perm_base .. perm_base + P - 1 (spec S4); with ``strata``
         (a StrataPlan of these traits) shuffled within its strata (spec S9)."""
@@ -607,8 +610,7 @@ class AssociationEngine:
         if strata is not None:
             self._strata_fits(strata, T, N)
             self._check(self.lib.scoary_perm_generate_strata(
-                self.h, self._ptr(masks), self._ptr(strata.strata), self._ptr(strata.members),
-                self._ptr(strata.offsets), self._ptr(strata.smargins), T, N, strata.S, P, perm_base, trait_base,
+                self.h, self._ptr(masks), *self._strata_ptrs(strata), T, N, strata.S, P, perm_base, trait_base,
                 ctypes.c_uint64(seed), self._ptr(out), self._stream()), "scoary_perm_generate_strata")
             return out
         self._check(self.lib.scoary_perm_generate(self.h, self._ptr(masks), self._ptr(margins), T,

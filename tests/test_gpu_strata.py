@@ -142,6 +142,36 @@ def test_rows_and_tiles_equal_the_python_restatement(eng, name):
     assert np.array_equal(shifted, rows[:, 7:])
 
 
+def test_two_columns_per_block_tiles(eng):
+    """N = 130, T = 8, P = 4096: 64 tiles of 16 dword columns, enough for two blocks per CU at two columns per
+    block, so the tiles come from k_labels_strata<2, 0> (the other cases here launch too few blocks for it).
+    They equal the transposed rows, which come from <1, 1>; with one stratum they are k_labels' tiles."""
+    import torch
+    N, _, strata, four, _ = _spec_case("n130")
+    T, P = 8, 4096
+    traits = np.concatenate([four, _random_traits(np.random.default_rng(77), T - four.shape[0], N)])
+    n_tiles, _tw = eng.tiles_per_batch(N, P, T)
+    TW = eng.list_params(N)[0]
+    assert (TW, n_tiles) == (16, 64)
+    # the launch rule for two columns per block: without this the test would pass through <1, 0> unnoticed
+    assert n_tiles * (TW // 2) >= 2 * torch.cuda.get_device_properties(0).multi_processor_count
+    trv, mkv, margins = _device_traits(eng, traits)
+    sp = eng.strata_plan(strata, trv, mkv, N)
+    assert sp.sizes.tolist() == [1, 64, 65]
+    rows = _row_bits(eng.perm_generate(mkv, margins, N, P, 0, SEED, strata=sp), N)
+    tiles = _tile_bits(eng, eng.perm_generate_tiles(mkv, margins, N, P, 0, SEED, strata=sp), T, N, P)
+    assert np.array_equal(tiles, rows)
+    assert (rows != (traits == 1)[:, None, :]).any()
+    one = eng.strata_plan(np.zeros(N, dtype=np.int64), trv, mkv, N)
+    words = int(eng.lib.scoary_list_tiles_words(N, P, T))       # (zeroed: a tile ends in up to 3 dwords nobody writes)
+    want = eng.perm_generate_tiles(mkv, margins, N, P, 0, SEED,
+                                   out=torch.zeros(words, dtype=torch.int32, device=eng.device)).cpu().numpy()
+    got = eng.perm_generate_tiles(mkv, margins, N, P, 0, SEED, strata=one,
+                                  out=torch.zeros(words, dtype=torch.int32, device=eng.device)).cpu().numpy()
+    assert want.any()
+    assert np.array_equal(got, want)
+
+
 def test_tile_range_halves_concatenate_to_the_whole(eng):
     import torch
     N, T, P = 700, 3, 1100

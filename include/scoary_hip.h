@@ -363,6 +363,33 @@ int scoary_perm_generate_tiles_strata_range(scoary_handle h, const uint32_t *d_m
                                             int64_t perm_base, int64_t trait_base, uint64_t seed,
                                             int64_t first_tile, int64_t n_tiles, uint32_t *d_tiles,
                                             scoary_stream_t stream);
+/* ---- Cochran-Mantel-Haenszel test over the strata (spec S10 of DESIGN.md; additive, ABI 11) -----------
+ * No counterpart in the reference.  Per (trait, gene) the 2x2 tables of the S strata -- a = popc(gene & label &
+ * stratum), m = popc(gene & valid & stratum), k = npos_ts, n = nval_ts -- are counted and folded in ascending
+ * stratum order into fp64 sums whose operation order S10 fixes: the continuity-corrected CMH chi-square (R's
+ * mantelhaen.test(correct = TRUE)), its p = erfc(sqrt(stat / 2)), the Mantel-Haenszel common odds ratio, and the
+ * rejection region of the POOLED overlap count a' = popc(gene & label) under within-stratum shuffles (S9), in
+ * the (base, span) form scoary_permute / scoary_permute_lists / scoary_permute_hybrid consume: the exact
+ * stratified permutation test of the CMH statistic is those kernels run with this d_crit.
+ *   d_labels / d_masks : vecrows [T][Wp], as scoary_strata_margins took them
+ *   d_strata / d_members / d_offsets / d_smargins : the strata plan of scoary_perm_generate_strata (d_offsets is
+ *       part of the plan and is not read: the stratum of a member is d_strata's)
+ *   d_stat, d_p, d_odds, d_e2 (twice the expectation of the pooled count), d_var : double [T][G];
+ *   d_a : int32 [T][G], the pooled count; d_crit : uint32 [T][G][2]
+ *   (trait, gene) pairs without an informative stratum (d_var = 0; the genes the reference never tests among
+ *   them) get stat = nan, p = 1 and the region (0, 0): every permutation counts
+ *   d_scounts : int32 [T][G][S][2] = (a, m) of every stratum, or NULL (the usual case: the per-stratum tables
+ *       live in registers only)
+ *   d_scratch : scoary_cmh_scratch_bytes(N) bytes, the strata as a table of (word, stratum, mask) segments,
+ *       rebuilt by every call; nothing in it has to survive the call
+ * Asynchronous on `stream`, allocates nothing, may be recorded into a graph.  The size limits of the strata
+ * plan: S <= scoary_perm_max_strata(), N <= scoary_perm_strata_max_isolates(), T <= 65535 (SCOARY_ERR_SIZE). */
+int64_t scoary_cmh_scratch_bytes(int64_t N);
+int scoary_cmh(scoary_handle h, const uint32_t *d_tiled, const uint32_t *d_labels, const uint32_t *d_masks,
+               const uint16_t *d_strata, const int32_t *d_members, const int32_t *d_offsets,
+               const int32_t *d_smargins, int64_t G, int64_t T, int64_t N, int64_t S, double *d_stat,
+               double *d_p, double *d_odds, double *d_e2, double *d_var, int32_t *d_a, uint32_t *d_crit,
+               int32_t *d_scounts, void *d_scratch, scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

@@ -67,6 +67,8 @@ SIGNATURES = {
     "scoary_strata_margins": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "scoary_perm_generate_strata": (_i32, [_vp] * 6 + [_i64] * 6 + [_u64, _vp, _vp]),
     "scoary_perm_generate_tiles_strata_range": (_i32, [_vp] * 6 + [_i64] * 6 + [_u64, _i64, _i64, _vp, _vp]),
+    "scoary_cmh_scratch_bytes": (_i64, [_i64]),
+    "scoary_cmh": (_i32, [_vp] * 8 + [_i64] * 4 + [_vp] * 10),
     "scoary_permute_lists_scratch_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "scoary_permute_lists": (_i32, [_vp, _vp, _vp, _i64] + [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp,
                                                                        _i32, _vp]),

@@ -1,0 +1,231 @@
+// scoary_cmh.hip -- the Cochran-Mantel-Haenszel test over the per-stratum 2x2 tables (spec S10 of DESIGN.md):
+// per (trait, gene) the stratified chi-square with its p, the Mantel-Haenszel common odds ratio, and the
+// rejection region of the pooled overlap count that the permutation kernels consume under the S9 null.
+//
+//   k_cmh_segments : once per call, one block: the strata as a SEGMENT TABLE -- (32-bit word of the isolate row,
+//       stratum, mask of that stratum's isolates inside the word), sorted by (stratum, word).  The members array
+//       of the strata plan is ordered by (stratum, isolate), so a segment is a run of consecutive members with
+//       the same key: at most N of them, about W + S when the isolates of a stratum are adjacent.
+//   k_cmh : one lane per gene on the tiled matrix (a wavefront's quad loads are 1 KiB coalesced), kTraits traits
+//       per block with their fp64 accumulators in registers.  A lane walks the table: per segment two AND +
+//       popcounts per trait against wave-uniform label / validity words, and on every change of stratum the
+//       stratum's (a, m) is folded into the accumulators -- strata in ascending order, the operations of S10
+//       each rounded on its own (the library is built with -ffp-contract=off).  The cost follows the number of
+//       segments, not S; nothing is re-tiled and the per-stratum tables exist only in registers (d_scounts, for
+//       callers that want them, is the one exception).
+#include <cstddef>
+
+#include "scoary_common.hpp"
+
+namespace {
+
+constexpr int kCmhTraits = 4;        // traits per block: 9 accumulator registers each, far from a spill
+constexpr int kCmhThreads = 256;     // = kGeneAlign: a block is 256 consecutive genes
+constexpr int kSegThreads = 1024;
+constexpr double kCmhTau = 1e-6;     // S10: the tie tolerance of the region, above the fp64 error of E2
+
+struct CmhSegments {                 // the layout of d_scratch
+  uint32_t count, pad[3];
+  uint2 seg[1];                      // [count] = ((stratum << 16) | word, mask)
+};
+
+// the isolate at position j of the members array and its segment key; every index clamped (a bad plan gives
+// wrong counts, never a wild access)
+__device__ __forceinline__ uint32_t seg_key(const int32_t* __restrict__ members, const uint16_t* __restrict__ strata,
+                                            int j, int N, int S, int& isolate) {
+  isolate = min(max(members[j], 0), N - 1);
+  const uint32_t s = min((int)strata[isolate], S - 1);
+  return (s << 16) | (uint32_t)(isolate >> 5);
+}
+
+__global__ __launch_bounds__(kSegThreads) void k_cmh_segments(const uint16_t* __restrict__ strata,
+                                                              const int32_t* __restrict__ members, int N, int S,
+                                                              CmhSegments* __restrict__ out) {
+  __shared__ int heads[kSegThreads];
+  const int tid = threadIdx.x;
+  const int per = (N + kSegThreads - 1) / kSegThreads;
+  const int j0 = min(tid * per, N), j1 = min(j0 + per, N);
+  // a member starts a segment when its key differs from its predecessor's
+  auto is_head = [&](int j) {
+    int i;
+    return j == 0 || seg_key(members, strata, j, N, S, i) != seg_key(members, strata, j - 1, N, S, i);
+  };
+  int mine = 0;
+  for (int j = j0; j < j1; ++j) mine += is_head(j);
+  heads[tid] = mine;
+  __syncthreads();
+  for (int o = 1; o < kSegThreads; o <<= 1) {           // inclusive scan of the per-thread head counts
+    const int v = tid >= o ? heads[tid - o] : 0;
+    __syncthreads();
+    heads[tid] += v;
+    __syncthreads();
+  }
+  int slot = heads[tid] - mine;
+  if (tid == kSegThreads - 1) out->count = (uint32_t)heads[tid];
+  for (int j = j0; j < j1; ++j) {
+    if (!is_head(j)) continue;
+    int i;
+    const uint32_t key = seg_key(members, strata, j, N, S, i);
+    uint32_t mask = 1u << (i & 31);
+    for (int k = j + 1; k < N; ++k) {                   // the run of this key: at most 32 members of a sound plan
+      if (seg_key(members, strata, k, N, S, i) != key) break;
+      mask |= 1u << (i & 31);
+    }
+    out->seg[slot++] = make_uint2(key, mask);           // slot < number of heads <= N
+  }
+}
+
+struct CmhOut {
+  double *stat, *p, *odds, *e2, *var;
+  int32_t* a;
+  uint32_t* crit;
+  int32_t* scounts;
+};
+
+__global__ __launch_bounds__(kCmhThreads) void k_cmh(const uint32_t* __restrict__ tiled,
+                                                     const uint32_t* __restrict__ labels,
+                                                     const uint32_t* __restrict__ masks,
+                                                     const int32_t* __restrict__ smargins,
+                                                     const CmhSegments* __restrict__ segs, int64_t G, int64_t Gp,
+                                                     int T, int N, int Wp, int S, CmhOut out) {
+  const int64_t g = (int64_t)blockIdx.x * kCmhThreads + threadIdx.x;      // < Gp: the grid covers Gp exactly
+  const int t0 = blockIdx.y * kCmhTraits;
+  const uint4* __restrict__ quads = reinterpret_cast<const uint4*>(tiled);
+  const int nseg = min((int)segs->count, N);
+
+  int32_t A[kCmhTraits], K[kCmhTraits];     // K: the positives of the counted strata (wave-uniform)
+  double E2[kCmhTraits], V[kCmhTraits], R[kCmhTraits], Q[kCmhTraits];
+  uint32_t a[kCmhTraits], m[kCmhTraits];
+#pragma unroll
+  for (int j = 0; j < kCmhTraits; ++j) A[j] = K[j] = 0, E2[j] = V[j] = R[j] = Q[j] = 0.0, a[j] = m[j] = 0;
+
+  // trait j of the block, clamped for reading (the surplus traits of the last block are computed and dropped)
+  auto trait = [&](int j) { return min(t0 + j, T - 1); };
+  auto put_scounts = [&](int j, int s, uint32_t aa, uint32_t mm) {
+    if (out.scounts && g < G && t0 + j < T)
+      reinterpret_cast<int2*>(out.scounts)[((int64_t)(t0 + j) * G + g) * S + s] = make_int2((int)aa, (int)mm);
+  };
+  // S10, accumulation: stratum s with this lane's (a, m) and the stratum's margins (k, n)
+  auto fold = [&](int s) {
+#pragma unroll
+    for (int j = 0; j < kCmhTraits; ++j) {
+      const int2 kn = reinterpret_cast<const int2*>(smargins)[(int64_t)trait(j) * S + s];
+      const int64_t k = kn.x, n = kn.y, mm = m[j], aa = a[j];
+      put_scounts(j, s, a[j], m[j]);
+      a[j] = m[j] = 0;
+      if (n <= 0) continue;
+      const double dn = (double)n;
+      A[j] += (int32_t)aa;
+      K[j] += (int32_t)k;
+      E2[j] += (double)(2 * k * mm) / dn;
+      if (n >= 2)
+        V[j] += (((double)k * (double)(n - k)) * ((double)mm * (double)(n - mm))) / ((dn * dn) * (double)(n - 1));
+      const int64_t b = k - aa, c = mm - aa, d = n - k - mm + aa;
+      R[j] += (double)(aa * d) / dn;
+      Q[j] += (double)(b * c) / dn;
+    }
+  };
+
+  int cur_s = -1, cur_q = -1;
+  uint4 gq = make_uint4(0, 0, 0, 0);
+  for (int i = 0; i < nseg; ++i) {
+    const uint2 sg = segs->seg[i];                                        // wave-uniform
+    const int s = min((int)(sg.x >> 16), S - 1), w = min((int)(sg.x & 0xffffu), Wp - 1);
+    if (s != cur_s) {
+      if (cur_s >= 0) fold(cur_s);
+      for (int z = cur_s + 1; z < s; ++z)                                 // strata without a member: all-zero tables
+        for (int j = 0; j < kCmhTraits; ++j) put_scounts(j, z, 0, 0);
+      cur_s = s;
+    }
+    if ((w >> 2) != cur_q) {
+      cur_q = w >> 2;
+      gq = quads[(int64_t)cur_q * Gp + g];
+    }
+    const int c = w & 3;
+    const uint32_t gw = (c == 0 ? gq.x : c == 1 ? gq.y : c == 2 ? gq.z : gq.w) & sg.y;
+#pragma unroll
+    for (int j = 0; j < kCmhTraits; ++j) {
+      const int64_t row = (int64_t)trait(j) * Wp + w;
+      bcnt_acc(m[j], gw & masks[row]);
+      bcnt_acc(a[j], gw & labels[row]);
+    }
+  }
+  if (cur_s >= 0) fold(cur_s);
+  for (int z = cur_s + 1; z < S; ++z)
+    for (int j = 0; j < kCmhTraits; ++j) put_scounts(j, z, 0, 0);
+
+  if (g >= G) return;
+#pragma unroll
+  for (int j = 0; j < kCmhTraits; ++j) {
+    if (t0 + j >= T) continue;
+    const int64_t o = (int64_t)(t0 + j) * G + g;
+    const double dA = (double)A[j];
+    double stat = __builtin_nan(""), p = 1.0;
+    int64_t lo = 0, hi = -1;                                              // the accepted integers; empty: (0, 0)
+    if (V[j] != 0.0) {
+      const double delta = fabs(dA - 0.5 * E2[j]);
+      const double y = fmin(0.5, delta);
+      stat = ((delta - y) * (delta - y)) / V[j];
+      p = erfc(sqrt(stat / 2.0));
+      const double diff = 2.0 * dA - E2[j];
+      if (diff > kCmhTau) {
+        lo = (int64_t)floor((E2[j] - dA) + kCmhTau) + 1, hi = (int64_t)A[j] - 1;
+      } else if (diff < -kCmhTau) {
+        lo = (int64_t)A[j] + 1, hi = (int64_t)ceil((E2[j] - dA) - kCmhTau) - 1;
+      }
+    }
+    if (lo < 0) lo = 0;
+    if (hi > K[j]) hi = K[j];           // no pooled count exceeds the positives; the list kernels want base + span <= npos + 1
+    const int64_t span = hi - lo + 1;
+    out.stat[o] = stat;
+    out.p[o] = p;
+    out.odds[o] = Q[j] != 0.0 ? R[j] / Q[j] : (R[j] > 0.0 ? __builtin_inf() : __builtin_nan(""));
+    out.e2[o] = E2[j];
+    out.var[o] = V[j];
+    out.a[o] = A[j];
+    reinterpret_cast<uint2*>(out.crit)[o] = span > 0 ? make_uint2((uint32_t)lo, (uint32_t)span) : make_uint2(0u, 0u);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t scoary_cmh_scratch_bytes(int64_t N) {
+  return N < 1 ? 0 : (int64_t)offsetof(CmhSegments, seg) + N * (int64_t)sizeof(uint2);
+}
+
+int scoary_cmh(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d_labels, const uint32_t* d_masks,
+               const uint16_t* d_strata, const int32_t* d_members, const int32_t* d_offsets,
+               const int32_t* d_smargins, int64_t G, int64_t T, int64_t N, int64_t S, double* d_stat, double* d_p,
+               double* d_odds, double* d_e2, double* d_var, int32_t* d_a, uint32_t* d_crit, int32_t* d_scounts,
+               void* d_scratch, scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (!d_tiled || !d_labels || !d_masks || !d_strata || !d_members || !d_offsets || !d_smargins || !d_stat || !d_p ||
+      !d_odds || !d_e2 || !d_var || !d_a || !d_crit || !d_scratch || G < 1 || T < 1 || N < 1 || S < 1)
+    return fail(h, SCOARY_ERR_ARG, "scoary_cmh: bad argument");
+  if (T > 65535) return fail(h, SCOARY_ERR_SIZE, "scoary_cmh: T > 65535");
+  if (S > scoary_perm_max_strata())
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh: more strata than scoary_perm_max_strata()");
+  if (N > scoary_perm_strata_max_isolates())
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh: more isolates than scoary_perm_strata_max_isolates()");
+  const int64_t Gp = scoary_tiled_genes(G);
+  if (Gp / kCmhThreads > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_cmh: grid too large");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CmhSegments* segs = static_cast<CmhSegments*>(d_scratch);
+  {
+    KernelTimer kt(h, s, "k_cmh_segments");
+    hipLaunchKernelGGL(k_cmh_segments, dim3(1), dim3(kSegThreads), 0, s, d_strata, d_members, (int)N, (int)S, segs);
+    HIP_TRY(h, hipGetLastError());
+  }
+  const CmhOut out{d_stat, d_p, d_odds, d_e2, d_var, d_a, d_crit, d_scounts};
+  KernelTimer kt(h, s, "k_cmh");
+  hipLaunchKernelGGL(k_cmh, dim3((unsigned)(Gp / kCmhThreads), (unsigned)((T + kCmhTraits - 1) / kCmhTraits)),
+                     dim3(kCmhThreads), 0, s, d_tiled, d_labels, d_masks, d_smargins, segs, G, Gp, (int)T, (int)N,
+                     (int)scoary_row_words(N), (int)S, out);
+  HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+
+}  // extern "C"

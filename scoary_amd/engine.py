@@ -599,6 +599,32 @@ class AssociationEngine:
         """The four device arrays of a StrataPlan, in the order the stratified generators take them."""
         return tuple(self._ptr(x) for x in (strata.strata, strata.members, strata.offsets, strata.smargins))
 
+    # -- Cochran-Mantel-Haenszel test over the strata (spec S10) -------------------
+    def cmh(self, genes, traits, masks, strata, scounts=False):
+        """The stratified test of every (trait, gene) over the strata of ``strata`` (the StrataPlan of these label
+        rows ``traits`` and validity rows ``masks``): dict of device tensors -- stat (the continuity-corrected CMH
+        chi-square, nan without an informative stratum), p, odds (the Mantel-Haenszel common odds ratio), e2 (twice
+        the expectation of the pooled count) and var, float64 [T, G]; a int32 [T, G] = the pooled count
+        popc(gene & label); crit int32 [T, G, 2] (uint32 bits) = the rejection region of the pooled count under
+        within-stratum shuffles, in the form permute() / permute_lists(crit=...) take.  ``scounts=True`` adds
+        scounts int32 [T, G, S, 2] = (a, m) of every stratum (tests; T G S 8 bytes)."""
+        torch = _torch()
+        T, G, N = int(traits.shape[0]), genes.G, genes.N
+        self._strata_fits(strata, T, N)
+        if int(masks.shape[0]) != T or not (traits.is_contiguous() and masks.is_contiguous()):
+            raise ValueError("cmh: label and validity rows must be contiguous [T, Wp] tensors of the same traits")
+        out = {k: self._empty((T, G), torch.float64) for k in ("stat", "p", "odds", "e2", "var")}
+        out["a"] = self._empty((T, G), torch.int32)
+        out["crit"] = self._empty((T, G, 2), torch.int32)
+        if scounts:
+            out["scounts"] = self._empty((T, G, strata.S, 2), torch.int32)
+        scratch = self._empty(((int(self.lib.scoary_cmh_scratch_bytes(N)) + 7) // 8,), torch.int64)
+        self._check(self.lib.scoary_cmh(
+            self.h, self._ptr(genes.tiled), self._ptr(traits), self._ptr(masks), *self._strata_ptrs(strata),
+            G, T, N, strata.S, *(self._ptr(out[k]) for k in ("stat", "p", "odds", "e2", "var", "a", "crit")),
+            self._ptr(out["scounts"]) if scounts else None, self._ptr(scratch), self._stream()), "scoary_cmh")
+        return out
+
     def perm_generate(self, masks, margins, N, P, perm_base, seed, out=None, trait_base=0, strata=None):
         """Label rows [T, P, Wp] of the permutations perm_base .. perm_base + P - 1 (spec S4); with ``strata``
         (a StrataPlan of these traits) shuffled within its strata (spec S9)."""
@@ -946,7 +972,7 @@ class AssociationEngine:
 
     def associate(self, genes, traits, masks, permutations=0, seed=0, perm_buffer=None,
                   use_lists=None, workspace=None, plan=None, graph=None, records=None, fwer=False,
-                  table_budget_bytes=8 << 30, stepdown=False, strata=None):
+                  table_budget_bytes=8 << 30, stepdown=False, strata=None, cmh=False):
         """counts -> Fisher -> (optional) permutation exceedance counts.
         Returns dict of device tensors: counts [T,G,4], margins [T,2],
         p / odds [T,G], r [T,G] (uint32 bit pattern in int32) or None.  With
@@ -964,16 +990,23 @@ class AssociationEngine:
         the step-down counts res["r_fwer_sd"] int32 [T, G] and res["minp"] (minp_stepdown(), spec S8); together with
         ``fwer`` res["r_fwer"] comes from those same minima, k_permute_minp is not launched.  ``strata``: a
         StrataPlan of these traits (strata_plan) -- every permutation shuffles the labels within its strata only
-        (spec S9): r, minp, r_fwer and r_fwer_sd are then counted under that null; None: the code as it was."""
+        (spec S9): r, minp, r_fwer and r_fwer_sd are then counted under that null; None: the code as it was.
+        ``cmh=True`` (needs ``strata``, not permutations): the Cochran-Mantel-Haenszel test over the strata (cmh(),
+        spec S10) as res["cmh_stat"], ["cmh_p"], ["cmh_odds"] and ["cmh_crit"]; with permutations also res["r_cmh"]
+        int32 [T, G] (uint32 bits) = the permutations whose pooled count lies in cmh_crit -- every batch of labels
+        is generated once and counted twice, r with the Fisher regions and r_cmh with these.  Never replayed from
+        a graph.  The other results are those of the same call without it, bit for bit."""
         if (fwer or stepdown) and permutations <= 0:
             raise ValueError("fwer=True / stepdown=True need permutations > 0")
-        if strata is not None and permutations > 0:
+        if cmh and strata is None:
+            raise ValueError("cmh=True needs strata (a StrataPlan of these traits)")
+        if strata is not None and (permutations > 0 or cmh):
             self._strata_fits(strata, traits.shape[0], genes.N)
         elif permutations <= 0:
             strata = None
         res = self._associate(genes, traits, masks, permutations, seed, perm_buffer, use_lists,
-                              workspace, plan, graph if records is None and not (fwer or stepdown) else False,
-                              strata=strata)
+                              workspace, plan, graph if records is None and not (fwer or stepdown or cmh) else False,
+                              strata=strata, cmh=cmh)
         if stepdown:
             res = dict(res)
             res["r_fwer_sd"], res["minp"] = self.minp_stepdown(genes, traits, masks, permutations, seed, res=res,
@@ -994,7 +1027,7 @@ class AssociationEngine:
         return res
 
     def _associate(self, genes, traits, masks, permutations, seed, perm_buffer, use_lists, workspace,
-                   plan, graph, strata=None):
+                   plan, graph, strata=None, cmh=False):
         """The step behind associate() (its docstring)."""
         torch = _torch()
         T = traits.shape[0]
@@ -1034,6 +1067,7 @@ class AssociationEngine:
                 self._label_tiles(ws, masks, margins, genes.N, nb0, 0, seed, strata)
             p, odds, crit, lcrit = self.fisher(counts, out=(ws.p, ws.odds, ws.crit),
                                                lists=genes.lists, lcrit=ws.lcrit)
+            extra = self._cmh_results(genes, traits, masks, strata, permutations) if cmh else {}
             main.wait_stream(side)
             done = 0
             while done < permutations:
@@ -1042,10 +1076,14 @@ class AssociationEngine:
                     self._label_tiles(ws, masks, margins, genes.N, nb, done, seed, strata)
                 self.permute_lists(genes, ws.tiles, None, margins, nb, ws.r, scratch=ws.scratch,
                                    lcrit=lcrit, accumulate=done > 0, bfrag=ws.bfrag)
+                if cmh:     # the same label tiles against the CMH regions (gene order: converted by the library)
+                    self.permute_lists(genes, ws.tiles, extra["cmh_crit"], margins, nb, extra["r_cmh"],
+                                       scratch=ws.scratch, accumulate=done > 0, bfrag=ws.bfrag)
                 done += nb
             return {"counts": counts, "margins": margins, "p": p, "odds": odds, "crit": crit,
-                    "r": ws.r}
+                    "r": ws.r, **extra}
         p, odds, crit = self.fisher(counts, out=(ws.p, ws.odds, ws.crit))
+        extra = self._cmh_results(genes, traits, masks, strata, permutations) if cmh else {}
         r = None
         if permutations > 0:
             r = ws.r
@@ -1056,8 +1094,21 @@ class AssociationEngine:
                 nb = min(batch, permutations - done)
                 self.perm_generate(masks, margins, genes.N, nb, done, seed, out=ws.perms, strata=strata)
                 self.permute(genes, ws.perms[:, :nb] if nb == batch else ws.perms, crit, r, P=nb)
+                if cmh:
+                    self.permute(genes, ws.perms[:, :nb] if nb == batch else ws.perms, extra["cmh_crit"],
+                                 extra["r_cmh"], P=nb)
                 done += nb
-        return {"counts": counts, "margins": margins, "p": p, "odds": odds, "crit": crit, "r": r}
+        return {"counts": counts, "margins": margins, "p": p, "odds": odds, "crit": crit, "r": r, **extra}
+
+    def _cmh_results(self, genes, traits, masks, strata, permutations):
+        """The entries associate(cmh=True) adds to its result: cmh() under the names of the step and, for a step
+        with permutations, the zeroed count r_cmh."""
+        torch = _torch()
+        c = self.cmh(genes, traits, masks, strata)
+        out = {"cmh_stat": c["stat"], "cmh_p": c["p"], "cmh_odds": c["odds"], "cmh_crit": c["crit"]}
+        if permutations > 0:
+            out["r_cmh"] = torch.zeros((traits.shape[0], genes.G), dtype=torch.int32, device=self.device)
+        return out
 
     def capture(self, genes, traits, masks, permutations, seed, workspace, use_lists=None, plan=None,
                 records=None, strata=None):

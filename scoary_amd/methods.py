@@ -770,7 +770,7 @@ def _pattern_groups(table, maskrow, idx, hashes):
 
 
 def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, fwer=False,
-               fwer_stepdown=False, strata=None):
+               fwer_stepdown=False, strata=None, cmh=False):
     """Whole hot path for all traits; under torchrun (world > 1) every rank
     takes a stride gene shard (dist.GenePartition: the reference's domains,
     scoary/methods.py:1076-1078) and the per-gene records are all-gathered
@@ -786,7 +786,10 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
     successive minima run over all genes in one order, gene shards do not compose; they reach the host beside the
     records, as the minima do.  With ``fwer`` as well, r_fwer is counted from the same pass's minima.
     ``strata``: the stratum index of every isolate of the table (--permute-strata): every permutation shuffles
-    the labels within the strata only (spec S9); every rank generates the same labels."""
+    the labels within the strata only (spec S9); every rank generates the same labels.
+    ``cmh`` (needs ``strata``; single process, no early abort): the Cochran-Mantel-Haenszel test over the strata
+    (spec S10): out["cmh_p"], out["cmh_odds"] [T, G] and, with permutations, out["r_cmh"]; they reach the host
+    beside the records, as the step-down counts do."""
     import torch
     from . import dist
     eng = get_engine()
@@ -795,7 +798,7 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         trv = eng.vecrows(pack_bits_rows(tarr == 1), N)
         mkv = eng.vecrows(pack_bits_rows(tarr != 2), N)
         plan = eng.trait_plan(trv, mkv, N)            # margins + mask classes: once per trait set
-        sp = eng.strata_plan(strata, trv, mkv, N) if strata is not None and permutations > 0 else None
+        sp = eng.strata_plan(strata, trv, mkv, N) if strata is not None and (permutations > 0 or cmh) else None
 
     def scipy_digits(res):
         # Up to 170 isolates k_fisher's p IS scipy.stats.fisher_exact's double; above, it is the exact value of SciPy's
@@ -853,8 +856,10 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
             res["r"] = r
             return eng.pack_records(res, nstop=nstop)
         with _stage("kernels (counts, Fisher, permutations)"):
-            res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan, strata=sp)
+            res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan, strata=sp, cmh=cmh)
             torch.cuda.synchronize(eng.device)
+        if cmh:
+            cmh_all.append({k: res[k] for k in ("cmh_p", "cmh_odds", "r_cmh") if k in res})
         r_fwer = None
         if fwer_stepdown:
             with _stage("Westfall-Young step-down minP (p tables, k_stepdown_minp)"):
@@ -878,7 +883,7 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
             torch.cuda.synchronize(eng.device)
         return rec
 
-    minp_all, sd_all = [], []
+    minp_all, sd_all, cmh_all = [], [], []
     rec = dist.associate_sharded(local, G)
     with _stage("results D2H"):
         # the stable p order for BH: numpy does 200 000 doubles in 25-40 ms, which beats the
@@ -896,6 +901,9 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         out["minp"] = minp_all[0].cpu().numpy()
     if fwer_stepdown:
         out["r_fwer_sd"] = sd_all[0].cpu().numpy() if sd_all else np.zeros((T, 0), dtype=np.int32)
+    if cmh:
+        for k, v in (cmh_all[0] if cmh_all else {}).items():
+            out[k] = v.cpu().numpy()
     return out
 
 
@@ -953,7 +961,7 @@ def _usable_cpus():
 
 
 def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEED,
-                  early_abort=False, fwer=False, fwer_stepdown=False, strata=None):
+                  early_abort=False, fwer=False, fwer_stepdown=False, strata=None, cmh=False):
     """Counts, Fisher's exact test and B/BH correction for every trait x gene
     (methods.py:757-928).  ``permutations`` >= 10 additionally attaches the
     Fisher-statistic ``Empirical_p`` (= (r+1)/(P+1), methods.py:1365) to every
@@ -962,8 +970,19 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
     ``fwer_stepdown`` (with permutations, one process): also ``Westfall_Young_stepdown_p`` = (r_sd+1)/(P+1), the
     step-down minP adjusted p (spec S8).  ``strata`` (with permutations): one stratum index per isolate, in
     the table's strain order -- the permutations shuffle the labels within the strata only (spec S9), which
-    changes the values of Empirical_p and of the Westfall-Young columns and nothing else."""
-    if strata is not None and permutations < 10:
+    changes the values of Empirical_p and of the Westfall-Young columns and nothing else.  ``cmh`` (needs
+    ``strata``, not permutations; one process, no early abort): also ``CMH_p`` and ``CMH_odds_ratio``, the
+    Cochran-Mantel-Haenszel test and the Mantel-Haenszel common odds ratio over the strata (spec S10), and with
+    permutations ``CMH_empirical_p`` = (r_cmh+1)/(P+1), the exact permutation p of that statistic."""
+    if cmh:
+        if strata is None:
+            raise ValueError("cmh needs strata")
+        if early_abort:
+            raise ValueError("cmh excludes early_abort")
+        from . import dist
+        if dist.world_rank()[0] > 1:
+            raise ValueError("cmh needs a single process: its results reach the host beside the gathered records")
+    elif strata is not None and permutations < 10:
         raise ValueError("strata need the Fisher-statistic permutations of --no_pairwise (permutations >= 10)")
     if fwer and (permutations < 10 or early_abort):
         raise ValueError("fwer needs permutations >= 10 and excludes early_abort")
@@ -984,7 +1003,7 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
     if strata is not None and len(strata) != len(table.strains):
         raise ValueError("strata: one stratum index per isolate of the gene table")
     dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, fwer, fwer_stepdown,
-                     strata=strata)
+                     strata=strata, cmh=cmh)
     collapse_hashes = None
     if collapse:
         eng = get_engine()
@@ -1081,6 +1100,11 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
             cols["Westfall_Young_p"] = wy[rows_idx]
         if wy_sd is not None:
             cols["Westfall_Young_stepdown_p"] = wy_sd[rows_idx]
+        if cmh:
+            cols["CMH_p"], cols["CMH_odds_ratio"] = dev["cmh_p"][t][rows_idx], dev["cmh_odds"][t][rows_idx]
+            if "r_cmh" in dev:
+                cols["CMH_empirical_p"] = ((dev["r_cmh"][t].view(np.uint32).astype(np.float64) + 1.0)
+                                           / (permutations + 1.0))[rows_idx]
         if collapse:
             tr = TraitResults(names_out, nugn, ann, cols, number_of_tests, members)
         else:
@@ -1405,6 +1429,9 @@ def _write_rows_python(fname, delimiter, header_line, Trait, table, sel_i, sel_k
             out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
 
 
+CMH_COLUMNS = ("CMH_p", "CMH_odds_ratio", "CMH_empirical_p")     # --cmh: after every other numeric column
+
+
 def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Prunedic, outdir,
                      permutations, num_threads, no_pairwise, genedic, extracolstoprint,
                      firstcolnames, time="", delimiter=",", seed=DEFAULT_SEED, writer_threads=0):
@@ -1432,6 +1459,8 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
     with_wy_sd = no_pairwise and with_emp and "Westfall_Young_stepdown_p" in Trait.cols      # --permute-fwer-stepdown
     if with_wy_sd:
         columns.append("Westfall_Young_stepdown_p")
+    cmh_cols = [k for k in CMH_COLUMNS if no_pairwise and k in Trait.cols]                    # --cmh
+    columns += cmh_cols
     columns += list(extracolstoprint)
     table = _as_table(genedic) if extracolstoprint else None
 
@@ -1465,6 +1494,9 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
         if with_wy_sd:
             colget["Westfall_Young_stepdown_p"] = np.asarray(Trait.column("Westfall_Young_stepdown_p"))
             fields.append("Westfall_Young_stepdown_p")
+        for k in cmh_cols:
+            colget[k] = np.asarray(Trait.column(k))
+            fields.append(k)
         keyed = {CUT_FIELD[m]: colget[CUT_FIELD[m]] for m in cutoffs}
         sel = cand[np.all([keyed[CUT_FIELD[m]][cand] <= c for m, c in cutoffs.items()], axis=0)] \
             if cutoffs else cand
@@ -1524,7 +1556,7 @@ def _trait_results_from_dict(rows):
     """Plain {gene: row dict} (the reference's Results[trait]) -> TraitResults."""
     genes = list(rows.keys())
     cols = {}
-    for k in TraitResults.FIELDS + ("Empirical_p", "Westfall_Young_p", "Westfall_Young_stepdown_p"):
+    for k in TraitResults.FIELDS + ("Empirical_p", "Westfall_Young_p", "Westfall_Young_stepdown_p") + CMH_COLUMNS:
         if genes and k in rows[genes[0]]:
             cols[k] = np.array([rows[g][k] for g in genes])
     return TraitResults(genes, [rows[g]["NUGN"] for g in genes],
@@ -1644,6 +1676,12 @@ def ScoaryArgumentParser(argv=None):
                    "population. FILE is a CSV with a header row (read with --delimiter): column 1 the isolate "
                    "name, column 2 its stratum label; further columns are ignored. Changes Empirical_p and the "
                    "Westfall-Young columns (scoary_amd extension)")
+    a.add_argument("--cmh", dest="cmh", metavar="FILE", default=None,
+                   help="With --no_pairwise: the Cochran-Mantel-Haenszel test over the strata of FILE (the format of "
+                   "--permute-strata): adds the columns CMH_p and CMH_odds_ratio (the Mantel-Haenszel common odds "
+                   "ratio), the association inside the strata instead of across them. With --permute also "
+                   "CMH_empirical_p, the exact permutation p of the CMH statistic, and every permutation then "
+                   "shuffles the labels within these strata (single process; scoary_amd extension)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1800,18 +1838,23 @@ def main(**kwargs):
         # default mode: tree-statistic permutations of the surviving genes, done
         # in the pairwise stage like the reference does.
         strata = None
-        if getattr(args, "permute_strata", None):
+        if getattr(args, "permute_strata", None) or getattr(args, "cmh", None):
             # the authoritative call, on the strains the reader kept (_validate's early one reads the header on its
             # own: should the two ever disagree, the same exit message appears here, after the engine has started)
             strata, labels = strata_indices(args.strata_map, strains)
             sizes = np.bincount(strata, minlength=len(labels))
-            log.info("Permuting trait labels within %d strata of %d to %d isolates (%s)"
-                     % (len(labels), int(sizes.min()), int(sizes.max()), args.permute_strata))
+            if getattr(args, "cmh", None):
+                log.info("Cochran-Mantel-Haenszel test over %d strata of %d to %d isolates (%s)"
+                         % (len(labels), int(sizes.min()), int(sizes.max()), args.cmh))
+            if args.permute >= 10:
+                log.info("Permuting trait labels within %d strata of %d to %d isolates (%s)"
+                         % (len(labels), int(sizes.min()), int(sizes.max()), args.permute_strata or args.cmh))
         res = Setup_results(genedic, traitsdic, args.collapse,
                             permutations=args.permute if args.no_pairwise else 0, seed=seed,
                             early_abort=getattr(args, "permute_early_abort", False),
                             fwer=getattr(args, "permute_fwer", False),
-                            fwer_stepdown=getattr(args, "permute_fwer_stepdown", False), strata=strata)
+                            fwer_stepdown=getattr(args, "permute_fwer_stepdown", False), strata=strata,
+                            cmh=bool(getattr(args, "cmh", None)))
         t_stats = _time.time()
         if args.upgma_tree and rank == 0:
             # (with --no_pairwise there is no tree and the reference writes str(None) + ";", :277-280, :741-751)
@@ -1960,6 +2003,24 @@ def _validate(args, cutoffs):
         if dist.world_rank()[0] > 1:
             sys.exit("Cannot use --permute-fwer-stepdown under more than one rank: the successive minima run over "
                      "all genes in one order; gene shards do not compose")
+    if getattr(args, "cmh", None):
+        if not args.no_pairwise:
+            sys.exit("Cannot use --cmh without --no_pairwise. The Cochran-Mantel-Haenszel test is a test of every "
+                     "gene, beside Fisher's")
+        if getattr(args, "permute_early_abort", False):
+            sys.exit("Cannot use --cmh together with --permute-early-abort. Every gene has to see every permutation")
+        if not os.path.isfile(args.cmh):
+            sys.exit("Could not find the strata file: %s" % args.cmh)
+        other = getattr(args, "permute_strata", None)
+        if other and not (os.path.isfile(other) and os.path.samefile(other, args.cmh)):
+            sys.exit("--cmh %s and --permute-strata %s name different strata files. With --cmh the permutations "
+                     "shuffle the labels within the strata of its file: give one file" % (args.cmh, other))
+        from . import dist
+        if dist.world_rank()[0] > 1:
+            sys.exit("Cannot use --cmh under more than one rank: its results reach the host beside the gathered "
+                     "records of a single process")
+    strata_flag = "--permute-strata" if getattr(args, "permute_strata", None) else "--cmh"
+    strata_path = getattr(args, "permute_strata", None) or getattr(args, "cmh", None)
     if getattr(args, "permute_strata", None):
         if not args.no_pairwise:
             sys.exit("Cannot use --permute-strata without --no_pairwise. The strata restrict the permutations of "
@@ -1969,17 +2030,18 @@ def _validate(args, cutoffs):
                      "is a number equal to or larger than 10")
         if not os.path.isfile(args.permute_strata):
             sys.exit("Could not find the strata file: %s" % args.permute_strata)
-        args.strata_map = read_strata_file(args.permute_strata, args.delimiter)
+    if strata_path:
+        args.strata_map = read_strata_file(strata_path, args.delimiter)
         # the isolates of the analysis are the header of the gene table (after -s and -r): checked here, before the
         # engine starts and the table is read
         strata, labels = strata_indices(args.strata_map, _analysed_isolates(args))
         from . import _abi
         if len(labels) > _abi.PERM_MAX_STRATA:
-            sys.exit("The strata file %s names %d strata for the analysed isolates; --permute-strata takes at "
-                     "most %d" % (args.permute_strata, len(labels), _abi.PERM_MAX_STRATA))
+            sys.exit("The strata file %s names %d strata for the analysed isolates; %s takes at "
+                     "most %d" % (strata_path, len(labels), strata_flag, _abi.PERM_MAX_STRATA))
         if len(strata) > _abi.PERM_STRATA_MAX_ISOLATES:
-            sys.exit("--permute-strata takes at most %d isolates; this analysis has %d"
-                     % (_abi.PERM_STRATA_MAX_ISOLATES, len(strata)))
+            sys.exit("%s takes at most %d isolates; this analysis has %d"
+                     % (strata_flag, _abi.PERM_STRATA_MAX_ISOLATES, len(strata)))
     if "P" in cutoffs and args.permute == 0:
         sys.exit("Cannot use empirical p-values in filtration without performing "
                  "permutations. Use '--permute X' where X is a number equal to or larger than 10")

@@ -121,8 +121,6 @@ class Workspace:
     def __init__(self, eng, genes, T, permutations, use_lists, perm_buffer=None):
         torch = _torch()
         G, N = genes.G, genes.N
-        if use_lists is None:
-            use_lists = genes.lists is not None and eng.lists_supported(N)
         self.key = (G, N, int(T), int(permutations), bool(use_lists and permutations > 0))
         self.eng = eng
         self.counts = eng._empty((T, G, 4), torch.int32)
@@ -806,6 +804,29 @@ class AssociationEngine:
         srt = torch.sort(minp, dim=1).values.contiguous()
         return torch.searchsorted(srt, p.contiguous(), right=True).to(torch.int32)
 
+    def westfall_young(self, genes, traits, masks, permutations, seed, res, fwer=False, stepdown=False,
+                       table_budget_bytes=8 << 30, plan=None, strata=None, reduce=None):
+        """The Westfall-Young results of the step ``res`` (an associate() result of these genes and traits), composed
+        in this one place: dict with minp float64 [T, P], r_fwer int32 [T, G] (``fwer``) and r_fwer_sd int32 [T, G]
+        (``stepdown``).  The step-down pass yields the single-step minima as well, so with ``stepdown``
+        k_permute_minp is not launched and r_fwer is counted from that pass's minima.  ``reduce``: [T, P] -> [T, P],
+        applied to the minima before r_fwer is counted -- dist.all_reduce_min for gene shards, whose minima compose
+        by min (the step-down counts do not: minp_stepdown()).  r_fwer is counted on res["p"] as the step produced
+        it, k_fisher's own bits: call this before fisher_scipy() rewrites their last ulp.  ``table_budget_bytes``,
+        ``plan`` and ``strata`` as in minp()."""
+        out = {}
+        if stepdown:
+            out["r_fwer_sd"], minp = self.minp_stepdown(genes, traits, masks, permutations, seed, res=res,
+                                                        table_budget_bytes=table_budget_bytes, plan=plan,
+                                                        strata=strata)
+        else:
+            minp = self.minp(genes, traits, masks, permutations, seed, res=res,
+                             table_budget_bytes=table_budget_bytes, plan=plan, strata=strata)
+        out["minp"] = minp if reduce is None else reduce(minp)
+        if fwer:
+            out["r_fwer"] = self.r_fwer(out["minp"], res["p"])
+        return out
+
     # -- Westfall-Young step-down minP (spec S8) ----------------------------------
     def stepdown_chunks(self, G, T, P):
         """Chunks the rank order of G genes is walked in for T traits and P permutations per call
@@ -906,7 +927,11 @@ class AssociationEngine:
         """Every device buffer one associate() step needs, allocated once: steps that
         reuse it allocate nothing (a precondition for hipGraph capture, and what
         small launch-bound workloads need anyway)."""
-        return Workspace(self, genes, T, permutations, use_lists, perm_buffer)
+        return Workspace(self, genes, T, permutations, self._lists_default(genes, use_lists), perm_buffer)
+
+    def _lists_default(self, genes, use_lists):
+        """``use_lists`` of a step; None = the list-driven kernels whenever the matrix has its lists."""
+        return (genes.lists is not None and self.lists_supported(genes.N)) if use_lists is None else use_lists
 
     # -- launch-bound steps: automatic hipGraph replay -----------------------------
     AUTO_GRAPH_MAX_TESTS = 5e8      # ~0.5 ms of kernels at 1e12 tests/s: below it launches dominate
@@ -973,29 +998,22 @@ class AssociationEngine:
     def associate(self, genes, traits, masks, permutations=0, seed=0, perm_buffer=None,
                   use_lists=None, workspace=None, plan=None, graph=None, records=None, fwer=False,
                   table_budget_bytes=8 << 30, stepdown=False, strata=None, cmh=False):
-        """counts -> Fisher -> (optional) permutation exceedance counts.
-        Returns dict of device tensors: counts [T,G,4], margins [T,2],
-        p / odds [T,G], r [T,G] (uint32 bit pattern in int32) or None.  With
-        ``workspace`` the result tensors are the workspace's (overwritten by the
-        next step that uses it).  ``plan``: the TraitPlan of these traits (trait_plan, once
-        per trait set); without one every step rebuilds it (one more small launch).  With a
-        workspace AND a plan, a launch-bound step (auto_graph_eligible) is recorded into a
-        hipGraph on its second call and replayed afterwards; ``graph=False`` keeps it eager.
-        ``records``: an int32 [T, G, 10] device tensor -- the result is also packed into it
-        (pack_records) and returned as res["records"].  ``fwer=True`` (needs permutations): also the
-        Westfall-Young minima res["minp"] float64 [T, P] (minp()) and res["r_fwer"] int32 [T, G] = the number of
-        permutations whose minimum is <= the gene's own p; the p tables of a trait group stay under
-        ``table_budget_bytes`` and, with a ``plan``, are built once per (gene matrix, plan) and reused (minp()).
-        Such a step is never replayed from a graph (it reads sizes back).  ``stepdown=True`` (needs permutations):
-        the step-down counts res["r_fwer_sd"] int32 [T, G] and res["minp"] (minp_stepdown(), spec S8); together with
-        ``fwer`` res["r_fwer"] comes from those same minima, k_permute_minp is not launched.  ``strata``: a
-        StrataPlan of these traits (strata_plan) -- every permutation shuffles the labels within its strata only
-        (spec S9): r, minp, r_fwer and r_fwer_sd are then counted under that null; None: the code as it was.
-        ``cmh=True`` (needs ``strata``, not permutations): the Cochran-Mantel-Haenszel test over the strata (cmh(),
-        spec S10) as res["cmh_stat"], ["cmh_p"], ["cmh_odds"] and ["cmh_crit"]; with permutations also res["r_cmh"]
-        int32 [T, G] (uint32 bits) = the permutations whose pooled count lies in cmh_crit -- every batch of labels
-        is generated once and counted twice, r with the Fisher regions and r_cmh with these.  Never replayed from
-        a graph.  The other results are those of the same call without it, bit for bit."""
+        """counts -> Fisher -> (optional) permutation exceedance counts.  Returns a dict of device tensors:
+        counts [T, G, 4], margins [T, 2], p / odds [T, G], crit [T, G, 2], r [T, G] (uint32 bits in int32) or None.
+        ``workspace``: the result tensors are the workspace's, overwritten by the next step that uses it.
+        ``plan``: the TraitPlan of these traits (trait_plan, once per trait set); without one every step rebuilds it.
+        ``graph``: with a workspace AND a plan a launch-bound step (auto_graph_eligible) is recorded into a hipGraph
+        on its second call and replayed afterwards; False keeps it eager.  A step with ``records``, ``fwer``,
+        ``stepdown`` or ``cmh`` is never replayed.
+        ``records``: an int32 [T, G, 10] tensor the result is also packed into (pack_records): res["records"].
+        ``fwer`` / ``stepdown`` (need permutations): res["minp"] float64 [T, P] and res["r_fwer"] / res["r_fwer_sd"]
+        int32 [T, G] (westfall_young()); ``table_budget_bytes`` bounds the p tables of a trait group (minp()).
+        ``strata``: a StrataPlan of these traits (strata_plan) -- every permutation shuffles the labels within its
+        strata only (spec S9), for r and for the Westfall-Young results alike.
+        ``cmh`` (needs ``strata``, not permutations): the Cochran-Mantel-Haenszel test over the strata (cmh(), spec
+        S10) as res["cmh_stat"], ["cmh_p"], ["cmh_odds"], ["cmh_crit"]; with permutations also res["r_cmh"] int32
+        [T, G] (uint32 bits) = the permutations whose pooled count lies in cmh_crit, counted on the same labels as r.
+        Every other result is that of the same call without the option, bit for bit."""
         if (fwer or stepdown) and permutations <= 0:
             raise ValueError("fwer=True / stepdown=True need permutations > 0")
         if cmh and strata is None:
@@ -1007,18 +1025,9 @@ class AssociationEngine:
         res = self._associate(genes, traits, masks, permutations, seed, perm_buffer, use_lists,
                               workspace, plan, graph if records is None and not (fwer or stepdown or cmh) else False,
                               strata=strata, cmh=cmh)
-        if stepdown:
-            res = dict(res)
-            res["r_fwer_sd"], res["minp"] = self.minp_stepdown(genes, traits, masks, permutations, seed, res=res,
-                                                               table_budget_bytes=table_budget_bytes, plan=plan,
-                                                               strata=strata)
-            if fwer:
-                res["r_fwer"] = self.r_fwer(res["minp"], res["p"])
-        elif fwer:
-            res = dict(res)
-            res["minp"] = self.minp(genes, traits, masks, permutations, seed, res=res,
-                                    table_budget_bytes=table_budget_bytes, plan=plan, strata=strata)
-            res["r_fwer"] = self.r_fwer(res["minp"], res["p"])
+        if fwer or stepdown:
+            res = {**res, **self.westfall_young(genes, traits, masks, permutations, seed, res, fwer, stepdown,
+                                                table_budget_bytes, plan, strata)}
         if records is not None:
             # the exchange records of the step, packed as its last kernel (inside a captured step:
             # one launch less per replay for a gene-sharded rank)
@@ -1031,8 +1040,7 @@ class AssociationEngine:
         """The step behind associate() (its docstring)."""
         torch = _torch()
         T = traits.shape[0]
-        if use_lists is None:
-            use_lists = genes.lists is not None and self.lists_supported(genes.N)
+        use_lists = self._lists_default(genes, use_lists)
         if use_lists and permutations > 0 and genes.lists is None:
             raise ValueError("use_lists=True but the gene matrix has no index lists: call "
                              "build_lists(genes) once per data set first")
@@ -1050,7 +1058,8 @@ class AssociationEngine:
                 return res
         counts, margins = self.counts(genes, traits, masks,
                                       out=(ws.counts, ws.margins, ws.mask_class, ws.plan_buf), plan=plan)
-        if permutations > 0 and use_lists:
+        lists = permutations > 0 and use_lists
+        if lists:
             # The first batch of label tiles needs only the trait margins, not the
             # Fisher pass: generate it on a side stream while k_fisher runs.  (With a plan the
             # margins are there before k_counts, and the fork could move in front of it: tried,
@@ -1060,45 +1069,41 @@ class AssociationEngine:
             # (Round 5, with the 0.04-0.08 ms generator: the overlap is still worth 0.3 % at cfg3 and
             # 2.5 % on a 25 000-gene shard of cfg4, nothing on cfg4 itself.)
             main = torch.cuda.current_stream(self.device)
-            nb0 = min(ws.batch, permutations)
             side = self._side_stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                self._label_tiles(ws, masks, margins, genes.N, nb0, 0, seed, strata)
+                self._label_tiles(ws, masks, margins, genes.N, min(ws.batch, permutations), 0, seed, strata)
             p, odds, crit, lcrit = self.fisher(counts, out=(ws.p, ws.odds, ws.crit),
                                                lists=genes.lists, lcrit=ws.lcrit)
-            extra = self._cmh_results(genes, traits, masks, strata, permutations) if cmh else {}
+        else:
+            p, odds, crit = self.fisher(counts, out=(ws.p, ws.odds, ws.crit))
+        extra = self._cmh_results(genes, traits, masks, strata, permutations) if cmh else {}
+        # every batch of labels is generated once and counted against each (regions, counter) pair of the step:
+        # the Fisher regions always (slot order on the list path), the CMH regions (gene order) with cmh
+        counted = [({"crit": None, "lcrit": lcrit} if lists else {"crit": crit}, ws.r)]
+        if "r_cmh" in extra:
+            counted.append(({"crit": extra["cmh_crit"]}, extra["r_cmh"]))
+        done = 0
+        if lists:
             main.wait_stream(side)
-            done = 0
             while done < permutations:
                 nb = min(ws.batch, permutations - done)
                 if done > 0:
                     self._label_tiles(ws, masks, margins, genes.N, nb, done, seed, strata)
-                self.permute_lists(genes, ws.tiles, None, margins, nb, ws.r, scratch=ws.scratch,
-                                   lcrit=lcrit, accumulate=done > 0, bfrag=ws.bfrag)
-                if cmh:     # the same label tiles against the CMH regions (gene order: converted by the library)
-                    self.permute_lists(genes, ws.tiles, extra["cmh_crit"], margins, nb, extra["r_cmh"],
-                                       scratch=ws.scratch, accumulate=done > 0, bfrag=ws.bfrag)
+                for regions, r in counted:
+                    self.permute_lists(genes, ws.tiles, margins=margins, P=nb, r=r, scratch=ws.scratch,
+                                       accumulate=done > 0, bfrag=ws.bfrag, **regions)
                 done += nb
-            return {"counts": counts, "margins": margins, "p": p, "odds": odds, "crit": crit,
-                    "r": ws.r, **extra}
-        p, odds, crit = self.fisher(counts, out=(ws.p, ws.odds, ws.crit))
-        extra = self._cmh_results(genes, traits, masks, strata, permutations) if cmh else {}
-        r = None
-        if permutations > 0:
-            r = ws.r
-            r.zero_()
+        elif permutations > 0:
+            ws.r.zero_()
             batch = ws.perms.shape[1]
-            done = 0
             while done < permutations:
                 nb = min(batch, permutations - done)
                 self.perm_generate(masks, margins, genes.N, nb, done, seed, out=ws.perms, strata=strata)
-                self.permute(genes, ws.perms[:, :nb] if nb == batch else ws.perms, crit, r, P=nb)
-                if cmh:
-                    self.permute(genes, ws.perms[:, :nb] if nb == batch else ws.perms, extra["cmh_crit"],
-                                 extra["r_cmh"], P=nb)
+                for regions, r in counted:
+                    self.permute(genes, ws.perms[:, :nb] if nb == batch else ws.perms, r=r, P=nb, **regions)
                 done += nb
-        return {"counts": counts, "margins": margins, "p": p, "odds": odds, "crit": crit, "r": r, **extra}
+        return {"counts": counts, "margins": margins, "p": p, "odds": odds, "crit": crit, "r": ws.r, **extra}
 
     def _cmh_results(self, genes, traits, masks, strata, permutations):
         """The entries associate(cmh=True) adds to its result: cmh() under the names of the step and, for a step

@@ -769,6 +769,65 @@ def _pattern_groups(table, maskrow, idx, hashes):
     return inv.reshape(-1)
 
 
+# The optional per-gene columns of a --no_pairwise results file, in file order (after Empirical_p, which has the
+# early-abort denominator and exists in pairwise mode too): (CSV name, key of its array in _associate's result,
+# True = a count r, read as uint32 and written as (r + 1) / (P + 1); False = the value as it is).  The arrays
+# reach the host beside the gathered records -- which is why their flags need a single process -- except r_fwer,
+# which travels in the records' nstop word (--permute-fwer excludes early abort): so a sharded run gathers it.
+OPTIONAL_COLUMNS = (
+    ("Westfall_Young_p", "r_fwer", True),
+    ("Westfall_Young_stepdown_p", "r_fwer_sd", True),
+    ("CMH_p", "cmh_p", False),
+    ("CMH_odds_ratio", "cmh_odds", False),
+    ("CMH_empirical_p", "r_cmh", True),
+)
+
+# The rules of the flags behind them, in the order they are checked: (flag, Setup_results keyword, the sentence
+# after "needs --no_pairwise", needs --permute >= 10, excludes --permute-early-abort, why it needs a single rank
+# or None).
+FLAG_RULES = (
+    ("--permute-fwer", "fwer", "The Westfall-Young minima are taken over the Fisher statistic of every gene",
+     True, True, None),
+    ("--permute-fwer-stepdown", "fwer_stepdown",
+     "The Westfall-Young minima are taken over the Fisher statistic of every gene", True, True,
+     "the successive minima run over all genes in one order; gene shards do not compose"),
+    ("--cmh", "cmh", "The Cochran-Mantel-Haenszel test is a test of every gene, beside Fisher's", False, True,
+     "its results reach the host beside the gathered records of a single process"),
+    ("--permute-strata", "strata", "The strata restrict the permutations of the Fisher statistic", True, False, None),
+)
+# a broken rule as the command line reports it / as Setup_results raises it
+RULE_TEXT = {
+    "no_pairwise": ("Cannot use %(flag)s without --no_pairwise. %(why)s", None),
+    "permutations": ("Cannot use %(flag)s without performing permutations. Use '--permute X' where X is a number "
+                     "equal to or larger than 10",
+                     "%(kw)s needs the Fisher-statistic permutations of --no_pairwise (permutations >= 10)"),
+    "early_abort": ("Cannot use %(flag)s together with --permute-early-abort. Every gene has to see every "
+                    "permutation", "%(kw)s excludes early_abort"),
+    "ranks": ("Cannot use %(flag)s under more than one rank: %(why)s", "%(kw)s needs a single process: %(why)s"),
+}
+
+
+def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None):
+    """The messages of the rules of one row of FLAG_RULES that a run breaks, in the order they are reported.
+    ``files``: the messages of the command line's checks of the flag's own file, which come before the rank rule
+    (() for a flag without one); None: the run is Setup_results' and the messages are its ValueErrors."""
+    flag, kw, sentence, needs_permutations, no_early_abort, one_rank = rule
+
+    def text(what, why=None):
+        return RULE_TEXT[what][files is None] % {"flag": flag, "kw": kw, "why": why}
+    if not no_pairwise:
+        yield text("no_pairwise", sentence)
+    if needs_permutations and permutations < 10:
+        yield text("permutations")
+    if no_early_abort and early_abort:
+        yield text("early_abort")
+    yield from files or ()
+    if one_rank:
+        from . import dist
+        if dist.world_rank()[0] > 1:
+            yield text("ranks", one_rank)
+
+
 def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, fwer=False,
                fwer_stepdown=False, strata=None, cmh=False):
     """Whole hot path for all traits; under torchrun (world > 1) every rank
@@ -778,18 +837,15 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
     ``early_abort``: the reference's sequential estimator (scoary/methods.py:1360-1363)
     on the Fisher statistic instead of the fixed-P count: out["nstop"] then holds the
     permutation count every gene stopped at (0 = ran to the end).
-    ``fwer``: also the Westfall-Young minima (spec S7): out["minp"] [T, P] and out["r_fwer"] [T, G] = the
-    number of permutations whose smallest p over ALL genes is <= the gene's own p.  Under gene sharding
-    every rank takes the minima over its own genes, one all_reduce(MIN) of the [T, P] doubles follows, and
-    r_fwer travels in the record's nstop word (the feature excludes early abort).
-    ``fwer_stepdown``: the step-down counts (spec S8) out["r_fwer_sd"] [T, G], single process only -- the
-    successive minima run over all genes in one order, gene shards do not compose; they reach the host beside the
-    records, as the minima do.  With ``fwer`` as well, r_fwer is counted from the same pass's minima.
+    ``fwer`` / ``fwer_stepdown``: the Westfall-Young results (engine.westfall_young, spec S7 / S8): out["minp"]
+    [T, P] and out["r_fwer"] / out["r_fwer_sd"] [T, G].  Under gene sharding every rank takes the minima over its
+    own genes and one all_reduce(MIN) of the [T, P] doubles precedes the count of r_fwer; the step-down counts do
+    not compose over shards (single process only).
     ``strata``: the stratum index of every isolate of the table (--permute-strata): every permutation shuffles
     the labels within the strata only (spec S9); every rank generates the same labels.
     ``cmh`` (needs ``strata``; single process, no early abort): the Cochran-Mantel-Haenszel test over the strata
-    (spec S10): out["cmh_p"], out["cmh_odds"] [T, G] and, with permutations, out["r_cmh"]; they reach the host
-    beside the records, as the step-down counts do."""
+    (spec S10): out["cmh_p"], out["cmh_odds"] [T, G] and, with permutations, out["r_cmh"].
+    How each of these arrays reaches the host: OPTIONAL_COLUMNS."""
     import torch
     from . import dist
     eng = get_engine()
@@ -822,8 +878,8 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         whole = sel == slice(0, G, 1)
         if len(range(*sel.indices(G))) == 0:
             if fwer:            # a rank without genes still takes part in the reduction of the minima
-                minp_all.append(dist.all_reduce_min(torch.ones((T, permutations), dtype=torch.float64,
-                                                               device=eng.device)))
+                beside["minp"] = dist.all_reduce_min(torch.ones((T, permutations), dtype=torch.float64,
+                                                                device=eng.device))
             return torch.zeros((T, 0, dist.REC_WORDS), dtype=torch.int32, device=eng.device)
         with _stage("device setup (H2D, tiling, trait plan)"):
             gm = table.on_device(eng) if whole else eng.tile_rows(table.rows64[sel], N)
@@ -858,32 +914,21 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         with _stage("kernels (counts, Fisher, permutations)"):
             res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan, strata=sp, cmh=cmh)
             torch.cuda.synchronize(eng.device)
-        if cmh:
-            cmh_all.append({k: res[k] for k in ("cmh_p", "cmh_odds", "r_cmh") if k in res})
-        r_fwer = None
-        if fwer_stepdown:
-            with _stage("Westfall-Young step-down minP (p tables, k_stepdown_minp)"):
-                # ranked on k_fisher's own bits, before the SciPy-digits pass rewrites the last ulp of p
-                r_sd, minp = eng.minp_stepdown(gm, trv, mkv, permutations, seed, res=res, strata=sp)
-                sd_all.append(r_sd)
-                if fwer:
-                    r_fwer = eng.r_fwer(minp, res["p"])
-                minp_all.append(minp)
-                torch.cuda.synchronize(eng.device)
-        elif fwer:
-            with _stage("Westfall-Young minP (p tables, k_permute_minp)"):
-                minp = dist.all_reduce_min(eng.minp(gm, trv, mkv, permutations, seed, res=res, strata=sp))
-                # counted on k_fisher's own bits, before the SciPy-digits pass rewrites the last ulp of p
-                r_fwer = eng.r_fwer(minp, res["p"])
-                minp_all.append(minp)
+        beside.update({k: res[k] for k in ("cmh_p", "cmh_odds", "r_cmh") if k in res})
+        if fwer or fwer_stepdown:
+            with _stage("Westfall-Young step-down minP (p tables, k_stepdown_minp)" if fwer_stepdown else
+                        "Westfall-Young minP (p tables, k_permute_minp)"):
+                # before the SciPy-digits pass rewrites the last ulp of p (westfall_young)
+                beside.update(eng.westfall_young(gm, trv, mkv, permutations, seed, res, fwer, fwer_stepdown,
+                                                 strata=sp, reduce=dist.all_reduce_min))
                 torch.cuda.synchronize(eng.device)
         scipy_digits(res)
         with _stage("kernels (counts, Fisher, permutations)"):
-            rec = eng.pack_records(res, nstop=r_fwer)
+            rec = eng.pack_records(res, nstop=beside.pop("r_fwer", None))
             torch.cuda.synchronize(eng.device)
         return rec
 
-    minp_all, sd_all, cmh_all = [], [], []
+    beside = {}         # the device arrays that reach the host beside the gathered records (OPTIONAL_COLUMNS)
     rec = dist.associate_sharded(local, G)
     with _stage("results D2H"):
         # the stable p order for BH: numpy does 200 000 doubles in 25-40 ms, which beats the
@@ -897,13 +942,11 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         out["r"] = None
     if fwer:
         out["r_fwer"], out["nstop"] = out["nstop"], np.zeros_like(out["nstop"])
-    if fwer or fwer_stepdown:
-        out["minp"] = minp_all[0].cpu().numpy()
     if fwer_stepdown:
-        out["r_fwer_sd"] = sd_all[0].cpu().numpy() if sd_all else np.zeros((T, 0), dtype=np.int32)
-    if cmh:
-        for k, v in (cmh_all[0] if cmh_all else {}).items():
-            out[k] = v.cpu().numpy()
+        out["r_fwer_sd"] = np.zeros((T, 0), dtype=np.int32)         # (a table without genes)
+    for key in ("minp",) + tuple(key for _name, key, _count in OPTIONAL_COLUMNS):
+        if key in beside:
+            out[key] = beside[key].cpu().numpy()
     return out
 
 
@@ -974,30 +1017,13 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
     ``strata``, not permutations; one process, no early abort): also ``CMH_p`` and ``CMH_odds_ratio``, the
     Cochran-Mantel-Haenszel test and the Mantel-Haenszel common odds ratio over the strata (spec S10), and with
     permutations ``CMH_empirical_p`` = (r_cmh+1)/(P+1), the exact permutation p of that statistic."""
-    if cmh:
-        if strata is None:
-            raise ValueError("cmh needs strata")
-        if early_abort:
-            raise ValueError("cmh excludes early_abort")
-        from . import dist
-        if dist.world_rank()[0] > 1:
-            raise ValueError("cmh needs a single process: its results reach the host beside the gathered records")
-    elif strata is not None and permutations < 10:
-        raise ValueError("strata need the Fisher-statistic permutations of --no_pairwise (permutations >= 10)")
-    if fwer and (permutations < 10 or early_abort):
-        raise ValueError("fwer needs permutations >= 10 and excludes early_abort")
-    if fwer_stepdown:
-        # (permutations are 0 here whenever the run is not --no_pairwise)
-        if permutations <= 0:
-            raise ValueError("fwer_stepdown needs the Fisher-statistic permutations of --no_pairwise")
-        if permutations < 10:
-            raise ValueError("fwer_stepdown needs permutations >= 10")
-        if early_abort:
-            raise ValueError("fwer_stepdown excludes early_abort")
-        from . import dist
-        if dist.world_rank()[0] > 1:
-            raise ValueError("fwer_stepdown needs a single process: the successive minima run over all genes in "
-                             "one order; gene shards do not compose")
+    if cmh and strata is None:
+        raise ValueError("cmh needs strata")
+    # (permutations are 0 here whenever the run is not --no_pairwise; with cmh the strata are its own)
+    active = {"fwer": fwer, "fwer_stepdown": fwer_stepdown, "cmh": cmh, "strata": strata is not None and not cmh}
+    for rule in (rule for rule in FLAG_RULES if active[rule[1]]):
+        for text in _broken_rules(rule, True, permutations, early_abort):
+            raise ValueError(text)
     table = _as_table(genedic)
     names, tarr = _trait_arrays(traitsdic, table.strains)
     if strata is not None and len(strata) != len(table.strains):
@@ -1030,12 +1056,6 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
             # permutations gets (r+1)/(n+1) = the reference's (r+1.0)/(i+2.0), :1362
             n_used = np.where(dev["nstop"][t] > 0, dev["nstop"][t], permutations).astype(np.float64)
             emp = (dev["r"][t].astype(np.float64) + 1.0) / (n_used + 1.0)
-        wy = None
-        if fwer:
-            wy = (dev["r_fwer"][t].astype(np.float64) + 1.0) / (permutations + 1.0)
-        wy_sd = None
-        if fwer_stepdown:
-            wy_sd = (dev["r_fwer_sd"][t].astype(np.float64) + 1.0) / (permutations + 1.0)
 
         if not collapse:
             # names stay in the GeneTable: the result rows are (table, idx) -- nothing per
@@ -1096,15 +1116,10 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
                 "B_p": B, "BH_p": BH}
         if emp is not None:
             cols["Empirical_p"] = emp[rows_idx]
-        if wy is not None:
-            cols["Westfall_Young_p"] = wy[rows_idx]
-        if wy_sd is not None:
-            cols["Westfall_Young_stepdown_p"] = wy_sd[rows_idx]
-        if cmh:
-            cols["CMH_p"], cols["CMH_odds_ratio"] = dev["cmh_p"][t][rows_idx], dev["cmh_odds"][t][rows_idx]
-            if "r_cmh" in dev:
-                cols["CMH_empirical_p"] = ((dev["r_cmh"][t].view(np.uint32).astype(np.float64) + 1.0)
-                                           / (permutations + 1.0))[rows_idx]
+        for name, key, count in OPTIONAL_COLUMNS:
+            if key in dev:
+                v = dev[key][t][rows_idx]
+                cols[name] = (v.view(np.uint32).astype(np.float64) + 1.0) / (permutations + 1.0) if count else v
         if collapse:
             tr = TraitResults(names_out, nugn, ann, cols, number_of_tests, members)
         else:
@@ -1429,9 +1444,6 @@ def _write_rows_python(fname, delimiter, header_line, Trait, table, sel_i, sel_k
             out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
 
 
-CMH_COLUMNS = ("CMH_p", "CMH_odds_ratio", "CMH_empirical_p")     # --cmh: after every other numeric column
-
-
 def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Prunedic, outdir,
                      permutations, num_threads, no_pairwise, genedic, extracolstoprint,
                      firstcolnames, time="", delimiter=",", seed=DEFAULT_SEED, writer_threads=0):
@@ -1453,14 +1465,10 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
         columns.append("Empirical_p")
     if not isinstance(Trait, TraitResults):
         Trait = _trait_results_from_dict(Trait)
-    with_wy = no_pairwise and with_emp and "Westfall_Young_p" in Trait.cols      # --permute-fwer
-    if with_wy:
-        columns.append("Westfall_Young_p")
-    with_wy_sd = no_pairwise and with_emp and "Westfall_Young_stepdown_p" in Trait.cols      # --permute-fwer-stepdown
-    if with_wy_sd:
-        columns.append("Westfall_Young_stepdown_p")
-    cmh_cols = [k for k in CMH_COLUMNS if no_pairwise and k in Trait.cols]                    # --cmh
-    columns += cmh_cols
+    # (a count has its denominator from the permutations: without them it is not written)
+    optional = [name for name, _key, count in OPTIONAL_COLUMNS
+                if no_pairwise and name in Trait.cols and (with_emp or not count)]
+    columns += optional
     columns += list(extracolstoprint)
     table = _as_table(genedic) if extracolstoprint else None
 
@@ -1485,16 +1493,7 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
                  % permutations)
         cand = order
         colget = {k: np.asarray(Trait.column(k)) for k in fields}
-        if with_emp:
-            colget["Empirical_p"] = np.asarray(Trait.column("Empirical_p"))
-            fields.append("Empirical_p")
-        if with_wy:
-            colget["Westfall_Young_p"] = np.asarray(Trait.column("Westfall_Young_p"))
-            fields.append("Westfall_Young_p")
-        if with_wy_sd:
-            colget["Westfall_Young_stepdown_p"] = np.asarray(Trait.column("Westfall_Young_stepdown_p"))
-            fields.append("Westfall_Young_stepdown_p")
-        for k in cmh_cols:
+        for k in (["Empirical_p"] if with_emp else []) + optional:
             colget[k] = np.asarray(Trait.column(k))
             fields.append(k)
         keyed = {CUT_FIELD[m]: colget[CUT_FIELD[m]] for m in cutoffs}
@@ -1556,7 +1555,7 @@ def _trait_results_from_dict(rows):
     """Plain {gene: row dict} (the reference's Results[trait]) -> TraitResults."""
     genes = list(rows.keys())
     cols = {}
-    for k in TraitResults.FIELDS + ("Empirical_p", "Westfall_Young_p", "Westfall_Young_stepdown_p") + CMH_COLUMNS:
+    for k in TraitResults.FIELDS + ("Empirical_p",) + tuple(name for name, _key, _count in OPTIONAL_COLUMNS):
         if genes and k in rows[genes[0]]:
             cols[k] = np.array([rows[g][k] for g in genes])
     return TraitResults(genes, [rows[g]["NUGN"] for g in genes],
@@ -1957,6 +1956,16 @@ def _analysed_isolates(args):
     return strains
 
 
+def _strata_file_problems(args, flag, path):
+    """What is wrong with the strata file ``path`` of ``flag`` (--cmh or --permute-strata), as exit messages."""
+    if not os.path.isfile(path):
+        yield "Could not find the strata file: %s" % path
+    other = getattr(args, "permute_strata", None) if flag == "--cmh" else None
+    if other and not (os.path.isfile(other) and os.path.samefile(other, path)):
+        yield ("--cmh %s and --permute-strata %s name different strata files. With --cmh the permutations "
+               "shuffle the labels within the strata of its file: give one file" % (path, other))
+
+
 def _validate(args, cutoffs):
     """Argument checks of methods.py:126-181 (same conditions, same exits)."""
     if args.traits is None or args.genes is None:
@@ -1979,57 +1988,15 @@ def _validate(args, cutoffs):
                  "exactly as many as the number of correction methods and in corresponding "
                  "sequence. e.g. -c I EPW -p 0.1 0.05 will apply an individual p-value cutoff "
                  "of 0.1 AND a pairwise comparisons p-value cutoff of 0.05.")
-    if getattr(args, "permute_fwer", False):
-        if not args.no_pairwise:
-            sys.exit("Cannot use --permute-fwer without --no_pairwise. The Westfall-Young minima are taken "
-                     "over the Fisher statistic of every gene")
-        if args.permute < 10:
-            sys.exit("Cannot use --permute-fwer without performing permutations. Use '--permute X' where X "
-                     "is a number equal to or larger than 10")
-        if getattr(args, "permute_early_abort", False):
-            sys.exit("Cannot use --permute-fwer together with --permute-early-abort. Every gene has to see "
-                     "every permutation")
-    if getattr(args, "permute_fwer_stepdown", False):
-        if not args.no_pairwise:
-            sys.exit("Cannot use --permute-fwer-stepdown without --no_pairwise. The Westfall-Young minima are "
-                     "taken over the Fisher statistic of every gene")
-        if args.permute < 10:
-            sys.exit("Cannot use --permute-fwer-stepdown without performing permutations. Use '--permute X' "
-                     "where X is a number equal to or larger than 10")
-        if getattr(args, "permute_early_abort", False):
-            sys.exit("Cannot use --permute-fwer-stepdown together with --permute-early-abort. Every gene has to "
-                     "see every permutation")
-        from . import dist
-        if dist.world_rank()[0] > 1:
-            sys.exit("Cannot use --permute-fwer-stepdown under more than one rank: the successive minima run over "
-                     "all genes in one order; gene shards do not compose")
-    if getattr(args, "cmh", None):
-        if not args.no_pairwise:
-            sys.exit("Cannot use --cmh without --no_pairwise. The Cochran-Mantel-Haenszel test is a test of every "
-                     "gene, beside Fisher's")
-        if getattr(args, "permute_early_abort", False):
-            sys.exit("Cannot use --cmh together with --permute-early-abort. Every gene has to see every permutation")
-        if not os.path.isfile(args.cmh):
-            sys.exit("Could not find the strata file: %s" % args.cmh)
-        other = getattr(args, "permute_strata", None)
-        if other and not (os.path.isfile(other) and os.path.samefile(other, args.cmh)):
-            sys.exit("--cmh %s and --permute-strata %s name different strata files. With --cmh the permutations "
-                     "shuffle the labels within the strata of its file: give one file" % (args.cmh, other))
-        from . import dist
-        if dist.world_rank()[0] > 1:
-            sys.exit("Cannot use --cmh under more than one rank: its results reach the host beside the gathered "
-                     "records of a single process")
+    for rule in FLAG_RULES:
+        value = getattr(args, rule[0][2:].replace("-", "_"), None)
+        if value:
+            files = _strata_file_problems(args, rule[0], value) if isinstance(value, str) else ()
+            for text in _broken_rules(rule, args.no_pairwise, args.permute,
+                                      getattr(args, "permute_early_abort", False), files):
+                sys.exit(text)
     strata_flag = "--permute-strata" if getattr(args, "permute_strata", None) else "--cmh"
     strata_path = getattr(args, "permute_strata", None) or getattr(args, "cmh", None)
-    if getattr(args, "permute_strata", None):
-        if not args.no_pairwise:
-            sys.exit("Cannot use --permute-strata without --no_pairwise. The strata restrict the permutations of "
-                     "the Fisher statistic")
-        if args.permute < 10:
-            sys.exit("Cannot use --permute-strata without performing permutations. Use '--permute X' where X "
-                     "is a number equal to or larger than 10")
-        if not os.path.isfile(args.permute_strata):
-            sys.exit("Could not find the strata file: %s" % args.permute_strata)
     if strata_path:
         args.strata_map = read_strata_file(strata_path, args.delimiter)
         # the isolates of the analysis are the header of the gene table (after -s and -r): checked here, before the

@@ -238,6 +238,17 @@ def test_shards_batches_and_trait_groups_compose(eng):
     acc = eng.minp(eng.pack_dense(np.ascontiguousarray(genes[part.index(0)])), trv, mkv, P, SEED)
     eng.minp(eng.pack_dense(np.ascontiguousarray(genes[part.index(1)])), trv, mkv, P, SEED, out=acc)
     assert torch.equal(acc.view(torch.int64), whole.view(torch.int64))
+    # ... or each shard through westfall_young(), the other shard's minima entering by ``reduce``: minp and r_fwer are
+    # those of the whole matrix at the shard's genes
+    full = eng.associate(gm, trv, mkv, permutations=P, seed=SEED, fwer=True)["r_fwer"]
+    for r in range(2):
+        sg = eng.pack_dense(np.ascontiguousarray(genes[part.index(r)]))
+        res = eng.associate(sg, trv, mkv, permutations=P, seed=SEED)
+        wy = eng.westfall_young(sg, trv, mkv, P, SEED, res, fwer=True,
+                                reduce=lambda m, other=shards[1 - r]: torch.minimum(m, other))
+        assert sorted(wy) == ["minp", "r_fwer"]
+        assert torch.equal(wy["minp"].view(torch.int64), whole.view(torch.int64))
+        assert torch.equal(wy["r_fwer"], full[:, part.index(r)])
     # two permutation batches (the second starts inside a group of 64 and a Philox block of 32)
     two = eng.minp(gm, trv, mkv, P, SEED, perm_range=(0, 100))
     assert (two[:, 100:] == 1.0).all()

@@ -327,6 +327,55 @@ def test_native_results_writer_equals_the_python_writer(tmp_path, roary):
     assert not m._write_rows_native(a, ",", header, tr, table, sel_i, None, tr.cols, fields, None, False, ["QC"])
 
 
+def test_optional_columns_reach_the_file_in_one_order_through_every_writer(tmp_path, monkeypatch):
+    """Empirical_p and the five optional --no_pairwise columns together (Westfall-Young, its step-down, the three
+    of --cmh): the header ends in them, in this order; the file is the same bytes through the native writer, the
+    Python writer and from a plain {gene: row dict}; a result set without one of them simply lacks that column."""
+    from scoary_amd import io_native, methods as m
+    assert io_native.available()
+    rng = np.random.default_rng(11)
+    G, N, P = 40, 30, 100
+    table = m.GeneTable(["gene_%d" % i for i in range(G)], ["nu%d" % (i % 7) if i % 5 else "" for i in range(G)],
+                        ["ann%d" % i for i in range(G)], ["s%d" % j for j in range(N)],
+                        rng.integers(0, 2**30, (G, 1), dtype=np.uint64), {})
+    odds = rng.random(G) * 50
+    odds[::7], odds[3::11] = np.inf, np.nan
+    last = ["Empirical_p", "Westfall_Young_p", "Westfall_Young_stepdown_p", "CMH_p", "CMH_odds_ratio",
+            "CMH_empirical_p"]
+    cols = {"tpgp": rng.integers(0, N, G).astype(np.int32), "tngp": rng.integers(0, N, G).astype(np.int32),
+            "tpgn": rng.integers(0, N, G).astype(np.int32), "tngn": rng.integers(0, N, G).astype(np.int32),
+            "sens": np.round(rng.random(G) * 100, 2), "spes": rng.random(G) * 100, "OR": odds,
+            "p_v": rng.random(G) ** 20, "B_p": np.minimum(rng.random(G) * 3, 1.0), "BH_p": rng.random(G),
+            "CMH_p": rng.random(G) ** 9, "CMH_odds_ratio": odds[::-1].copy()}
+    for k in ("Empirical_p", "Westfall_Young_p", "Westfall_Young_stepdown_p", "CMH_empirical_p"):
+        cols[k] = (rng.integers(0, P + 1, G).astype(np.uint32).astype(np.float64) + 1.0) / (P + 1.0)
+
+    def store(trait, tag):
+        outdir = str(tmp_path / tag) + os.sep
+        os.mkdir(outdir)
+        fn = m.StoreTraitResult(trait, "T", None, {}, None, None, None, outdir, permutations=P, num_threads=1,
+                                no_pairwise=True, genedic=table, extracolstoprint=[],
+                                firstcolnames=["Gene", "Non-unique Gene name", "Annotation"])
+        with open(fn, "rb") as f:
+            return f.read()
+
+    def header(data):
+        return data.split(b"\n")[0].decode().replace('"', "").split(",")
+
+    tr = m.TraitResults(None, None, None, cols, G, None, table=table, rows_idx=np.arange(G))
+    native = store(tr, "native")
+    assert header(native)[-6:] == last and len(header(native)) == 3 + 10 + 6 and native.count(b"\n") == G + 1
+    assert store({g: tr[g] for g in tr}, "dict") == native
+    monkeypatch.setenv("SCOARY_PY_WRITER", "1")
+    assert store(tr, "python") == native
+    assert store({g: tr[g] for g in tr}, "python_dict") == native
+    monkeypatch.delenv("SCOARY_PY_WRITER")
+    for drop in last[1:]:
+        fewer = m.TraitResults(None, None, None, {k: v for k, v in cols.items() if k != drop}, G, None, table=table,
+                               rows_idx=np.arange(G))
+        assert header(store(fewer, "without_" + drop))[-5:] == [k for k in last if k != drop]
+
+
 # -------------------------------------------------------------- vcf2scoary ---
 def test_vcf2scoary_matches_reference_output(exampledir, tmp_path):
     """tests/test_scoary_output.py:16-17,123-136 of the reference pins the first

@@ -136,17 +136,12 @@ def test_tree_pairs_many_genes_vs_oracle(eng, orc):
     import torch
     from scoary_amd import tree as T
     from scoary_amd.engine import pack_bits_rows
+    from tree_stage_cases import rand_tree
     rng = np.random.default_rng(5)
-
-    def rand_tree(tips, cat):
-        if len(tips) == 1:
-            return tips[0]
-        k = 1 if rng.random() < cat else int(rng.integers(1, len(tips)))
-        return [rand_tree(tips[:k], cat), rand_tree(tips[k:], cat)]
     sys.setrecursionlimit(10000)
     for K, cat in [(2, 0), (9, 0.2), (64, 0.5), (333, 0.9), (700, 0.1), (1500, 0.97)]:
         names = ["t%d" % i for i in range(K)]
-        tree = rand_tree(names, cat)
+        tree = rand_tree(rng, names, cat)
         prog = T.TreeProgram(tree, {t: i for i, t in enumerate(names)})
         assert prog.depth <= int(np.log2(K)) + 2
         G, L = 37, 11

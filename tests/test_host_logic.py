@@ -730,6 +730,44 @@ def test_native_upgma_equals_numpy_loop_and_reference_goldens():
             T.upgma_from_counts(cnt, X.shape[1], names, native=False)
 
 
+@pytest.mark.parametrize("n", [1025, 1280, 1300])
+def test_native_upgma_equals_numpy_loop_past_1024_isolates(n):
+    """The host library's merge loop == the numpy quad-tree loop on the inputs that take the
+    device loop past one stride of its reductions (test_gpu_tree_stage.py): few ties at 1025,
+    duplicated strains -- hundreds of zero-distance ties -- at 1300, first merges between
+    rows past 1024 at 1280."""
+    import tree_stage_cases as tc
+    from scoary_amd import io_native, tree as T
+    assert io_native.available()
+    var, names, cnt = tc.upgma_case(n)
+    want = T.upgma_from_counts(cnt, var.shape[1], names, native=False)
+    D = cnt.astype(np.float64) / float(var.shape[1])
+    np.fill_diagonal(D, 1.0)
+    merges = io_native.upgma_merges(D)                    # no degenerate hand-back: the native loop itself
+    cluster = list(names)
+    for i, j in merges.tolist():
+        cluster[i], cluster[j] = [cluster[i], cluster[j]], None
+    assert tc.same_tree(cluster[i], want)
+    assert tc.same_tree(T.upgma_from_counts(cnt, var.shape[1], names, native=True), want)
+
+
+def test_tree_exceed_inputs_meet_every_branch():
+    """The inputs of test_gpu_tree_stage.test_exceed_flags_vs_oracle_and_exact_integers, judged
+    by the oracle alone (draw seed tree_stage_cases.EXCEED_DRAW_SEED = 2), over the five cases
+    together: flags of both values, an exact tie of the two ratios, a gene compared on its
+    opposing side, a gene with pro == anti > 0.  And the oracle's fp64 flags are the
+    exact-integer predicate of its own triples; the two constant genes are never exceeded."""
+    import tree_stage_cases as tc
+    from oracle import oracle as orc
+    cases = tc.exceed_references(orc)
+    cond = tc.exceed_conditions(cases)
+    assert all(cond.values()), cond
+    for c in cases:
+        assert np.array_equal(tc.exact_exceed(c.obs, c.pairs)[0], c.flags), c.K
+        assert not c.obs[-2:].any() and not c.flags[-2:].any()          # observed total 0: 0/0
+        assert (c.flags[c.ties] == 1).all()
+
+
 # ------------------------------------------------------------- custom trees ----
 def test_read_newick_resolves_polytomies_like_ete3(tmp_path):
     """-n trees with more than two children per node: the reference calls ete3's

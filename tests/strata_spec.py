@@ -20,9 +20,10 @@ def _philox(ctr, key):
     return list(_philox_cached(tuple(ctr), tuple(key)))
 
 
-def s9_labels(seed, t, pi, valid, labels, strata, S=None):
+def s9_labels(seed, t, pi, valid, labels, strata, S=None, deficits=None):
     """The 0/1 labels of permutation ``pi`` of trait ``t``: ``valid`` / ``labels`` / ``strata`` are N-long
-    sequences (validity 0/1, observed label 0/1, stratum index in [0, S))."""
+    sequences (validity 0/1, observed label 0/1, stratum index in [0, S)).  ``deficits``: a dict that receives
+    {stratum: d}, the marks every non-empty stratum's fix-up starts short of (d > 0) or past (d < 0) its target."""
     N = len(valid)
     if S is None:
         S = max(strata) + 1
@@ -51,6 +52,8 @@ def s9_labels(seed, t, pi, valid, labels, strata, S=None):
             marks[i] = (x >> bit) & 1
         # fix-up: draws c = 0, 1, ... from counter ((s << 20) | (c >> 2), pi, t, "SCOD"), word c & 3
         d = m - sum(marks[i] for i in mem if valid[i])
+        if deficits is not None:
+            deficits[s] = d
         thr = (1 << 32) % n_s
         c, rnd = 0, None
         while d != 0:

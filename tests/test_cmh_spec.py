@@ -5,8 +5,11 @@ import random
 from fractions import Fraction
 
 import numpy as np
+import pytest
 
+import cmh_cases as C
 import cmh_spec as S
+
 
 def test_ucb_admissions_anchor():
     """R: mantelhaen.test(UCBAdmissions) -> X-squared = 1.4269, p-value = 0.2323, common odds ratio 0.9047."""
@@ -124,3 +127,131 @@ def test_degenerate_cases():
     assert S.cmh([(3, 3, 4, 8)])["crit"] == (1, 2) == S.cmh([(0, 3, 4, 8)])["crit"]
     # odds: inf when only Q vanishes, nan when both do
     assert S.cmh([(3, 3, 3, 8)])["odds"] == math.inf and math.isnan(S.cmh([(0, 0, 3, 8)])["odds"])
+
+
+# -- the constructed cases of tests/cmh_cases.py reach what the GPU tests (test_gpu_cmh_limits.py) hold the kernel to --
+
+def _edge_tables():
+    genes, traits, strata, names = C.edge_case()
+    a, m, k, n = C.recount(genes, traits, strata, len(C.EDGE_NK))
+    assert [(int(n[0, s]), int(k[0, s])) for s in range(len(C.EDGE_NK))] == list(C.EDGE_NK)
+    for g, name in enumerate(names):                 # the expansion to isolates gives back the (a, m) it was given
+        assert [(int(a[0, g, s]), int(m[0, g, s])) for s in range(len(C.EDGE_NK))] == list(C.EDGE_GENES[name])
+    return a, m, k, n, names
+
+
+def test_the_edge_case_meets_every_condition_it_is_built_for():
+    a, m, k, n, names = _edge_tables()
+    G = a.shape[1]
+    tabs = {name: C.tables(a, m, k, n, 0, g) for g, name in enumerate(names)}
+    res = {name: S.cmh(t) for name, t in tabs.items()}
+    K = sum(kk for _n, kk in C.EDGE_NK)
+    # no informative stratum
+    assert res["dead"]["var"] == 0.0 and res["none"]["var"] == 0.0 and res["all"]["var"] == 0.0
+    # A = E: the middle branch of the region
+    r = res["a_equals_e"]
+    assert r["var"] > 0 and abs(2.0 * r["a"] - r["e2"]) <= S.TAU and r["crit"] == (0, 0) and r["stat"] == 0.0
+    assert S.exact(tabs["a_equals_e"])[0] == S.exact(tabs["a_equals_e"])[1]
+    # half a count from E: inside the continuity correction, outside the middle branch
+    r = res["inside_cc"]
+    A, E, _V = S.exact(tabs["inside_cc"])
+    assert abs(A - E) == Fraction(1, 2) and r["stat"] == 0.0 and r["var"] > 0 and abs(2.0 * r["a"] - r["e2"]) > S.TAU
+    # lo of S10 below 0 before the clamp: A > 2E + 1
+    r = res["lo_clamp"]
+    A, E, _V = S.exact(tabs["lo_clamp"])
+    assert A > 2 * E + 1 and math.floor((r["e2"] - float(r["a"])) + S.TAU) + 1 < 0
+    assert r["crit"][0] == 0 and r["crit"][1] == r["a"] > 0              # base == 0 with span > 0: accepts 0 .. A - 1
+    # hi of S10 above K before the clamp: 2E - A > K
+    r = res["hi_clamp"]
+    A, E, _V = S.exact(tabs["hi_clamp"])
+    assert 2 * E - A > K and math.ceil((r["e2"] - float(r["a"])) - S.TAU) - 1 > K
+    assert r["crit"] == (A + 1, K - A) and r["crit"][0] + r["crit"][1] == K + 1
+    # an exact tie: the mirror image of A is an integer of the support, and extreme
+    r = res["mirror_tie"]
+    A, E, _V = S.exact(tabs["mirror_tie"])
+    mirror = 2 * E - A
+    lo, hi = S.support(tabs["mirror_tie"])
+    assert mirror.denominator == 1 and mirror != A and lo <= mirror <= hi
+    assert S.in_region(r["crit"], int(mirror)) and S.in_region(r["crit"], A)
+    assert not S.in_region(r["crit"], int(E)) and r["crit"][1] == abs(int(mirror) - A) - 1
+    # odds = inf: no discordant pair of one kind
+    assert res["odds_inf"]["odds"] == math.inf and res["odds_inf"]["var"] > 0
+    assert math.isnan(res["none"]["odds"])
+    # the second trait: strata with n = 0 and n = 1 that the mask made
+    assert [int(x) for x in n[1, [0, 3, 7]]] == [1, 0, 0] and (n[0] > 0).all()
+    live = sum(S.cmh(C.tables(a, m, k, n, 1, g))["var"] > 0 for g in range(G))
+    assert 0 < live < G
+    # region and exact rule agree on the whole support of every gene of both traits
+    for t in range(2):
+        for g in range(G):
+            tb = C.tables(a, m, k, n, t, g)
+            lo, hi = S.support(tb)
+            assert C.exact_rule_mismatches(tb, S.cmh(tb)["crit"], range(lo, hi + 1)) == []
+
+
+def test_the_graded_case_has_tiny_subnormal_and_zero_p():
+    genes, traits, strata = C.graded_case()
+    want = C.restate(*C.recount(genes, traits, strata, 4))
+    stat, p = want["stat"][0], want["p"][0]
+    assert stat.min() < 70 and stat.max() > 1500 and (want["var"] > 0).all()
+    assert ((p >= C.P_NORMAL) & (p < 1e-200)).sum() >= 3                 # normal doubles below 1e-200
+    assert ((p > 0) & (p < 2.2250738585072014e-308)).sum() >= 1          # subnormals
+    assert ((p == 0.0) & (stat > 1400)).sum() >= 1                       # underflow to an exact zero
+    assert (p > 1e-30).sum() >= 3
+    print("graded case: stat %.1f .. %.1f, %d subnormal p, %d zero p"
+          % (stat.min(), stat.max(), ((p > 0) & (p < 2.2250738585072014e-308)).sum(), (p == 0).sum()))
+
+
+@pytest.mark.parametrize("name", list(C.BATCH_CASES))
+def test_the_batch_cases_regions_equal_the_exact_rule_on_the_whole_support(name):
+    """The counts a permutation can reach are those of the support: on all of them the restatement's region is the
+    exact rule, up to the stated slack at a near tie."""
+    genes, traits, strata, Sn, _P, _batch, _tw = C.batch_case(name)
+    a, m, k, n = C.recount(genes, traits, strata, Sn)
+    informative = 0
+    for t, g in C.subsample_pairs(traits.shape[0], genes.shape[0]):
+        tb = C.tables(a, m, k, n, t, g)
+        r = S.cmh(tb)
+        lo, hi = S.support(tb)
+        assert C.exact_rule_mismatches(tb, r["crit"], range(lo, hi + 1)) == [], (name, t, g)
+        informative += r["crit"][1] > 0
+    assert informative >= 10
+
+
+def test_the_limit_layouts_are_what_they_claim():
+    N, Sn = C.LIMIT_N, C.LIMIT_S
+    word = np.arange(N) // 32
+    assert word.max() == 639 and N == 20479 and Sn == 1024
+    segments = {}
+    for name in C.LIMIT_GENES:
+        st = C.limit_strata(name)
+        assert st.shape == (N,) and st.min() >= 0 and st.max() == Sn - 1 - (name == "blocked")
+        segments[name] = len(np.unique(st * 1024 + word))
+        # stratum indices and word indices past 8 bits together, in every layout
+        assert ((st >= 256) & (word >= 256)).any()
+    # interleaved: no two members of a stratum share a word, so there are N segments, as many as the scratch holds
+    assert segments["interleaved"] == N
+    # blocked: contiguous, blocks of one, of more than 32 and more than 64 members, indices without a member
+    st = C.limit_strata("blocked")
+    sizes = np.bincount(st, minlength=Sn)
+    assert (np.diff(st) >= 0).all()
+    assert (sizes == 1).sum() >= 20 and ((sizes > 32) & (sizes <= 64)).sum() >= 5 and (sizes > 64).sum() >= 5
+    assert sizes[0] == 0 and sizes[512] == 0 and sizes[Sn - 1] == 0
+    assert (sizes[1:512] > 0).any() and (sizes[513:] > 0).any()
+    assert (np.flatnonzero(np.diff(st)) % 32 != 31).sum() > 500          # boundaries inside words
+    _genes, traits, _st = C.limit_case("blocked")
+    assert sizes[7] > 0 and (traits[1, st == 7] == 2).all() and (traits[0, st == 7] != 2).all()
+    # two_level: several members of a stratum per word, not adjacent; runs longer than a word cannot occur, runs
+    # of up to 16 members start at every offset of the segment builder's 20-member chunks
+    st = C.limit_strata("two_level")
+    order = np.argsort(st, kind="stable")
+    key = st[order] * 1024 + word[order]
+    heads = np.flatnonzero(np.r_[True, key[1:] != key[:-1]])
+    runs = np.diff(np.r_[heads, N])
+    assert segments["two_level"] < N // 8 and runs.max() == 16 and (runs >= 10).sum() > 1000
+    per = -(-N // 1024)
+    assert per == 20 and ((heads % per) + runs > per).sum() > 300        # runs that cross a chunk end
+    for name in C.LIMIT_GENES:
+        _g, traits, _s = C.limit_case(name)
+        assert traits.shape == (C.LIMIT_T, N) and (traits == 2).any(1).sum() >= 2
+    assert max(C.LIMIT_GENES.values()) > 256 and max(C.LIMIT_GENES.values()) % 256

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import cmh_spec as S10
+from cmh_cases import Case, check_p, random_genes_traits
 
 pytestmark = pytest.mark.gpu
 SEED = 20261018
@@ -24,74 +25,26 @@ def eng():
     e.close()
 
 
-class Case:
-    """Genes, traits (0 / 1, 2 = missing) and strata as numpy arrays and on the device."""
-
-    def __init__(self, eng, genes, traits, strata, S=None):
-        from scoary_amd.engine import pack_bits_rows
-        self.genes, self.traits, self.strata = genes.astype(np.uint8), traits.astype(np.uint8), np.asarray(strata)
-        (self.G, self.N), self.T = genes.shape, traits.shape[0]
-        self.gm = eng.pack_dense(self.genes)
-        self.trv = eng.vecrows(pack_bits_rows((self.traits == 1).astype(np.uint8)), self.N)
-        self.mkv = eng.vecrows(pack_bits_rows((self.traits != 2).astype(np.uint8)), self.N)
-        self.sp = eng.strata_plan(self.strata, self.trv, self.mkv, self.N, S=S)
-        self.S = self.sp.S
-
-    def recount(self):
-        """(a, m) int64 [T, G, S] and (k, n) int64 [T, S] with numpy."""
-        onehot = (self.strata[:, None] == np.arange(self.S)[None, :]).astype(np.int64)
-        lab, val, g = (self.traits == 1).astype(np.int64), (self.traits != 2).astype(np.int64), self.genes.astype(np.int64)
-        return (np.einsum("gn,tn,ns->tgs", g, lab, onehot), np.einsum("gn,tn,ns->tgs", g, val, onehot),
-                lab @ onehot, val @ onehot)
-
-    def labels(self, eng, P, seed):
-        """The stratified label bits [T, P, N] and the pooled counts [T, P, G] of P permutations."""
-        plan = eng.trait_plan(self.trv, self.mkv, self.N)
-        rows = eng.perm_generate(self.mkv, plan.margins, self.N, P, 0, seed, strata=self.sp).cpu().numpy()
-        bits = np.unpackbits(rows.view(np.uint8).reshape(self.T, P, -1), axis=2, bitorder="little")[:, :, :self.N]
-        return bits, np.einsum("tpn,gn->tpg", bits.astype(np.int64), self.genes.astype(np.int64))
-
-
-def random_case(eng, G, N, T, S, dense_genes=False):
-    rng = np.random.default_rng(G + N + S)
-    lo, hi = (0.3, 0.7) if dense_genes else (0.02, 0.98)
-    genes = (rng.random((G, N)) < rng.uniform(lo, hi, (G, 1))).astype(np.uint8)
-    genes[1], genes[2] = 0, 1
-    traits = (rng.random((T, N)) < rng.uniform(0.2, 0.8, (T, 1))).astype(np.uint8)
-    traits[0] = np.where(rng.random(N) < 0.7, genes[3], traits[0])              # one strong association
-    traits[T - 1, rng.random(N) < 0.06] = 2
-    return genes, traits, rng
-
-
 def build_case(eng, name):
     if name == "interleaved":            # random strata, 257 isolates = 9 words: a quad tail, missing values in trait 2
-        genes, traits, rng = random_case(eng, 300, 257, 3, 4)
+        genes, traits, rng = random_genes_traits(300, 257, 3, 4)
         return Case(eng, genes, traits, rng.integers(0, 4, 257), S=4)
     if name == "singletons":             # strata of one isolate, strata emptied by the mask, a stratum without members
-        genes, traits, rng = random_case(eng, 130, 129, 2, 40)
+        genes, traits, rng = random_genes_traits(130, 129, 2, 40)
         strata = rng.integers(0, 36, 129)
         strata[5], strata[77], strata[[9, 10]] = 36, 37, 38
         traits[1, [9, 10, 77]] = 2                                              # 38 and 37 are empty for trait 1
         return Case(eng, genes, traits, strata, S=40)
     if name == "contiguous":             # boundaries inside words; more isolates than the matrix-core kernel takes
-        genes, traits, rng = random_case(eng, 200, 2100, 2, 7)
+        genes, traits, rng = random_genes_traits(200, 2100, 2, 7)
         bounds = np.array([13, 300, 301, 1000, 1555, 2047])
         return Case(eng, genes, traits, np.searchsorted(bounds, np.arange(2100), side="right"), S=7)
     if name == "traits33":               # more traits than one pass of the counts kernel (32)
-        genes, traits, rng = random_case(eng, 64, 96, 33, 3)
+        genes, traits, rng = random_genes_traits(64, 96, 33, 3)
         return Case(eng, genes, traits, rng.integers(0, 3, 96), S=3)
     assert name == "one_stratum"
-    genes, traits, rng = random_case(eng, 300, 257, 3, 1)
+    genes, traits, rng = random_genes_traits(300, 257, 3, 1)
     return Case(eng, genes, traits, np.zeros(257, dtype=np.int64), S=1)
-
-
-def check_p(got, want):
-    """|dp| <= 1e-12 and <= 1e-10 |p| against math.erfc (erfc amplifies the few ulp of the device
-    erfc by about 2 x^2, <= ~2e4 on these shapes)."""
-    err = np.abs(got - want)
-    rel = err / np.where(want > 0, want, 1.0)
-    print("cmh p: max abs error %.3e, max relative error %.3e" % (err.max(), rel.max()))
-    assert err.max() <= 1e-12 and rel.max() <= 1e-10
 
 
 @pytest.mark.parametrize("name", ["interleaved", "singletons", "contiguous", "traits33", "one_stratum"])
@@ -173,7 +126,7 @@ def test_associate_counts_the_cmh_region_on_the_same_labels(eng, use_lists):
 
 
 def test_associate_cmh_with_the_matrix_core_kernel(eng):
-    genes, traits, rng = random_case(eng, 512, 600, 2, 5, dense_genes=True)
+    genes, traits, rng = random_genes_traits(512, 600, 2, 5, dense_genes=True)
     c = Case(eng, genes, traits, rng.integers(0, 5, 600), S=5)
     eng.set_mfma_route("all")
     try:

@@ -88,6 +88,30 @@ def test_one_stratum_is_the_unstratified_generator_bit_for_bit(eng, N):
     assert np.array_equal(got, want)
 
 
+def _multipass_case():
+    """(N, P, strata, traits, perms) with more strata than a block has lanes per permutation: N = 5000, S = 70 of
+    which 60 have members -- six of 1 to 3, two above 300, the rest 40 to 120, all interleaved; trait 0 with missing
+    values.  A few blocks of bit rows at this N run 1024 threads = 32 lanes per permutation, so the strata are walked
+    in three passes; ``perms`` are the permutations compared with s9_labels."""
+    rng = np.random.default_rng(70)
+    N, P, S = 5000, 40, 70
+    sizes = np.zeros(S, dtype=np.int64)
+    live = np.sort(rng.choice(S, 60, replace=False))
+    sizes[live] = rng.integers(40, 121, 60)
+    sizes[live[[1, 17, 30, 41, 50, 58]]] = [1, 2, 3, 1, 2, 3]
+    sizes[live[[5, 47]]] = [350, 420]
+    mid, i = [s for s in live if 40 <= sizes[s] <= 120], 0
+    while sizes.sum() != N:                                 # the sizes of 40 to 120 take up the remainder in turn
+        step = 1 if sizes.sum() < N else -1
+        if 40 <= sizes[mid[i % len(mid)]] + step <= 120:
+            sizes[mid[i % len(mid)]] += step
+        i += 1
+    strata = np.repeat(np.arange(S), sizes)[rng.permutation(N)]
+    traits = (rng.random((2, N)) < 0.4).astype(np.uint8)
+    traits[0, rng.random(N) < 0.1] = 2
+    return N, P, strata, traits, (0, 1, 31, 32, 33, P - 1)
+
+
 def _spec_case(name):
     rng = np.random.default_rng(31)
     if name == "n130":
@@ -113,18 +137,30 @@ def _spec_case(name):
         strata = rng.integers(0, 7, N)
         traits = _random_traits(rng, 2, N)
         return N, P, strata, traits, None
+    if name == "n5000_three_passes":
+        # S = 70 > the 32 lanes a permutation has: the later passes over the strata, with fix-ups of every size
+        # (test_strata_spec.py shows from the restatement that the checked permutations have them)
+        return _multipass_case()
     N, P = 600, 33                                           # as many strata as the kernel takes: most are empty
     strata = rng.integers(0, 1024, N)
     traits = _random_traits(rng, 2, N)
     return N, P, strata, traits, None
 
 
-@pytest.mark.parametrize("name", ["n130", "n2100", "n600_max_strata"])
+@pytest.mark.parametrize("name", ["n130", "n2100", "n600_max_strata", "n5000_three_passes"])
 def test_rows_and_tiles_equal_the_python_restatement(eng, name):
     N, P, strata, traits, perms = _spec_case(name)
     T = traits.shape[0]
-    S = int(eng.lib.scoary_perm_max_strata()) if name == "n600_max_strata" else int(strata.max()) + 1
+    S = {"n600_max_strata": int(eng.lib.scoary_perm_max_strata()), "n5000_three_passes": 70}.get(
+        name, int(strata.max()) + 1)
     trait_base = 3
+    if name == "n5000_three_passes":
+        # the bit rows come from ceil(40 / 32) x 2 traits = 4 blocks: labels_threads(4, 5000, CUs) doubles the block
+        # from 256 threads while 4 blocks of it are fewer than 8 wavefronts per CU and a thread keeps >= 4 isolates,
+        # so it ends at 1024 threads = 32 lanes per permutation and 70 strata take three passes.  (This holds for the
+        # rows, which are what s9_labels is compared with; the tiles may run another block size and must equal them.)
+        import torch
+        assert 4 * (512 // 64) < 8 * torch.cuda.get_device_properties(0).multi_processor_count and N // 512 >= 4
     trv, mkv, margins = _device_traits(eng, traits)
     sp = eng.strata_plan(strata, trv, mkv, N, S=S)
     rows = _row_bits(eng.perm_generate(mkv, margins, N, P, 0, SEED, trait_base=trait_base, strata=sp), N)

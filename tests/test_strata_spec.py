@@ -6,6 +6,7 @@ import numpy as np
 
 from oracle import oracle as orc
 from strata_spec import s9_labels
+from test_gpu_strata import _spec_case
 
 SEED = 0x0123456789ABCDEF
 
@@ -101,3 +102,32 @@ def test_the_law_is_uniform_and_independent_across_strata():
     chi2 = sum((c - exp) ** 2 / exp for c in outcomes.values())
     print("chi2 = %.2f on 119 degrees of freedom" % chi2)
     assert chi2 < 119 + 5 * (2 * 119) ** 0.5
+
+
+def test_the_multipass_case_has_small_and_batched_fix_ups_past_the_first_pass():
+    """The case test_gpu_strata.py compares with this restatement: strata of every size class, and among the
+    checked permutations strata with index >= 32 (a block's second and third pass over the strata at 32 lanes per
+    permutation) whose fix-up starts 4 or more marks off its target, and others 1 to 3 off."""
+    N, P, strata, traits, perms = _spec_case("n5000_three_passes")
+    S = 70
+    sizes = np.bincount(strata, minlength=S)
+    assert N == 5000 and traits.shape == (2, N) and (traits[0] == 2).any() and not (traits[1] == 2).any()
+    assert (sizes > 0).sum() == 60 and ((sizes > 0) & (sizes <= 3)).sum() == 6 and (sizes > 300).sum() == 2
+    assert ((sizes >= 40) & (sizes <= 120)).sum() == 52 and sizes[64:].any() and sizes[32:64].any()
+    assert (np.diff(strata) != 0).mean() > 0.9                       # interleaved
+    assert set(perms) == {0, 1, 31, 32, 33, P - 1}
+    valid, lab = (traits != 2).astype(int), (traits == 1).astype(int)
+    big, small = set(), set()
+    for t in range(2):
+        for pi in perms:
+            d = {}
+            got = s9_labels(0xDEADBEEF12345678, 3 + t, pi, valid[t].tolist(), lab[t].tolist(), strata.tolist(), S,
+                            deficits=d)
+            assert sorted(d) == np.flatnonzero(sizes).tolist()
+            assert np.array_equal(np.bincount(strata, weights=got, minlength=S),
+                                  np.bincount(strata, weights=lab[t], minlength=S))
+            big |= {s for s, v in d.items() if s >= 32 and abs(v) >= 4}
+            small |= {s for s, v in d.items() if s >= 32 and 0 < abs(v) < 4}
+    print("strata >= 32 with |d| >= 4: %d, with 0 < |d| < 4: %d" % (len(big), len(small)))
+    assert any(s >= 64 for s in big) and any(32 <= s < 64 for s in big)
+    assert any(s >= 64 for s in small) and any(32 <= s < 64 for s in small)

@@ -390,6 +390,35 @@ int scoary_cmh(scoary_handle h, const uint32_t *d_tiled, const uint32_t *d_label
                const int32_t *d_smargins, int64_t G, int64_t T, int64_t N, int64_t S, double *d_stat,
                double *d_p, double *d_odds, double *d_e2, double *d_var, int32_t *d_a, uint32_t *d_crit,
                int32_t *d_scounts, void *d_scratch, scoary_stream_t stream);
+/* ---- Westfall-Young tables of the CMH statistic (spec S11 of DESIGN.md; additive, ABI 11) ---------------
+ * The family-wise adjusted p of the stratified test: scoary_permute_minp / scoary_permute_stepdown run unchanged
+ * over tables of the CMH statistic instead of Fisher's p.  Under within-stratum shuffles (S9) E and V of a
+ * (trait, gene) are constants, so its statistic is a function of the pooled count a' = popc(gene & label) alone:
+ * the table holds u(x) = 1 / (1 + stat(x)) in (0, 1] -- smaller is more extreme, 1.0 the identity of the minimum --
+ * for every x of the support of a', in the CSR layout of scoary_minp_plan / _fill.
+ *   scoary_cmh_minp_plan : per (trait, gene), with m_s = popc(gene & valid & stratum_s) and (k_s, n_s) = d_smargins,
+ *       strata with n_s = 0 skipped: lo = sum max(0, k_s + m_s - n_s), hi = sum min(k_s, m_s).  d_lo int32 [T][G]
+ *       = lo, d_off int64 [T * G + 1] = the exclusive prefix sum of hi - lo + 1 (the total last), *entries_out
+ *       (HOST) = that total.  The strata plan and d_masks are scoary_cmh's; d_scratch = scoary_cmh_scratch_bytes(N)
+ *       bytes (the segment table, rebuilt here).  Synchronises `stream` like scoary_minp_plan.  [lo, hi] lies
+ *       inside the support scoary_minp_plan gives the same (trait, gene).
+ *   scoary_cmh_minp_fill : d_tab double [entries]; with E2 = d_e2[t][g], V = d_var[t][g] as scoary_cmh wrote them,
+ *       E2' = rint(E2) if |E2 - rint(E2)| <= 1e-6 else E2 (an exact tie a' + A = 2E needs an integer 2E; the fp64
+ *       sum is off by up to 1.5e-8), every operation rounded on its own:
+ *         D = |(double)x - 0.5 E2'|, y = min(0.5, D), stat = ((D - y)(D - y)) / V,
+ *         d_tab[d_off[t G + g] + x - lo] = 1.0 / (1.0 + stat)          (1.0 when V == 0).
+ *       entries may exceed 2^31; no scratch.  Asynchronous on `stream`, allocates nothing.
+ * The observed value of a gene is ITS OWN table entry at x = d_a[t][g] (gathered, never recomputed), so an observed
+ * and a permuted gene at the same count tie exactly.  Limits: S <= scoary_perm_max_strata(), N <=
+ * scoary_perm_strata_max_isolates(), T <= 65535 (SCOARY_ERR_SIZE). */
+int scoary_cmh_minp_plan(scoary_handle h, const uint32_t *d_tiled, const uint32_t *d_masks,
+                         const uint16_t *d_strata, const int32_t *d_members, const int32_t *d_offsets,
+                         const int32_t *d_smargins, int64_t G, int64_t T, int64_t N, int64_t S,
+                         void *d_scratch, int64_t *d_off, int32_t *d_lo, int64_t *entries_out,
+                         scoary_stream_t stream);
+int scoary_cmh_minp_fill(scoary_handle h, const double *d_e2, const double *d_var, const int64_t *d_off,
+                         const int32_t *d_lo, int64_t T, int64_t G, int64_t entries, double *d_tab,
+                         scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

@@ -13,6 +13,17 @@
 //       each rounded on its own (the library is built with -ffp-contract=off).  The cost follows the number of
 //       segments, not S; nothing is re-tiled and the per-stratum tables exist only in registers (d_scounts, for
 //       callers that want them, is the one exception).
+//
+// The Westfall-Young tables of the CMH statistic (spec S11): what scoary_permute_minp / scoary_permute_stepdown
+// gather from, in the CSR layout of scoary_minp_plan / _fill, indexed by the pooled count a' = popc(gene & label).
+//   k_cmh_support : k_cmh's walk over the same segment table with the validity words alone -- per stratum
+//       m = popc(gene & valid & stratum), folded into the two integer sums lo = sum max(0, k + m - n) and
+//       hi = sum min(k, m): the support of a' under within-stratum shuffles.  A kernel of its own, so that k_cmh
+//       compiles to what it compiled to before there were tables.  k_minp_scan (scoary_common.hpp) turns the sizes
+//       into offsets.
+//   k_cmh_fill : one wavefront per (trait, gene); its lanes stride over the gene's entries, so a wavefront's stores
+//       are one contiguous run of the table.  u(x) = 1 / (1 + stat(x)) from d_e2 and d_var as scoary_cmh wrote
+//       them: a few flops per entry, no table list, 64-bit entry indices throughout.
 #include <cstddef>
 
 #include "scoary_common.hpp"
@@ -187,6 +198,101 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh(const uint32_t* __restrict_
   }
 }
 
+
+// ---- S11: the tables of the Westfall-Young passes over the CMH statistic ----
+
+constexpr int64_t kCmhFillRows = (int64_t)1 << 28;   // (trait, gene) rows per k_cmh_fill launch: 2^26 blocks
+
+// S11 step 1.  k_cmh's geometry and walk (lane = gene, kCmhTraits traits per block, every index clamped alike); the
+// stratum's m of a trait is folded at every change of stratum, strata without a valid isolate skipped as in S10.
+__global__ __launch_bounds__(kCmhThreads) void k_cmh_support(const uint32_t* __restrict__ tiled,
+                                                             const uint32_t* __restrict__ masks,
+                                                             const int32_t* __restrict__ smargins,
+                                                             const CmhSegments* __restrict__ segs, int64_t G,
+                                                             int64_t Gp, int T, int N, int Wp, int S,
+                                                             int64_t* __restrict__ off, int32_t* __restrict__ lo_out) {
+  const int64_t g = (int64_t)blockIdx.x * kCmhThreads + threadIdx.x;      // < Gp: the grid covers Gp exactly
+  const int t0 = blockIdx.y * kCmhTraits;
+  const uint4* __restrict__ quads = reinterpret_cast<const uint4*>(tiled);
+  const int nseg = min((int)segs->count, N);
+
+  int32_t lo[kCmhTraits], hi[kCmhTraits];
+  uint32_t m[kCmhTraits];
+#pragma unroll
+  for (int j = 0; j < kCmhTraits; ++j) lo[j] = hi[j] = 0, m[j] = 0;
+  auto trait = [&](int j) { return min(t0 + j, T - 1); };
+  auto fold = [&](int s) {
+#pragma unroll
+    for (int j = 0; j < kCmhTraits; ++j) {
+      const int2 kn = reinterpret_cast<const int2*>(smargins)[(int64_t)trait(j) * S + s];
+      const int mm = (int)m[j];
+      m[j] = 0;
+      if (kn.y <= 0) continue;
+      lo[j] += max(0, kn.x + mm - kn.y);
+      hi[j] += min(kn.x, mm);
+    }
+  };
+
+  int cur_s = -1, cur_q = -1;
+  uint4 gq = make_uint4(0, 0, 0, 0);
+  for (int i = 0; i < nseg; ++i) {
+    const uint2 sg = segs->seg[i];                                        // wave-uniform
+    const int s = min((int)(sg.x >> 16), S - 1), w = min((int)(sg.x & 0xffffu), Wp - 1);
+    if (s != cur_s) {
+      if (cur_s >= 0) fold(cur_s);
+      cur_s = s;
+    }
+    if ((w >> 2) != cur_q) {
+      cur_q = w >> 2;
+      gq = quads[(int64_t)cur_q * Gp + g];
+    }
+    const int c = w & 3;
+    const uint32_t gw = (c == 0 ? gq.x : c == 1 ? gq.y : c == 2 ? gq.z : gq.w) & sg.y;
+#pragma unroll
+    for (int j = 0; j < kCmhTraits; ++j) bcnt_acc(m[j], gw & masks[(int64_t)trait(j) * Wp + w]);
+  }
+  if (cur_s >= 0) fold(cur_s);
+
+  if (g >= G) return;
+#pragma unroll
+  for (int j = 0; j < kCmhTraits; ++j) {
+    if (t0 + j >= T) continue;
+    const int64_t o = (int64_t)(t0 + j) * G + g;
+    off[o] = max(hi[j] - lo[j], 0) + 1;       // a sound plan has hi >= lo; any other still gets a table of one entry
+    lo_out[o] = lo[j];
+  }
+}
+
+// S11 steps 2 and 3 for the rows [r0, r0 + nrows) of the [T * G] (trait, gene) pairs: wavefront = row, lane l writes
+// the entries l, l + 64, ... of the row's run tab[off[i] .. off[i + 1]).  The run is clamped into [0, entries): a
+// bad offset array writes wrong values, never outside the table.
+__global__ __launch_bounds__(kCmhThreads) void k_cmh_fill(const double* __restrict__ e2, const double* __restrict__ var,
+                                                          const int64_t* __restrict__ off,
+                                                          const int32_t* __restrict__ lo, int64_t r0, int64_t nrows,
+                                                          int64_t entries, double* __restrict__ tab) {
+  const int64_t r = (int64_t)blockIdx.x * (kCmhThreads / kWave) + (threadIdx.x / kWave);
+  if (r >= nrows) return;
+  const int64_t i = r0 + r;                                               // wave-uniform
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t o0 = min(max(off[i], (int64_t)0), entries), o1 = min(max(off[i + 1], o0), entries);
+  const double v = var[i];
+  double e = e2[i];
+  const double whole = rint(e);
+  if (fabs(e - whole) <= kCmhTau) e = whole;                               // step 2: the snap
+  const double half = 0.5 * e;
+  const double x0 = (double)lo[i];
+  for (int64_t k = lane; k < o1 - o0; k += kWave) {
+    double u = 1.0;
+    if (v != 0.0) {
+      const double delta = fabs((x0 + (double)k) - half);                 // (double)x: lo + k is an exact integer
+      const double y = fmin(0.5, delta);
+      const double stat = ((delta - y) * (delta - y)) / v;
+      u = 1.0 / (1.0 + stat);
+    }
+    tab[o0 + k] = u;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -225,6 +331,63 @@ int scoary_cmh(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d_label
                      dim3(kCmhThreads), 0, s, d_tiled, d_labels, d_masks, d_smargins, segs, G, Gp, (int)T, (int)N,
                      (int)scoary_row_words(N), (int)S, out);
   HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+
+
+int scoary_cmh_minp_plan(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d_masks, const uint16_t* d_strata,
+                         const int32_t* d_members, const int32_t* d_offsets, const int32_t* d_smargins, int64_t G,
+                         int64_t T, int64_t N, int64_t S, void* d_scratch, int64_t* d_off, int32_t* d_lo,
+                         int64_t* entries_out, scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (!d_tiled || !d_masks || !d_strata || !d_members || !d_offsets || !d_smargins || !d_scratch || !d_off || !d_lo ||
+      !entries_out || G < 1 || T < 1 || N < 1 || S < 1)
+    return fail(h, SCOARY_ERR_ARG, "scoary_cmh_minp_plan: bad argument");
+  if (T > 65535 || G > (int64_t)1 << 30)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_minp_plan: T > 65535 or G > 2^30");
+  if (S > scoary_perm_max_strata())
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_minp_plan: more strata than scoary_perm_max_strata()");
+  if (N > scoary_perm_strata_max_isolates())
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_minp_plan: more isolates than scoary_perm_strata_max_isolates()");
+  const int64_t Gp = scoary_tiled_genes(G);
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CmhSegments* segs = static_cast<CmhSegments*>(d_scratch);
+  const int64_t M = T * G;
+  {
+    KernelTimer kt(h, s, "k_cmh_minp_plan");
+    hipLaunchKernelGGL(k_cmh_segments, dim3(1), dim3(kSegThreads), 0, s, d_strata, d_members, (int)N, (int)S, segs);
+    hipLaunchKernelGGL(k_cmh_support, dim3((unsigned)(Gp / kCmhThreads), (unsigned)((T + kCmhTraits - 1) / kCmhTraits)),
+                       dim3(kCmhThreads), 0, s, d_tiled, d_masks, d_smargins, segs, G, Gp, (int)T, (int)N,
+                       (int)scoary_row_words(N), (int)S, d_off, d_lo);
+    hipLaunchKernelGGL(k_minp_scan, dim3(1), dim3(1024), 0, s, d_off, M);
+    HIP_TRY(h, hipGetLastError());
+  }
+  // the one read-back of the path, as in scoary_minp_plan: the caller sizes the table with it
+  HIP_TRY(h, hipMemcpyAsync(entries_out, d_off + M, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return SCOARY_OK;
+}
+
+int scoary_cmh_minp_fill(scoary_handle h, const double* d_e2, const double* d_var, const int64_t* d_off,
+                         const int32_t* d_lo, int64_t T, int64_t G, int64_t entries, double* d_tab,
+                         scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (!d_e2 || !d_var || !d_off || !d_lo || !d_tab || T < 1 || G < 1 || entries < T * G)
+    return fail(h, SCOARY_ERR_ARG, "scoary_cmh_minp_fill: bad argument");
+  if (T > 65535 || G > (int64_t)1 << 30)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_minp_fill: T > 65535 or G > 2^30");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t M = T * G;
+  constexpr int rows_per_block = kCmhThreads / kWave;
+  KernelTimer kt(h, s, "k_cmh_minp_fill");
+  for (int64_t r0 = 0; r0 < M; r0 += kCmhFillRows) {
+    const int64_t nrows = std::min(kCmhFillRows, M - r0);
+    hipLaunchKernelGGL(k_cmh_fill, dim3((unsigned)((nrows + rows_per_block - 1) / rows_per_block)), dim3(kCmhThreads),
+                       0, s, d_e2, d_var, d_off, d_lo, r0, nrows, entries, d_tab);
+    HIP_TRY(h, hipGetLastError());
+  }
   return SCOARY_OK;
 }
 

@@ -226,5 +226,36 @@ __device__ __forceinline__ void and_popc(uint32_t& acc, const uint4 a, const uin
   bcnt_acc(acc, a.w & b.w);
 }
 
+
+// exclusive prefix sum of off[0 .. M) in place, off[M] = total.  One block walks the array in tiles of
+// 1024 with a running carry (once per trait group: 0.5 M entries are ~500 tiles).  Shared by the
+// table plans of scoary_minp.hip (S7) and scoary_cmh.hip (S11): CSR offsets from the support sizes.
+__global__ __launch_bounds__(1024) void k_minp_scan(int64_t* __restrict__ off, int64_t M) {
+  __shared__ int64_t s_wave[16];
+  __shared__ int64_t s_carry;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) s_carry = 0;
+  __syncthreads();
+  for (int64_t base = 0; base < M; base += 1024) {
+    const int64_t i = base + tid;
+    const int64_t v = i < M ? off[i] : 0;
+    int64_t x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int64_t y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63) s_wave[wave] = x;
+    __syncthreads();
+    int64_t before = s_carry;
+    for (int w = 0; w < wave; ++w) before += s_wave[w];
+    if (i < M) off[i] = before + x - v;
+    __syncthreads();
+    if (tid == 1023) s_carry = before + x;
+    __syncthreads();
+  }
+  if (tid == 0) off[M] = s_carry;
+}
+
 }  // namespace
 #endif

@@ -129,34 +129,7 @@ __global__ __launch_bounds__(256) void k_minp_sizes(const int4* __restrict__ cou
   lo_out[i] = lo;
 }
 
-// exclusive prefix sum of off[0 .. M) in place, off[M] = total.  One block walks the array in tiles of
-// 1024 with a running carry (once per trait group: 0.5 M entries are ~500 tiles).
-__global__ __launch_bounds__(1024) void k_minp_scan(int64_t* __restrict__ off, int64_t M) {
-  __shared__ int64_t s_wave[16];
-  __shared__ int64_t s_carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < M; base += 1024) {
-    const int64_t i = base + tid;
-    const int64_t v = i < M ? off[i] : 0;
-    int64_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int64_t y = __shfl_up(x, d);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    int64_t before = s_carry;
-    for (int w = 0; w < wave; ++w) before += s_wave[w];
-    if (i < M) off[i] = before + x - v;
-    __syncthreads();
-    if (tid == 1023) s_carry = before + x;
-    __syncthreads();
-  }
-  if (tid == 0) off[M] = s_carry;
-}
+// (k_minp_scan, the exclusive prefix sum of the sizes, is scoary_common.hpp's: scoary_cmh.hip plans its tables with it too)
 
 // entries [e0, e0 + ne) of the table list: entry e belongs to the (trait, gene) i with off[i] <= e < off[i + 1]
 // and is the table with overlap count lo[i] + e - off[i] and the margins of counts[i]

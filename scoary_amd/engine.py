@@ -36,7 +36,21 @@ class GeneMatrix:
         self.G = int(G)
         self.N = int(N)
         self.lists = None       # GeneLists, for the list-driven permutation kernel
-        self.minp_cache = None  # the p tables of the last minp(..., plan=...) on this matrix (engine.minp)
+        # the tables of the last minp(..., plan=...) on this matrix, one slot per kind of table (engine._minp_batches):
+        # "fisher" = the p tables, "cmh" = the CMH tables of a strata plan.  A step with both keeps both.
+        self.minp_caches = {}
+
+    @property
+    def minp_cache(self):
+        """The slot of Fisher's p tables (None: nothing kept)."""
+        return self.minp_caches.get("fisher")
+
+    @minp_cache.setter
+    def minp_cache(self, slot):
+        if slot is None:
+            self.minp_caches.pop("fisher", None)
+        else:
+            self.minp_caches["fisher"] = slot
 
 
 class ListMemoryError(_abi.ScoaryHipError):
@@ -64,6 +78,16 @@ class MinpTables:
 
     def __init__(self, off, lo, tab, entries):
         self.off, self.lo, self.tab, self.entries = off, lo, tab, int(entries)
+
+
+class TableSource:
+    """Where a Westfall-Young pass (minp / minp_stepdown) takes its tables and observed values from: ``kind`` and
+    ``key`` name the tables in genes.minp_caches (Fisher's p tables depend on the traits alone, key None; the CMH
+    tables on the strata plan as well), ``build(t0, t1)`` -> the MinpTables of the traits [t0, t1), ``observed(t0,
+    t1, tables)`` -> float64 [t1 - t0, G], the value every gene of those traits is ranked and counted by."""
+
+    def __init__(self, kind, key, build, observed):
+        self.kind, self.key, self.build, self.observed = kind, key, build, observed
 
 
 class TraitPlan:
@@ -697,6 +721,60 @@ class AssociationEngine:
                     "scoary_minp_fill")
         return MinpTables(off, lo, tab, total)
 
+    def cmh_tables(self, genes, masks, strata, cmh_res):
+        """The Westfall-Young tables of the CMH statistic (spec S11; scoary_cmh_minp_plan / _fill): for every (trait,
+        gene) u(x) = 1 / (1 + stat(x)) at every pooled count x of its support under the within-stratum shuffles of
+        ``strata`` -- MinpTables, the layout permute_minp / permute_stepdown take.  ``masks``: the validity rows
+        [T, Wp] of the traits of ``strata``; ``cmh_res``: cmh()'s result for them (its e2 and var are read).  One
+        8-byte read-back (the entry count)."""
+        torch = _torch()
+        T, G, N = int(masks.shape[0]), genes.G, genes.N
+        self._strata_fits(strata, T, N)
+        e2, var = cmh_res["e2"], cmh_res["var"]
+        if not (masks.is_contiguous() and e2.is_contiguous() and var.is_contiguous()) or \
+                tuple(e2.shape) != (T, G) or tuple(var.shape) != (T, G):
+            raise ValueError("cmh_tables: validity rows [T, Wp] and cmh()'s e2 / var [T, G] of the same traits, "
+                             "contiguous")
+        off = self._empty((T * G + 1,), torch.int64)
+        lo = self._empty((T, G), torch.int32)
+        scratch = self._empty(((int(self.lib.scoary_cmh_scratch_bytes(N)) + 7) // 8,), torch.int64)
+        entries = ctypes.c_int64()
+        self._check(self.lib.scoary_cmh_minp_plan(
+            self.h, self._ptr(genes.tiled), self._ptr(masks), *self._strata_ptrs(strata), G, T, N, strata.S,
+            self._ptr(scratch), self._ptr(off), self._ptr(lo), ctypes.byref(entries), self._stream()),
+            "scoary_cmh_minp_plan")
+        total = int(entries.value)
+        tab = self._empty((total,), torch.float64)
+        self._check(self.lib.scoary_cmh_minp_fill(self.h, self._ptr(e2), self._ptr(var), self._ptr(off),
+                                                  self._ptr(lo), T, G, total, self._ptr(tab), self._stream()),
+                    "scoary_cmh_minp_fill")
+        return MinpTables(off, lo, tab, total)
+
+    def cmh_observed(self, tables, a):
+        """u_obs float64 [T, G] (spec S11 step 4): every gene's own table entry at its pooled count ``a`` (cmh()'s
+        int32 [T, G]) -- gathered, never recomputed, so an observed and a permuted gene at the same count tie."""
+        torch = _torch()
+        T, G = int(a.shape[0]), int(a.shape[1])
+        if tuple(tables.lo.shape) != (T, G) or int(tables.off.shape[0]) != T * G + 1:
+            raise ValueError("cmh_observed: the tables are those of other traits or genes")
+        off = tables.off[:T * G].view(T, G)
+        at = (a - tables.lo).to(torch.int64)
+        if bool(((at < 0) | (at >= tables.off[1:].view(T, G) - off)).any()):       # one read-back per trait group
+            raise ValueError("cmh_observed: a pooled count lies outside its gene's support -- the tables and the "
+                             "CMH result do not belong to the same traits and strata")
+        return tables.tab[off + at]
+
+    def cmh_source(self, genes, masks, strata, cmh_res):
+        """The TableSource of spec S11: the CMH tables of ``strata`` (cmh_tables) and u_obs (cmh_observed), both per
+        trait group.  ``cmh_res``: cmh()'s result for all traits (e2, var and a are read)."""
+        def build(t0, t1):
+            return self.cmh_tables(genes, masks[t0:t1], strata.rows(t0, t1),
+                                   {"e2": cmh_res["e2"][t0:t1], "var": cmh_res["var"][t0:t1]})
+
+        def observed(t0, t1, tables):
+            return self.cmh_observed(tables, cmh_res["a"][t0:t1])
+        return TableSource("cmh", strata, build, observed)
+
     def permute_minp(self, genes, perms, tables, minp, P=None, perm_base=0):
         """minp[t, perm_base + i] = min(itself, min over the genes of p_tg(popcount(gene & perms[t, i]))) for the
         label rows ``perms`` (int32 [T, P, Wp], perm_generate's layout).  ``minp``: float64 [T, >= perm_base + P],
@@ -730,7 +808,8 @@ class AssociationEngine:
         return groups
 
     def minp(self, genes, traits, masks, permutations, seed=0, res=None, out=None, perm_range=None,
-             table_budget_bytes=8 << 30, label_budget_bytes=8 << 30, plan=None, strata=None):
+             table_budget_bytes=8 << 30, label_budget_bytes=8 << 30, plan=None, strata=None, source=None,
+             observed_out=None):
         """Westfall-Young minP (spec S7): float64 device tensor [T, permutations], minp[t, pi] = the smallest raw
         Fisher p over the genes of ``genes`` under the S4 labels of (seed, t, pi).  ``res``: an associate() result of
         the same genes and traits (its counts and margins are used; without one they are counted here).
@@ -740,9 +819,13 @@ class AssociationEngine:
         one, and when all traits fit one group, the tables stay attached to ``genes`` (genes.minp_cache, as the
         index lists do) and later calls with the same plan reuse them: the tables depend on the gene matrix and
         the traits alone, and building them is most of a step (cfg3: 119 of 150 ms).  ``strata``: a StrataPlan
-        of these traits -- the labels are those of spec S9 (the tables do not depend on it)."""
+        of these traits -- the labels are those of spec S9 (the tables do not depend on it).  ``source``: a
+        TableSource -- the minima are taken over its tables instead of Fisher's p tables (cmh_source: spec S11);
+        ``observed_out``: a float64 [T, G] tensor that takes the source's observed values."""
         torch = _torch()
         counts, margins = self._minp_inputs(genes, traits, masks, res, plan)
+        if source is None:
+            source = self.fisher_source(counts)
         T, P = int(counts.shape[0]), int(permutations)
         if out is None:
             out = torch.ones((T, P), dtype=torch.float64, device=self.device)
@@ -751,8 +834,27 @@ class AssociationEngine:
         def launch(t0, t1, tables, perms, nb, done):
             self.permute_minp(genes, perms, tables, out[t0:t1], P=nb, perm_base=done)
         self._minp_batches(genes, masks, counts, margins, p0, p1, seed, table_budget_bytes, label_budget_bytes, plan,
-                           launch, strata=strata)
+                           launch, source, strata=strata, begin=self._keep_observed(observed_out))
         return out
+
+    @staticmethod
+    def _keep_observed(observed_out):
+        """The ``begin`` of _minp_batches that copies a group's observed values into ``observed_out`` (None: none)."""
+        if observed_out is None:
+            return None
+        return lambda t0, t1, observed: observed_out[t0:t1].copy_(observed)
+
+    def fisher_source(self, counts, p=None):
+        """The TableSource of S7 / S8: Fisher's p tables of ``counts`` and the association step's own p (``p``;
+        without one k_fisher is run over the counts when the observed values are first asked for)."""
+        own = {"p": p}
+
+        def observed(t0, t1, _tables):
+            if own["p"] is None:
+                own["p"] = self.fisher(counts.reshape(-1, 4), want_crit=False)[0].view(counts.shape[0],
+                                                                                      counts.shape[1])
+            return own["p"][t0:t1]
+        return TableSource("fisher", None, lambda t0, t1: self.minp_tables(counts[t0:t1]), observed)
 
     def _minp_inputs(self, genes, traits, masks, res, plan):
         """(counts, margins) of minp() / minp_stepdown(): an associate() result's, or counted here."""
@@ -763,26 +865,36 @@ class AssociationEngine:
         return self.counts(genes, traits, masks, plan=plan)
 
     def _minp_batches(self, genes, masks, counts, margins, p0, p1, seed, table_budget_bytes, label_budget_bytes, plan,
-                      launch, strata=None):
-        """The loop minp() and minp_stepdown() share: trait groups under the table budget (their p tables built, or
-        taken from / left in genes.minp_cache when there is a plan), label batches under the label budget, and per
-        batch ``launch(t0, t1, tables, perms, nb, done)`` -- the traits [t0, t1) with their tables and the label rows
-        ``perms`` [t1 - t0, nb, Wp] of the permutations done .. done + nb - 1."""
+                      launch, source, strata=None, begin=None):
+        """The loop minp() and minp_stepdown() share: trait groups under the table budget (their tables built by
+        ``source``, or taken from / left in genes.minp_cache when there is a plan), label batches under the label
+        budget, and per batch ``launch(t0, t1, tables, perms, nb, done)`` -- the traits [t0, t1) with their tables
+        and the label rows ``perms`` [t1 - t0, nb, Wp] of the permutations done .. done + nb - 1.  ``begin(t0, t1,
+        observed)``: called once per trait group before its first batch, with the source's observed values of the
+        group.  The groups are cut by Fisher's support sizes for every source: the support of the pooled count
+        under within-stratum shuffles lies inside Fisher's (S11), so the bound holds.  genes.minp_caches has one
+        slot per kind of source, checked against the plan, the budget and the source's key: Fisher's tables are
+        never handed to a CMH pass, or the reverse, and a step that runs both keeps both."""
         torch = _torch()
         if p1 <= p0:
             return
         N = genes.N
         Wp = self.row_words(N)
         buf = None
-        cached = genes.minp_cache if plan is not None else None
-        if cached is not None and (cached["plan"] is not plan or cached["budget"] != table_budget_bytes):
-            cached = genes.minp_cache = None
+        cached = genes.minp_caches.get(source.kind) if plan is not None else None
+        if cached is not None and (cached["plan"] is not plan or cached["budget"] != table_budget_bytes
+                                   or cached["key"] is not source.key):
+            del genes.minp_caches[source.kind]
+            cached = None
         groups = cached["groups"] if cached else self.minp_trait_groups(counts, table_budget_bytes)
         for t0, t1 in groups:
             Tg = t1 - t0
-            tables = cached["tables"] if cached else self.minp_tables(counts[t0:t1])
+            tables = cached["tables"] if cached else source.build(t0, t1)
             if plan is not None and cached is None and len(groups) == 1:
-                genes.minp_cache = {"plan": plan, "budget": table_budget_bytes, "groups": groups, "tables": tables}
+                genes.minp_caches[source.kind] = {"plan": plan, "budget": table_budget_bytes, "groups": groups,
+                                                  "tables": tables, "key": source.key}
+            if begin is not None:
+                begin(t0, t1, source.observed(t0, t1, tables))
             batch = self.perm_batch(Tg, N, p1 - p0, budget_bytes=label_budget_bytes)
             if buf is None or buf.numel() < Tg * batch * Wp:
                 buf = self._empty((Tg * batch * Wp,), torch.int32)
@@ -805,7 +917,8 @@ class AssociationEngine:
         return torch.searchsorted(srt, p.contiguous(), right=True).to(torch.int32)
 
     def westfall_young(self, genes, traits, masks, permutations, seed, res, fwer=False, stepdown=False,
-                       table_budget_bytes=8 << 30, plan=None, strata=None, reduce=None):
+                       table_budget_bytes=8 << 30, plan=None, strata=None, reduce=None, cmh_fwer=False,
+                       cmh_stepdown=False, label_budget_bytes=8 << 30):
         """The Westfall-Young results of the step ``res`` (an associate() result of these genes and traits), composed
         in this one place: dict with minp float64 [T, P], r_fwer int32 [T, G] (``fwer``) and r_fwer_sd int32 [T, G]
         (``stepdown``).  The step-down pass yields the single-step minima as well, so with ``stepdown``
@@ -813,18 +926,37 @@ class AssociationEngine:
         applied to the minima before r_fwer is counted -- dist.all_reduce_min for gene shards, whose minima compose
         by min (the step-down counts do not: minp_stepdown()).  r_fwer is counted on res["p"] as the step produced
         it, k_fisher's own bits: call this before fisher_scipy() rewrites their last ulp.  ``table_budget_bytes``,
-        ``plan`` and ``strata`` as in minp()."""
+        ``label_budget_bytes``, ``plan`` and ``strata`` as in minp().
+        ``cmh_fwer`` / ``cmh_stepdown`` (spec S11; ``res`` is a step with cmh=True and ``strata`` its plan): the same
+        two passes over the tables of the CMH statistic -- minu float64 [T, P], r_cmh_fwer and r_cmh_fwer_sd int32
+        [T, G], counted on u_obs (every gene's own table entry at its pooled count).  The Fisher results are those
+        of the call without them, and the reverse."""
+        kw = dict(res=res, table_budget_bytes=table_budget_bytes, label_budget_bytes=label_budget_bytes, plan=plan,
+                  strata=strata)
         out = {}
-        if stepdown:
-            out["r_fwer_sd"], minp = self.minp_stepdown(genes, traits, masks, permutations, seed, res=res,
-                                                        table_budget_bytes=table_budget_bytes, plan=plan,
-                                                        strata=strata)
-        else:
-            minp = self.minp(genes, traits, masks, permutations, seed, res=res,
-                             table_budget_bytes=table_budget_bytes, plan=plan, strata=strata)
-        out["minp"] = minp if reduce is None else reduce(minp)
-        if fwer:
-            out["r_fwer"] = self.r_fwer(out["minp"], res["p"])
+        if fwer or stepdown or not (cmh_fwer or cmh_stepdown):
+            if stepdown:
+                out["r_fwer_sd"], minp = self.minp_stepdown(genes, traits, masks, permutations, seed, **kw)
+            else:
+                minp = self.minp(genes, traits, masks, permutations, seed, **kw)
+            out["minp"] = minp if reduce is None else reduce(minp)
+            if fwer:
+                out["r_fwer"] = self.r_fwer(out["minp"], res["p"])
+        if cmh_fwer or cmh_stepdown:
+            if strata is None or "cmh_e2" not in res:
+                raise ValueError("cmh_fwer / cmh_stepdown need the result of a step with cmh=True and its strata")
+            source = self.cmh_source(genes, masks, strata,
+                                     {"e2": res["cmh_e2"], "var": res["cmh_var"], "a": res["cmh_a"]})
+            u_obs = self._empty(tuple(res["cmh_a"].shape), _torch().float64)
+            if cmh_stepdown:
+                out["r_cmh_fwer_sd"], out["minu"] = self.minp_stepdown(genes, traits, masks, permutations, seed,
+                                                                       source=source, observed_out=u_obs, **kw)
+            else:
+                out["minu"] = self.minp(genes, traits, masks, permutations, seed, source=source,
+                                        observed_out=u_obs, **kw)
+            out["u_obs"] = u_obs
+            if cmh_fwer:
+                out["r_cmh_fwer"] = self.r_fwer(out["minu"], u_obs)
         return out
 
     # -- Westfall-Young step-down minP (spec S8) ----------------------------------
@@ -865,7 +997,7 @@ class AssociationEngine:
         return c
 
     def minp_stepdown(self, genes, traits, masks, permutations, seed=0, res=None, table_budget_bytes=8 << 30,
-                      label_budget_bytes=8 << 30, plan=None, strata=None):
+                      label_budget_bytes=8 << 30, plan=None, strata=None, source=None, observed_out=None):
         """Westfall-Young step-down minP (spec S8): (r_sd int32 [T, G], minp float64 [T, permutations]).  Per
         trait the genes are ranked by (p, gene index) -- one stable device sort of the association step's own p --
         and the gene at rank k is compared, per permuted labelling, with the smallest permuted p over the genes at
@@ -875,24 +1007,31 @@ class AssociationEngine:
         for bit (the same pass produces it).  ``res``, the budgets and ``plan`` as in minp(): the same trait groups,
         label batches and genes.minp_cache; the result depends on none of them.
         On a GENE SHARD this is the step-down within that shard; shards do NOT compose (the successive minimum at
-        a global rank mixes the genes of all shards): run it on the whole matrix.  ``strata`` as in minp()."""
+        a global rank mixes the genes of all shards): run it on the whole matrix.  ``strata`` as in minp().
+        ``source``: a TableSource -- its tables and observed values take the place of Fisher's p tables and the
+        step's p (cmh_source: spec S11, S8 word for word over u); ``observed_out`` as in minp()."""
         torch = _torch()
         counts, margins = self._minp_inputs(genes, traits, masks, res, plan)
-        if res is not None:
-            p = res["p"]
-        else:
-            p = self.fisher(counts.reshape(-1, 4), want_crit=False)[0].view(counts.shape[0], counts.shape[1])
+        if source is None:
+            source = self.fisher_source(counts, res["p"] if res is not None else None)
         T, G, P = int(counts.shape[0]), genes.G, int(permutations)
-        ps, order = torch.sort(p.contiguous(), dim=1, stable=True)          # ascending (p, gene index)
-        ps, order32 = ps.contiguous(), order.to(torch.int32).contiguous()
+        ps = self._empty((T, G), torch.float64)
+        order32 = self._empty((T, G), torch.int32)
         c = torch.zeros((T, G), dtype=torch.int32, device=self.device)
         minp = torch.ones((T, P), dtype=torch.float64, device=self.device)
+
+        keep = self._keep_observed(observed_out)
+
+        def begin(t0, t1, observed):                                        # ascending (observed value, gene index)
+            ps[t0:t1], order32[t0:t1] = torch.sort(observed.contiguous(), dim=1, stable=True)
+            if keep is not None:
+                keep(t0, t1, observed)
 
         def launch(t0, t1, tables, perms, nb, done):
             self.permute_stepdown(genes, perms, tables, order32[t0:t1], ps[t0:t1], c[t0:t1], minp=minp[t0:t1], P=nb,
                                   perm_base=done)
         self._minp_batches(genes, masks, counts, margins, 0, P, seed, table_budget_bytes, label_budget_bytes, plan,
-                           launch, strata=strata)
+                           launch, source, strata=strata, begin=begin)
         # steps 4 and 5: every tie group takes the count of its first position, then the running maximum
         pos = torch.arange(G, device=self.device).expand(T, G)
         first = torch.ones((T, G), dtype=torch.bool, device=self.device)
@@ -900,7 +1039,7 @@ class AssociationEngine:
         head = torch.cummax(torch.where(first, pos, torch.zeros_like(pos)), dim=1).values
         r_rank = torch.cummax(c.gather(1, head), dim=1).values
         r_sd = torch.empty_like(c)
-        r_sd.scatter_(1, order, r_rank)
+        r_sd.scatter_(1, order32.to(torch.int64), r_rank)
         return r_sd, minp
 
     def perm_batch(self, T, N, P, budget_bytes=8 << 30):
@@ -997,7 +1136,8 @@ class AssociationEngine:
 
     def associate(self, genes, traits, masks, permutations=0, seed=0, perm_buffer=None,
                   use_lists=None, workspace=None, plan=None, graph=None, records=None, fwer=False,
-                  table_budget_bytes=8 << 30, stepdown=False, strata=None, cmh=False):
+                  table_budget_bytes=8 << 30, stepdown=False, strata=None, cmh=False, cmh_fwer=False,
+                  cmh_stepdown=False):
         """counts -> Fisher -> (optional) permutation exceedance counts.  Returns a dict of device tensors:
         counts [T, G, 4], margins [T, 2], p / odds [T, G], crit [T, G, 2], r [T, G] (uint32 bits in int32) or None.
         ``workspace``: the result tensors are the workspace's, overwritten by the next step that uses it.
@@ -1012,10 +1152,16 @@ class AssociationEngine:
         strata only (spec S9), for r and for the Westfall-Young results alike.
         ``cmh`` (needs ``strata``, not permutations): the Cochran-Mantel-Haenszel test over the strata (cmh(), spec
         S10) as res["cmh_stat"], ["cmh_p"], ["cmh_odds"], ["cmh_crit"]; with permutations also res["r_cmh"] int32
-        [T, G] (uint32 bits) = the permutations whose pooled count lies in cmh_crit, counted on the same labels as r.
+        [T, G] (uint32 bits) = the permutations whose pooled count lies in cmh_crit, counted on the same labels as r;
+        cmh_e2, cmh_var and cmh_a are cmh()'s e2, var and a.
+        ``cmh_fwer`` / ``cmh_stepdown`` (need ``cmh`` and permutations; spec S11): the Westfall-Young passes over the
+        CMH statistic -- res["minu"] float64 [T, P], res["u_obs"] float64 [T, G] and res["r_cmh_fwer"] /
+        res["r_cmh_fwer_sd"] int32 [T, G] (westfall_young()).
         Every other result is that of the same call without the option, bit for bit."""
         if (fwer or stepdown) and permutations <= 0:
             raise ValueError("fwer=True / stepdown=True need permutations > 0")
+        if (cmh_fwer or cmh_stepdown) and (permutations <= 0 or not cmh):
+            raise ValueError("cmh_fwer=True / cmh_stepdown=True need cmh=True and permutations > 0")
         if cmh and strata is None:
             raise ValueError("cmh=True needs strata (a StrataPlan of these traits)")
         if strata is not None and (permutations > 0 or cmh):
@@ -1025,9 +1171,10 @@ class AssociationEngine:
         res = self._associate(genes, traits, masks, permutations, seed, perm_buffer, use_lists,
                               workspace, plan, graph if records is None and not (fwer or stepdown or cmh) else False,
                               strata=strata, cmh=cmh)
-        if fwer or stepdown:
+        if fwer or stepdown or cmh_fwer or cmh_stepdown:
             res = {**res, **self.westfall_young(genes, traits, masks, permutations, seed, res, fwer, stepdown,
-                                                table_budget_bytes, plan, strata)}
+                                                table_budget_bytes, plan, strata, cmh_fwer=cmh_fwer,
+                                                cmh_stepdown=cmh_stepdown)}
         if records is not None:
             # the exchange records of the step, packed as its last kernel (inside a captured step:
             # one launch less per replay for a gene-sharded rank)
@@ -1110,7 +1257,8 @@ class AssociationEngine:
         with permutations, the zeroed count r_cmh."""
         torch = _torch()
         c = self.cmh(genes, traits, masks, strata)
-        out = {"cmh_stat": c["stat"], "cmh_p": c["p"], "cmh_odds": c["odds"], "cmh_crit": c["crit"]}
+        out = {"cmh_stat": c["stat"], "cmh_p": c["p"], "cmh_odds": c["odds"], "cmh_crit": c["crit"],
+               "cmh_e2": c["e2"], "cmh_var": c["var"], "cmh_a": c["a"]}
         if permutations > 0:
             out["r_cmh"] = torch.zeros((traits.shape[0], genes.G), dtype=torch.int32, device=self.device)
         return out

@@ -780,20 +780,28 @@ OPTIONAL_COLUMNS = (
     ("CMH_p", "cmh_p", False),
     ("CMH_odds_ratio", "cmh_odds", False),
     ("CMH_empirical_p", "r_cmh", True),
+    ("CMH_Westfall_Young_p", "r_cmh_fwer", True),
+    ("CMH_Westfall_Young_stepdown_p", "r_cmh_fwer_sd", True),
 )
 
 # The rules of the flags behind them, in the order they are checked: (flag, Setup_results keyword, the sentence
 # after "needs --no_pairwise", needs --permute >= 10, excludes --permute-early-abort, why it needs a single rank
-# or None).
+# or None, needs --cmh FILE).
 FLAG_RULES = (
     ("--permute-fwer", "fwer", "The Westfall-Young minima are taken over the Fisher statistic of every gene",
-     True, True, None),
+     True, True, None, False),
     ("--permute-fwer-stepdown", "fwer_stepdown",
      "The Westfall-Young minima are taken over the Fisher statistic of every gene", True, True,
-     "the successive minima run over all genes in one order; gene shards do not compose"),
+     "the successive minima run over all genes in one order; gene shards do not compose", False),
     ("--cmh", "cmh", "The Cochran-Mantel-Haenszel test is a test of every gene, beside Fisher's", False, True,
-     "its results reach the host beside the gathered records of a single process"),
-    ("--permute-strata", "strata", "The strata restrict the permutations of the Fisher statistic", True, False, None),
+     "its results reach the host beside the gathered records of a single process", False),
+    ("--permute-strata", "strata", "The strata restrict the permutations of the Fisher statistic", True, False, None,
+     False),
+    ("--cmh-fwer", "cmh_fwer", "The Westfall-Young minima are taken over the Cochran-Mantel-Haenszel statistic of "
+     "every gene", True, True, "its results reach the host beside the gathered records of a single process", True),
+    ("--cmh-fwer-stepdown", "cmh_fwer_stepdown", "The Westfall-Young minima are taken over the "
+     "Cochran-Mantel-Haenszel statistic of every gene", True, True,
+     "the successive minima run over all genes in one order; gene shards do not compose", True),
 )
 # a broken rule as the command line reports it / as Setup_results raises it
 RULE_TEXT = {
@@ -803,15 +811,18 @@ RULE_TEXT = {
                      "%(kw)s needs the Fisher-statistic permutations of --no_pairwise (permutations >= 10)"),
     "early_abort": ("Cannot use %(flag)s together with --permute-early-abort. Every gene has to see every "
                     "permutation", "%(kw)s excludes early_abort"),
+    "cmh": ("Cannot use %(flag)s without --cmh FILE. The minima are taken over the statistic of the "
+            "Cochran-Mantel-Haenszel test over the strata of FILE", "%(kw)s needs cmh (and its strata)"),
     "ranks": ("Cannot use %(flag)s under more than one rank: %(why)s", "%(kw)s needs a single process: %(why)s"),
 }
 
 
-def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None):
+def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None, cmh=False):
     """The messages of the rules of one row of FLAG_RULES that a run breaks, in the order they are reported.
     ``files``: the messages of the command line's checks of the flag's own file, which come before the rank rule
-    (() for a flag without one); None: the run is Setup_results' and the messages are its ValueErrors."""
-    flag, kw, sentence, needs_permutations, no_early_abort, one_rank = rule
+    (() for a flag without one); None: the run is Setup_results' and the messages are its ValueErrors.  ``cmh``: the
+    run has --cmh FILE / cmh=True."""
+    flag, kw, sentence, needs_permutations, no_early_abort, one_rank, needs_cmh = rule
 
     def text(what, why=None):
         return RULE_TEXT[what][files is None] % {"flag": flag, "kw": kw, "why": why}
@@ -821,6 +832,8 @@ def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None):
         yield text("permutations")
     if no_early_abort and early_abort:
         yield text("early_abort")
+    if needs_cmh and not cmh:
+        yield text("cmh")
     yield from files or ()
     if one_rank:
         from . import dist
@@ -829,7 +842,7 @@ def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None):
 
 
 def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, fwer=False,
-               fwer_stepdown=False, strata=None, cmh=False):
+               fwer_stepdown=False, strata=None, cmh=False, cmh_fwer=False, cmh_fwer_stepdown=False):
     """Whole hot path for all traits; under torchrun (world > 1) every rank
     takes a stride gene shard (dist.GenePartition: the reference's domains,
     scoary/methods.py:1076-1078) and the per-gene records are all-gathered
@@ -845,6 +858,8 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
     the labels within the strata only (spec S9); every rank generates the same labels.
     ``cmh`` (needs ``strata``; single process, no early abort): the Cochran-Mantel-Haenszel test over the strata
     (spec S10): out["cmh_p"], out["cmh_odds"] [T, G] and, with permutations, out["r_cmh"].
+    ``cmh_fwer`` / ``cmh_fwer_stepdown`` (need ``cmh`` and permutations): the Westfall-Young passes over the CMH
+    statistic (spec S11): out["r_cmh_fwer"] / out["r_cmh_fwer_sd"] [T, G].
     How each of these arrays reaches the host: OPTIONAL_COLUMNS."""
     import torch
     from . import dist
@@ -921,6 +936,12 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
                 # before the SciPy-digits pass rewrites the last ulp of p (westfall_young)
                 beside.update(eng.westfall_young(gm, trv, mkv, permutations, seed, res, fwer, fwer_stepdown,
                                                  strata=sp, reduce=dist.all_reduce_min))
+                torch.cuda.synchronize(eng.device)
+        if cmh_fwer or cmh_fwer_stepdown:
+            with _stage("Westfall-Young minP of the CMH statistic (tables, %s)"
+                        % ("k_stepdown_minp" if cmh_fwer_stepdown else "k_permute_minp")):
+                beside.update(eng.westfall_young(gm, trv, mkv, permutations, seed, res, strata=sp, cmh_fwer=cmh_fwer,
+                                                 cmh_stepdown=cmh_fwer_stepdown))
                 torch.cuda.synchronize(eng.device)
         scipy_digits(res)
         with _stage("kernels (counts, Fisher, permutations)"):
@@ -1004,7 +1025,8 @@ def _usable_cpus():
 
 
 def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEED,
-                  early_abort=False, fwer=False, fwer_stepdown=False, strata=None, cmh=False):
+                  early_abort=False, fwer=False, fwer_stepdown=False, strata=None, cmh=False, cmh_fwer=False,
+                  cmh_fwer_stepdown=False):
     """Counts, Fisher's exact test and B/BH correction for every trait x gene
     (methods.py:757-928).  ``permutations`` >= 10 additionally attaches the
     Fisher-statistic ``Empirical_p`` (= (r+1)/(P+1), methods.py:1365) to every
@@ -1016,20 +1038,24 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
     changes the values of Empirical_p and of the Westfall-Young columns and nothing else.  ``cmh`` (needs
     ``strata``, not permutations; one process, no early abort): also ``CMH_p`` and ``CMH_odds_ratio``, the
     Cochran-Mantel-Haenszel test and the Mantel-Haenszel common odds ratio over the strata (spec S10), and with
-    permutations ``CMH_empirical_p`` = (r_cmh+1)/(P+1), the exact permutation p of that statistic."""
+    permutations ``CMH_empirical_p`` = (r_cmh+1)/(P+1), the exact permutation p of that statistic.
+    ``cmh_fwer`` / ``cmh_fwer_stepdown`` (with ``cmh`` and permutations): also ``CMH_Westfall_Young_p`` =
+    (r_cmh_fwer+1)/(P+1) and ``CMH_Westfall_Young_stepdown_p`` = (r_cmh_fwer_sd+1)/(P+1), the single-step and
+    step-down family-wise adjusted p of the CMH statistic under the within-stratum shuffles (spec S11)."""
     if cmh and strata is None:
         raise ValueError("cmh needs strata")
     # (permutations are 0 here whenever the run is not --no_pairwise; with cmh the strata are its own)
-    active = {"fwer": fwer, "fwer_stepdown": fwer_stepdown, "cmh": cmh, "strata": strata is not None and not cmh}
+    active = {"fwer": fwer, "fwer_stepdown": fwer_stepdown, "cmh": cmh, "strata": strata is not None and not cmh,
+              "cmh_fwer": cmh_fwer, "cmh_fwer_stepdown": cmh_fwer_stepdown}
     for rule in (rule for rule in FLAG_RULES if active[rule[1]]):
-        for text in _broken_rules(rule, True, permutations, early_abort):
+        for text in _broken_rules(rule, True, permutations, early_abort, cmh=cmh):
             raise ValueError(text)
     table = _as_table(genedic)
     names, tarr = _trait_arrays(traitsdic, table.strains)
     if strata is not None and len(strata) != len(table.strains):
         raise ValueError("strata: one stratum index per isolate of the gene table")
     dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, fwer, fwer_stepdown,
-                     strata=strata, cmh=cmh)
+                     strata=strata, cmh=cmh, cmh_fwer=cmh_fwer, cmh_fwer_stepdown=cmh_fwer_stepdown)
     collapse_hashes = None
     if collapse:
         eng = get_engine()
@@ -1681,6 +1707,16 @@ def ScoaryArgumentParser(argv=None):
                    "ratio), the association inside the strata instead of across them. With --permute also "
                    "CMH_empirical_p, the exact permutation p of the CMH statistic, and every permutation then "
                    "shuffles the labels within these strata (single process; scoary_amd extension)")
+    a.add_argument("--cmh-fwer", dest="cmh_fwer", action="store_true", default=False,
+                   help="With --no_pairwise --cmh FILE --permute: add the column CMH_Westfall_Young_p, the single-step "
+                   "family-wise adjusted p of the CMH statistic -- (1 + number of within-stratum permutations whose "
+                   "largest CMH statistic over all genes is >= the gene's own) / (permutations + 1) (single process; "
+                   "scoary_amd extension)")
+    a.add_argument("--cmh-fwer-stepdown", dest="cmh_fwer_stepdown", action="store_true", default=False,
+                   help="With --no_pairwise --cmh FILE --permute: add the column CMH_Westfall_Young_stepdown_p, the "
+                   "step-down family-wise adjusted p of the CMH statistic -- every gene is compared, per permutation, "
+                   "with the largest CMH statistic over the genes ranked at or behind it only; never above "
+                   "CMH_Westfall_Young_p (single process; scoary_amd extension)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1853,7 +1889,8 @@ def main(**kwargs):
                             early_abort=getattr(args, "permute_early_abort", False),
                             fwer=getattr(args, "permute_fwer", False),
                             fwer_stepdown=getattr(args, "permute_fwer_stepdown", False), strata=strata,
-                            cmh=bool(getattr(args, "cmh", None)))
+                            cmh=bool(getattr(args, "cmh", None)), cmh_fwer=getattr(args, "cmh_fwer", False),
+                            cmh_fwer_stepdown=getattr(args, "cmh_fwer_stepdown", False))
         t_stats = _time.time()
         if args.upgma_tree and rank == 0:
             # (with --no_pairwise there is no tree and the reference writes str(None) + ";", :277-280, :741-751)
@@ -1993,7 +2030,8 @@ def _validate(args, cutoffs):
         if value:
             files = _strata_file_problems(args, rule[0], value) if isinstance(value, str) else ()
             for text in _broken_rules(rule, args.no_pairwise, args.permute,
-                                      getattr(args, "permute_early_abort", False), files):
+                                      getattr(args, "permute_early_abort", False), files,
+                                      cmh=bool(getattr(args, "cmh", None))):
                 sys.exit(text)
     strata_flag = "--permute-strata" if getattr(args, "permute_strata", None) else "--cmh"
     strata_path = getattr(args, "permute_strata", None) or getattr(args, "cmh", None)

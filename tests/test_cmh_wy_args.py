@@ -1,0 +1,154 @@
+"""--cmh-fwer / --cmh-fwer-stepdown: the argument checks on the command line (they exit before the engine is touched)
+and in Setup_results (the same rules as ValueErrors), the place of the two columns, and the declaration of the two
+entry points (additive: the ABI version stays 11)."""
+import os
+import re
+import sys
+
+import pytest
+
+FLAGS = (("--cmh-fwer", "cmh_fwer"), ("--cmh-fwer-stepdown", "cmh_fwer_stepdown"))
+
+
+def _strata_file(exampledir, tmp_path):
+    with open(os.path.join(exampledir, "Gene_presence_absence.csv")) as f:
+        strains = f.readline().rstrip("\n").split(",")[14:]
+    path = os.path.join(str(tmp_path), "strata.csv")
+    with open(path, "w") as f:
+        f.write("Isolate,Stratum\n" + "".join("%s,L%d\n" % (s, i % 3) for i, s in enumerate(strains)))
+    return path
+
+
+def _run(argv, exampledir, tmp_path, monkeypatch):
+    from scoary_amd import methods as m
+
+    def no_engine():
+        raise AssertionError("the engine was started before the arguments were refused")
+    monkeypatch.setattr(m, "get_engine", no_engine)
+    monkeypatch.setenv("SCOARY_OVERLAP_STARTUP", "0")
+    out = os.path.join(str(tmp_path), "out")
+    monkeypatch.setattr(sys, "argv", ["scoary", "-g", os.path.join(exampledir, "Gene_presence_absence.csv"),
+                                      "-t", os.path.join(exampledir, "Tetracycline_resistance.csv"),
+                                      "-o", out, "--no-time"] + argv)
+    with pytest.raises(SystemExit) as e:
+        m.main()
+    assert not [f for f in os.listdir(out) if f.endswith(".results.csv")]
+    assert isinstance(e.value.code, str), e.value.code
+    return e.value.code
+
+
+@pytest.mark.parametrize("flag,kw", FLAGS)
+def test_command_line_refusals(exampledir, tmp_path, monkeypatch, flag, kw):
+    path = _strata_file(exampledir, tmp_path)
+    run = lambda argv: _run(argv, exampledir, tmp_path, monkeypatch)          # noqa: E731
+    from scoary_amd import methods as m
+    rule = [r for r in m.FLAG_RULES if r[0] == flag][0]
+    no_pairwise = ("Cannot use %s without --no_pairwise. The Westfall-Young minima are taken over the "
+                   "Cochran-Mantel-Haenszel statistic of every gene" % flag)
+    early_abort = ("Cannot use %s together with --permute-early-abort. Every gene has to see every permutation"
+                   % flag)
+    assert run([flag, "-e", "100"]) == no_pairwise
+    # (with --cmh FILE in the same faulty run, the row of --cmh comes first and reports the same rule of its own)
+    assert run([flag, "--cmh", path, "-e", "100"]).startswith("Cannot use --cmh without --no_pairwise")
+    for argv in (["--no_pairwise", flag, "--cmh", path], ["--no_pairwise", flag, "--cmh", path, "-e", "9"]):
+        code = run(argv)
+        assert code == ("Cannot use %s without performing permutations. Use '--permute X' where X is a number equal "
+                        "to or larger than 10" % flag), code
+    assert run(["--no_pairwise", flag, "-e", "100", "--permute-early-abort"]) == early_abort
+    assert run(["--no_pairwise", flag, "--cmh", path, "-e", "100", "--permute-early-abort"]) \
+        .startswith("Cannot use --cmh together with --permute-early-abort")
+    assert list(m._broken_rules(rule, False, 100, True, (), cmh=True)) == [no_pairwise, early_abort]
+    for argv in (["--no_pairwise", flag, "-e", "100"], ["--no_pairwise", flag, "-e", "100", "--permute-strata", path]):
+        code = run(argv)
+        assert code == ("Cannot use %s without --cmh FILE. The minima are taken over the statistic of the "
+                        "Cochran-Mantel-Haenszel test over the strata of FILE" % flag), code
+
+
+@pytest.mark.parametrize("flag,kw", FLAGS)
+def test_rank_rule(exampledir, tmp_path, monkeypatch, flag, kw):
+    from scoary_amd import dist
+    path = _strata_file(exampledir, tmp_path)
+    monkeypatch.setattr(dist, "world_rank", lambda: (2, 0))
+    code = _run(["--no_pairwise", flag, "--cmh", path, "-e", "100"], exampledir, tmp_path, monkeypatch)
+    # --cmh's own rank rule is met first (its row comes first); alone, the new flag's rule has the row's reason
+    assert code.startswith("Cannot use --cmh under more than one rank"), code
+    from scoary_amd import methods as m
+    rule = [r for r in m.FLAG_RULES if r[0] == flag][0]
+    why = {"--cmh-fwer": [r for r in m.FLAG_RULES if r[0] == "--cmh"][0][5],
+           "--cmh-fwer-stepdown": [r for r in m.FLAG_RULES if r[0] == "--permute-fwer-stepdown"][0][5]}[flag]
+    assert why and list(m._broken_rules(rule, True, 100, False, (), cmh=True)) == \
+        ["Cannot use %s under more than one rank: %s" % (flag, why)]
+    assert list(m._broken_rules(rule, True, 100, False, None, cmh=True)) == \
+        ["%s needs a single process: %s" % (kw, why)]
+
+
+@pytest.mark.parametrize("flag,kw", FLAGS)
+def test_setup_results_raises_the_same_rules(flag, kw):
+    from scoary_amd import methods as m
+    with pytest.raises(ValueError, match="%s needs the Fisher-statistic permutations of --no_pairwise "
+                                         r"\(permutations >= 10\)" % kw):
+        m.Setup_results({}, {}, False, strata=[0, 1], cmh=True, **{kw: True})
+    with pytest.raises(ValueError, match="%s excludes early_abort" % kw):
+        m.Setup_results({}, {}, False, permutations=100, early_abort=True, strata=[0, 1], **{kw: True})
+    with pytest.raises(ValueError, match=r"%s needs cmh \(and its strata\)" % kw):
+        m.Setup_results({}, {}, False, permutations=100, **{kw: True})
+    with pytest.raises(ValueError, match=r"%s needs cmh \(and its strata\)" % kw):
+        m.Setup_results({}, {}, False, permutations=100, strata=[0, 1], **{kw: True})
+
+
+def test_flags_are_off_by_default_and_may_all_be_combined():
+    from scoary_amd import methods as m
+    args, _cut = m.ScoaryArgumentParser(["-g", "g.csv", "-t", "t.csv"])
+    assert args.cmh_fwer is False and args.cmh_fwer_stepdown is False
+    args, _cut = m.ScoaryArgumentParser(["-g", "g.csv", "-t", "t.csv", "--cmh", "s.csv", "--cmh-fwer",
+                                         "--cmh-fwer-stepdown", "--permute-fwer", "--permute-fwer-stepdown"])
+    assert args.cmh_fwer and args.cmh_fwer_stepdown and args.permute_fwer and args.permute_fwer_stepdown
+    for rule in m.FLAG_RULES:                                   # none of the four excludes another
+        assert list(m._broken_rules(rule, True, 100, False, (), cmh=True)) == []
+
+
+def test_columns_and_rules_are_in_their_places():
+    from scoary_amd import methods as m
+    names = [name for name, _key, _count in m.OPTIONAL_COLUMNS]
+    at = names.index("CMH_empirical_p")
+    assert names[at + 1:at + 3] == ["CMH_Westfall_Young_p", "CMH_Westfall_Young_stepdown_p"]
+    assert m.OPTIONAL_COLUMNS[at + 1][1:] == ("r_cmh_fwer", True) and m.OPTIONAL_COLUMNS[at + 2][1:] == \
+        ("r_cmh_fwer_sd", True)
+    assert names[:at + 1] == ["Westfall_Young_p", "Westfall_Young_stepdown_p", "CMH_p", "CMH_odds_ratio",
+                              "CMH_empirical_p"]
+    rules = {r[0]: r for r in m.FLAG_RULES}
+    for flag, kw in FLAGS:
+        _flag, key, _sentence, needs_permutations, no_early_abort, one_rank, needs_cmh = rules[flag]
+        assert (key, needs_permutations, no_early_abort, needs_cmh) == (kw, True, True, True) and one_rank
+    assert rules["--cmh-fwer"][5] == rules["--cmh"][5]
+    assert rules["--cmh-fwer-stepdown"][5] == rules["--permute-fwer-stepdown"][5]
+    assert not any(r[6] for f, r in rules.items() if f not in dict(FLAGS))
+
+
+def test_entry_points_are_declared():
+    from scoary_amd import _abi
+    assert _abi.ABI_VERSION == 11
+    header = open(_abi.HEADER_PATH).read()
+    assert re.search(r"#define SCOARY_ABI_VERSION 11\b", header)
+    for name in ("scoary_cmh_minp_plan", "scoary_cmh_minp_fill"):
+        assert name in _abi.SIGNATURES
+        m = re.search(r"\b%s\(([^;]*)\);" % name, header)
+        assert m, name
+        nargs = len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"])
+        assert nargs == len(_abi.SIGNATURES[name][1]), name
+
+
+def test_table_kernels_compiled_without_scratch_or_spills_and_k_cmh_is_one_kernel_still():
+    import json
+    import __graft_entry__ as ge
+    if not os.path.exists(ge.HIP_RESOURCES):
+        ge.build()
+    with open(ge.HIP_RESOURCES) as f:
+        res = json.load(f)
+    for name in ("k_cmh_support", "k_cmh_fill"):
+        hit = [v for k, v in res.items() if name in k]
+        assert len(hit) == 1, name
+        assert hit[0]["ScratchSize"] == 0 and hit[0]["VGPRs Spill"] == 0 and hit[0]["SGPRs Spill"] == 0
+    assert len([k for k in res if re.search(r"\d+k_cmhE", k)]) == 1
+    assert {rule["name"] for rule in ge.CMH_RULES} == {"k_cmhE", "k_cmh_support", "k_cmh_fill"}
+    ge.check_kernel_resources(res, ge.RESOURCE_RULES + ge.CMH_RULES)

@@ -419,6 +419,37 @@ int scoary_cmh_minp_plan(scoary_handle h, const uint32_t *d_tiled, const uint32_
 int scoary_cmh_minp_fill(scoary_handle h, const double *d_e2, const double *d_var, const int64_t *d_off,
                          const int32_t *d_lo, int64_t T, int64_t G, int64_t entries, double *d_tab,
                          scoary_stream_t stream);
+/* ---- Exact conditional test over the strata (spec S12 of DESIGN.md; additive, ABI 11) ---------------------
+ * Under within-stratum shuffles (S9) every stratum's margins are fixed and its count is hypergeometric, so the
+ * pooled count a' = popc(gene & label) of a (trait, gene) is distributed as the CONVOLUTION of the strata's
+ * hypergeometrics.  k_cmh_exact builds that pmf f on the support [lo, hi] of scoary_cmh_minp_plan, in fp64 (every
+ * stratum's pmf by the ratio recurrence outward from its mode and normalised to sum 1, strata in ascending order,
+ * strata with n_s = 0 skipped; the summation order inside a convolution is the kernel's, so the results are held
+ * to a tolerance -- 1e-12 absolute and relative -- not to the bit), and from it
+ *   p(x) = min(1, sum{f(y) : f(y) <= (1 + 1e-7) f(x)} / sum f)    for every x of [lo, hi]
+ * -- the two-sided exact conditional p under the probability-ordering rule with the relErr of R's fisher.test and
+ * mantelhaen.test(exact = TRUE); with one stratum Fisher's exact test.
+ *   d_a / d_crit : scoary_cmh's, int32 [T][G] and uint32 [T][G][2]
+ *   d_off / d_lo / entries : scoary_cmh_minp_plan's (the rows are taken in its CSR order)
+ *   d_p        : double [T][G] or NULL, p(d_a[t][g]) -- the gene's own table entry (read back from d_tab when there
+ *                is one), so an observed and a permuted gene at the same count tie exactly
+ *   d_p_region : double [T][G] or NULL, sum{f(x) : (uint32)(x - base) >= span} / sum f with (base, span) = d_crit,
+ *                at most 1 and 1 for the region (0, 0): the exact mass of S10's rejection region, what
+ *                (r_cmh + 1) / (P + 1) estimates
+ *   d_tab      : double [entries] or NULL, p(x) at d_off[t G + g] + x - lo: the layout scoary_permute_minp /
+ *                scoary_permute_stepdown gather from (smaller is more extreme, 1.0 the identity of the minimum)
+ *   (not all three NULL.)  A support of one entry gives p = p_region = 1 and the table entry 1.0; below 1e-290 the
+ *   tails may underflow and any value in [0, 1e-290] stands for the true one.
+ *   d_scratch  : scoary_cmh_scratch_bytes(N) bytes (the segment table, rebuilt here)
+ * Asynchronous on `stream`, allocates nothing; entries may exceed 2^31.  Limits: those of the strata plan, T <=
+ * 65535, G <= 2^30 and N <= 8190, which scoary_cmh_exact_max_isolates reports (a support of at most 4096 entries:
+ * the pmf of a gene is held in LDS) -- SCOARY_ERR_SIZE with a message, never a partial result. */
+int64_t scoary_cmh_exact_max_isolates(void);
+int scoary_cmh_exact(scoary_handle h, const uint32_t *d_tiled, const uint32_t *d_masks, const uint16_t *d_strata,
+                     const int32_t *d_members, const int32_t *d_offsets, const int32_t *d_smargins, int64_t G,
+                     int64_t T, int64_t N, int64_t S, const int32_t *d_a, const uint32_t *d_crit,
+                     const int64_t *d_off, const int32_t *d_lo, int64_t entries, double *d_p, double *d_p_region,
+                     double *d_tab, void *d_scratch, scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

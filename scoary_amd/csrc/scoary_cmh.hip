@@ -35,11 +35,6 @@ constexpr int kCmhThreads = 256;     // = kGeneAlign: a block is 256 consecutive
 constexpr int kSegThreads = 1024;
 constexpr double kCmhTau = 1e-6;     // S10: the tie tolerance of the region, above the fp64 error of E2
 
-struct CmhSegments {                 // the layout of d_scratch
-  uint32_t count, pad[3];
-  uint2 seg[1];                      // [count] = ((stratum << 16) | word, mask)
-};
-
 // the isolate at position j of the members array and its segment key; every index clamped (a bad plan gives
 // wrong counts, never a wild access)
 __device__ __forceinline__ uint32_t seg_key(const int32_t* __restrict__ members, const uint16_t* __restrict__ strata,
@@ -294,6 +289,15 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh_fill(const double* __restri
 }
 
 }  // namespace
+
+int scoary_cmh_segments_launch(scoary_handle h, hipStream_t s, const uint16_t* d_strata, const int32_t* d_members,
+                               int64_t N, int64_t S, void* d_scratch) {
+  KernelTimer kt(h, s, "k_cmh_segments");
+  hipLaunchKernelGGL(k_cmh_segments, dim3(1), dim3(kSegThreads), 0, s, d_strata, d_members, (int)N, (int)S,
+                     static_cast<CmhSegments*>(d_scratch));
+  HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
 
 extern "C" {
 

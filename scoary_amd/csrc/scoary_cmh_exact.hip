@@ -1,0 +1,286 @@
+// scoary_cmh_exact.hip -- the exact conditional test over the strata (spec S12 of DESIGN.md): under the S9 null
+// the pooled count of a (trait, gene) is the sum of independent hypergeometrics, one per stratum, so its
+// distribution is their convolution.  From that one pmf: the two-sided p of every count of the support under the
+// probability-ordering rule (R's mantelhaen.test(exact = TRUE); Fisher's exact test when there is one stratum), the
+// observed count's own entry, and the exact mass of S10's rejection region.
+//
+//   k_cmh_exact : one work group of 256 lanes per (trait, gene) row, rows in the CSR order of scoary_cmh_minp_plan.
+//     1. the lanes stride over the segment table of k_cmh_segments, gather the gene's words from the tiled matrix
+//        and add popc(gene & valid & mask) into m[s] in LDS;
+//     2. a lane per stratum (a few strata each): the support sizes, their offsets (a block scan) and the stratum's
+//        pmf by the ratio recurrence outward from the mode, normalised to sum 1 -- all strata at once, side by side
+//        in one LDS buffer of at most N / 2 + S doubles;
+//     3. the running pmf is convolved with one stratum after the other between two LDS buffers, lane = output
+//        index (neighbouring lanes read neighbouring words, the stratum's entry is a broadcast), strata with a
+//        single support point skipped: they only shift the support;
+//     4. prefix sums from the left and suffix sums from the right, and the mode; f is log-concave, so the set
+//        {y : f(y) <= gamma f(x)} is a left tail and a right tail, found by two binary searches: p(x) is two
+//        reads of the sums.  Tails are summed from their small end, so a p of 1e-190 keeps its relative accuracy;
+//     5. the row's run of the table is written with contiguous stores; the observed p is read back from it.
+//   Every index is clamped: a bad plan gives wrong values, never a wild access.  LDS per work group follows N and S
+//   (three buffers of N / 2 + 1 doubles): 25 KB at N = 2000, 115 KB at the limit of 8190 isolates.
+#include "scoary_common.hpp"
+
+namespace {
+
+constexpr int kExactThreads = 256;
+constexpr int kExactMaxIsolates = 8190;               // the support is then at most 4096 entries
+constexpr double kExactGamma = 1.0 + 1e-7;            // S12 step 3: the relErr of R's fisher.test / mantelhaen.test
+constexpr int64_t kExactRows = (int64_t)1 << 30;      // (trait, gene) rows per launch
+
+// the most entries a support can have: every stratum adds at most n_s / 2 to hi - lo
+inline int exact_cap(int64_t N) { return (int)(N / 2 + 1); }
+inline int64_t exact_lds_bytes(int64_t N, int64_t S) {
+  return (3 * (int64_t)exact_cap(N) + S) * (int64_t)sizeof(double) + (2 * S + 1) * (int64_t)sizeof(int32_t);
+}
+
+struct ExactOut {
+  double *p, *p_region, *tab;
+};
+
+// exclusive prefix sum of v over the lanes of the block in the order of `idx` (a permutation of 0 .. 255); every
+// partial sum is a sum of the terms themselves (no subtraction), so sums of positive terms keep their accuracy
+__device__ __forceinline__ double exact_scan(double* s_d, int idx, double v) {
+  s_d[idx] = v;
+  __syncthreads();
+  for (int o = 1; o < kExactThreads; o <<= 1) {
+    const double u = idx >= o ? s_d[idx - o] : 0.0;
+    __syncthreads();
+    s_d[idx] += u;
+    __syncthreads();
+  }
+  const double before = idx > 0 ? s_d[idx - 1] : 0.0;
+  __syncthreads();
+  return before;
+}
+
+__global__ __launch_bounds__(kExactThreads) void k_cmh_exact(
+    const uint32_t* __restrict__ tiled, const uint32_t* __restrict__ masks, const int32_t* __restrict__ smargins,
+    const CmhSegments* __restrict__ segs, const int32_t* __restrict__ a_obs, const uint32_t* __restrict__ crit,
+    const int64_t* __restrict__ off, const int32_t* __restrict__ lo, int64_t G, int64_t Gp, int N, int Wp, int S,
+    int cap, int64_t r0, int64_t entries, ExactOut out) {
+  extern __shared__ double lds[];
+  __shared__ double s_d[kExactThreads];
+  __shared__ int s_i[kExactThreads];
+  double* cur = lds;                                   // [cap] the running pmf
+  double* nxt = lds + cap;                             // [cap]
+  double* fs = lds + 2 * cap;                          // [cap + S] the strata's pmfs side by side
+  uint32_t* m = reinterpret_cast<uint32_t*>(fs + cap + S);   // [S]
+  int* zoff = reinterpret_cast<int*>(m + S);           // [S + 1] offsets of the informative strata's pmfs in fs
+  const int fs_cap = cap + S;
+  const int tid = threadIdx.x;
+  const int64_t row = r0 + blockIdx.x;                 // < T * G: the launches cover the rows exactly
+  const int t = (int)(row / G);
+  const int64_t g = row % G;
+
+  // 1. m[s] = popc(gene & valid & stratum s)
+  for (int s = tid; s < S; s += kExactThreads) m[s] = 0;
+  __syncthreads();
+  const int nseg = min((int)segs->count, N);
+  for (int i = tid; i < nseg; i += kExactThreads) {
+    const uint2 sg = segs->seg[i];
+    const int s = min((int)(sg.x >> 16), S - 1), w = min((int)(sg.x & 0xffffu), Wp - 1);
+    const uint32_t gw = tiled[((int64_t)(w >> 2) * Gp + g) * 4 + (w & 3)];
+    const uint32_t v = gw & sg.y & masks[(int64_t)t * Wp + w];
+    if (v) atomicAdd(&m[s], (uint32_t)__popc(v));
+  }
+  __syncthreads();
+
+  // 2. the strata of this lane: [s0, s1); a stratum is informative when its support has more than one point
+  const int per = (S + kExactThreads - 1) / kExactThreads;
+  const int s0 = min(tid * per, S), s1 = min(s0 + per, S);
+  const int2* __restrict__ kn = reinterpret_cast<const int2*>(smargins) + (int64_t)t * S;
+  auto shape = [&](int s, int& k, int& n, int& mm, int& lo_s) {         // -> the size of the stratum's support
+    const int2 v = kn[s];
+    k = v.x, n = v.y, mm = (int)m[s];
+    if (n <= 0) return 0;
+    lo_s = max(0, k + mm - n);
+    const int z = min(k, mm) - lo_s + 1;
+    return z > 1 ? z : 0;
+  };
+  int mine = 0;
+  for (int s = s0; s < s1; ++s) {
+    int k, n, mm, lo_s;
+    mine += min(shape(s, k, n, mm, lo_s), fs_cap + 1);                 // (no overflow of the sum, whatever the plan)
+  }
+  s_i[tid] = mine;
+  __syncthreads();
+  for (int o = 1; o < kExactThreads; o <<= 1) {                         // inclusive scan of the lanes' sizes
+    const int v = tid >= o ? s_i[tid - o] : 0;
+    __syncthreads();
+    s_i[tid] = min(s_i[tid] + v, 2 * fs_cap);
+    __syncthreads();
+  }
+  int at = s_i[tid] - mine;
+  if (tid == kExactThreads - 1) zoff[S] = s_i[tid];
+  for (int s = s0; s < s1; ++s) {
+    int k, n, mm, lo_s;
+    const int z = min(shape(s, k, n, mm, lo_s), fs_cap + 1);
+    zoff[s] = at;
+    if (z > 1 && at + z <= fs_cap) {
+      // f(x) = C(m, x) C(n - m, k - x) / C(n, k) on [lo_s, lo_s + z): the mode's weight 1, its neighbours by the
+      // ratio f(x + 1) / f(x) = (m - x)(k - x) / ((x + 1)(n - m - k + x + 1)); products of counts are exact
+      double* f = fs + at;
+      const int hi_s = lo_s + z - 1;
+      const int xm = min(max((int)(((int64_t)(mm + 1) * (k + 1)) / (n + 2)), lo_s), hi_s);
+      const int c = n - mm - k;
+      double w = 1.0, sum = 1.0;
+      f[xm - lo_s] = 1.0;
+      for (int x = xm; x < hi_s; ++x) {
+        w = (w * ((double)(mm - x) * (double)(k - x))) / ((double)(x + 1) * (double)(c + x + 1));
+        f[x + 1 - lo_s] = w;
+        sum += w;
+      }
+      w = 1.0;
+      for (int x = xm; x > lo_s; --x) {
+        w = (w * ((double)x * (double)(c + x))) / ((double)(mm - x + 1) * (double)(k - x + 1));
+        f[x - 1 - lo_s] = w;
+        sum += w;
+      }
+      for (int j = 0; j < z; ++j) f[j] = f[j] / sum;
+    }
+    at = min(at + z, 2 * fs_cap);
+  }
+  if (tid == 0) cur[0] = 1.0;
+  __syncthreads();
+
+  // 3. the convolution, strata in ascending order
+  int L = 1;
+  for (int s = 0; s < S; ++s) {
+    const int o = zoff[s], z = zoff[s + 1] - o;                         // block-uniform
+    if (z <= 1) continue;
+    if (o + z > fs_cap || L + z - 1 > cap) break;                       // not with a sound plan
+    const double* __restrict__ f = fs + o;
+    const int Ln = L + z - 1;
+    for (int j = tid; j < Ln; j += kExactThreads) {
+      const int i0 = max(0, j - L + 1), i1 = min(z - 1, j);
+      double acc = 0.0;
+      for (int i = i0; i <= i1; ++i) acc += cur[j - i] * f[i];        // (unrolled 4 or 8 times: 1 to 19 % slower)
+      nxt[j] = acc;
+    }
+    __syncthreads();
+    double* const swap = cur;
+    cur = nxt, nxt = swap;
+    L = Ln;
+  }
+
+  // 4. left[j] = f(0) + ... + f(j), right[j] = f(j) + ... + f(L - 1), and the mode (the first largest entry)
+  double* left = nxt;
+  double* right = fs;
+  const int chunk = (L + kExactThreads - 1) / kExactThreads;
+  const int c0 = min(tid * chunk, L), c1 = min(c0 + chunk, L);
+  double sum = 0.0, best = -1.0;
+  int best_at = 0x7fffffff;
+  for (int j = c0; j < c1; ++j) {
+    const double v = cur[j];
+    sum += v;
+    if (v > best) best = v, best_at = j;
+  }
+  double run = exact_scan(s_d, tid, sum);
+  for (int j = c0; j < c1; ++j) left[j] = (run += cur[j]);
+  sum = 0.0;
+  for (int j = c1 - 1; j >= c0; --j) sum += cur[j];
+  run = exact_scan(s_d, kExactThreads - 1 - tid, sum);
+  for (int j = c1 - 1; j >= c0; --j) right[j] = (run += cur[j]);
+  s_d[tid] = best, s_i[tid] = best_at;
+  __syncthreads();
+  for (int o = kExactThreads / 2; o > 0; o >>= 1) {
+    if (tid < o && (s_d[tid + o] > s_d[tid] || (s_d[tid + o] == s_d[tid] && s_i[tid + o] < s_i[tid])))
+      s_d[tid] = s_d[tid + o], s_i[tid] = s_i[tid + o];
+    __syncthreads();
+  }
+  const int mode = min(max(s_i[0], 0), L - 1);
+  const double total = left[L - 1];
+
+  // S12 step 3 at the count lo + x: the entries up to gamma f(x) are [0, nl) and [rb, L)
+  auto p_at = [&](int x) {
+    const double thr = kExactGamma * cur[x];
+    int a = 0, b = mode;                                  // nl: the first entry of [0, mode) above thr (rising side)
+    while (a < b) {
+      const int c = (a + b) >> 1;
+      if (cur[c] <= thr) a = c + 1; else b = c;
+    }
+    const int nl = a;
+    a = mode, b = L;                                      // rb: the first entry of [mode, L) not above thr (falling side)
+    while (a < b) {
+      const int c = (a + b) >> 1;
+      if (cur[c] <= thr) b = c; else a = c + 1;
+    }
+    const int rb = a;
+    if (nl >= rb) return 1.0;                             // the whole support: x is a mode
+    const double tails = (nl > 0 ? left[nl - 1] : 0.0) + (rb < L ? right[rb] : 0.0);
+    return fmin(1.0, tails / total);
+  };
+
+  // 5. the row's run of the table, the observed count's entry and the mass of the region
+  const int64_t o0 = min(max(off[row], (int64_t)0), entries), o1 = min(max(off[row + 1], o0), entries);
+  const int64_t ntab = out.tab ? o1 - o0 : 0;
+  for (int64_t x = tid; x < ntab; x += kExactThreads) out.tab[o0 + x] = x < L ? p_at((int)x) : 1.0;
+  const int64_t lo_row = lo[row];
+  if (out.p) {
+    const int xa = (int)min(max((int64_t)a_obs[row] - lo_row, (int64_t)0), (int64_t)(L - 1));
+    if (tid == (xa & (kExactThreads - 1))) out.p[row] = xa < ntab ? out.tab[o0 + xa] : p_at(xa);   // this lane's own store
+  }
+  if (out.p_region && tid == 0) {
+    const uint2 br = reinterpret_cast<const uint2*>(crit)[row];
+    double pr = 1.0;                                      // the region (0, 0): every count
+    if (br.y != 0) {
+      const int nl = (int)min(max((int64_t)br.x - lo_row, (int64_t)0), (int64_t)L);
+      const int rb = (int)min(max((int64_t)br.x + (int64_t)br.y - lo_row, (int64_t)nl), (int64_t)L);
+      const double tails = (nl > 0 ? left[nl - 1] : 0.0) + (rb < L ? right[rb] : 0.0);
+      pr = fmin(1.0, tails / total);
+    }
+    out.p_region[row] = pr;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t scoary_cmh_exact_max_isolates(void) { return kExactMaxIsolates; }
+
+int scoary_cmh_exact(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d_masks, const uint16_t* d_strata,
+                     const int32_t* d_members, const int32_t* d_offsets, const int32_t* d_smargins, int64_t G,
+                     int64_t T, int64_t N, int64_t S, const int32_t* d_a, const uint32_t* d_crit,
+                     const int64_t* d_off, const int32_t* d_lo, int64_t entries, double* d_p, double* d_p_region,
+                     double* d_tab, void* d_scratch, scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (!d_tiled || !d_masks || !d_strata || !d_members || !d_offsets || !d_smargins || !d_a || !d_crit || !d_off ||
+      !d_lo || !d_scratch || (!d_p && !d_p_region && !d_tab) || G < 1 || T < 1 || N < 1 || S < 1 || entries < T * G)
+    return fail(h, SCOARY_ERR_ARG, "scoary_cmh_exact: bad argument");
+  if (T > 65535 || G > (int64_t)1 << 30)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: T > 65535 or G > 2^30");
+  if (S > scoary_perm_max_strata())
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: more strata than scoary_perm_max_strata()");
+  if (N > scoary_perm_strata_max_isolates())
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: more isolates than scoary_perm_strata_max_isolates()");
+  if (N > kExactMaxIsolates)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: more isolates than scoary_cmh_exact_max_isolates() = " +
+                                        std::to_string(kExactMaxIsolates) + " (the pmf of a gene is held in LDS)");
+  const int64_t lds_bytes = exact_lds_bytes(N, S);
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (lds_bytes > 64 * 1024 && !h->cmh_exact_lds_optin) {
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cmh_exact),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)exact_lds_bytes(kExactMaxIsolates, scoary_perm_max_strata())));
+    h->cmh_exact_lds_optin = 1;
+  }
+  const int rc = scoary_cmh_segments_launch(h, s, d_strata, d_members, N, S, d_scratch);
+  if (rc != SCOARY_OK) return rc;
+  const ExactOut out{d_p, d_p_region, d_tab};
+  const int64_t M = T * G;
+  KernelTimer kt(h, s, "k_cmh_exact");
+  for (int64_t r0 = 0; r0 < M; r0 += kExactRows) {
+    const int64_t nrows = std::min(kExactRows, M - r0);
+    hipLaunchKernelGGL(k_cmh_exact, dim3((unsigned)nrows), dim3(kExactThreads), (size_t)lds_bytes, s, d_tiled,
+                       d_masks, d_smargins, static_cast<const CmhSegments*>(d_scratch), d_a, d_crit, d_off, d_lo, G,
+                       scoary_tiled_genes(G), (int)N, (int)scoary_row_words(N), (int)S, exact_cap(N), r0, entries,
+                       out);
+    HIP_TRY(h, hipGetLastError());
+  }
+  return SCOARY_OK;
+}
+
+}  // extern "C"

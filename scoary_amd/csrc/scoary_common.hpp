@@ -25,6 +25,7 @@ struct scoary_ctx {
   int lists_lds_optin = 0;   // k_permute_lists instances (by tile width) with the 160 KB LDS opt-in done
   int labels_lds_optin = 0;  // k_labels instances with it
   int mfma_lds_optin = 0;    // k_permute_mfma with it
+  int cmh_exact_lds_optin = 0;   // k_cmh_exact with it
   int mfma_route = SCOARY_MFMA_ROUTE_AUTO;   // scoary_set_mfma_route: which list slots take the matrix-core kernel
   uint32_t* scipy_primes = nullptr;  // scoary_fisher_scipy's prime table and reciprocals (device,
   float* scipy_inv = nullptr;        // built on the handle's first call, freed by scoary_destroy)
@@ -46,6 +47,11 @@ MfmaGeom scoary_mfma_geom(int num_cu, int64_t k_split, int64_t T, int64_t P, int
 int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, const void* d_panels, void* d_bfrag,
                        const uint32_t* d_lcrit, uint16_t* d_partial, int64_t k_split, int64_t G, int64_t T,
                        int64_t N, int64_t P, int64_t ntiles, int64_t gs);
+
+// scoary_cmh.hip: the strata plan as the segment table (CmhSegments, below) in d_scratch = scoary_cmh_scratch_bytes(N)
+// bytes; scoary_cmh_exact.hip walks the same table
+int scoary_cmh_segments_launch(scoary_handle h, hipStream_t s, const uint16_t* d_strata, const int32_t* d_members,
+                               int64_t N, int64_t S, void* d_scratch);
 
 namespace {
 
@@ -209,6 +215,11 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   out[2] = c2;
   out[3] = c3;
 }
+
+struct CmhSegments {                 // the layout of scoary_cmh's d_scratch (k_cmh_segments)
+  uint32_t count, pad[3];
+  uint2 seg[1];                      // [count] = ((stratum << 16) | word, mask)
+};
 
 // acc += popcount(x) as ONE v_bcnt_u32_b32 (its second operand is the
 // accumulator).  Opaque to the optimiser on purpose: left to itself LLVM

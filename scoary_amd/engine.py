@@ -735,6 +735,18 @@ class AssociationEngine:
                 tuple(e2.shape) != (T, G) or tuple(var.shape) != (T, G):
             raise ValueError("cmh_tables: validity rows [T, Wp] and cmh()'s e2 / var [T, G] of the same traits, "
                              "contiguous")
+        off, lo, total, _scratch = self._cmh_support(genes, masks, strata)
+        tab = self._empty((total,), torch.float64)
+        self._check(self.lib.scoary_cmh_minp_fill(self.h, self._ptr(e2), self._ptr(var), self._ptr(off),
+                                                  self._ptr(lo), T, G, total, self._ptr(tab), self._stream()),
+                    "scoary_cmh_minp_fill")
+        return MinpTables(off, lo, tab, total)
+
+    def _cmh_support(self, genes, masks, strata):
+        """scoary_cmh_minp_plan for the traits of ``strata``: (off int64 [T G + 1], lo int32 [T, G], the entry count,
+        the scratch buffer of the segment table).  One 8-byte read-back."""
+        torch = _torch()
+        T, G, N = int(masks.shape[0]), genes.G, genes.N
         off = self._empty((T * G + 1,), torch.int64)
         lo = self._empty((T, G), torch.int32)
         scratch = self._empty(((int(self.lib.scoary_cmh_scratch_bytes(N)) + 7) // 8,), torch.int64)
@@ -743,12 +755,57 @@ class AssociationEngine:
             self.h, self._ptr(genes.tiled), self._ptr(masks), *self._strata_ptrs(strata), G, T, N, strata.S,
             self._ptr(scratch), self._ptr(off), self._ptr(lo), ctypes.byref(entries), self._stream()),
             "scoary_cmh_minp_plan")
-        total = int(entries.value)
-        tab = self._empty((total,), torch.float64)
-        self._check(self.lib.scoary_cmh_minp_fill(self.h, self._ptr(e2), self._ptr(var), self._ptr(off),
-                                                  self._ptr(lo), T, G, total, self._ptr(tab), self._stream()),
-                    "scoary_cmh_minp_fill")
-        return MinpTables(off, lo, tab, total)
+        return off, lo, int(entries.value), scratch
+
+    # -- exact conditional test over the strata (spec S12) ----------------------------
+    def cmh_exact_max_isolates(self):
+        """The most isolates cmh_exact() takes (the pmf of a gene is held in LDS)."""
+        return int(self.lib.scoary_cmh_exact_max_isolates())
+
+    def cmh_exact(self, genes, masks, strata, cmh_res, tables=False):
+        """The exact conditional test of every (trait, gene) over the strata of ``strata`` (spec S12;
+        scoary_cmh_exact): the pooled count under within-stratum shuffles is the convolution of the strata's
+        hypergeometrics.  ``masks``: the validity rows [T, Wp] of the traits of ``strata``; ``cmh_res``: cmh()'s
+        result for them (its a and crit are read).  Dict of float64 [T, G] device tensors: p = the two-sided exact
+        p of the observed pooled count (probability ordering; Fisher's exact p when there is one stratum), p_region
+        = the exact mass of cmh()'s rejection region, the limit of (r_cmh + 1) / (P + 1).  ``tables=True`` adds
+        tables = the MinpTables of p over every gene's support (the layout permute_minp / permute_stepdown take);
+        p is then read from them.  One 8-byte read-back (the entry count)."""
+        torch = _torch()
+        T, G, N = int(masks.shape[0]), genes.G, genes.N
+        self._strata_fits(strata, T, N)
+        a, crit = cmh_res["a"], cmh_res["crit"]
+        if not (masks.is_contiguous() and a.is_contiguous() and crit.is_contiguous()) or \
+                tuple(a.shape) != (T, G) or tuple(crit.shape) != (T, G, 2):
+            raise ValueError("cmh_exact: validity rows [T, Wp] and cmh()'s a [T, G] / crit [T, G, 2] of the same "
+                             "traits, contiguous")
+        if N > self.cmh_exact_max_isolates():
+            off = lo = self._empty((1,), torch.int64)       # the library refuses the size before it reads anything
+            total, scratch = T * G, off
+        else:
+            off, lo, total, scratch = self._cmh_support(genes, masks, strata)
+        out = {"p": self._empty((T, G), torch.float64), "p_region": self._empty((T, G), torch.float64)}
+        tab = self._empty((total,), torch.float64) if tables else None
+        self._check(self.lib.scoary_cmh_exact(
+            self.h, self._ptr(genes.tiled), self._ptr(masks), *self._strata_ptrs(strata), G, T, N, strata.S,
+            self._ptr(a), self._ptr(crit), self._ptr(off), self._ptr(lo), total, self._ptr(out["p"]),
+            self._ptr(out["p_region"]), self._ptr(tab) if tables else None, self._ptr(scratch), self._stream()),
+            "scoary_cmh_exact")
+        if tables:
+            out["tables"] = MinpTables(off, lo, tab, total)
+        return out
+
+    def cmh_exact_source(self, genes, masks, strata, cmh_res):
+        """The TableSource of the exact test (spec S12): the tables of cmh_exact() and, as observed values, every
+        gene's own entry at its pooled count (cmh_observed), both per trait group -- minp() and minp_stepdown() then
+        run over exact stratified p-values.  ``cmh_res``: cmh()'s result for all traits (a and crit are read)."""
+        def build(t0, t1):
+            return self.cmh_exact(genes, masks[t0:t1], strata.rows(t0, t1),
+                                  {"a": cmh_res["a"][t0:t1], "crit": cmh_res["crit"][t0:t1]}, tables=True)["tables"]
+
+        def observed(t0, t1, tables):
+            return self.cmh_observed(tables, cmh_res["a"][t0:t1])
+        return TableSource("cmh_exact", strata, build, observed)
 
     def cmh_observed(self, tables, a):
         """u_obs float64 [T, G] (spec S11 step 4): every gene's own table entry at its pooled count ``a`` (cmh()'s
@@ -1137,7 +1194,7 @@ class AssociationEngine:
     def associate(self, genes, traits, masks, permutations=0, seed=0, perm_buffer=None,
                   use_lists=None, workspace=None, plan=None, graph=None, records=None, fwer=False,
                   table_budget_bytes=8 << 30, stepdown=False, strata=None, cmh=False, cmh_fwer=False,
-                  cmh_stepdown=False):
+                  cmh_stepdown=False, cmh_exact=False):
         """counts -> Fisher -> (optional) permutation exceedance counts.  Returns a dict of device tensors:
         counts [T, G, 4], margins [T, 2], p / odds [T, G], crit [T, G, 2], r [T, G] (uint32 bits in int32) or None.
         ``workspace``: the result tensors are the workspace's, overwritten by the next step that uses it.
@@ -1157,11 +1214,15 @@ class AssociationEngine:
         ``cmh_fwer`` / ``cmh_stepdown`` (need ``cmh`` and permutations; spec S11): the Westfall-Young passes over the
         CMH statistic -- res["minu"] float64 [T, P], res["u_obs"] float64 [T, G] and res["r_cmh_fwer"] /
         res["r_cmh_fwer_sd"] int32 [T, G] (westfall_young()).
+        ``cmh_exact`` (needs ``cmh``, not permutations; spec S12): the exact conditional test over the strata --
+        res["cmh_exact_p"] and res["cmh_exact_region_p"] float64 [T, G] (cmh_exact()'s p and p_region).
         Every other result is that of the same call without the option, bit for bit."""
         if (fwer or stepdown) and permutations <= 0:
             raise ValueError("fwer=True / stepdown=True need permutations > 0")
         if (cmh_fwer or cmh_stepdown) and (permutations <= 0 or not cmh):
             raise ValueError("cmh_fwer=True / cmh_stepdown=True need cmh=True and permutations > 0")
+        if cmh_exact and not cmh:
+            raise ValueError("cmh_exact=True needs cmh=True (and its strata)")
         if cmh and strata is None:
             raise ValueError("cmh=True needs strata (a StrataPlan of these traits)")
         if strata is not None and (permutations > 0 or cmh):
@@ -1175,6 +1236,9 @@ class AssociationEngine:
             res = {**res, **self.westfall_young(genes, traits, masks, permutations, seed, res, fwer, stepdown,
                                                 table_budget_bytes, plan, strata, cmh_fwer=cmh_fwer,
                                                 cmh_stepdown=cmh_stepdown)}
+        if cmh_exact:
+            exact = self.cmh_exact(genes, masks, strata, {"a": res["cmh_a"], "crit": res["cmh_crit"]})
+            res = {**res, "cmh_exact_p": exact["p"], "cmh_exact_region_p": exact["p_region"]}
         if records is not None:
             # the exchange records of the step, packed as its last kernel (inside a captured step:
             # one launch less per replay for a gene-sharded rank)

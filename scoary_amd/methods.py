@@ -782,6 +782,7 @@ OPTIONAL_COLUMNS = (
     ("CMH_empirical_p", "r_cmh", True),
     ("CMH_Westfall_Young_p", "r_cmh_fwer", True),
     ("CMH_Westfall_Young_stepdown_p", "r_cmh_fwer_sd", True),
+    ("CMH_exact_p", "cmh_exact_p", False),
 )
 
 # The rules of the flags behind them, in the order they are checked: (flag, Setup_results keyword, the sentence
@@ -802,6 +803,9 @@ FLAG_RULES = (
     ("--cmh-fwer-stepdown", "cmh_fwer_stepdown", "The Westfall-Young minima are taken over the "
      "Cochran-Mantel-Haenszel statistic of every gene", True, True,
      "the successive minima run over all genes in one order; gene shards do not compose", True),
+    # (its need of --cmh FILE has a message of its own, checked beside the row: RULE_TEXT["cmh_exact"])
+    ("--cmh-exact", "cmh_exact", "The exact conditional test is a test of every gene over the strata, beside "
+     "Fisher's", False, False, "its results reach the host beside the gathered records of a single process", False),
 )
 # a broken rule as the command line reports it / as Setup_results raises it
 RULE_TEXT = {
@@ -813,6 +817,8 @@ RULE_TEXT = {
                     "permutation", "%(kw)s excludes early_abort"),
     "cmh": ("Cannot use %(flag)s without --cmh FILE. The minima are taken over the statistic of the "
             "Cochran-Mantel-Haenszel test over the strata of FILE", "%(kw)s needs cmh (and its strata)"),
+    "cmh_exact": ("Cannot use %(flag)s without --cmh FILE. The exact test is taken over the strata of FILE",
+                  "%(kw)s needs cmh (and its strata)"),
     "ranks": ("Cannot use %(flag)s under more than one rank: %(why)s", "%(kw)s needs a single process: %(why)s"),
 }
 
@@ -834,6 +840,8 @@ def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None, cmh=
         yield text("early_abort")
     if needs_cmh and not cmh:
         yield text("cmh")
+    if kw == "cmh_exact" and not cmh:
+        yield text("cmh_exact")
     yield from files or ()
     if one_rank:
         from . import dist
@@ -842,7 +850,8 @@ def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None, cmh=
 
 
 def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, fwer=False,
-               fwer_stepdown=False, strata=None, cmh=False, cmh_fwer=False, cmh_fwer_stepdown=False):
+               fwer_stepdown=False, strata=None, cmh=False, cmh_fwer=False, cmh_fwer_stepdown=False,
+               cmh_exact=False):
     """Whole hot path for all traits; under torchrun (world > 1) every rank
     takes a stride gene shard (dist.GenePartition: the reference's domains,
     scoary/methods.py:1076-1078) and the per-gene records are all-gathered
@@ -860,6 +869,8 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
     (spec S10): out["cmh_p"], out["cmh_odds"] [T, G] and, with permutations, out["r_cmh"].
     ``cmh_fwer`` / ``cmh_fwer_stepdown`` (need ``cmh`` and permutations): the Westfall-Young passes over the CMH
     statistic (spec S11): out["r_cmh_fwer"] / out["r_cmh_fwer_sd"] [T, G].
+    ``cmh_exact`` (needs ``cmh``, not permutations): the exact conditional test over the strata (spec S12):
+    out["cmh_exact_p"] [T, G].
     How each of these arrays reaches the host: OPTIONAL_COLUMNS."""
     import torch
     from . import dist
@@ -927,9 +938,10 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
             res["r"] = r
             return eng.pack_records(res, nstop=nstop)
         with _stage("kernels (counts, Fisher, permutations)"):
-            res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan, strata=sp, cmh=cmh)
+            res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan, strata=sp, cmh=cmh,
+                                cmh_exact=cmh_exact)
             torch.cuda.synchronize(eng.device)
-        beside.update({k: res[k] for k in ("cmh_p", "cmh_odds", "r_cmh") if k in res})
+        beside.update({k: res[k] for k in ("cmh_p", "cmh_odds", "r_cmh", "cmh_exact_p") if k in res})
         if fwer or fwer_stepdown:
             with _stage("Westfall-Young step-down minP (p tables, k_stepdown_minp)" if fwer_stepdown else
                         "Westfall-Young minP (p tables, k_permute_minp)"):
@@ -1026,7 +1038,7 @@ def _usable_cpus():
 
 def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEED,
                   early_abort=False, fwer=False, fwer_stepdown=False, strata=None, cmh=False, cmh_fwer=False,
-                  cmh_fwer_stepdown=False):
+                  cmh_fwer_stepdown=False, cmh_exact=False):
     """Counts, Fisher's exact test and B/BH correction for every trait x gene
     (methods.py:757-928).  ``permutations`` >= 10 additionally attaches the
     Fisher-statistic ``Empirical_p`` (= (r+1)/(P+1), methods.py:1365) to every
@@ -1041,12 +1053,14 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
     permutations ``CMH_empirical_p`` = (r_cmh+1)/(P+1), the exact permutation p of that statistic.
     ``cmh_fwer`` / ``cmh_fwer_stepdown`` (with ``cmh`` and permutations): also ``CMH_Westfall_Young_p`` =
     (r_cmh_fwer+1)/(P+1) and ``CMH_Westfall_Young_stepdown_p`` = (r_cmh_fwer_sd+1)/(P+1), the single-step and
-    step-down family-wise adjusted p of the CMH statistic under the within-stratum shuffles (spec S11)."""
+    step-down family-wise adjusted p of the CMH statistic under the within-stratum shuffles (spec S11).
+    ``cmh_exact`` (with ``cmh``, not permutations; one process): also ``CMH_exact_p``, the two-sided exact conditional
+    p over the strata (spec S12; R's mantelhaen.test(exact = TRUE), Fisher's exact test when there is one stratum)."""
     if cmh and strata is None:
         raise ValueError("cmh needs strata")
     # (permutations are 0 here whenever the run is not --no_pairwise; with cmh the strata are its own)
     active = {"fwer": fwer, "fwer_stepdown": fwer_stepdown, "cmh": cmh, "strata": strata is not None and not cmh,
-              "cmh_fwer": cmh_fwer, "cmh_fwer_stepdown": cmh_fwer_stepdown}
+              "cmh_fwer": cmh_fwer, "cmh_fwer_stepdown": cmh_fwer_stepdown, "cmh_exact": cmh_exact}
     for rule in (rule for rule in FLAG_RULES if active[rule[1]]):
         for text in _broken_rules(rule, True, permutations, early_abort, cmh=cmh):
             raise ValueError(text)
@@ -1055,7 +1069,8 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
     if strata is not None and len(strata) != len(table.strains):
         raise ValueError("strata: one stratum index per isolate of the gene table")
     dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, fwer, fwer_stepdown,
-                     strata=strata, cmh=cmh, cmh_fwer=cmh_fwer, cmh_fwer_stepdown=cmh_fwer_stepdown)
+                     strata=strata, cmh=cmh, cmh_fwer=cmh_fwer, cmh_fwer_stepdown=cmh_fwer_stepdown,
+                     cmh_exact=cmh_exact)
     collapse_hashes = None
     if collapse:
         eng = get_engine()
@@ -1717,6 +1732,11 @@ def ScoaryArgumentParser(argv=None):
                    "step-down family-wise adjusted p of the CMH statistic -- every gene is compared, per permutation, "
                    "with the largest CMH statistic over the genes ranked at or behind it only; never above "
                    "CMH_Westfall_Young_p (single process; scoary_amd extension)")
+    a.add_argument("--cmh-exact", dest="cmh_exact", action="store_true", default=False,
+                   help="With --no_pairwise --cmh FILE: add the column CMH_exact_p, the two-sided exact conditional p "
+                   "over the strata of FILE -- the pooled count against the convolution of the strata's "
+                   "hypergeometric distributions, R's mantelhaen.test(exact = TRUE); needs no permutations; at most "
+                   "8190 isolates (single process; scoary_amd extension)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1890,7 +1910,8 @@ def main(**kwargs):
                             fwer=getattr(args, "permute_fwer", False),
                             fwer_stepdown=getattr(args, "permute_fwer_stepdown", False), strata=strata,
                             cmh=bool(getattr(args, "cmh", None)), cmh_fwer=getattr(args, "cmh_fwer", False),
-                            cmh_fwer_stepdown=getattr(args, "cmh_fwer_stepdown", False))
+                            cmh_fwer_stepdown=getattr(args, "cmh_fwer_stepdown", False),
+                            cmh_exact=getattr(args, "cmh_exact", False))
         t_stats = _time.time()
         if args.upgma_tree and rank == 0:
             # (with --no_pairwise there is no tree and the reference writes str(None) + ";", :277-280, :741-751)

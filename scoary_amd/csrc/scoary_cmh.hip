@@ -6,6 +6,8 @@
 //       stratum, mask of that stratum's isolates inside the word), sorted by (stratum, word).  The members array
 //       of the strata plan is ordered by (stratum, isolate), so a segment is a run of consecutive members with
 //       the same key: at most N of them, about W + S when the isolates of a stratum are adjacent.
+//   cmh_walk : THE walk of a lane over the table (k_cmh and k_cmh_support pass it what they do per segment, per
+//       stratum and for the strata without a member); cmh_stat : THE statistic at a pooled count (k_cmh, k_cmh_fill).
 //   k_cmh : one lane per gene on the tiled matrix (a wavefront's quad loads are 1 KiB coalesced), kTraits traits
 //       per block with their fp64 accumulators in registers.  A lane walks the table: per segment two AND +
 //       popcounts per trait against wave-uniform label / validity words, and on every change of stratum the
@@ -16,14 +18,17 @@
 //
 // The Westfall-Young tables of the CMH statistic (spec S11): what scoary_permute_minp / scoary_permute_stepdown
 // gather from, in the CSR layout of scoary_minp_plan / _fill, indexed by the pooled count a' = popc(gene & label).
-//   k_cmh_support : k_cmh's walk over the same segment table with the validity words alone -- per stratum
+//   k_cmh_support : cmh_walk over the same segment table with the validity words alone -- per stratum
 //       m = popc(gene & valid & stratum), folded into the two integer sums lo = sum max(0, k + m - n) and
 //       hi = sum min(k, m): the support of a' under within-stratum shuffles.  A kernel of its own, so that k_cmh
 //       compiles to what it compiled to before there were tables.  k_minp_scan (scoary_common.hpp) turns the sizes
 //       into offsets.
 //   k_cmh_fill : one wavefront per (trait, gene); its lanes stride over the gene's entries, so a wavefront's stores
-//       are one contiguous run of the table.  u(x) = 1 / (1 + stat(x)) from d_e2 and d_var as scoary_cmh wrote
+//       are one contiguous run of the table.  u(x) = 1 / (1 + cmh_stat(x)) from d_e2 and d_var as scoary_cmh wrote
 //       them: a few flops per entry, no table list, 64-bit entry indices throughout.
+//
+// The entry points check their arguments with strata_check / check_args and build the table through
+// scoary_cmh_segments_launch (both declared in scoary_common.hpp, shared with scoary_cmh_exact.hip).
 #include <cstddef>
 
 #include "scoary_common.hpp"
@@ -59,13 +64,7 @@ __global__ __launch_bounds__(kSegThreads) void k_cmh_segments(const uint16_t* __
   int mine = 0;
   for (int j = j0; j < j1; ++j) mine += is_head(j);
   heads[tid] = mine;
-  __syncthreads();
-  for (int o = 1; o < kSegThreads; o <<= 1) {           // inclusive scan of the per-thread head counts
-    const int v = tid >= o ? heads[tid - o] : 0;
-    __syncthreads();
-    heads[tid] += v;
-    __syncthreads();
-  }
+  block_scan<kSegThreads>(heads, tid, [](int x, int y) { return x + y; });   // the per-thread head counts
   int slot = heads[tid] - mine;
   if (tid == kSegThreads - 1) out->count = (uint32_t)heads[tid];
   for (int j = j0; j < j1; ++j) {
@@ -79,6 +78,45 @@ __global__ __launch_bounds__(kSegThreads) void k_cmh_segments(const uint16_t* __
     }
     out->seg[slot++] = make_uint2(key, mask);           // slot < number of heads <= N
   }
+}
+
+// THE walk of the segment table by the lane of gene g (k_cmh, k_cmh_support): seg(w, gene word & segment mask) per
+// segment, fold(s) on every change of stratum and at the end, empty(s0, s1) for the strata [s0, s1) without a
+// member.  Stratum and word are clamped (a bad table gives wrong counts, never a wild access); the quad of the gene
+// row is reloaded only when the word leaves it.
+template <class Seg, class Fold, class Empty>
+__device__ __forceinline__ void cmh_walk(const uint32_t* __restrict__ tiled, const CmhSegments* __restrict__ segs,
+                                         int64_t Gp, int64_t g, int N, int Wp, int S, Seg seg, Fold fold,
+                                         Empty empty) {
+  const uint4* __restrict__ quads = reinterpret_cast<const uint4*>(tiled);
+  const int nseg = min((int)segs->count, N);
+  int cur_s = -1, cur_q = -1;
+  uint4 gq = make_uint4(0, 0, 0, 0);
+  for (int i = 0; i < nseg; ++i) {
+    const uint2 sg = segs->seg[i];                                        // wave-uniform
+    const int s = min((int)(sg.x >> 16), S - 1), w = min((int)(sg.x & 0xffffu), Wp - 1);
+    if (s != cur_s) {
+      if (cur_s >= 0) fold(cur_s);
+      empty(cur_s + 1, s);
+      cur_s = s;
+    }
+    if ((w >> 2) != cur_q) {
+      cur_q = w >> 2;
+      gq = quads[(int64_t)cur_q * Gp + g];
+    }
+    const int c = w & 3;
+    seg(w, (c == 0 ? gq.x : c == 1 ? gq.y : c == 2 ? gq.z : gq.w) & sg.y);
+  }
+  if (cur_s >= 0) fold(cur_s);
+  empty(cur_s + 1, S);
+}
+
+// S10 / S11: the continuity-corrected statistic at the pooled count x, half = E2 / 2, v != 0; every operation
+// rounded on its own, so k_cmh's stat and k_cmh_fill's entry at the same count are the same double
+__device__ __forceinline__ double cmh_stat(double x, double half, double v) {
+  const double delta = fabs(x - half);
+  const double y = fmin(0.5, delta);
+  return ((delta - y) * (delta - y)) / v;
 }
 
 struct CmhOut {
@@ -96,8 +134,6 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh(const uint32_t* __restrict_
                                                      int T, int N, int Wp, int S, CmhOut out) {
   const int64_t g = (int64_t)blockIdx.x * kCmhThreads + threadIdx.x;      // < Gp: the grid covers Gp exactly
   const int t0 = blockIdx.y * kCmhTraits;
-  const uint4* __restrict__ quads = reinterpret_cast<const uint4*>(tiled);
-  const int nseg = min((int)segs->count, N);
 
   int32_t A[kCmhTraits], K[kCmhTraits];     // K: the positives of the counted strata (wave-uniform)
   double E2[kCmhTraits], V[kCmhTraits], R[kCmhTraits], Q[kCmhTraits];
@@ -132,33 +168,21 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh(const uint32_t* __restrict_
     }
   };
 
-  int cur_s = -1, cur_q = -1;
-  uint4 gq = make_uint4(0, 0, 0, 0);
-  for (int i = 0; i < nseg; ++i) {
-    const uint2 sg = segs->seg[i];                                        // wave-uniform
-    const int s = min((int)(sg.x >> 16), S - 1), w = min((int)(sg.x & 0xffffu), Wp - 1);
-    if (s != cur_s) {
-      if (cur_s >= 0) fold(cur_s);
-      for (int z = cur_s + 1; z < s; ++z)                                 // strata without a member: all-zero tables
-        for (int j = 0; j < kCmhTraits; ++j) put_scounts(j, z, 0, 0);
-      cur_s = s;
-    }
-    if ((w >> 2) != cur_q) {
-      cur_q = w >> 2;
-      gq = quads[(int64_t)cur_q * Gp + g];
-    }
-    const int c = w & 3;
-    const uint32_t gw = (c == 0 ? gq.x : c == 1 ? gq.y : c == 2 ? gq.z : gq.w) & sg.y;
+  cmh_walk(
+      tiled, segs, Gp, g, N, Wp, S,
+      [&](int w, uint32_t gw) {
 #pragma unroll
-    for (int j = 0; j < kCmhTraits; ++j) {
-      const int64_t row = (int64_t)trait(j) * Wp + w;
-      bcnt_acc(m[j], gw & masks[row]);
-      bcnt_acc(a[j], gw & labels[row]);
-    }
-  }
-  if (cur_s >= 0) fold(cur_s);
-  for (int z = cur_s + 1; z < S; ++z)
-    for (int j = 0; j < kCmhTraits; ++j) put_scounts(j, z, 0, 0);
+        for (int j = 0; j < kCmhTraits; ++j) {
+          const int64_t row = (int64_t)trait(j) * Wp + w;
+          bcnt_acc(m[j], gw & masks[row]);
+          bcnt_acc(a[j], gw & labels[row]);
+        }
+      },
+      fold,
+      [&](int s0, int s1) {                                               // strata without a member: all-zero tables
+        for (int z = s0; z < s1; ++z)
+          for (int j = 0; j < kCmhTraits; ++j) put_scounts(j, z, 0, 0);
+      });
 
   if (g >= G) return;
 #pragma unroll
@@ -169,9 +193,7 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh(const uint32_t* __restrict_
     double stat = __builtin_nan(""), p = 1.0;
     int64_t lo = 0, hi = -1;                                              // the accepted integers; empty: (0, 0)
     if (V[j] != 0.0) {
-      const double delta = fabs(dA - 0.5 * E2[j]);
-      const double y = fmin(0.5, delta);
-      stat = ((delta - y) * (delta - y)) / V[j];
+      stat = cmh_stat(dA, 0.5 * E2[j], V[j]);
       p = erfc(sqrt(stat / 2.0));
       const double diff = 2.0 * dA - E2[j];
       if (diff > kCmhTau) {
@@ -198,8 +220,8 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh(const uint32_t* __restrict_
 
 constexpr int64_t kCmhFillRows = (int64_t)1 << 28;   // (trait, gene) rows per k_cmh_fill launch: 2^26 blocks
 
-// S11 step 1.  k_cmh's geometry and walk (lane = gene, kCmhTraits traits per block, every index clamped alike); the
-// stratum's m of a trait is folded at every change of stratum, strata without a valid isolate skipped as in S10.
+// S11 step 1.  k_cmh's geometry (lane = gene, kCmhTraits traits per block) and cmh_walk with the validity words alone;
+// the stratum's m of a trait is folded at every change of stratum, strata without a valid isolate skipped as in S10.
 __global__ __launch_bounds__(kCmhThreads) void k_cmh_support(const uint32_t* __restrict__ tiled,
                                                              const uint32_t* __restrict__ masks,
                                                              const int32_t* __restrict__ smargins,
@@ -208,8 +230,6 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh_support(const uint32_t* __r
                                                              int64_t* __restrict__ off, int32_t* __restrict__ lo_out) {
   const int64_t g = (int64_t)blockIdx.x * kCmhThreads + threadIdx.x;      // < Gp: the grid covers Gp exactly
   const int t0 = blockIdx.y * kCmhTraits;
-  const uint4* __restrict__ quads = reinterpret_cast<const uint4*>(tiled);
-  const int nseg = min((int)segs->count, N);
 
   int32_t lo[kCmhTraits], hi[kCmhTraits];
   uint32_t m[kCmhTraits];
@@ -228,25 +248,13 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh_support(const uint32_t* __r
     }
   };
 
-  int cur_s = -1, cur_q = -1;
-  uint4 gq = make_uint4(0, 0, 0, 0);
-  for (int i = 0; i < nseg; ++i) {
-    const uint2 sg = segs->seg[i];                                        // wave-uniform
-    const int s = min((int)(sg.x >> 16), S - 1), w = min((int)(sg.x & 0xffffu), Wp - 1);
-    if (s != cur_s) {
-      if (cur_s >= 0) fold(cur_s);
-      cur_s = s;
-    }
-    if ((w >> 2) != cur_q) {
-      cur_q = w >> 2;
-      gq = quads[(int64_t)cur_q * Gp + g];
-    }
-    const int c = w & 3;
-    const uint32_t gw = (c == 0 ? gq.x : c == 1 ? gq.y : c == 2 ? gq.z : gq.w) & sg.y;
+  cmh_walk(
+      tiled, segs, Gp, g, N, Wp, S,
+      [&](int w, uint32_t gw) {
 #pragma unroll
-    for (int j = 0; j < kCmhTraits; ++j) bcnt_acc(m[j], gw & masks[(int64_t)trait(j) * Wp + w]);
-  }
-  if (cur_s >= 0) fold(cur_s);
+        for (int j = 0; j < kCmhTraits; ++j) bcnt_acc(m[j], gw & masks[(int64_t)trait(j) * Wp + w]);
+      },
+      fold, [](int, int) {});
 
   if (g >= G) return;
 #pragma unroll
@@ -278,12 +286,7 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh_fill(const double* __restri
   const double x0 = (double)lo[i];
   for (int64_t k = lane; k < o1 - o0; k += kWave) {
     double u = 1.0;
-    if (v != 0.0) {
-      const double delta = fabs((x0 + (double)k) - half);                 // (double)x: lo + k is an exact integer
-      const double y = fmin(0.5, delta);
-      const double stat = ((delta - y) * (delta - y)) / v;
-      u = 1.0 / (1.0 + stat);
-    }
+    if (v != 0.0) u = 1.0 / (1.0 + cmh_stat(x0 + (double)k, half, v));   // lo + k is an exact integer
     tab[o0 + k] = u;
   }
 }
@@ -291,8 +294,8 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh_fill(const double* __restri
 }  // namespace
 
 int scoary_cmh_segments_launch(scoary_handle h, hipStream_t s, const uint16_t* d_strata, const int32_t* d_members,
-                               int64_t N, int64_t S, void* d_scratch) {
-  KernelTimer kt(h, s, "k_cmh_segments");
+                               int64_t N, int64_t S, void* d_scratch, const char* event) {
+  KernelTimer kt(h, s, event);
   hipLaunchKernelGGL(k_cmh_segments, dim3(1), dim3(kSegThreads), 0, s, d_strata, d_members, (int)N, (int)S,
                      static_cast<CmhSegments*>(d_scratch));
   HIP_TRY(h, hipGetLastError());
@@ -311,29 +314,21 @@ int scoary_cmh(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d_label
                double* d_odds, double* d_e2, double* d_var, int32_t* d_a, uint32_t* d_crit, int32_t* d_scounts,
                void* d_scratch, scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
-  if (!d_tiled || !d_labels || !d_masks || !d_strata || !d_members || !d_offsets || !d_smargins || !d_stat || !d_p ||
-      !d_odds || !d_e2 || !d_var || !d_a || !d_crit || !d_scratch || G < 1 || T < 1 || N < 1 || S < 1)
-    return fail(h, SCOARY_ERR_ARG, "scoary_cmh: bad argument");
-  if (T > 65535) return fail(h, SCOARY_ERR_SIZE, "scoary_cmh: T > 65535");
-  if (S > scoary_perm_max_strata())
-    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh: more strata than scoary_perm_max_strata()");
-  if (N > scoary_perm_strata_max_isolates())
-    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh: more isolates than scoary_perm_strata_max_isolates()");
+  if (int rc = strata_check(h, "scoary_cmh", d_tiled && d_labels && d_masks && d_strata && d_members && d_offsets &&
+                                                  d_smargins && d_stat && d_p && d_odds && d_e2 && d_var && d_a &&
+                                                  d_crit && d_scratch && G >= 1, T, N, S))
+    return rc;
   const int64_t Gp = scoary_tiled_genes(G);
   if (Gp / kCmhThreads > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_cmh: grid too large");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  CmhSegments* segs = static_cast<CmhSegments*>(d_scratch);
-  {
-    KernelTimer kt(h, s, "k_cmh_segments");
-    hipLaunchKernelGGL(k_cmh_segments, dim3(1), dim3(kSegThreads), 0, s, d_strata, d_members, (int)N, (int)S, segs);
-    HIP_TRY(h, hipGetLastError());
-  }
+  if (int rc = scoary_cmh_segments_launch(h, s, d_strata, d_members, N, S, d_scratch, "k_cmh_segments")) return rc;
   const CmhOut out{d_stat, d_p, d_odds, d_e2, d_var, d_a, d_crit, d_scounts};
   KernelTimer kt(h, s, "k_cmh");
   hipLaunchKernelGGL(k_cmh, dim3((unsigned)(Gp / kCmhThreads), (unsigned)((T + kCmhTraits - 1) / kCmhTraits)),
-                     dim3(kCmhThreads), 0, s, d_tiled, d_labels, d_masks, d_smargins, segs, G, Gp, (int)T, (int)N,
-                     (int)scoary_row_words(N), (int)S, out);
+                     dim3(kCmhThreads), 0, s, d_tiled, d_labels, d_masks, d_smargins,
+                     static_cast<const CmhSegments*>(d_scratch), G, Gp, (int)T, (int)N, (int)scoary_row_words(N), (int)S,
+                     out);
   HIP_TRY(h, hipGetLastError());
   return SCOARY_OK;
 }
@@ -344,26 +339,21 @@ int scoary_cmh_minp_plan(scoary_handle h, const uint32_t* d_tiled, const uint32_
                          int64_t T, int64_t N, int64_t S, void* d_scratch, int64_t* d_off, int32_t* d_lo,
                          int64_t* entries_out, scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
-  if (!d_tiled || !d_masks || !d_strata || !d_members || !d_offsets || !d_smargins || !d_scratch || !d_off || !d_lo ||
-      !entries_out || G < 1 || T < 1 || N < 1 || S < 1)
-    return fail(h, SCOARY_ERR_ARG, "scoary_cmh_minp_plan: bad argument");
-  if (T > 65535 || G > (int64_t)1 << 30)
-    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_minp_plan: T > 65535 or G > 2^30");
-  if (S > scoary_perm_max_strata())
-    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_minp_plan: more strata than scoary_perm_max_strata()");
-  if (N > scoary_perm_strata_max_isolates())
-    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_minp_plan: more isolates than scoary_perm_strata_max_isolates()");
+  if (int rc = strata_check(h, "scoary_cmh_minp_plan", d_tiled && d_masks && d_strata && d_members && d_offsets &&
+                                                            d_smargins && d_scratch && d_off && d_lo && entries_out &&
+                                                            G >= 1, T, N, S))
+    return rc;
+  if (G > (int64_t)1 << 30) return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_minp_plan: G > 2^30");
   const int64_t Gp = scoary_tiled_genes(G);
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  CmhSegments* segs = static_cast<CmhSegments*>(d_scratch);
   const int64_t M = T * G;
   {
-    KernelTimer kt(h, s, "k_cmh_minp_plan");
-    hipLaunchKernelGGL(k_cmh_segments, dim3(1), dim3(kSegThreads), 0, s, d_strata, d_members, (int)N, (int)S, segs);
+    KernelTimer kt(h, s, "k_cmh_minp_plan");           // the one event of the plan's three launches
+    if (int rc = scoary_cmh_segments_launch(h, s, d_strata, d_members, N, S, d_scratch, nullptr)) return rc;
     hipLaunchKernelGGL(k_cmh_support, dim3((unsigned)(Gp / kCmhThreads), (unsigned)((T + kCmhTraits - 1) / kCmhTraits)),
-                       dim3(kCmhThreads), 0, s, d_tiled, d_masks, d_smargins, segs, G, Gp, (int)T, (int)N,
-                       (int)scoary_row_words(N), (int)S, d_off, d_lo);
+                       dim3(kCmhThreads), 0, s, d_tiled, d_masks, d_smargins, static_cast<const CmhSegments*>(d_scratch),
+                       G, Gp, (int)T, (int)N, (int)scoary_row_words(N), (int)S, d_off, d_lo);
     hipLaunchKernelGGL(k_minp_scan, dim3(1), dim3(1024), 0, s, d_off, M);
     HIP_TRY(h, hipGetLastError());
   }
@@ -377,8 +367,9 @@ int scoary_cmh_minp_fill(scoary_handle h, const double* d_e2, const double* d_va
                          const int32_t* d_lo, int64_t T, int64_t G, int64_t entries, double* d_tab,
                          scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
-  if (!d_e2 || !d_var || !d_off || !d_lo || !d_tab || T < 1 || G < 1 || entries < T * G)
-    return fail(h, SCOARY_ERR_ARG, "scoary_cmh_minp_fill: bad argument");
+  if (int rc = check_args(h, "scoary_cmh_minp_fill",
+                          d_e2 && d_var && d_off && d_lo && d_tab && T >= 1 && G >= 1 && entries >= T * G))
+    return rc;
   if (T > 65535 || G > (int64_t)1 << 30)
     return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_minp_fill: T > 65535 or G > 2^30");
   DeviceGuard guard(h->device);

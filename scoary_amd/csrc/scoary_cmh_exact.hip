@@ -7,7 +7,8 @@
 //   k_cmh_exact : one work group of 256 lanes per (trait, gene) row, rows in the CSR order of scoary_cmh_minp_plan.
 //     1. the lanes stride over the segment table of k_cmh_segments, gather the gene's words from the tiled matrix
 //        and add popc(gene & valid & mask) into m[s] in LDS;
-//     2. a lane per stratum (a few strata each): the support sizes, their offsets (a block scan) and the stratum's
+//     2. a lane per stratum (a few strata each): the support sizes, their offsets (block_scan of
+//        scoary_common.hpp, as every scan of this file) and the stratum's
 //        pmf by the ratio recurrence outward from the mode, normalised to sum 1 -- all strata at once, side by side
 //        in one LDS buffer of at most N / 2 + S doubles;
 //     3. the running pmf is convolved with one stratum after the other between two LDS buffers, lane = output
@@ -17,7 +18,8 @@
 //        {y : f(y) <= gamma f(x)} is a left tail and a right tail, found by two binary searches: p(x) is two
 //        reads of the sums.  Tails are summed from their small end, so a p of 1e-190 keeps its relative accuracy;
 //     5. the row's run of the table is written with contiguous stores; the observed p is read back from it.
-//   Every index is clamped: a bad plan gives wrong values, never a wild access.  LDS per work group follows N and S
+//   The table is built by scoary_cmh_segments_launch and the arguments are checked by strata_check (scoary_cmh.hip,
+//   scoary_common.hpp).  Every index is clamped: a bad plan gives wrong values, never a wild access.  LDS per work group follows N and S
 //   (three buffers of N / 2 + 1 doubles): 25 KB at N = 2000, 115 KB at the limit of 8190 isolates.
 #include "scoary_common.hpp"
 
@@ -42,13 +44,7 @@ struct ExactOut {
 // partial sum is a sum of the terms themselves (no subtraction), so sums of positive terms keep their accuracy
 __device__ __forceinline__ double exact_scan(double* s_d, int idx, double v) {
   s_d[idx] = v;
-  __syncthreads();
-  for (int o = 1; o < kExactThreads; o <<= 1) {
-    const double u = idx >= o ? s_d[idx - o] : 0.0;
-    __syncthreads();
-    s_d[idx] += u;
-    __syncthreads();
-  }
+  block_scan<kExactThreads>(s_d, idx, [](double x, double y) { return x + y; });
   const double before = idx > 0 ? s_d[idx - 1] : 0.0;
   __syncthreads();
   return before;
@@ -103,14 +99,8 @@ __global__ __launch_bounds__(kExactThreads) void k_cmh_exact(
     int k, n, mm, lo_s;
     mine += min(shape(s, k, n, mm, lo_s), fs_cap + 1);                 // (no overflow of the sum, whatever the plan)
   }
-  s_i[tid] = mine;
-  __syncthreads();
-  for (int o = 1; o < kExactThreads; o <<= 1) {                         // inclusive scan of the lanes' sizes
-    const int v = tid >= o ? s_i[tid - o] : 0;
-    __syncthreads();
-    s_i[tid] = min(s_i[tid] + v, 2 * fs_cap);
-    __syncthreads();
-  }
+  s_i[tid] = mine;                                                      // the lanes' sizes, clamped (no overflow)
+  block_scan<kExactThreads>(s_i, tid, [&](int x, int y) { return min(x + y, 2 * fs_cap); });
   int at = s_i[tid] - mine;
   if (tid == kExactThreads - 1) zoff[S] = s_i[tid];
   for (int s = s0; s < s1; ++s) {
@@ -246,15 +236,12 @@ int scoary_cmh_exact(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d
                      const int64_t* d_off, const int32_t* d_lo, int64_t entries, double* d_p, double* d_p_region,
                      double* d_tab, void* d_scratch, scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
-  if (!d_tiled || !d_masks || !d_strata || !d_members || !d_offsets || !d_smargins || !d_a || !d_crit || !d_off ||
-      !d_lo || !d_scratch || (!d_p && !d_p_region && !d_tab) || G < 1 || T < 1 || N < 1 || S < 1 || entries < T * G)
-    return fail(h, SCOARY_ERR_ARG, "scoary_cmh_exact: bad argument");
-  if (T > 65535 || G > (int64_t)1 << 30)
-    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: T > 65535 or G > 2^30");
-  if (S > scoary_perm_max_strata())
-    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: more strata than scoary_perm_max_strata()");
-  if (N > scoary_perm_strata_max_isolates())
-    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: more isolates than scoary_perm_strata_max_isolates()");
+  if (int rc = strata_check(h, "scoary_cmh_exact", d_tiled && d_masks && d_strata && d_members && d_offsets &&
+                                                        d_smargins && d_a && d_crit && d_off && d_lo && d_scratch &&
+                                                        (d_p || d_p_region || d_tab) && G >= 1 && entries >= T * G,
+                            T, N, S))
+    return rc;
+  if (G > (int64_t)1 << 30) return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: G > 2^30");
   if (N > kExactMaxIsolates)
     return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: more isolates than scoary_cmh_exact_max_isolates() = " +
                                         std::to_string(kExactMaxIsolates) + " (the pmf of a gene is held in LDS)");
@@ -267,8 +254,7 @@ int scoary_cmh_exact(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d
                                    (int)exact_lds_bytes(kExactMaxIsolates, scoary_perm_max_strata())));
     h->cmh_exact_lds_optin = 1;
   }
-  const int rc = scoary_cmh_segments_launch(h, s, d_strata, d_members, N, S, d_scratch);
-  if (rc != SCOARY_OK) return rc;
+  if (int rc = scoary_cmh_segments_launch(h, s, d_strata, d_members, N, S, d_scratch, "k_cmh_segments")) return rc;
   const ExactOut out{d_p, d_p_region, d_tab};
   const int64_t M = T * G;
   KernelTimer kt(h, s, "k_cmh_exact");

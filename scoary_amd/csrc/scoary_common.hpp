@@ -49,9 +49,10 @@ int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, 
                        int64_t N, int64_t P, int64_t ntiles, int64_t gs);
 
 // scoary_cmh.hip: the strata plan as the segment table (CmhSegments, below) in d_scratch = scoary_cmh_scratch_bytes(N)
-// bytes; scoary_cmh_exact.hip walks the same table
+// bytes -- THE launch of k_cmh_segments, for scoary_cmh, scoary_cmh_minp_plan and scoary_cmh_exact.  `event`: the
+// timing event the launch is recorded under, or nullptr when the caller's own event covers it
 int scoary_cmh_segments_launch(scoary_handle h, hipStream_t s, const uint16_t* d_strata, const int32_t* d_members,
-                               int64_t N, int64_t S, void* d_scratch);
+                               int64_t N, int64_t S, void* d_scratch, const char* event);
 
 namespace {
 
@@ -155,6 +156,21 @@ int fail(scoary_handle h, int code, const std::string& msg) {
   return code;
 }
 
+// the checks the entry points share; `what` names the entry point in the message
+inline int check_args(scoary_handle h, const char* what, bool ok) {
+  return ok ? SCOARY_OK : fail(h, SCOARY_ERR_ARG, std::string(what) + ": bad argument");
+}
+// the stratified entry points (S9 to S12): arguments, then the limits of the per-stratum tables
+inline int strata_check(scoary_handle h, const char* what, bool ok, int64_t T, int64_t N, int64_t S) {
+  if (int rc = check_args(h, what, ok && T >= 1 && N >= 1 && S >= 1)) return rc;
+  if (T > 65535) return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": T > 65535");
+  if (S > scoary_perm_max_strata())
+    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more strata than scoary_perm_max_strata()");
+  if (N > scoary_perm_strata_max_isolates())
+    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more isolates than scoary_perm_strata_max_isolates()");
+  return SCOARY_OK;
+}
+
 #define HIP_TRY(h, expr)                                                              \
   do {                                                                                \
     hipError_t e_ = (expr);                                                           \
@@ -179,8 +195,8 @@ struct KernelTimer {
   scoary_handle h;
   hipStream_t s;
   hipEvent_t start = nullptr, stop = nullptr;
-  KernelTimer(scoary_handle h_, hipStream_t s_, const char* name) : h(h_), s(s_) {
-    if (!h->timing) return;
+  KernelTimer(scoary_handle h_, hipStream_t s_, const char* name) : h(h_), s(s_) {   // no name: times nothing
+    if (!name || !h->timing) return;
     if (hipEventCreate(&start) != hipSuccess || hipEventCreate(&stop) != hipSuccess) {
       start = stop = nullptr;
       return;
@@ -237,6 +253,20 @@ __device__ __forceinline__ void and_popc(uint32_t& acc, const uint4 a, const uin
   bcnt_acc(acc, a.w & b.w);
 }
 
+
+// inclusive Hillis-Steele scan of s[0 .. THREADS) in place by a block of THREADS lanes, s[idx] = op(s[idx],
+// s[idx - o]) for o = 1, 2, 4, ...: lane idx (a permutation of the lanes) has written s[idx] and reads the
+// results after the return.  Elements without a left neighbour combine with T(0), so op(x, 0) = x must hold.
+template <int THREADS, class T, class Op>
+__device__ __forceinline__ void block_scan(T* s, int idx, Op op) {
+  __syncthreads();
+  for (int o = 1; o < THREADS; o <<= 1) {
+    const T v = idx >= o ? s[idx - o] : T(0);
+    __syncthreads();
+    s[idx] = op(s[idx], v);
+    __syncthreads();
+  }
+}
 
 // exclusive prefix sum of off[0 .. M) in place, off[M] = total.  One block walks the array in tiles of
 // 1024 with a running carry (once per trait group: 0.5 M entries are ~500 tiles).  Shared by the

@@ -732,26 +732,13 @@ LabelArgs label_args(const uint32_t* d_masks, const int32_t* d_margins, int64_t 
   return a;
 }
 
-// ---- the checks the entry points share; `what` names the entry point in the message -------------
-int check_args(scoary_handle h, const char* what, bool ok) {
-  return ok ? SCOARY_OK : fail(h, SCOARY_ERR_ARG, std::string(what) + ": bad argument");
-}
+// ---- the checks the entry points share beside check_args / strata_check (scoary_common.hpp) ------
 int check_tile_base(scoary_handle h, const char* what, int64_t perm_base) {
   return (perm_base & 31) ? fail(h, SCOARY_ERR_ARG, std::string(what) + ": perm_base must be a multiple of 32")
                           : SCOARY_OK;
 }
 int check_grid(scoary_handle h, const char* what, int64_t gx) {
   return gx > 0x7fffffffLL ? fail(h, SCOARY_ERR_SIZE, std::string(what) + ": grid too large") : SCOARY_OK;
-}
-// the stratified entry points: arguments, then the limits of the per-stratum tables
-int strata_check(scoary_handle h, const char* what, bool ok, int64_t T, int64_t N, int64_t S) {
-  if (int rc = check_args(h, what, ok && T >= 1 && N >= 1 && S >= 1)) return rc;
-  if (T > 65535) return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": T > 65535");
-  if (S > kMaxStrata)
-    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more strata than scoary_perm_max_strata()");
-  if (N > kStrataMaxIsolates)
-    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more isolates than scoary_perm_strata_max_isolates()");
-  return SCOARY_OK;
 }
 
 // bit rows: one block per (Philox block touched, sub-dword piece)

@@ -622,6 +622,21 @@ class AssociationEngine:
         return tuple(self._ptr(x) for x in (strata.strata, strata.members, strata.offsets, strata.smargins))
 
     # -- Cochran-Mantel-Haenszel test over the strata (spec S10) -------------------
+    def _cmh_scratch(self, N):
+        """The buffer of the segment table that scoary_cmh, scoary_cmh_minp_plan and scoary_cmh_exact build."""
+        return self._empty(((int(self.lib.scoary_cmh_scratch_bytes(N)) + 7) // 8,), _torch().int64)
+
+    def _cmh_fits(self, who, genes, masks, strata, outputs, what):
+        """(T, G, N) for cmh_tables / cmh_exact (``who``): the validity rows ``masks`` [T, Wp] belong to the traits of
+        ``strata`` and the cmh() outputs they read -- ``outputs``: (tensor, shape after [T, G]) pairs, ``what`` names
+        them in the message -- are contiguous and of these T traits x G genes."""
+        T, G, N = int(masks.shape[0]), genes.G, genes.N
+        self._strata_fits(strata, T, N)
+        if not masks.is_contiguous() or any(not x.is_contiguous() or tuple(x.shape) != (T, G) + tail
+                                            for x, tail in outputs):
+            raise ValueError("%s: validity rows [T, Wp] and cmh()'s %s of the same traits, contiguous" % (who, what))
+        return T, G, N
+
     def cmh(self, genes, traits, masks, strata, scounts=False):
         """The stratified test of every (trait, gene) over the strata of ``strata`` (the StrataPlan of these label
         rows ``traits`` and validity rows ``masks``): dict of device tensors -- stat (the continuity-corrected CMH
@@ -640,7 +655,7 @@ class AssociationEngine:
         out["crit"] = self._empty((T, G, 2), torch.int32)
         if scounts:
             out["scounts"] = self._empty((T, G, strata.S, 2), torch.int32)
-        scratch = self._empty(((int(self.lib.scoary_cmh_scratch_bytes(N)) + 7) // 8,), torch.int64)
+        scratch = self._cmh_scratch(N)
         self._check(self.lib.scoary_cmh(
             self.h, self._ptr(genes.tiled), self._ptr(traits), self._ptr(masks), *self._strata_ptrs(strata),
             G, T, N, strata.S, *(self._ptr(out[k]) for k in ("stat", "p", "odds", "e2", "var", "a", "crit")),
@@ -727,16 +742,10 @@ class AssociationEngine:
         ``strata`` -- MinpTables, the layout permute_minp / permute_stepdown take.  ``masks``: the validity rows
         [T, Wp] of the traits of ``strata``; ``cmh_res``: cmh()'s result for them (its e2 and var are read).  One
         8-byte read-back (the entry count)."""
-        torch = _torch()
-        T, G, N = int(masks.shape[0]), genes.G, genes.N
-        self._strata_fits(strata, T, N)
         e2, var = cmh_res["e2"], cmh_res["var"]
-        if not (masks.is_contiguous() and e2.is_contiguous() and var.is_contiguous()) or \
-                tuple(e2.shape) != (T, G) or tuple(var.shape) != (T, G):
-            raise ValueError("cmh_tables: validity rows [T, Wp] and cmh()'s e2 / var [T, G] of the same traits, "
-                             "contiguous")
+        T, G, _N = self._cmh_fits("cmh_tables", genes, masks, strata, ((e2, ()), (var, ())), "e2 / var [T, G]")
         off, lo, total, _scratch = self._cmh_support(genes, masks, strata)
-        tab = self._empty((total,), torch.float64)
+        tab = self._empty((total,), _torch().float64)
         self._check(self.lib.scoary_cmh_minp_fill(self.h, self._ptr(e2), self._ptr(var), self._ptr(off),
                                                   self._ptr(lo), T, G, total, self._ptr(tab), self._stream()),
                     "scoary_cmh_minp_fill")
@@ -749,7 +758,7 @@ class AssociationEngine:
         T, G, N = int(masks.shape[0]), genes.G, genes.N
         off = self._empty((T * G + 1,), torch.int64)
         lo = self._empty((T, G), torch.int32)
-        scratch = self._empty(((int(self.lib.scoary_cmh_scratch_bytes(N)) + 7) // 8,), torch.int64)
+        scratch = self._cmh_scratch(N)
         entries = ctypes.c_int64()
         self._check(self.lib.scoary_cmh_minp_plan(
             self.h, self._ptr(genes.tiled), self._ptr(masks), *self._strata_ptrs(strata), G, T, N, strata.S,
@@ -772,13 +781,9 @@ class AssociationEngine:
         tables = the MinpTables of p over every gene's support (the layout permute_minp / permute_stepdown take);
         p is then read from them.  One 8-byte read-back (the entry count)."""
         torch = _torch()
-        T, G, N = int(masks.shape[0]), genes.G, genes.N
-        self._strata_fits(strata, T, N)
         a, crit = cmh_res["a"], cmh_res["crit"]
-        if not (masks.is_contiguous() and a.is_contiguous() and crit.is_contiguous()) or \
-                tuple(a.shape) != (T, G) or tuple(crit.shape) != (T, G, 2):
-            raise ValueError("cmh_exact: validity rows [T, Wp] and cmh()'s a [T, G] / crit [T, G, 2] of the same "
-                             "traits, contiguous")
+        T, G, N = self._cmh_fits("cmh_exact", genes, masks, strata, ((a, ()), (crit, (2,))),
+                                 "a [T, G] / crit [T, G, 2]")
         if N > self.cmh_exact_max_isolates():
             off = lo = self._empty((1,), torch.int64)       # the library refuses the size before it reads anything
             total, scratch = T * G, off
@@ -795,17 +800,20 @@ class AssociationEngine:
             out["tables"] = MinpTables(off, lo, tab, total)
         return out
 
+    def _cmh_table_source(self, kind, strata, cmh_res, build):
+        """The TableSource ``kind`` over the strata: ``build(t0, t1)`` makes the tables of a trait group; the observed
+        values are every gene's own entry at its pooled count cmh_res["a"] (cmh_observed)."""
+        def observed(t0, t1, tables):
+            return self.cmh_observed(tables, cmh_res["a"][t0:t1])
+        return TableSource(kind, strata, build, observed)
+
     def cmh_exact_source(self, genes, masks, strata, cmh_res):
         """The TableSource of the exact test (spec S12): the tables of cmh_exact() and, as observed values, every
         gene's own entry at its pooled count (cmh_observed), both per trait group -- minp() and minp_stepdown() then
         run over exact stratified p-values.  ``cmh_res``: cmh()'s result for all traits (a and crit are read)."""
-        def build(t0, t1):
-            return self.cmh_exact(genes, masks[t0:t1], strata.rows(t0, t1),
-                                  {"a": cmh_res["a"][t0:t1], "crit": cmh_res["crit"][t0:t1]}, tables=True)["tables"]
-
-        def observed(t0, t1, tables):
-            return self.cmh_observed(tables, cmh_res["a"][t0:t1])
-        return TableSource("cmh_exact", strata, build, observed)
+        return self._cmh_table_source("cmh_exact", strata, cmh_res, lambda t0, t1: self.cmh_exact(
+            genes, masks[t0:t1], strata.rows(t0, t1), {k: cmh_res[k][t0:t1] for k in ("a", "crit")},
+            tables=True)["tables"])
 
     def cmh_observed(self, tables, a):
         """u_obs float64 [T, G] (spec S11 step 4): every gene's own table entry at its pooled count ``a`` (cmh()'s
@@ -824,13 +832,8 @@ class AssociationEngine:
     def cmh_source(self, genes, masks, strata, cmh_res):
         """The TableSource of spec S11: the CMH tables of ``strata`` (cmh_tables) and u_obs (cmh_observed), both per
         trait group.  ``cmh_res``: cmh()'s result for all traits (e2, var and a are read)."""
-        def build(t0, t1):
-            return self.cmh_tables(genes, masks[t0:t1], strata.rows(t0, t1),
-                                   {"e2": cmh_res["e2"][t0:t1], "var": cmh_res["var"][t0:t1]})
-
-        def observed(t0, t1, tables):
-            return self.cmh_observed(tables, cmh_res["a"][t0:t1])
-        return TableSource("cmh", strata, build, observed)
+        return self._cmh_table_source("cmh", strata, cmh_res, lambda t0, t1: self.cmh_tables(
+            genes, masks[t0:t1], strata.rows(t0, t1), {k: cmh_res[k][t0:t1] for k in ("e2", "var")}))
 
     def permute_minp(self, genes, perms, tables, minp, P=None, perm_base=0):
         """minp[t, perm_base + i] = min(itself, min over the genes of p_tg(popcount(gene & perms[t, i]))) for the

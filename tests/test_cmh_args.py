@@ -1,5 +1,5 @@
-"""--cmh: the argument checks (host only -- they exit before the engine is touched), the declaration of the entry
-point (additive: the ABI version stays 11) and the build's report on k_cmh."""
+"""--cmh: the argument checks (host only -- they exit before the engine is touched) and the build's report on k_cmh
+(the declarations of the entry points: test_host_logic.py)."""
 import json
 import os
 import re
@@ -107,18 +107,6 @@ def test_flag_is_off_by_default_and_setup_results_refuses_cmh_without_strata():
         m.Setup_results({}, {}, False, cmh=True)
     with pytest.raises(ValueError, match="early_abort"):
         m.Setup_results({}, {}, False, permutations=100, early_abort=True, strata=[0, 1], cmh=True)
-
-
-def test_cmh_entry_points_are_declared():
-    from scoary_amd import _abi
-    assert _abi.ABI_VERSION == 11
-    header = open(_abi.HEADER_PATH).read()
-    for name in ("scoary_cmh", "scoary_cmh_scratch_bytes"):
-        assert name in _abi.SIGNATURES
-        m = re.search(r"\b%s\(([^;]*)\);" % name, header)
-        assert m, name
-        nargs = len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"])
-        assert nargs == len(_abi.SIGNATURES[name][1]), name
 
 
 def test_k_cmh_compiled_without_scratch_or_spills():

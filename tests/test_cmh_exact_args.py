@@ -1,8 +1,7 @@
 """--cmh-exact: the argument checks on the command line (they exit before the engine is touched) and in
-Setup_results (the same rules as ValueErrors), the place of the column, the declaration of the entry points
-(additive: the ABI version stays 11) and the resource rule of the kernel."""
+Setup_results (the same rules as ValueErrors), the place of the column and the resource rule of the kernel (the
+declarations of the entry points: test_host_logic.py)."""
 import os
-import re
 import sys
 
 import pytest
@@ -100,19 +99,6 @@ def test_column_is_the_last_and_the_rule_keeps_the_shape_of_its_row():
     assert (flag, key, needs_permutations, no_early_abort, needs_cmh) == (FLAG, KW, False, False, False)
     assert one_rank == [r for r in m.FLAG_RULES if r[0] == "--cmh"][0][5]
     assert m.RULE_TEXT["cmh_exact"][0] % {"flag": FLAG} == NO_CMH
-
-
-def test_entry_points_are_declared():
-    from scoary_amd import _abi
-    assert _abi.ABI_VERSION == 11
-    header = open(_abi.HEADER_PATH).read()
-    assert re.search(r"#define SCOARY_ABI_VERSION 11\b", header) and "spec S12" in header
-    for name in ("scoary_cmh_exact_max_isolates", "scoary_cmh_exact"):
-        assert name in _abi.SIGNATURES
-        m = re.search(r"\b%s\(([^;]*)\);" % name, header)
-        assert m, name
-        nargs = len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"])
-        assert nargs == len(_abi.SIGNATURES[name][1]), name
 
 
 def test_kernel_compiled_to_its_resource_rule_and_the_cmh_kernels_kept_theirs():

@@ -1,6 +1,6 @@
 """--cmh-fwer / --cmh-fwer-stepdown: the argument checks on the command line (they exit before the engine is touched)
-and in Setup_results (the same rules as ValueErrors), the place of the two columns, and the declaration of the two
-entry points (additive: the ABI version stays 11)."""
+and in Setup_results (the same rules as ValueErrors), the place of the two columns and the build's report on the
+table kernels (the declarations of the entry points: test_host_logic.py)."""
 import os
 import re
 import sys
@@ -123,19 +123,6 @@ def test_columns_and_rules_are_in_their_places():
     assert rules["--cmh-fwer"][5] == rules["--cmh"][5]
     assert rules["--cmh-fwer-stepdown"][5] == rules["--permute-fwer-stepdown"][5]
     assert not any(r[6] for f, r in rules.items() if f not in dict(FLAGS))
-
-
-def test_entry_points_are_declared():
-    from scoary_amd import _abi
-    assert _abi.ABI_VERSION == 11
-    header = open(_abi.HEADER_PATH).read()
-    assert re.search(r"#define SCOARY_ABI_VERSION 11\b", header)
-    for name in ("scoary_cmh_minp_plan", "scoary_cmh_minp_fill"):
-        assert name in _abi.SIGNATURES
-        m = re.search(r"\b%s\(([^;]*)\);" % name, header)
-        assert m, name
-        nargs = len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"])
-        assert nargs == len(_abi.SIGNATURES[name][1]), name
 
 
 def test_table_kernels_compiled_without_scratch_or_spills_and_k_cmh_is_one_kernel_still():

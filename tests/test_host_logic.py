@@ -37,6 +37,29 @@ def test_abi_library_exports_every_declared_symbol():
     assert lib.scoary_abi_version() == _abi.ABI_VERSION
 
 
+def test_binding_takes_the_arguments_the_header_declares():
+    """Every function of include/scoary_hip.h has a ctypes signature with the declared number of arguments, the
+    entry points added since ABI 11 are among them, and the version is still 11 (they were additive)."""
+    from scoary_amd import _abi
+    required = ("scoary_minp_fill_scratch_bytes", "scoary_minp_plan", "scoary_minp_fill", "scoary_permute_minp",
+                "scoary_stepdown_chunks", "scoary_stepdown_scratch_bytes", "scoary_permute_stepdown",
+                "scoary_strata_margins", "scoary_perm_generate_strata", "scoary_perm_generate_tiles_strata_range",
+                "scoary_perm_max_strata", "scoary_perm_strata_max_isolates", "scoary_cmh", "scoary_cmh_scratch_bytes",
+                "scoary_cmh_minp_plan", "scoary_cmh_minp_fill", "scoary_cmh_exact_max_isolates", "scoary_cmh_exact")
+    with open(_abi.HEADER_PATH) as f:
+        header = f.read()
+    assert _abi.ABI_VERSION == 11 and re.search(r"#define SCOARY_ABI_VERSION 11\b", header) and "spec S12" in header
+    declared = _header_functions()
+    assert set(required) <= set(declared)
+    for name in declared:
+        assert name in _abi.SIGNATURES, name
+        m = re.search(r"\b%s\(([^;]*)\);" % name, re.sub(r"/\*.*?\*/", "", header, flags=re.S))
+        assert m, name
+        nargs = len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"])
+        assert nargs == len(_abi.SIGNATURES[name][1]), name
+    assert _abi.PERM_MAX_STRATA >= 256 and _abi.PERM_STRATA_MAX_ISOLATES == 20479
+
+
 def test_abi_layout_arithmetic():
     from scoary_amd import _abi
     lib = _abi.load()

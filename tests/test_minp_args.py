@@ -1,7 +1,6 @@
-"""--permute-fwer: the argument checks (host only -- they exit before the engine is touched) and the
-declarations of the ABI 11 entry points."""
+"""--permute-fwer: the argument checks (host only -- they exit before the engine is touched; the declarations of
+the entry points: test_host_logic.py)."""
 import os
-import re
 import sys
 
 import pytest
@@ -49,16 +48,3 @@ def test_setup_results_refuses_fwer_without_permutations():
         m.Setup_results({}, {}, False, permutations=0, fwer=True)
     with pytest.raises(ValueError):
         m.Setup_results({}, {}, False, permutations=100, early_abort=True, fwer=True)
-
-
-def test_minp_entry_points_are_declared():
-    from scoary_amd import _abi
-    assert _abi.ABI_VERSION == 11
-    header = open(_abi.HEADER_PATH).read()
-    assert re.search(r"#define SCOARY_ABI_VERSION 11\b", header)
-    for name in ("scoary_minp_fill_scratch_bytes", "scoary_minp_plan", "scoary_minp_fill", "scoary_permute_minp"):
-        assert name in _abi.SIGNATURES
-        m = re.search(r"\b%s\(([^;]*)\);" % name, header)
-        assert m, name
-        nargs = len([a for a in m.group(1).split(",") if a.strip()])
-        assert nargs == len(_abi.SIGNATURES[name][1]), name

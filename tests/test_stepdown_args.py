@@ -1,7 +1,6 @@
-"""--permute-fwer-stepdown: the argument checks (host only -- they exit before the engine is touched) and the
-declarations of the step-down entry points (added without an ABI version change)."""
+"""--permute-fwer-stepdown: the argument checks (host only -- they exit before the engine is touched; the declarations
+of the step-down entry points: test_host_logic.py)."""
 import os
-import re
 import sys
 
 import pytest
@@ -70,16 +69,3 @@ def test_setup_results_refuses_stepdown(monkeypatch):
     monkeypatch.setattr(dist, "world_rank", lambda: (2, 0))
     with pytest.raises(ValueError, match="gene shards do not compose"):
         m.Setup_results({}, {}, False, permutations=100, fwer_stepdown=True)
-
-
-def test_stepdown_entry_points_are_declared():
-    from scoary_amd import _abi
-    assert _abi.ABI_VERSION == 11
-    header = open(_abi.HEADER_PATH).read()
-    assert re.search(r"#define SCOARY_ABI_VERSION 11\b", header)
-    for name in ("scoary_stepdown_chunks", "scoary_stepdown_scratch_bytes", "scoary_permute_stepdown"):
-        assert name in _abi.SIGNATURES
-        m = re.search(r"\b%s\(([^;]*)\);" % name, header)
-        assert m, name
-        nargs = len([a for a in m.group(1).split(",") if a.strip()])
-        assert nargs == len(_abi.SIGNATURES[name][1]), name

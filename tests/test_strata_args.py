@@ -1,7 +1,6 @@
-"""--permute-strata: the argument checks (host only -- they exit before the engine is touched) and the declarations
-of the stratified entry points (additive: the ABI version stays 11)."""
+"""--permute-strata: the argument checks (host only -- they exit before the engine is touched; the declarations of
+the stratified entry points: test_host_logic.py)."""
 import os
-import re
 import sys
 
 import pytest
@@ -111,18 +110,3 @@ def test_setup_results_refuses_strata_without_permutations():
     from scoary_amd import methods as m
     with pytest.raises(ValueError):
         m.Setup_results({}, {}, False, permutations=0, strata=[0, 1])
-
-
-def test_strata_entry_points_are_declared():
-    from scoary_amd import _abi
-    assert _abi.ABI_VERSION == 11
-    header = open(_abi.HEADER_PATH).read()
-    assert re.search(r"#define SCOARY_ABI_VERSION 11\b", header)
-    for name in ("scoary_strata_margins", "scoary_perm_generate_strata", "scoary_perm_generate_tiles_strata_range",
-                 "scoary_perm_max_strata", "scoary_perm_strata_max_isolates"):
-        assert name in _abi.SIGNATURES
-        m = re.search(r"\b%s\(([^;]*)\);" % name, header)
-        assert m, name
-        nargs = len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"])
-        assert nargs == len(_abi.SIGNATURES[name][1]), name
-    assert _abi.PERM_MAX_STRATA >= 256 and _abi.PERM_STRATA_MAX_ISOLATES == 20479

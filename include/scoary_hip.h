@@ -450,6 +450,27 @@ int scoary_cmh_exact(scoary_handle h, const uint32_t *d_tiled, const uint32_t *d
                      int64_t T, int64_t N, int64_t S, const int32_t *d_a, const uint32_t *d_crit,
                      const int64_t *d_off, const int32_t *d_lo, int64_t entries, double *d_p, double *d_p_region,
                      double *d_tab, void *d_scratch, scoary_stream_t stream);
+/* ---- Exact conditional odds ratio and confidence limits (spec S13 of DESIGN.md; additive, ABI 11) ------------
+ * From the same pmf f of the pooled count (S12 steps 1 and 2, the same code) and the tilted family
+ * f_psi(x) ~ f(x) psi^x, at the observed count A = d_a[t][g] of the support [lo, hi]:
+ *   d_or    : double [T][G], the conditional maximum-likelihood estimate of the common odds ratio: E_psi[X] = A;
+ *             0 when A = lo, +inf when A = hi
+ *   d_or_lo : double [T][G], the lower confidence limit: P_psi(X >= A) = half; 0 when A = lo
+ *   d_or_hi : double [T][G], the upper confidence limit: P_psi(X <= A) = half; +inf when A = hi
+ *   half    : 0.5 * (1.0 - level), computed in double by the caller, 0 < half < 0.5
+ * -- R's mantelhaen.test(exact = TRUE) (its estimate and conf.int); with one stratum fisher.test's.  A support of
+ * one entry (no informative stratum) gives (nan, 0, +inf).  k_cmh_odds_exact solves the three monotone equations
+ * in theta = log psi over [-700, 700] by safeguarded Newton steps on terms taken in the log domain; every finite
+ * positive result is within 1e-12 relative of the exact root, the special values are exact, a root outside the
+ * range is 0 or +inf.  Where f(A) < 1e-290 the values are unspecified, non-negative and not nan.
+ *   d_a / d_off / d_lo / entries / d_scratch : as scoary_cmh_exact takes them (d_off is checked, not read)
+ * Asynchronous on `stream`, allocates nothing.  Limits and errors: scoary_cmh_exact's. */
+int scoary_cmh_exact_odds(scoary_handle h, const uint32_t *d_tiled, const uint32_t *d_masks,
+                          const uint16_t *d_strata, const int32_t *d_members, const int32_t *d_offsets,
+                          const int32_t *d_smargins, int64_t G, int64_t T, int64_t N, int64_t S,
+                          const int32_t *d_a, const int64_t *d_off, const int32_t *d_lo, int64_t entries, double half,
+                          double *d_or, double *d_or_lo, double *d_or_hi, void *d_scratch,
+                          scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

@@ -18,6 +18,8 @@
 //        {y : f(y) <= gamma f(x)} is a left tail and a right tail, found by two binary searches: p(x) is two
 //        reads of the sums.  Tails are summed from their small end, so a p of 1e-190 keeps its relative accuracy;
 //     5. the row's run of the table is written with contiguous stores; the observed p is read back from it.
+//   k_cmh_odds_exact (spec S13; further down): steps 1 to 3 through the same function (exact_pmf), then the conditional
+//     maximum-likelihood odds ratio and its exact confidence limits, three roots solved in lockstep.
 //   The table is built by scoary_cmh_segments_launch and the arguments are checked by strata_check (scoary_cmh.hip,
 //   scoary_common.hpp).  Every index is clamped: a bad plan gives wrong values, never a wild access.  LDS per work group follows N and S
 //   (three buffers of N / 2 + 1 doubles): 25 KB at N = 2000, 115 KB at the limit of 8190 isolates.
@@ -50,24 +52,20 @@ __device__ __forceinline__ double exact_scan(double* s_d, int idx, double v) {
   return before;
 }
 
-__global__ __launch_bounds__(kExactThreads) void k_cmh_exact(
-    const uint32_t* __restrict__ tiled, const uint32_t* __restrict__ masks, const int32_t* __restrict__ smargins,
-    const CmhSegments* __restrict__ segs, const int32_t* __restrict__ a_obs, const uint32_t* __restrict__ crit,
-    const int64_t* __restrict__ off, const int32_t* __restrict__ lo, int64_t G, int64_t Gp, int N, int Wp, int S,
-    int cap, int64_t r0, int64_t entries, ExactOut out) {
-  extern __shared__ double lds[];
-  __shared__ double s_d[kExactThreads];
-  __shared__ int s_i[kExactThreads];
-  double* cur = lds;                                   // [cap] the running pmf
-  double* nxt = lds + cap;                             // [cap]
-  double* fs = lds + 2 * cap;                          // [cap + S] the strata's pmfs side by side
+// steps 1 to 3 of k_cmh_exact for the row (t, g), shared with k_cmh_odds_exact: the stratum counts, the strata's pmfs
+// and their convolution in the dynamic LDS of exact_lds_bytes(N, S) at `lds`.  -> L, the entries of the support; the
+// pmf is cur[0 .. L), nxt and fs (cap and cap + S doubles) are free.  Ends on a barrier whenever L > 1.
+__device__ __forceinline__ int exact_pmf(double* lds, int* s_i, const uint32_t* __restrict__ tiled,
+                                         const uint32_t* __restrict__ masks, const int32_t* __restrict__ smargins,
+                                         const CmhSegments* __restrict__ segs, int64_t Gp, int N, int Wp, int S, int cap,
+                                         int t, int64_t g, double*& cur, double*& nxt, double*& fs) {
+  cur = lds;                                           // [cap] the running pmf
+  nxt = lds + cap;                                     // [cap]
+  fs = lds + 2 * cap;                                  // [cap + S] the strata's pmfs side by side
   uint32_t* m = reinterpret_cast<uint32_t*>(fs + cap + S);   // [S]
   int* zoff = reinterpret_cast<int*>(m + S);           // [S + 1] offsets of the informative strata's pmfs in fs
   const int fs_cap = cap + S;
   const int tid = threadIdx.x;
-  const int64_t row = r0 + blockIdx.x;                 // < T * G: the launches cover the rows exactly
-  const int t = (int)(row / G);
-  const int64_t g = row % G;
 
   // 1. m[s] = popc(gene & valid & stratum s)
   for (int s = tid; s < S; s += kExactThreads) m[s] = 0;
@@ -153,6 +151,23 @@ __global__ __launch_bounds__(kExactThreads) void k_cmh_exact(
     cur = nxt, nxt = swap;
     L = Ln;
   }
+  return L;
+}
+
+__global__ __launch_bounds__(kExactThreads) void k_cmh_exact(
+    const uint32_t* __restrict__ tiled, const uint32_t* __restrict__ masks, const int32_t* __restrict__ smargins,
+    const CmhSegments* __restrict__ segs, const int32_t* __restrict__ a_obs, const uint32_t* __restrict__ crit,
+    const int64_t* __restrict__ off, const int32_t* __restrict__ lo, int64_t G, int64_t Gp, int N, int Wp, int S,
+    int cap, int64_t r0, int64_t entries, ExactOut out) {
+  extern __shared__ double lds[];
+  __shared__ double s_d[kExactThreads];
+  __shared__ int s_i[kExactThreads];
+  const int tid = threadIdx.x;
+  const int64_t row = r0 + blockIdx.x;                 // < T * G: the launches cover the rows exactly
+  const int t = (int)(row / G);
+  const int64_t g = row % G;
+  double *cur, *nxt, *fs;
+  const int L = exact_pmf(lds, s_i, tiled, masks, smargins, segs, Gp, N, Wp, S, cap, t, g, cur, nxt, fs);
 
   // 4. left[j] = f(0) + ... + f(j), right[j] = f(j) + ... + f(L - 1), and the mode (the first largest entry)
   double* left = nxt;
@@ -224,6 +239,154 @@ __global__ __launch_bounds__(kExactThreads) void k_cmh_exact(
   }
 }
 
+// ---- spec S13: the conditional maximum-likelihood odds ratio and its exact confidence limits ------------------
+constexpr int kOddsSums = 12;                         // the sums one block reduction carries (odds_solve)
+constexpr int kOddsWaves = kExactThreads / kWave;
+constexpr double kOddsTheta = 700.0;                  // theta = log psi is searched in [-700, 700]
+constexpr double kOddsStep = 1e-13;                   // a step or a bracket below it ends a search
+constexpr int kOddsMaxIter = 128;                     // (a bound on the loop; 5 to 9 iterations are the rule)
+constexpr double kOddsTiny = 1e-290;                  // S12's TINY
+
+struct OddsOut {
+  double *odds, *lo, *hi;
+};
+
+// one root search: the trial theta, its bracket and whether it has ended
+struct OddsRoot {
+  double th, lo, hi;
+  bool done;
+};
+
+// the largest exponent lf(j) + th (j - xa) over [j0, j1]: lf is concave, so the exponents rise up to their maximum
+// and fall behind it -- a binary search on the sign of the forward difference, every lane its own (no barrier)
+__device__ __forceinline__ double odds_peak(const double* lf, int j0, int j1, int xa, double th) {
+  int a = j0, b = j1;
+  while (a < b) {
+    const int c = (a + b) >> 1;
+    if (lf[c + 1] - lf[c] + th > 0.0) a = c + 1; else b = c;
+  }
+  return lf[a] + th * (double)(a - xa);
+}
+
+// safeguarded Newton: h (increasing in theta) and its derivative dh at r.th tighten the bracket; the Newton step is
+// taken while it stays inside the bracket, the bracket is bisected otherwise (h = +-inf and a nan step among it:
+// one side of a ratio underflowed far from the root).  Ends on a step or a bracket below kOddsStep.
+__device__ __forceinline__ void odds_step(OddsRoot& r, double h, double dh) {
+  if (r.done) return;
+  r.hi = h > 0.0 ? r.th : r.hi;
+  r.lo = h < 0.0 ? r.th : r.lo;
+  const double dn = -h / dh;
+  const bool small = fabs(dn) < kOddsStep;
+  double nt = r.th + dn;
+  if (!(nt > r.lo && nt < r.hi)) nt = small ? r.th : 0.5 * (r.lo + r.hi);
+  r.done = small || fabs(nt - r.th) < kOddsStep || r.hi - r.lo < kOddsStep;
+  r.th = nt;
+}
+
+// psi = exp(theta); a search that ran into an end of [-700, 700] has its root outside: 0 or +inf
+__device__ __forceinline__ double odds_psi(double th) {
+  return th <= -kOddsTheta + 1e-9 ? 0.0 : (th >= kOddsTheta - 1e-9 ? HUGE_VAL : exp(th));
+}
+
+//   k_cmh_odds_exact : one work group of 256 lanes per (trait, gene) row, in k_cmh_exact's row order.  Steps 1 to 3 are
+//     k_cmh_exact's (exact_pmf); then, with x = j - xa the distance to the observed count and w(j) = f(j) psi^x,
+//       the estimate    : log sum{w x : x > 0} - log sum{w |x| : x < 0} = 0          (E_psi[X] = A)
+//       the lower limit : log sum{w : x >= 0} - log sum{w : x < 0} = logit(half)     (P_psi(X >= A) = half)
+//       the upper limit : log sum{w : x > 0} - log sum{w : x <= 0} = -logit(half)    (P_psi(X <= A) = half)
+//     all three increasing in theta = log psi with a derivative of at least 1 (the distance between the means of
+//     the two sides) and close to linear far from the root, where a plain P - half or E - A is flat.  lf(j) = log(f(j) / f(A)) is written over nxt once; every
+//     iteration takes one pass over a lane's entries for the three trial thetas (terms exp(lf + theta x - M), M the
+//     largest exponent: odds_peak), one reduction of the kOddsSums sums -- shuffles inside a wavefront, the four
+//     wavefronts through LDS, double-buffered: ONE barrier per iteration -- and the same Newton step in every lane.
+__global__ __launch_bounds__(kExactThreads) void k_cmh_odds_exact(
+    const uint32_t* __restrict__ tiled, const uint32_t* __restrict__ masks, const int32_t* __restrict__ smargins,
+    const CmhSegments* __restrict__ segs, const int32_t* __restrict__ a_obs, const int32_t* __restrict__ lo, int64_t G,
+    int64_t Gp, int N, int Wp, int S, int cap, int64_t r0, double half, OddsOut out) {
+  extern __shared__ double lds[];
+  __shared__ double s_red[2][kOddsWaves][kOddsSums];
+  __shared__ int s_i[kExactThreads];
+  const int tid = threadIdx.x;
+  const int64_t row = r0 + blockIdx.x;                 // < T * G: the launches cover the rows exactly
+  const int t = (int)(row / G);
+  const int64_t g = row % G;
+  double *cur, *nxt, *fs;
+  const int L = exact_pmf(lds, s_i, tiled, masks, smargins, segs, Gp, N, Wp, S, cap, t, g, cur, nxt, fs);
+  if (L <= 1) {                                        // no informative stratum (block-uniform)
+    if (tid == 0) out.odds[row] = __builtin_nan(""), out.lo[row] = 0.0, out.hi[row] = HUGE_VAL;
+    return;
+  }
+  const int xa = (int)min(max((int64_t)a_obs[row] - (int64_t)lo[row], (int64_t)0), (int64_t)(L - 1));
+
+  // lf = log(f / f(A)) over nxt, and [j0, j1] = the entries with f > 0 (a run: f is log-concave)
+  double* lf = nxt;
+  const double fa = cur[xa];
+  const double ref = fa >= kOddsTiny ? fa : 1.0;       // (below TINY the values are unspecified: no overflow of f / ref)
+  if (tid == 0) s_i[0] = L - 1, s_i[1] = 0;
+  __syncthreads();
+  int first = L, last = -1;
+  for (int j = tid; j < L; j += kExactThreads) {
+    const double v = cur[j];
+    lf[j] = log(v / ref);                              // -inf where f underflowed
+    if (v > 0.0) first = min(first, j), last = j;
+  }
+  if (last >= 0) atomicMin(&s_i[0], first), atomicMax(&s_i[1], last);
+  __syncthreads();
+  const int j0 = min(s_i[0], xa), j1 = max(max(s_i[1], xa), j0);     // block-uniform, inside [0, L)
+
+  const double target = log(half) - log1p(-half);      // logit(half)
+  OddsRoot est{0.0, -kOddsTheta, kOddsTheta, !(xa > 0 && xa < L - 1)};
+  OddsRoot low{0.0, -kOddsTheta, kOddsTheta, !(xa > 0)};
+  OddsRoot upp{0.0, -kOddsTheta, kOddsTheta, !(xa < L - 1)};
+  const int lane = tid & (kWave - 1), wave = tid / kWave;
+  for (int it = 0; it < kOddsMaxIter && !(est.done && low.done && upp.done); ++it) {
+    const double m_est = odds_peak(lf, j0, j1, xa, est.th);
+    const double m_low = odds_peak(lf, j0, j1, xa, low.th);
+    const double m_upp = odds_peak(lf, j0, j1, xa, upp.th);
+    double acc[kOddsSums];
+#pragma unroll
+    for (int k = 0; k < kOddsSums; ++k) acc[k] = 0.0;
+    for (int j = j0 + tid; j <= j1; j += kExactThreads) {
+      const double l = lf[j], x = (double)(j - xa);
+      if (!est.done) {                                 // (the three tests are block-uniform)
+        const double w = exp(l + est.th * x - m_est), wx = w * fabs(x), wxx = wx * fabs(x);
+        const bool up = j > xa;                        // (the entry x = 0 adds 0 to either side)
+        acc[0] += up ? wx : 0.0, acc[1] += up ? wxx : 0.0, acc[2] += up ? 0.0 : wx, acc[11] += up ? 0.0 : wxx;
+      }
+      if (!low.done) {
+        const double w = exp(l + low.th * x - m_low), wx = w * x;
+        const bool up = j >= xa;
+        acc[3] += up ? w : 0.0, acc[4] += up ? wx : 0.0, acc[5] += up ? 0.0 : w, acc[6] += up ? 0.0 : wx;
+      }
+      if (!upp.done) {
+        const double w = exp(l + upp.th * x - m_upp), wx = w * x;
+        const bool up = j > xa;
+        acc[7] += up ? w : 0.0, acc[8] += up ? wx : 0.0, acc[9] += up ? 0.0 : w, acc[10] += up ? 0.0 : wx;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kOddsSums; ++k) {
+#pragma unroll
+      for (int o = kWave / 2; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);   // the same bits in every lane
+    }
+    double (*red)[kOddsSums] = s_red[it & 1];
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < kOddsSums; ++k) red[wave][k] = acc[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kOddsSums; ++k) acc[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    odds_step(est, log(acc[0]) - log(acc[2]), acc[1] / acc[0] + acc[11] / acc[2]);
+    odds_step(low, log(acc[3]) - log(acc[5]) - target, acc[4] / acc[3] - acc[6] / acc[5]);
+    odds_step(upp, log(acc[7]) - log(acc[9]) + target, acc[8] / acc[7] - acc[10] / acc[9]);
+  }
+  if (tid == 0) {
+    out.odds[row] = xa == 0 ? 0.0 : (xa == L - 1 ? HUGE_VAL : odds_psi(est.th));
+    out.lo[row] = xa == 0 ? 0.0 : odds_psi(low.th);
+    out.hi[row] = xa == L - 1 ? HUGE_VAL : odds_psi(upp.th);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -264,6 +427,45 @@ int scoary_cmh_exact(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d
                        d_masks, d_smargins, static_cast<const CmhSegments*>(d_scratch), d_a, d_crit, d_off, d_lo, G,
                        scoary_tiled_genes(G), (int)N, (int)scoary_row_words(N), (int)S, exact_cap(N), r0, entries,
                        out);
+    HIP_TRY(h, hipGetLastError());
+  }
+  return SCOARY_OK;
+}
+
+int scoary_cmh_exact_odds(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d_masks, const uint16_t* d_strata,
+                          const int32_t* d_members, const int32_t* d_offsets, const int32_t* d_smargins, int64_t G,
+                          int64_t T, int64_t N, int64_t S, const int32_t* d_a, const int64_t* d_off, const int32_t* d_lo,
+                          int64_t entries, double half, double* d_or, double* d_or_lo, double* d_or_hi, void* d_scratch,
+                          scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (int rc = strata_check(h, "scoary_cmh_exact_odds", d_tiled && d_masks && d_strata && d_members && d_offsets &&
+                                                             d_smargins && d_a && d_off && d_lo && d_scratch && d_or &&
+                                                             d_or_lo && d_or_hi && G >= 1 && entries >= T * G &&
+                                                             half > 0.0 && half < 0.5,
+                            T, N, S))
+    return rc;
+  if (G > (int64_t)1 << 30) return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact_odds: G > 2^30");
+  if (N > kExactMaxIsolates)
+    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact_odds: more isolates than scoary_cmh_exact_max_isolates() = " +
+                                        std::to_string(kExactMaxIsolates) + " (the pmf of a gene is held in LDS)");
+  const int64_t lds_bytes = exact_lds_bytes(N, S);
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (lds_bytes > 64 * 1024 && !h->cmh_exact_odds_lds_optin) {       // (the opt-in is per kernel function)
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cmh_odds_exact),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)exact_lds_bytes(kExactMaxIsolates, scoary_perm_max_strata())));
+    h->cmh_exact_odds_lds_optin = 1;
+  }
+  if (int rc = scoary_cmh_segments_launch(h, s, d_strata, d_members, N, S, d_scratch, "k_cmh_segments")) return rc;
+  const OddsOut out{d_or, d_or_lo, d_or_hi};
+  const int64_t M = T * G;
+  KernelTimer kt(h, s, "k_cmh_odds_exact");
+  for (int64_t r0 = 0; r0 < M; r0 += kExactRows) {
+    const int64_t nrows = std::min(kExactRows, M - r0);
+    hipLaunchKernelGGL(k_cmh_odds_exact, dim3((unsigned)nrows), dim3(kExactThreads), (size_t)lds_bytes, s, d_tiled,
+                       d_masks, d_smargins, static_cast<const CmhSegments*>(d_scratch), d_a, d_lo, G,
+                       scoary_tiled_genes(G), (int)N, (int)scoary_row_words(N), (int)S, exact_cap(N), r0, half, out);
     HIP_TRY(h, hipGetLastError());
   }
   return SCOARY_OK;

@@ -800,6 +800,32 @@ class AssociationEngine:
             out["tables"] = MinpTables(off, lo, tab, total)
         return out
 
+    def cmh_exact_odds(self, genes, masks, strata, cmh_res, level=0.95):
+        """The conditional maximum-likelihood estimate of the common odds ratio of every (trait, gene) over the
+        strata of ``strata`` and its exact confidence limits at ``level`` (spec S13; scoary_cmh_exact_odds): the
+        functionals of cmh_exact()'s pmf that R's mantelhaen.test(exact = TRUE) reports beside its p (fisher.test's
+        when there is one stratum).  ``masks`` / ``cmh_res``: as cmh_exact() takes them (a is read).  Dict of float64
+        [T, G] device tensors: odds (0 at the lower end of the support, inf at the upper end, nan when the support
+        is a single point), lower (0 at the lower end) and upper (inf at the upper end).  One 8-byte read-back."""
+        torch = _torch()
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError("cmh_exact_odds: the confidence level must lie inside (0, 1), not %r" % level)
+        a = cmh_res["a"]
+        T, G, N = self._cmh_fits("cmh_exact_odds", genes, masks, strata, ((a, ()),), "a [T, G]")
+        if N > self.cmh_exact_max_isolates():
+            off = lo = self._empty((1,), torch.int64)       # the library refuses the size before it reads anything
+            total, scratch = T * G, off
+        else:
+            off, lo, total, scratch = self._cmh_support(genes, masks, strata)
+        out = {k: self._empty((T, G), torch.float64) for k in ("odds", "lower", "upper")}
+        self._check(self.lib.scoary_cmh_exact_odds(
+            self.h, self._ptr(genes.tiled), self._ptr(masks), *self._strata_ptrs(strata), G, T, N, strata.S,
+            self._ptr(a), self._ptr(off), self._ptr(lo), total, 0.5 * (1.0 - level),
+            *(self._ptr(out[k]) for k in ("odds", "lower", "upper")), self._ptr(scratch), self._stream()),
+            "scoary_cmh_exact_odds")
+        return out
+
     def _cmh_table_source(self, kind, strata, cmh_res, build):
         """The TableSource ``kind`` over the strata: ``build(t0, t1)`` makes the tables of a trait group; the observed
         values are every gene's own entry at its pooled count cmh_res["a"] (cmh_observed)."""
@@ -1197,7 +1223,7 @@ class AssociationEngine:
     def associate(self, genes, traits, masks, permutations=0, seed=0, perm_buffer=None,
                   use_lists=None, workspace=None, plan=None, graph=None, records=None, fwer=False,
                   table_budget_bytes=8 << 30, stepdown=False, strata=None, cmh=False, cmh_fwer=False,
-                  cmh_stepdown=False, cmh_exact=False):
+                  cmh_stepdown=False, cmh_exact=False, cmh_exact_odds=False, cmh_exact_level=0.95):
         """counts -> Fisher -> (optional) permutation exceedance counts.  Returns a dict of device tensors:
         counts [T, G, 4], margins [T, 2], p / odds [T, G], crit [T, G, 2], r [T, G] (uint32 bits in int32) or None.
         ``workspace``: the result tensors are the workspace's, overwritten by the next step that uses it.
@@ -1219,6 +1245,9 @@ class AssociationEngine:
         res["r_cmh_fwer_sd"] int32 [T, G] (westfall_young()).
         ``cmh_exact`` (needs ``cmh``, not permutations; spec S12): the exact conditional test over the strata --
         res["cmh_exact_p"] and res["cmh_exact_region_p"] float64 [T, G] (cmh_exact()'s p and p_region).
+        ``cmh_exact_odds`` (needs ``cmh``, not permutations; spec S13): the conditional maximum-likelihood odds ratio
+        over the strata and its exact confidence limits at ``cmh_exact_level`` -- res["cmh_exact_odds"],
+        res["cmh_exact_odds_lower"] and res["cmh_exact_odds_upper"] float64 [T, G] (cmh_exact_odds()).
         Every other result is that of the same call without the option, bit for bit."""
         if (fwer or stepdown) and permutations <= 0:
             raise ValueError("fwer=True / stepdown=True need permutations > 0")
@@ -1226,6 +1255,10 @@ class AssociationEngine:
             raise ValueError("cmh_fwer=True / cmh_stepdown=True need cmh=True and permutations > 0")
         if cmh_exact and not cmh:
             raise ValueError("cmh_exact=True needs cmh=True (and its strata)")
+        if cmh_exact_odds and not cmh:
+            raise ValueError("cmh_exact_odds=True needs cmh=True (and its strata)")
+        if cmh_exact_odds and not 0.0 < float(cmh_exact_level) < 1.0:
+            raise ValueError("cmh_exact_level must lie inside (0, 1), not %r" % (cmh_exact_level,))
         if cmh and strata is None:
             raise ValueError("cmh=True needs strata (a StrataPlan of these traits)")
         if strata is not None and (permutations > 0 or cmh):
@@ -1242,6 +1275,10 @@ class AssociationEngine:
         if cmh_exact:
             exact = self.cmh_exact(genes, masks, strata, {"a": res["cmh_a"], "crit": res["cmh_crit"]})
             res = {**res, "cmh_exact_p": exact["p"], "cmh_exact_region_p": exact["p_region"]}
+        if cmh_exact_odds:
+            odds = self.cmh_exact_odds(genes, masks, strata, {"a": res["cmh_a"]}, level=cmh_exact_level)
+            res = {**res, "cmh_exact_odds": odds["odds"], "cmh_exact_odds_lower": odds["lower"],
+                   "cmh_exact_odds_upper": odds["upper"]}
         if records is not None:
             # the exchange records of the step, packed as its last kernel (inside a captured step:
             # one launch less per replay for a gene-sharded rank)

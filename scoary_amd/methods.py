@@ -784,6 +784,15 @@ OPTIONAL_COLUMNS = (
     ("CMH_Westfall_Young_stepdown_p", "r_cmh_fwer_sd", True),
     ("CMH_exact_p", "cmh_exact_p", False),
 )
+# The columns of --cmh-exact-odds (spec S13), written after every column of OPTIONAL_COLUMNS: the same triples.
+# (A tuple of their own: OPTIONAL_COLUMNS ends with CMH_exact_p.)  ALL_OPTIONAL_COLUMNS is what the consumers walk.
+EXACT_ODDS_COLUMNS = (
+    ("CMH_exact_odds_ratio", "cmh_exact_odds", False),
+    ("CMH_exact_odds_ratio_lower", "cmh_exact_odds_lower", False),
+    ("CMH_exact_odds_ratio_upper", "cmh_exact_odds_upper", False),
+)
+ALL_OPTIONAL_COLUMNS = OPTIONAL_COLUMNS + EXACT_ODDS_COLUMNS
+DEFAULT_EXACT_LEVEL = 0.95          # --cmh-exact-level
 
 # The rules of the flags behind them, in the order they are checked: (flag, Setup_results keyword, the sentence
 # after "needs --no_pairwise", needs --permute >= 10, excludes --permute-early-abort, why it needs a single rank
@@ -803,7 +812,10 @@ FLAG_RULES = (
     ("--cmh-fwer-stepdown", "cmh_fwer_stepdown", "The Westfall-Young minima are taken over the "
      "Cochran-Mantel-Haenszel statistic of every gene", True, True,
      "the successive minima run over all genes in one order; gene shards do not compose", True),
-    # (its need of --cmh FILE has a message of its own, checked beside the row: RULE_TEXT["cmh_exact"])
+    # (their need of --cmh FILE has a message of its own, checked beside the row: RULE_TEXT["cmh_exact"])
+    ("--cmh-exact-odds", "cmh_exact_odds", "The exact conditional odds ratio is an estimate for every gene over the "
+     "strata, beside Fisher's test", False, False, "its results reach the host beside the gathered records of a "
+     "single process", False),
     ("--cmh-exact", "cmh_exact", "The exact conditional test is a test of every gene over the strata, beside "
      "Fisher's", False, False, "its results reach the host beside the gathered records of a single process", False),
 )
@@ -840,7 +852,7 @@ def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None, cmh=
         yield text("early_abort")
     if needs_cmh and not cmh:
         yield text("cmh")
-    if kw == "cmh_exact" and not cmh:
+    if kw in ("cmh_exact", "cmh_exact_odds") and not cmh:
         yield text("cmh_exact")
     yield from files or ()
     if one_rank:
@@ -851,7 +863,7 @@ def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None, cmh=
 
 def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, fwer=False,
                fwer_stepdown=False, strata=None, cmh=False, cmh_fwer=False, cmh_fwer_stepdown=False,
-               cmh_exact=False):
+               cmh_exact=False, cmh_exact_odds=False, cmh_exact_level=0.95):
     """Whole hot path for all traits; under torchrun (world > 1) every rank
     takes a stride gene shard (dist.GenePartition: the reference's domains,
     scoary/methods.py:1076-1078) and the per-gene records are all-gathered
@@ -871,6 +883,9 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
     statistic (spec S11): out["r_cmh_fwer"] / out["r_cmh_fwer_sd"] [T, G].
     ``cmh_exact`` (needs ``cmh``, not permutations): the exact conditional test over the strata (spec S12):
     out["cmh_exact_p"] [T, G].
+    ``cmh_exact_odds`` (needs ``cmh``, not permutations): the conditional maximum-likelihood odds ratio over the strata
+    and its exact confidence limits at ``cmh_exact_level`` (spec S13): out["cmh_exact_odds"],
+    out["cmh_exact_odds_lower"], out["cmh_exact_odds_upper"] [T, G].
     How each of these arrays reaches the host: OPTIONAL_COLUMNS."""
     import torch
     from . import dist
@@ -939,9 +954,10 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
             return eng.pack_records(res, nstop=nstop)
         with _stage("kernels (counts, Fisher, permutations)"):
             res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan, strata=sp, cmh=cmh,
-                                cmh_exact=cmh_exact)
+                                cmh_exact=cmh_exact, cmh_exact_odds=cmh_exact_odds, cmh_exact_level=cmh_exact_level)
             torch.cuda.synchronize(eng.device)
-        beside.update({k: res[k] for k in ("cmh_p", "cmh_odds", "r_cmh", "cmh_exact_p") if k in res})
+        beside.update({k: res[k] for k in ("cmh_p", "cmh_odds", "r_cmh", "cmh_exact_p") +
+                       tuple(key for _name, key, _count in EXACT_ODDS_COLUMNS) if k in res})
         if fwer or fwer_stepdown:
             with _stage("Westfall-Young step-down minP (p tables, k_stepdown_minp)" if fwer_stepdown else
                         "Westfall-Young minP (p tables, k_permute_minp)"):
@@ -977,7 +993,7 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         out["r_fwer"], out["nstop"] = out["nstop"], np.zeros_like(out["nstop"])
     if fwer_stepdown:
         out["r_fwer_sd"] = np.zeros((T, 0), dtype=np.int32)         # (a table without genes)
-    for key in ("minp",) + tuple(key for _name, key, _count in OPTIONAL_COLUMNS):
+    for key in ("minp",) + tuple(key for _name, key, _count in ALL_OPTIONAL_COLUMNS):
         if key in beside:
             out[key] = beside[key].cpu().numpy()
     return out
@@ -1038,7 +1054,7 @@ def _usable_cpus():
 
 def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEED,
                   early_abort=False, fwer=False, fwer_stepdown=False, strata=None, cmh=False, cmh_fwer=False,
-                  cmh_fwer_stepdown=False, cmh_exact=False):
+                  cmh_fwer_stepdown=False, cmh_exact=False, cmh_exact_odds=False, cmh_exact_level=0.95):
     """Counts, Fisher's exact test and B/BH correction for every trait x gene
     (methods.py:757-928).  ``permutations`` >= 10 additionally attaches the
     Fisher-statistic ``Empirical_p`` (= (r+1)/(P+1), methods.py:1365) to every
@@ -1055,12 +1071,19 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
     (r_cmh_fwer+1)/(P+1) and ``CMH_Westfall_Young_stepdown_p`` = (r_cmh_fwer_sd+1)/(P+1), the single-step and
     step-down family-wise adjusted p of the CMH statistic under the within-stratum shuffles (spec S11).
     ``cmh_exact`` (with ``cmh``, not permutations; one process): also ``CMH_exact_p``, the two-sided exact conditional
-    p over the strata (spec S12; R's mantelhaen.test(exact = TRUE), Fisher's exact test when there is one stratum)."""
+    p over the strata (spec S12; R's mantelhaen.test(exact = TRUE), Fisher's exact test when there is one stratum).
+    ``cmh_exact_odds`` (with ``cmh``, not permutations; one process): also ``CMH_exact_odds_ratio``,
+    ``CMH_exact_odds_ratio_lower`` and ``CMH_exact_odds_ratio_upper``, the conditional maximum-likelihood estimate of
+    the common odds ratio and its exact confidence limits at ``cmh_exact_level`` (spec S13; the estimate and conf.int
+    of the same R test)."""
     if cmh and strata is None:
         raise ValueError("cmh needs strata")
     # (permutations are 0 here whenever the run is not --no_pairwise; with cmh the strata are its own)
     active = {"fwer": fwer, "fwer_stepdown": fwer_stepdown, "cmh": cmh, "strata": strata is not None and not cmh,
-              "cmh_fwer": cmh_fwer, "cmh_fwer_stepdown": cmh_fwer_stepdown, "cmh_exact": cmh_exact}
+              "cmh_fwer": cmh_fwer, "cmh_fwer_stepdown": cmh_fwer_stepdown, "cmh_exact": cmh_exact,
+              "cmh_exact_odds": cmh_exact_odds}
+    if cmh_exact_odds and not 0.0 < float(cmh_exact_level) < 1.0:
+        raise ValueError("cmh_exact_level must lie inside (0, 1), not %r" % (cmh_exact_level,))
     for rule in (rule for rule in FLAG_RULES if active[rule[1]]):
         for text in _broken_rules(rule, True, permutations, early_abort, cmh=cmh):
             raise ValueError(text)
@@ -1070,7 +1093,7 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
         raise ValueError("strata: one stratum index per isolate of the gene table")
     dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, fwer, fwer_stepdown,
                      strata=strata, cmh=cmh, cmh_fwer=cmh_fwer, cmh_fwer_stepdown=cmh_fwer_stepdown,
-                     cmh_exact=cmh_exact)
+                     cmh_exact=cmh_exact, cmh_exact_odds=cmh_exact_odds, cmh_exact_level=cmh_exact_level)
     collapse_hashes = None
     if collapse:
         eng = get_engine()
@@ -1157,7 +1180,7 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
                 "B_p": B, "BH_p": BH}
         if emp is not None:
             cols["Empirical_p"] = emp[rows_idx]
-        for name, key, count in OPTIONAL_COLUMNS:
+        for name, key, count in ALL_OPTIONAL_COLUMNS:
             if key in dev:
                 v = dev[key][t][rows_idx]
                 cols[name] = (v.view(np.uint32).astype(np.float64) + 1.0) / (permutations + 1.0) if count else v
@@ -1507,7 +1530,7 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
     if not isinstance(Trait, TraitResults):
         Trait = _trait_results_from_dict(Trait)
     # (a count has its denominator from the permutations: without them it is not written)
-    optional = [name for name, _key, count in OPTIONAL_COLUMNS
+    optional = [name for name, _key, count in ALL_OPTIONAL_COLUMNS
                 if no_pairwise and name in Trait.cols and (with_emp or not count)]
     columns += optional
     columns += list(extracolstoprint)
@@ -1596,7 +1619,7 @@ def _trait_results_from_dict(rows):
     """Plain {gene: row dict} (the reference's Results[trait]) -> TraitResults."""
     genes = list(rows.keys())
     cols = {}
-    for k in TraitResults.FIELDS + ("Empirical_p",) + tuple(name for name, _key, _count in OPTIONAL_COLUMNS):
+    for k in TraitResults.FIELDS + ("Empirical_p",) + tuple(name for name, _key, _count in ALL_OPTIONAL_COLUMNS):
         if genes and k in rows[genes[0]]:
             cols[k] = np.array([rows[g][k] for g in genes])
     return TraitResults(genes, [rows[g]["NUGN"] for g in genes],
@@ -1737,6 +1760,14 @@ def ScoaryArgumentParser(argv=None):
                    "over the strata of FILE -- the pooled count against the convolution of the strata's "
                    "hypergeometric distributions, R's mantelhaen.test(exact = TRUE); needs no permutations; at most "
                    "8190 isolates (single process; scoary_amd extension)")
+    a.add_argument("--cmh-exact-odds", dest="cmh_exact_odds", action="store_true", default=False,
+                   help="With --no_pairwise --cmh FILE: add the columns CMH_exact_odds_ratio, CMH_exact_odds_ratio_lower "
+                   "and CMH_exact_odds_ratio_upper, the conditional maximum-likelihood estimate of the common odds "
+                   "ratio over the strata of FILE and its exact confidence limits -- the estimate and conf.int of R's "
+                   "mantelhaen.test(exact = TRUE); needs no permutations and not --cmh-exact; at most 8190 isolates "
+                   "(single process; scoary_amd extension)")
+    a.add_argument("--cmh-exact-level", dest="cmh_exact_level", type=float, default=None, metavar="FLOAT",
+                   help="With --cmh-exact-odds: the confidence level of the limits, inside (0, 1) (default 0.95)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1911,7 +1942,9 @@ def main(**kwargs):
                             fwer_stepdown=getattr(args, "permute_fwer_stepdown", False), strata=strata,
                             cmh=bool(getattr(args, "cmh", None)), cmh_fwer=getattr(args, "cmh_fwer", False),
                             cmh_fwer_stepdown=getattr(args, "cmh_fwer_stepdown", False),
-                            cmh_exact=getattr(args, "cmh_exact", False))
+                            cmh_exact=getattr(args, "cmh_exact", False),
+                            cmh_exact_odds=getattr(args, "cmh_exact_odds", False),
+                            cmh_exact_level=getattr(args, "cmh_exact_level", None) or DEFAULT_EXACT_LEVEL)
         t_stats = _time.time()
         if args.upgma_tree and rank == 0:
             # (with --no_pairwise there is no tree and the reference writes str(None) + ";", :277-280, :741-751)
@@ -2054,6 +2087,12 @@ def _validate(args, cutoffs):
                                       getattr(args, "permute_early_abort", False), files,
                                       cmh=bool(getattr(args, "cmh", None))):
                 sys.exit(text)
+    level = getattr(args, "cmh_exact_level", None)
+    if level is not None and not getattr(args, "cmh_exact_odds", False):
+        sys.exit("Cannot use --cmh-exact-level without --cmh-exact-odds. It is the confidence level of the limits "
+                 "of the exact conditional odds ratio")
+    if level is not None and not 0.0 < level < 1.0:
+        sys.exit("The confidence level of --cmh-exact-level must be between 0.0 and 1.0 (both excluded)")
     strata_flag = "--permute-strata" if getattr(args, "permute_strata", None) else "--cmh"
     strata_path = getattr(args, "permute_strata", None) or getattr(args, "cmh", None)
     if strata_path:

@@ -387,6 +387,36 @@ __global__ __launch_bounds__(kExactThreads) void k_cmh_odds_exact(
   }
 }
 
+// What the two entry points (``who``) do after their own argument check: the sizes both kernels refuse, the
+// opt-in to more than 64 KB of LDS (``optin``: the kernel's own flag in the handle -- it is per kernel function),
+// the segment table, and the launches in blocks of kExactRows rows.  The kernels' parameter lists differ in the
+// middle, so ``block(s, nrows, lds_bytes, r0)`` launches ``kernel`` for the rows r0 .. r0 + nrows - 1.
+template <class... Args, class Block>
+int launch_exact(scoary_handle h, const std::string& who, void (*kernel)(Args...), const char* timer, int* optin,
+                 const uint16_t* d_strata, const int32_t* d_members, void* d_scratch, int64_t G, int64_t T, int64_t N,
+                 int64_t S, scoary_stream_t stream, Block block) {
+  if (G > (int64_t)1 << 30) return fail(h, SCOARY_ERR_SIZE, who + ": G > 2^30");
+  if (N > kExactMaxIsolates)
+    return fail(h, SCOARY_ERR_SIZE, who + ": more isolates than scoary_cmh_exact_max_isolates() = " +
+                                        std::to_string(kExactMaxIsolates) + " (the pmf of a gene is held in LDS)");
+  const int64_t lds_bytes = exact_lds_bytes(N, S);
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (lds_bytes > 64 * 1024 && !*optin) {
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)exact_lds_bytes(kExactMaxIsolates, scoary_perm_max_strata())));
+    *optin = 1;
+  }
+  if (int rc = scoary_cmh_segments_launch(h, s, d_strata, d_members, N, S, d_scratch, "k_cmh_segments")) return rc;
+  const int64_t M = T * G;
+  KernelTimer kt(h, s, timer);
+  for (int64_t r0 = 0; r0 < M; r0 += kExactRows) {
+    block(s, dim3((unsigned)std::min(kExactRows, M - r0)), (size_t)lds_bytes, r0);
+    HIP_TRY(h, hipGetLastError());
+  }
+  return SCOARY_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -404,32 +434,14 @@ int scoary_cmh_exact(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d
                                                         (d_p || d_p_region || d_tab) && G >= 1 && entries >= T * G,
                             T, N, S))
     return rc;
-  if (G > (int64_t)1 << 30) return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: G > 2^30");
-  if (N > kExactMaxIsolates)
-    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact: more isolates than scoary_cmh_exact_max_isolates() = " +
-                                        std::to_string(kExactMaxIsolates) + " (the pmf of a gene is held in LDS)");
-  const int64_t lds_bytes = exact_lds_bytes(N, S);
-  DeviceGuard guard(h->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (lds_bytes > 64 * 1024 && !h->cmh_exact_lds_optin) {
-    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cmh_exact),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)exact_lds_bytes(kExactMaxIsolates, scoary_perm_max_strata())));
-    h->cmh_exact_lds_optin = 1;
-  }
-  if (int rc = scoary_cmh_segments_launch(h, s, d_strata, d_members, N, S, d_scratch, "k_cmh_segments")) return rc;
   const ExactOut out{d_p, d_p_region, d_tab};
-  const int64_t M = T * G;
-  KernelTimer kt(h, s, "k_cmh_exact");
-  for (int64_t r0 = 0; r0 < M; r0 += kExactRows) {
-    const int64_t nrows = std::min(kExactRows, M - r0);
-    hipLaunchKernelGGL(k_cmh_exact, dim3((unsigned)nrows), dim3(kExactThreads), (size_t)lds_bytes, s, d_tiled,
-                       d_masks, d_smargins, static_cast<const CmhSegments*>(d_scratch), d_a, d_crit, d_off, d_lo, G,
-                       scoary_tiled_genes(G), (int)N, (int)scoary_row_words(N), (int)S, exact_cap(N), r0, entries,
-                       out);
-    HIP_TRY(h, hipGetLastError());
-  }
-  return SCOARY_OK;
+  return launch_exact(h, "scoary_cmh_exact", k_cmh_exact, "k_cmh_exact", &h->cmh_exact_lds_optin, d_strata, d_members,
+                      d_scratch, G, T, N, S, stream, [&](hipStream_t s, dim3 nrows, size_t lds_bytes, int64_t r0) {
+                        hipLaunchKernelGGL(k_cmh_exact, nrows, dim3(kExactThreads), lds_bytes, s, d_tiled, d_masks,
+                                           d_smargins, static_cast<const CmhSegments*>(d_scratch), d_a, d_crit, d_off,
+                                           d_lo, G, scoary_tiled_genes(G), (int)N, (int)scoary_row_words(N), (int)S,
+                                           exact_cap(N), r0, entries, out);
+                      });
 }
 
 int scoary_cmh_exact_odds(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d_masks, const uint16_t* d_strata,
@@ -444,31 +456,15 @@ int scoary_cmh_exact_odds(scoary_handle h, const uint32_t* d_tiled, const uint32
                                                              half > 0.0 && half < 0.5,
                             T, N, S))
     return rc;
-  if (G > (int64_t)1 << 30) return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact_odds: G > 2^30");
-  if (N > kExactMaxIsolates)
-    return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_exact_odds: more isolates than scoary_cmh_exact_max_isolates() = " +
-                                        std::to_string(kExactMaxIsolates) + " (the pmf of a gene is held in LDS)");
-  const int64_t lds_bytes = exact_lds_bytes(N, S);
-  DeviceGuard guard(h->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (lds_bytes > 64 * 1024 && !h->cmh_exact_odds_lds_optin) {       // (the opt-in is per kernel function)
-    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cmh_odds_exact),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)exact_lds_bytes(kExactMaxIsolates, scoary_perm_max_strata())));
-    h->cmh_exact_odds_lds_optin = 1;
-  }
-  if (int rc = scoary_cmh_segments_launch(h, s, d_strata, d_members, N, S, d_scratch, "k_cmh_segments")) return rc;
   const OddsOut out{d_or, d_or_lo, d_or_hi};
-  const int64_t M = T * G;
-  KernelTimer kt(h, s, "k_cmh_odds_exact");
-  for (int64_t r0 = 0; r0 < M; r0 += kExactRows) {
-    const int64_t nrows = std::min(kExactRows, M - r0);
-    hipLaunchKernelGGL(k_cmh_odds_exact, dim3((unsigned)nrows), dim3(kExactThreads), (size_t)lds_bytes, s, d_tiled,
-                       d_masks, d_smargins, static_cast<const CmhSegments*>(d_scratch), d_a, d_lo, G,
-                       scoary_tiled_genes(G), (int)N, (int)scoary_row_words(N), (int)S, exact_cap(N), r0, half, out);
-    HIP_TRY(h, hipGetLastError());
-  }
-  return SCOARY_OK;
+  return launch_exact(h, "scoary_cmh_exact_odds", k_cmh_odds_exact, "k_cmh_odds_exact", &h->cmh_exact_odds_lds_optin,
+                      d_strata, d_members, d_scratch, G, T, N, S, stream,
+                      [&](hipStream_t s, dim3 nrows, size_t lds_bytes, int64_t r0) {
+                        hipLaunchKernelGGL(k_cmh_odds_exact, nrows, dim3(kExactThreads), lds_bytes, s, d_tiled, d_masks,
+                                           d_smargins, static_cast<const CmhSegments*>(d_scratch), d_a, d_lo, G,
+                                           scoary_tiled_genes(G), (int)N, (int)scoary_row_words(N), (int)S,
+                                           exact_cap(N), r0, half, out);
+                      });
 }
 
 }  // extern "C"

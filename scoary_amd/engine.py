@@ -626,17 +626,6 @@ class AssociationEngine:
         """The buffer of the segment table that scoary_cmh, scoary_cmh_minp_plan and scoary_cmh_exact build."""
         return self._empty(((int(self.lib.scoary_cmh_scratch_bytes(N)) + 7) // 8,), _torch().int64)
 
-    def _cmh_fits(self, who, genes, masks, strata, outputs, what):
-        """(T, G, N) for cmh_tables / cmh_exact (``who``): the validity rows ``masks`` [T, Wp] belong to the traits of
-        ``strata`` and the cmh() outputs they read -- ``outputs``: (tensor, shape after [T, G]) pairs, ``what`` names
-        them in the message -- are contiguous and of these T traits x G genes."""
-        T, G, N = int(masks.shape[0]), genes.G, genes.N
-        self._strata_fits(strata, T, N)
-        if not masks.is_contiguous() or any(not x.is_contiguous() or tuple(x.shape) != (T, G) + tail
-                                            for x, tail in outputs):
-            raise ValueError("%s: validity rows [T, Wp] and cmh()'s %s of the same traits, contiguous" % (who, what))
-        return T, G, N
-
     def cmh(self, genes, traits, masks, strata, scounts=False):
         """The stratified test of every (trait, gene) over the strata of ``strata`` (the StrataPlan of these label
         rows ``traits`` and validity rows ``masks``): dict of device tensors -- stat (the continuity-corrected CMH
@@ -743,19 +732,30 @@ class AssociationEngine:
         [T, Wp] of the traits of ``strata``; ``cmh_res``: cmh()'s result for them (its e2 and var are read).  One
         8-byte read-back (the entry count)."""
         e2, var = cmh_res["e2"], cmh_res["var"]
-        T, G, _N = self._cmh_fits("cmh_tables", genes, masks, strata, ((e2, ()), (var, ())), "e2 / var [T, G]")
-        off, lo, total, _scratch = self._cmh_support(genes, masks, strata)
+        T, G, _N, off, lo, total, _scratch = self._cmh_support("cmh_tables", genes, masks, strata,
+                                                               ((e2, ()), (var, ())), "e2 / var [T, G]")
         tab = self._empty((total,), _torch().float64)
         self._check(self.lib.scoary_cmh_minp_fill(self.h, self._ptr(e2), self._ptr(var), self._ptr(off),
                                                   self._ptr(lo), T, G, total, self._ptr(tab), self._stream()),
                     "scoary_cmh_minp_fill")
         return MinpTables(off, lo, tab, total)
 
-    def _cmh_support(self, genes, masks, strata):
-        """scoary_cmh_minp_plan for the traits of ``strata``: (off int64 [T G + 1], lo int32 [T, G], the entry count,
-        the scratch buffer of the segment table).  One 8-byte read-back."""
+    def _cmh_support(self, who, genes, masks, strata, outputs, what, exact=False):
+        """What cmh_tables / cmh_exact / cmh_exact_odds (``who``) start from.  The check: the validity rows ``masks``
+        [T, Wp] belong to the traits of ``strata`` and the cmh() outputs they read -- ``outputs``: (tensor, shape after
+        [T, G]) pairs, ``what`` names them in the message -- are contiguous and of these T traits x G genes.  Then
+        scoary_cmh_minp_plan for these traits: (T, G, N, off int64 [T G + 1], lo int32 [T, G], the entry count, the
+        scratch buffer of the segment table).  One 8-byte read-back.  ``exact``: above cmh_exact_max_isolates() the
+        plan is left out and the buffers are placeholders."""
         torch = _torch()
         T, G, N = int(masks.shape[0]), genes.G, genes.N
+        self._strata_fits(strata, T, N)
+        if not masks.is_contiguous() or any(not x.is_contiguous() or tuple(x.shape) != (T, G) + tail
+                                            for x, tail in outputs):
+            raise ValueError("%s: validity rows [T, Wp] and cmh()'s %s of the same traits, contiguous" % (who, what))
+        if exact and N > self.cmh_exact_max_isolates():
+            off = self._empty((1,), torch.int64)            # the library refuses the size before it reads anything
+            return T, G, N, off, off, T * G, off
         off = self._empty((T * G + 1,), torch.int64)
         lo = self._empty((T, G), torch.int32)
         scratch = self._cmh_scratch(N)
@@ -764,7 +764,7 @@ class AssociationEngine:
             self.h, self._ptr(genes.tiled), self._ptr(masks), *self._strata_ptrs(strata), G, T, N, strata.S,
             self._ptr(scratch), self._ptr(off), self._ptr(lo), ctypes.byref(entries), self._stream()),
             "scoary_cmh_minp_plan")
-        return off, lo, int(entries.value), scratch
+        return T, G, N, off, lo, int(entries.value), scratch
 
     # -- exact conditional test over the strata (spec S12) ----------------------------
     def cmh_exact_max_isolates(self):
@@ -782,13 +782,8 @@ class AssociationEngine:
         p is then read from them.  One 8-byte read-back (the entry count)."""
         torch = _torch()
         a, crit = cmh_res["a"], cmh_res["crit"]
-        T, G, N = self._cmh_fits("cmh_exact", genes, masks, strata, ((a, ()), (crit, (2,))),
-                                 "a [T, G] / crit [T, G, 2]")
-        if N > self.cmh_exact_max_isolates():
-            off = lo = self._empty((1,), torch.int64)       # the library refuses the size before it reads anything
-            total, scratch = T * G, off
-        else:
-            off, lo, total, scratch = self._cmh_support(genes, masks, strata)
+        T, G, N, off, lo, total, scratch = self._cmh_support(
+            "cmh_exact", genes, masks, strata, ((a, ()), (crit, (2,))), "a [T, G] / crit [T, G, 2]", exact=True)
         out = {"p": self._empty((T, G), torch.float64), "p_region": self._empty((T, G), torch.float64)}
         tab = self._empty((total,), torch.float64) if tables else None
         self._check(self.lib.scoary_cmh_exact(
@@ -812,12 +807,8 @@ class AssociationEngine:
         if not 0.0 < level < 1.0:
             raise ValueError("cmh_exact_odds: the confidence level must lie inside (0, 1), not %r" % level)
         a = cmh_res["a"]
-        T, G, N = self._cmh_fits("cmh_exact_odds", genes, masks, strata, ((a, ()),), "a [T, G]")
-        if N > self.cmh_exact_max_isolates():
-            off = lo = self._empty((1,), torch.int64)       # the library refuses the size before it reads anything
-            total, scratch = T * G, off
-        else:
-            off, lo, total, scratch = self._cmh_support(genes, masks, strata)
+        T, G, N, off, lo, total, scratch = self._cmh_support(
+            "cmh_exact_odds", genes, masks, strata, ((a, ()),), "a [T, G]", exact=True)
         out = {k: self._empty((T, G), torch.float64) for k in ("odds", "lower", "upper")}
         self._check(self.lib.scoary_cmh_exact_odds(
             self.h, self._ptr(genes.tiled), self._ptr(masks), *self._strata_ptrs(strata), G, T, N, strata.S,
@@ -1031,8 +1022,7 @@ class AssociationEngine:
         if cmh_fwer or cmh_stepdown:
             if strata is None or "cmh_e2" not in res:
                 raise ValueError("cmh_fwer / cmh_stepdown need the result of a step with cmh=True and its strata")
-            source = self.cmh_source(genes, masks, strata,
-                                     {"e2": res["cmh_e2"], "var": res["cmh_var"], "a": res["cmh_a"]})
+            source = self.cmh_source(genes, masks, strata, self._cmh_of(res))
             u_obs = self._empty(tuple(res["cmh_a"].shape), _torch().float64)
             if cmh_stepdown:
                 out["r_cmh_fwer_sd"], out["minu"] = self.minp_stepdown(genes, traits, masks, permutations, seed,
@@ -1273,10 +1263,10 @@ class AssociationEngine:
                                                 table_budget_bytes, plan, strata, cmh_fwer=cmh_fwer,
                                                 cmh_stepdown=cmh_stepdown)}
         if cmh_exact:
-            exact = self.cmh_exact(genes, masks, strata, {"a": res["cmh_a"], "crit": res["cmh_crit"]})
+            exact = self.cmh_exact(genes, masks, strata, self._cmh_of(res))
             res = {**res, "cmh_exact_p": exact["p"], "cmh_exact_region_p": exact["p_region"]}
         if cmh_exact_odds:
-            odds = self.cmh_exact_odds(genes, masks, strata, {"a": res["cmh_a"]}, level=cmh_exact_level)
+            odds = self.cmh_exact_odds(genes, masks, strata, self._cmh_of(res), level=cmh_exact_level)
             res = {**res, "cmh_exact_odds": odds["odds"], "cmh_exact_odds_lower": odds["lower"],
                    "cmh_exact_odds_upper": odds["upper"]}
         if records is not None:
@@ -1361,11 +1351,17 @@ class AssociationEngine:
         with permutations, the zeroed count r_cmh."""
         torch = _torch()
         c = self.cmh(genes, traits, masks, strata)
-        out = {"cmh_stat": c["stat"], "cmh_p": c["p"], "cmh_odds": c["odds"], "cmh_crit": c["crit"],
-               "cmh_e2": c["e2"], "cmh_var": c["var"], "cmh_a": c["a"]}
+        out = {"cmh_" + k: c[k] for k in self.CMH_RESULT}
         if permutations > 0:
             out["r_cmh"] = torch.zeros((traits.shape[0], genes.G), dtype=torch.int32, device=self.device)
         return out
+
+    CMH_RESULT = ("stat", "p", "odds", "crit", "e2", "var", "a")        # cmh()'s keys; a step holds them as cmh_*
+
+    @classmethod
+    def _cmh_of(cls, res):
+        """cmh()'s result read back out of the step ``res`` (_cmh_results' inverse)."""
+        return {k: res["cmh_" + k] for k in cls.CMH_RESULT}
 
     def capture(self, genes, traits, masks, permutations, seed, workspace, use_lists=None, plan=None,
                 records=None, strata=None):

@@ -22,6 +22,7 @@ import os
 import re
 import sys
 import time as _time
+from collections import namedtuple
 from collections.abc import Mapping
 
 import numpy as np
@@ -783,41 +784,39 @@ OPTIONAL_COLUMNS = (
     ("CMH_Westfall_Young_p", "r_cmh_fwer", True),
     ("CMH_Westfall_Young_stepdown_p", "r_cmh_fwer_sd", True),
     ("CMH_exact_p", "cmh_exact_p", False),
-)
-# The columns of --cmh-exact-odds (spec S13), written after every column of OPTIONAL_COLUMNS: the same triples.
-# (A tuple of their own: OPTIONAL_COLUMNS ends with CMH_exact_p.)  ALL_OPTIONAL_COLUMNS is what the consumers walk.
-EXACT_ODDS_COLUMNS = (
-    ("CMH_exact_odds_ratio", "cmh_exact_odds", False),
+    ("CMH_exact_odds_ratio", "cmh_exact_odds", False),                  # --cmh-exact-odds (spec S13): these three
     ("CMH_exact_odds_ratio_lower", "cmh_exact_odds_lower", False),
     ("CMH_exact_odds_ratio_upper", "cmh_exact_odds_upper", False),
 )
-ALL_OPTIONAL_COLUMNS = OPTIONAL_COLUMNS + EXACT_ODDS_COLUMNS
 DEFAULT_EXACT_LEVEL = 0.95          # --cmh-exact-level
 
-# The rules of the flags behind them, in the order they are checked: (flag, Setup_results keyword, the sentence
-# after "needs --no_pairwise", needs --permute >= 10, excludes --permute-early-abort, why it needs a single rank
-# or None, needs --cmh FILE).
+# The rules of the flags behind them, in the order they are checked (which decides the message a faulty run sees
+# first, and is not the columns' order).  kw: the Setup_results keyword; sentence: what follows "needs
+# --no_pairwise"; one_rank: why the flag needs a single rank, or None; needs_cmh: the key of the RULE_TEXT entry that
+# reports a run without --cmh FILE, or None where the flag does not need it.
+FlagRule = namedtuple("FlagRule", "flag kw sentence needs_permutations no_early_abort one_rank needs_cmh")
 FLAG_RULES = (
-    ("--permute-fwer", "fwer", "The Westfall-Young minima are taken over the Fisher statistic of every gene",
-     True, True, None, False),
-    ("--permute-fwer-stepdown", "fwer_stepdown",
-     "The Westfall-Young minima are taken over the Fisher statistic of every gene", True, True,
-     "the successive minima run over all genes in one order; gene shards do not compose", False),
-    ("--cmh", "cmh", "The Cochran-Mantel-Haenszel test is a test of every gene, beside Fisher's", False, True,
-     "its results reach the host beside the gathered records of a single process", False),
-    ("--permute-strata", "strata", "The strata restrict the permutations of the Fisher statistic", True, False, None,
-     False),
-    ("--cmh-fwer", "cmh_fwer", "The Westfall-Young minima are taken over the Cochran-Mantel-Haenszel statistic of "
-     "every gene", True, True, "its results reach the host beside the gathered records of a single process", True),
-    ("--cmh-fwer-stepdown", "cmh_fwer_stepdown", "The Westfall-Young minima are taken over the "
-     "Cochran-Mantel-Haenszel statistic of every gene", True, True,
-     "the successive minima run over all genes in one order; gene shards do not compose", True),
-    # (their need of --cmh FILE has a message of its own, checked beside the row: RULE_TEXT["cmh_exact"])
-    ("--cmh-exact-odds", "cmh_exact_odds", "The exact conditional odds ratio is an estimate for every gene over the "
-     "strata, beside Fisher's test", False, False, "its results reach the host beside the gathered records of a "
-     "single process", False),
-    ("--cmh-exact", "cmh_exact", "The exact conditional test is a test of every gene over the strata, beside "
-     "Fisher's", False, False, "its results reach the host beside the gathered records of a single process", False),
+    FlagRule("--permute-fwer", "fwer", "The Westfall-Young minima are taken over the Fisher statistic of every gene",
+             True, True, None, None),
+    FlagRule("--permute-fwer-stepdown", "fwer_stepdown",
+             "The Westfall-Young minima are taken over the Fisher statistic of every gene", True, True,
+             "the successive minima run over all genes in one order; gene shards do not compose", None),
+    FlagRule("--cmh", "cmh", "The Cochran-Mantel-Haenszel test is a test of every gene, beside Fisher's", False, True,
+             "its results reach the host beside the gathered records of a single process", None),
+    FlagRule("--permute-strata", "strata", "The strata restrict the permutations of the Fisher statistic", True, False,
+             None, None),
+    FlagRule("--cmh-fwer", "cmh_fwer", "The Westfall-Young minima are taken over the Cochran-Mantel-Haenszel statistic "
+             "of every gene", True, True, "its results reach the host beside the gathered records of a single process",
+             "cmh"),
+    FlagRule("--cmh-fwer-stepdown", "cmh_fwer_stepdown", "The Westfall-Young minima are taken over the "
+             "Cochran-Mantel-Haenszel statistic of every gene", True, True,
+             "the successive minima run over all genes in one order; gene shards do not compose", "cmh"),
+    FlagRule("--cmh-exact-odds", "cmh_exact_odds", "The exact conditional odds ratio is an estimate for every gene "
+             "over the strata, beside Fisher's test", False, False, "its results reach the host beside the gathered "
+             "records of a single process", "cmh_exact"),
+    FlagRule("--cmh-exact", "cmh_exact", "The exact conditional test is a test of every gene over the strata, beside "
+             "Fisher's", False, False, "its results reach the host beside the gathered records of a single process",
+             "cmh_exact"),
 )
 # a broken rule as the command line reports it / as Setup_results raises it
 RULE_TEXT = {
@@ -840,30 +839,24 @@ def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None, cmh=
     ``files``: the messages of the command line's checks of the flag's own file, which come before the rank rule
     (() for a flag without one); None: the run is Setup_results' and the messages are its ValueErrors.  ``cmh``: the
     run has --cmh FILE / cmh=True."""
-    flag, kw, sentence, needs_permutations, no_early_abort, one_rank, needs_cmh = rule
-
     def text(what, why=None):
-        return RULE_TEXT[what][files is None] % {"flag": flag, "kw": kw, "why": why}
+        return RULE_TEXT[what][files is None] % {"flag": rule.flag, "kw": rule.kw, "why": why}
     if not no_pairwise:
-        yield text("no_pairwise", sentence)
-    if needs_permutations and permutations < 10:
+        yield text("no_pairwise", rule.sentence)
+    if rule.needs_permutations and permutations < 10:
         yield text("permutations")
-    if no_early_abort and early_abort:
+    if rule.no_early_abort and early_abort:
         yield text("early_abort")
-    if needs_cmh and not cmh:
-        yield text("cmh")
-    if kw in ("cmh_exact", "cmh_exact_odds") and not cmh:
-        yield text("cmh_exact")
+    if rule.needs_cmh and not cmh:
+        yield text(rule.needs_cmh)
     yield from files or ()
-    if one_rank:
+    if rule.one_rank:
         from . import dist
         if dist.world_rank()[0] > 1:
-            yield text("ranks", one_rank)
+            yield text("ranks", rule.one_rank)
 
 
-def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, fwer=False,
-               fwer_stepdown=False, strata=None, cmh=False, cmh_fwer=False, cmh_fwer_stepdown=False,
-               cmh_exact=False, cmh_exact_odds=False, cmh_exact_level=0.95):
+def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False, strata=None, options=None):
     """Whole hot path for all traits; under torchrun (world > 1) every rank
     takes a stride gene shard (dist.GenePartition: the reference's domains,
     scoary/methods.py:1076-1078) and the per-gene records are all-gathered
@@ -871,12 +864,13 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
     ``early_abort``: the reference's sequential estimator (scoary/methods.py:1360-1363)
     on the Fisher statistic instead of the fixed-P count: out["nstop"] then holds the
     permutation count every gene stopped at (0 = ran to the end).
+    ``strata``: the stratum index of every isolate of the table (--permute-strata): every permutation shuffles
+    the labels within the strata only (spec S9); every rank generates the same labels.
+    ``options``: Setup_results' ``active`` mapping with "cmh_exact_level" (None: nothing optional).  Its keys:
     ``fwer`` / ``fwer_stepdown``: the Westfall-Young results (engine.westfall_young, spec S7 / S8): out["minp"]
     [T, P] and out["r_fwer"] / out["r_fwer_sd"] [T, G].  Under gene sharding every rank takes the minima over its
     own genes and one all_reduce(MIN) of the [T, P] doubles precedes the count of r_fwer; the step-down counts do
     not compose over shards (single process only).
-    ``strata``: the stratum index of every isolate of the table (--permute-strata): every permutation shuffles
-    the labels within the strata only (spec S9); every rank generates the same labels.
     ``cmh`` (needs ``strata``; single process, no early abort): the Cochran-Mantel-Haenszel test over the strata
     (spec S10): out["cmh_p"], out["cmh_odds"] [T, G] and, with permutations, out["r_cmh"].
     ``cmh_fwer`` / ``cmh_fwer_stepdown`` (need ``cmh`` and permutations): the Westfall-Young passes over the CMH
@@ -889,13 +883,15 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
     How each of these arrays reaches the host: OPTIONAL_COLUMNS."""
     import torch
     from . import dist
+    opt = {**dict.fromkeys((rule.kw for rule in FLAG_RULES), False), **(options or {})}
     eng = get_engine()
     G, N, T = len(table), len(table.strains), tarr.shape[0]
     with _stage("device setup (H2D, tiling, trait plan)"):
         trv = eng.vecrows(pack_bits_rows(tarr == 1), N)
         mkv = eng.vecrows(pack_bits_rows(tarr != 2), N)
         plan = eng.trait_plan(trv, mkv, N)            # margins + mask classes: once per trait set
-        sp = eng.strata_plan(strata, trv, mkv, N) if strata is not None and (permutations > 0 or cmh) else None
+        with_strata = strata is not None and (permutations > 0 or opt["cmh"])
+        sp = eng.strata_plan(strata, trv, mkv, N) if with_strata else None
 
     def scipy_digits(res):
         # Up to 170 isolates k_fisher's p IS scipy.stats.fisher_exact's double; above, it is the exact value of SciPy's
@@ -918,7 +914,7 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         a = sel.start
         whole = sel == slice(0, G, 1)
         if len(range(*sel.indices(G))) == 0:
-            if fwer:            # a rank without genes still takes part in the reduction of the minima
+            if opt["fwer"]:     # a rank without genes still takes part in the reduction of the minima
                 beside["minp"] = dist.all_reduce_min(torch.ones((T, permutations), dtype=torch.float64,
                                                                 device=eng.device))
             return torch.zeros((T, 0, dist.REC_WORDS), dtype=torch.int32, device=eng.device)
@@ -953,23 +949,23 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
             res["r"] = r
             return eng.pack_records(res, nstop=nstop)
         with _stage("kernels (counts, Fisher, permutations)"):
-            res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan, strata=sp, cmh=cmh,
-                                cmh_exact=cmh_exact, cmh_exact_odds=cmh_exact_odds, cmh_exact_level=cmh_exact_level)
+            res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan, strata=sp,
+                                cmh=opt["cmh"], cmh_exact=opt["cmh_exact"], cmh_exact_odds=opt["cmh_exact_odds"],
+                                cmh_exact_level=opt.get("cmh_exact_level", DEFAULT_EXACT_LEVEL))
             torch.cuda.synchronize(eng.device)
-        beside.update({k: res[k] for k in ("cmh_p", "cmh_odds", "r_cmh", "cmh_exact_p") +
-                       tuple(key for _name, key, _count in EXACT_ODDS_COLUMNS) if k in res})
-        if fwer or fwer_stepdown:
-            with _stage("Westfall-Young step-down minP (p tables, k_stepdown_minp)" if fwer_stepdown else
+        beside.update({key: res[key] for _name, key, _count in OPTIONAL_COLUMNS if key in res})
+        if opt["fwer"] or opt["fwer_stepdown"]:
+            with _stage("Westfall-Young step-down minP (p tables, k_stepdown_minp)" if opt["fwer_stepdown"] else
                         "Westfall-Young minP (p tables, k_permute_minp)"):
                 # before the SciPy-digits pass rewrites the last ulp of p (westfall_young)
-                beside.update(eng.westfall_young(gm, trv, mkv, permutations, seed, res, fwer, fwer_stepdown,
-                                                 strata=sp, reduce=dist.all_reduce_min))
+                beside.update(eng.westfall_young(gm, trv, mkv, permutations, seed, res, opt["fwer"],
+                                                 opt["fwer_stepdown"], strata=sp, reduce=dist.all_reduce_min))
                 torch.cuda.synchronize(eng.device)
-        if cmh_fwer or cmh_fwer_stepdown:
+        if opt["cmh_fwer"] or opt["cmh_fwer_stepdown"]:
             with _stage("Westfall-Young minP of the CMH statistic (tables, %s)"
-                        % ("k_stepdown_minp" if cmh_fwer_stepdown else "k_permute_minp")):
-                beside.update(eng.westfall_young(gm, trv, mkv, permutations, seed, res, strata=sp, cmh_fwer=cmh_fwer,
-                                                 cmh_stepdown=cmh_fwer_stepdown))
+                        % ("k_stepdown_minp" if opt["cmh_fwer_stepdown"] else "k_permute_minp")):
+                beside.update(eng.westfall_young(gm, trv, mkv, permutations, seed, res, strata=sp,
+                                                 cmh_fwer=opt["cmh_fwer"], cmh_stepdown=opt["cmh_fwer_stepdown"]))
                 torch.cuda.synchronize(eng.device)
         scipy_digits(res)
         with _stage("kernels (counts, Fisher, permutations)"):
@@ -989,11 +985,11 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         out["p_order"] = p_order
     if permutations <= 0:
         out["r"] = None
-    if fwer:
+    if opt["fwer"]:
         out["r_fwer"], out["nstop"] = out["nstop"], np.zeros_like(out["nstop"])
-    if fwer_stepdown:
+    if opt["fwer_stepdown"]:
         out["r_fwer_sd"] = np.zeros((T, 0), dtype=np.int32)         # (a table without genes)
-    for key in ("minp",) + tuple(key for _name, key, _count in ALL_OPTIONAL_COLUMNS):
+    for key in ("minp",) + tuple(key for _name, key, _count in OPTIONAL_COLUMNS):
         if key in beside:
             out[key] = beside[key].cpu().numpy()
     return out
@@ -1084,16 +1080,15 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
               "cmh_exact_odds": cmh_exact_odds}
     if cmh_exact_odds and not 0.0 < float(cmh_exact_level) < 1.0:
         raise ValueError("cmh_exact_level must lie inside (0, 1), not %r" % (cmh_exact_level,))
-    for rule in (rule for rule in FLAG_RULES if active[rule[1]]):
+    for rule in (rule for rule in FLAG_RULES if active[rule.kw]):
         for text in _broken_rules(rule, True, permutations, early_abort, cmh=cmh):
             raise ValueError(text)
     table = _as_table(genedic)
     names, tarr = _trait_arrays(traitsdic, table.strains)
     if strata is not None and len(strata) != len(table.strains):
         raise ValueError("strata: one stratum index per isolate of the gene table")
-    dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, fwer, fwer_stepdown,
-                     strata=strata, cmh=cmh, cmh_fwer=cmh_fwer, cmh_fwer_stepdown=cmh_fwer_stepdown,
-                     cmh_exact=cmh_exact, cmh_exact_odds=cmh_exact_odds, cmh_exact_level=cmh_exact_level)
+    dev = _associate(table, tarr, permutations if permutations >= 10 else 0, seed, early_abort, strata,
+                     {**active, "cmh_exact_level": cmh_exact_level})
     collapse_hashes = None
     if collapse:
         eng = get_engine()
@@ -1180,7 +1175,7 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
                 "B_p": B, "BH_p": BH}
         if emp is not None:
             cols["Empirical_p"] = emp[rows_idx]
-        for name, key, count in ALL_OPTIONAL_COLUMNS:
+        for name, key, count in OPTIONAL_COLUMNS:
             if key in dev:
                 v = dev[key][t][rows_idx]
                 cols[name] = (v.view(np.uint32).astype(np.float64) + 1.0) / (permutations + 1.0) if count else v
@@ -1530,7 +1525,7 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
     if not isinstance(Trait, TraitResults):
         Trait = _trait_results_from_dict(Trait)
     # (a count has its denominator from the permutations: without them it is not written)
-    optional = [name for name, _key, count in ALL_OPTIONAL_COLUMNS
+    optional = [name for name, _key, count in OPTIONAL_COLUMNS
                 if no_pairwise and name in Trait.cols and (with_emp or not count)]
     columns += optional
     columns += list(extracolstoprint)
@@ -1619,7 +1614,7 @@ def _trait_results_from_dict(rows):
     """Plain {gene: row dict} (the reference's Results[trait]) -> TraitResults."""
     genes = list(rows.keys())
     cols = {}
-    for k in TraitResults.FIELDS + ("Empirical_p",) + tuple(name for name, _key, _count in ALL_OPTIONAL_COLUMNS):
+    for k in TraitResults.FIELDS + ("Empirical_p",) + tuple(name for name, _key, _count in OPTIONAL_COLUMNS):
         if genes and k in rows[genes[0]]:
             cols[k] = np.array([rows[g][k] for g in genes])
     return TraitResults(genes, [rows[g]["NUGN"] for g in genes],
@@ -1935,16 +1930,14 @@ def main(**kwargs):
             if args.permute >= 10:
                 log.info("Permuting trait labels within %d strata of %d to %d isolates (%s)"
                          % (len(labels), int(sizes.min()), int(sizes.max()), args.permute_strata or args.cmh))
+        # the flags' keywords, by _validate's mapping; the two flags that name a file arrive as ``strata`` and a bool
+        flags = {rule.kw: getattr(args, rule.flag[2:].replace("-", "_"), False)
+                 for rule in FLAG_RULES if rule.flag not in ("--cmh", "--permute-strata")}
         res = Setup_results(genedic, traitsdic, args.collapse,
                             permutations=args.permute if args.no_pairwise else 0, seed=seed,
-                            early_abort=getattr(args, "permute_early_abort", False),
-                            fwer=getattr(args, "permute_fwer", False),
-                            fwer_stepdown=getattr(args, "permute_fwer_stepdown", False), strata=strata,
-                            cmh=bool(getattr(args, "cmh", None)), cmh_fwer=getattr(args, "cmh_fwer", False),
-                            cmh_fwer_stepdown=getattr(args, "cmh_fwer_stepdown", False),
-                            cmh_exact=getattr(args, "cmh_exact", False),
-                            cmh_exact_odds=getattr(args, "cmh_exact_odds", False),
-                            cmh_exact_level=getattr(args, "cmh_exact_level", None) or DEFAULT_EXACT_LEVEL)
+                            early_abort=getattr(args, "permute_early_abort", False), strata=strata,
+                            cmh=bool(getattr(args, "cmh", None)),
+                            cmh_exact_level=getattr(args, "cmh_exact_level", None) or DEFAULT_EXACT_LEVEL, **flags)
         t_stats = _time.time()
         if args.upgma_tree and rank == 0:
             # (with --no_pairwise there is no tree and the reference writes str(None) + ";", :277-280, :741-751)
@@ -2080,9 +2073,9 @@ def _validate(args, cutoffs):
                  "sequence. e.g. -c I EPW -p 0.1 0.05 will apply an individual p-value cutoff "
                  "of 0.1 AND a pairwise comparisons p-value cutoff of 0.05.")
     for rule in FLAG_RULES:
-        value = getattr(args, rule[0][2:].replace("-", "_"), None)
+        value = getattr(args, rule.flag[2:].replace("-", "_"), None)
         if value:
-            files = _strata_file_problems(args, rule[0], value) if isinstance(value, str) else ()
+            files = _strata_file_problems(args, rule.flag, value) if isinstance(value, str) else ()
             for text in _broken_rules(rule, args.no_pairwise, args.permute,
                                       getattr(args, "permute_early_abort", False), files,
                                       cmh=bool(getattr(args, "cmh", None))):

@@ -7,41 +7,7 @@ import sys
 
 import pytest
 
-
-def _strains(exampledir):
-    with open(os.path.join(exampledir, "Gene_presence_absence.csv")) as f:
-        return f.readline().rstrip("\n").split(",")[14:]
-
-
-def _strata_file(tmp_path, rows, name="strata.csv"):
-    path = os.path.join(str(tmp_path), name)
-    with open(path, "w") as f:
-        f.write("Isolate,Stratum\n")
-        for r in rows:
-            f.write(",".join(r) + "\n")
-    return path
-
-
-def _run(argv, exampledir, tmp_path, monkeypatch):
-    from scoary_amd import methods as m
-
-    def no_engine():
-        raise AssertionError("the engine was started before the arguments were refused")
-    monkeypatch.setattr(m, "get_engine", no_engine)
-    monkeypatch.setenv("SCOARY_OVERLAP_STARTUP", "0")
-    out = os.path.join(str(tmp_path), "out")
-    monkeypatch.setattr(sys, "argv", ["scoary", "-g", os.path.join(exampledir, "Gene_presence_absence.csv"),
-                                      "-t", os.path.join(exampledir, "Tetracycline_resistance.csv"),
-                                      "-o", out, "--no-time"] + argv)
-    with pytest.raises(SystemExit) as e:
-        m.main()
-    assert not [f for f in os.listdir(out) if f.endswith(".results.csv")]
-    assert isinstance(e.value.code, str), e.value.code
-    return e.value.code
-
-
-def _good_rows(exampledir):
-    return [(s, "L%d" % (i % 3)) for i, s in enumerate(_strains(exampledir))]
+from args_cases import good_rows as _good_rows, run_refused as _run, strains as _strains, strata_file as _strata_file
 
 
 def test_refused_without_no_pairwise_and_with_early_abort(exampledir, tmp_path, monkeypatch):

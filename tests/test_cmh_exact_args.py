@@ -2,39 +2,13 @@
 Setup_results (the same rules as ValueErrors), the place of the column and the resource rule of the kernel (the
 declarations of the entry points: test_host_logic.py)."""
 import os
-import sys
 
 import pytest
 
+from args_cases import COLUMNS, good_strata_file as _strata_file, rule_of, run_refused as _run
+
 FLAG, KW = "--cmh-exact", "cmh_exact"
 NO_CMH = "Cannot use --cmh-exact without --cmh FILE. The exact test is taken over the strata of FILE"
-
-
-def _strata_file(exampledir, tmp_path):
-    with open(os.path.join(exampledir, "Gene_presence_absence.csv")) as f:
-        strains = f.readline().rstrip("\n").split(",")[14:]
-    path = os.path.join(str(tmp_path), "strata.csv")
-    with open(path, "w") as f:
-        f.write("Isolate,Stratum\n" + "".join("%s,L%d\n" % (s, i % 3) for i, s in enumerate(strains)))
-    return path
-
-
-def _run(argv, exampledir, tmp_path, monkeypatch):
-    from scoary_amd import methods as m
-
-    def no_engine():
-        raise AssertionError("the engine was started before the arguments were refused")
-    monkeypatch.setattr(m, "get_engine", no_engine)
-    monkeypatch.setenv("SCOARY_OVERLAP_STARTUP", "0")
-    out = os.path.join(str(tmp_path), "out")
-    monkeypatch.setattr(sys, "argv", ["scoary", "-g", os.path.join(exampledir, "Gene_presence_absence.csv"),
-                                      "-t", os.path.join(exampledir, "Tetracycline_resistance.csv"),
-                                      "-o", out, "--no-time"] + argv)
-    with pytest.raises(SystemExit) as e:
-        m.main()
-    assert not [f for f in os.listdir(out) if f.endswith(".results.csv")]
-    assert isinstance(e.value.code, str), e.value.code
-    return e.value.code
 
 
 def test_flag_parsing():
@@ -61,16 +35,16 @@ def test_command_line_refusals(exampledir, tmp_path, monkeypatch):
     assert run(["--no_pairwise", FLAG, "-e", "100", "--permute-strata", path]) == NO_CMH
     assert run(["--no_pairwise", FLAG, "--cmh", path, "-e", "100", "--permute-early-abort"]) \
         .startswith("Cannot use --cmh together with --permute-early-abort")
-    rule = [r for r in m.FLAG_RULES if r[0] == FLAG][0]
+    rule = rule_of(FLAG)
     assert list(m._broken_rules(rule, False, 0, False, (), cmh=False)) == [no_pairwise, NO_CMH]
     assert list(m._broken_rules(rule, True, 0, False, (), cmh=True)) == []         # no permutations needed
     assert list(m._broken_rules(rule, True, 100, False, (), cmh=True)) == []
     monkeypatch.setattr(dist, "world_rank", lambda: (2, 0))
     assert run(["--no_pairwise", FLAG, "--cmh", path]).startswith("Cannot use --cmh under more than one rank")
     assert list(m._broken_rules(rule, True, 0, False, (), cmh=True)) == \
-        ["Cannot use --cmh-exact under more than one rank: %s" % rule[5]]
+        ["Cannot use --cmh-exact under more than one rank: %s" % rule.one_rank]
     assert list(m._broken_rules(rule, True, 0, False, None, cmh=True)) == \
-        ["cmh_exact needs a single process: %s" % rule[5]]
+        ["cmh_exact needs a single process: %s" % rule.one_rank]
 
 
 def test_setup_results_raises_the_same_rules():
@@ -88,16 +62,13 @@ def test_the_engine_refuses_the_exact_test_without_cmh():
         AssociationEngine.associate(None, None, None, None, cmh_exact=True)
 
 
-def test_column_is_the_last_and_the_rule_keeps_the_shape_of_its_row():
+def test_columns_are_in_file_order_and_the_rule_keeps_the_shape_of_its_row():
     from scoary_amd import methods as m
-    assert m.OPTIONAL_COLUMNS[-1] == ("CMH_exact_p", "cmh_exact_p", False)
-    assert [name for name, _key, _count in m.OPTIONAL_COLUMNS[:-1]] == [
-        "Westfall_Young_p", "Westfall_Young_stepdown_p", "CMH_p", "CMH_odds_ratio", "CMH_empirical_p",
-        "CMH_Westfall_Young_p", "CMH_Westfall_Young_stepdown_p"]
-    assert all(len(rule) == 7 for rule in m.FLAG_RULES)
-    flag, key, _sentence, needs_permutations, no_early_abort, one_rank, needs_cmh = m.FLAG_RULES[-1]
-    assert (flag, key, needs_permutations, no_early_abort, needs_cmh) == (FLAG, KW, False, False, False)
-    assert one_rank == [r for r in m.FLAG_RULES if r[0] == "--cmh"][0][5]
+    assert m.OPTIONAL_COLUMNS == COLUMNS
+    rule = rule_of(FLAG)
+    assert rule is m.FLAG_RULES[len(m.FLAG_RULES) - 1]                      # checked after every other flag
+    assert (rule.kw, rule.needs_permutations, rule.no_early_abort, rule.needs_cmh) == (KW, False, False, "cmh_exact")
+    assert rule.one_rank == rule_of("--cmh").one_rank
     assert m.RULE_TEXT["cmh_exact"][0] % {"flag": FLAG} == NO_CMH
 
 

@@ -1,12 +1,11 @@
 """--cmh-exact-odds / --cmh-exact-level: the argument checks on the command line (they exit before the engine is
 touched) and in Setup_results / associate (the same rules as ValueErrors), the place of the three columns and of the
-rule row beside the pins test_cmh_exact_args.py keeps, the binding and the resource rule of the kernel."""
+rule row, the binding and the resource rule of the kernel."""
 import os
-import sys
 
 import pytest
 
-from test_cmh_exact_args import _strata_file
+from args_cases import COLUMNS, good_strata_file as _strata_file, rule_of, run_refused as _run
 
 FLAG, KW = "--cmh-exact-odds", "cmh_exact_odds"
 NO_CMH = "Cannot use --cmh-exact-odds without --cmh FILE. The exact test is taken over the strata of FILE"
@@ -16,24 +15,6 @@ NO_ODDS = ("Cannot use --cmh-exact-level without --cmh-exact-odds. It is the con
            "exact conditional odds ratio")
 BAD_LEVEL = "The confidence level of --cmh-exact-level must be between 0.0 and 1.0 (both excluded)"
 NAMES = ["CMH_exact_odds_ratio", "CMH_exact_odds_ratio_lower", "CMH_exact_odds_ratio_upper"]
-
-
-def _run(argv, exampledir, tmp_path, monkeypatch):
-    from scoary_amd import methods as m
-
-    def no_engine():
-        raise AssertionError("the engine was started before the arguments were refused")
-    monkeypatch.setattr(m, "get_engine", no_engine)
-    monkeypatch.setenv("SCOARY_OVERLAP_STARTUP", "0")
-    out = os.path.join(str(tmp_path), "out")
-    monkeypatch.setattr(sys, "argv", ["scoary", "-g", os.path.join(exampledir, "Gene_presence_absence.csv"),
-                                      "-t", os.path.join(exampledir, "Tetracycline_resistance.csv"),
-                                      "-o", out, "--no-time"] + argv)
-    with pytest.raises(SystemExit) as e:
-        m.main()
-    assert not [f for f in os.listdir(out) if f.endswith(".results.csv")]
-    assert isinstance(e.value.code, str), e.value.code
-    return e.value.code
 
 
 def test_flag_parsing():
@@ -58,16 +39,16 @@ def test_command_line_refusals(exampledir, tmp_path, monkeypatch):
     assert run(["--no_pairwise", FLAG, "-e", "100", "--permute-strata", path]) == NO_CMH
     assert run(["--no_pairwise", FLAG, "--cmh", path, "-e", "100", "--permute-early-abort"]) \
         .startswith("Cannot use --cmh together with --permute-early-abort")
-    rule = [r for r in m.FLAG_RULES if r[0] == FLAG][0]
+    rule = rule_of(FLAG)
     assert list(m._broken_rules(rule, False, 0, False, (), cmh=False)) == [NO_PAIRWISE, NO_CMH]
     assert list(m._broken_rules(rule, True, 0, False, (), cmh=True)) == []         # no permutations needed
     assert list(m._broken_rules(rule, True, 100, True, (), cmh=True)) == []
     monkeypatch.setattr(dist, "world_rank", lambda: (2, 0))
     assert run(["--no_pairwise", FLAG, "--cmh", path]).startswith("Cannot use --cmh under more than one rank")
     assert list(m._broken_rules(rule, True, 0, False, (), cmh=True)) == \
-        ["Cannot use --cmh-exact-odds under more than one rank: %s" % rule[5]]
+        ["Cannot use --cmh-exact-odds under more than one rank: %s" % rule.one_rank]
     assert list(m._broken_rules(rule, True, 0, False, None, cmh=True)) == \
-        ["cmh_exact_odds needs a single process: %s" % rule[5]]
+        ["cmh_exact_odds needs a single process: %s" % rule.one_rank]
 
 
 def test_the_level_is_refused_outside_its_range_and_without_the_flag(exampledir, tmp_path, monkeypatch):
@@ -107,20 +88,15 @@ def test_the_engine_refuses_the_odds_without_cmh_and_a_level_outside_its_range()
 
 def test_columns_come_after_every_other_and_the_existing_pins_hold():
     from scoary_amd import methods as m
-    assert [name for name, _key, _count in m.EXACT_ODDS_COLUMNS] == NAMES
-    assert [key for _name, key, _count in m.EXACT_ODDS_COLUMNS] == [
-        "cmh_exact_odds", "cmh_exact_odds_lower", "cmh_exact_odds_upper"]
-    assert not any(count for _name, _key, count in m.EXACT_ODDS_COLUMNS)
-    assert m.ALL_OPTIONAL_COLUMNS == m.OPTIONAL_COLUMNS + m.EXACT_ODDS_COLUMNS
-    # the pins of test_cmh_exact_args.py and test_cmh_wy_args.py
-    assert m.OPTIONAL_COLUMNS[-1] == ("CMH_exact_p", "cmh_exact_p", False) and len(m.OPTIONAL_COLUMNS) == 8
-    assert not set(NAMES) & {name for name, _key, _count in m.OPTIONAL_COLUMNS}
-    assert all(len(rule) == 7 for rule in m.FLAG_RULES)
-    assert m.FLAG_RULES[-1][:2] == ("--cmh-exact", "cmh_exact")
-    flag, key, _sentence, needs_permutations, no_early_abort, one_rank, needs_cmh = m.FLAG_RULES[-2]
-    assert (flag, key, needs_permutations, no_early_abort, needs_cmh) == (FLAG, KW, False, False, False)
-    assert one_rank == [r for r in m.FLAG_RULES if r[0] == "--cmh"][0][5]
-    assert [r[0] for r in m.FLAG_RULES if r[6]] == ["--cmh-fwer", "--cmh-fwer-stepdown"]
+    assert m.OPTIONAL_COLUMNS == COLUMNS and [name for name, _key, _count in COLUMNS[len(COLUMNS) - 3:]] == NAMES
+    flags = [r.flag for r in m.FLAG_RULES]
+    assert flags[len(flags) - 2:] == [FLAG, "--cmh-exact"]                  # checked before --cmh-exact, written after
+    assert flags.index("--cmh") < flags.index("--cmh-fwer")
+    rule = rule_of(FLAG)
+    assert (rule.kw, rule.needs_permutations, rule.no_early_abort, rule.needs_cmh) == (KW, False, False, "cmh_exact")
+    assert rule.one_rank == rule_of("--cmh").one_rank
+    assert {r.flag: r.needs_cmh for r in m.FLAG_RULES if r.needs_cmh} == {
+        "--cmh-fwer": "cmh", "--cmh-fwer-stepdown": "cmh", FLAG: "cmh_exact", "--cmh-exact": "cmh_exact"}
     assert m.RULE_TEXT["cmh_exact"][0] % {"flag": FLAG} == NO_CMH
 
 

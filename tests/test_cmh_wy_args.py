@@ -3,38 +3,12 @@ and in Setup_results (the same rules as ValueErrors), the place of the two colum
 table kernels (the declarations of the entry points: test_host_logic.py)."""
 import os
 import re
-import sys
 
 import pytest
 
+from args_cases import COLUMNS, good_strata_file as _strata_file, rule_of, run_refused as _run
+
 FLAGS = (("--cmh-fwer", "cmh_fwer"), ("--cmh-fwer-stepdown", "cmh_fwer_stepdown"))
-
-
-def _strata_file(exampledir, tmp_path):
-    with open(os.path.join(exampledir, "Gene_presence_absence.csv")) as f:
-        strains = f.readline().rstrip("\n").split(",")[14:]
-    path = os.path.join(str(tmp_path), "strata.csv")
-    with open(path, "w") as f:
-        f.write("Isolate,Stratum\n" + "".join("%s,L%d\n" % (s, i % 3) for i, s in enumerate(strains)))
-    return path
-
-
-def _run(argv, exampledir, tmp_path, monkeypatch):
-    from scoary_amd import methods as m
-
-    def no_engine():
-        raise AssertionError("the engine was started before the arguments were refused")
-    monkeypatch.setattr(m, "get_engine", no_engine)
-    monkeypatch.setenv("SCOARY_OVERLAP_STARTUP", "0")
-    out = os.path.join(str(tmp_path), "out")
-    monkeypatch.setattr(sys, "argv", ["scoary", "-g", os.path.join(exampledir, "Gene_presence_absence.csv"),
-                                      "-t", os.path.join(exampledir, "Tetracycline_resistance.csv"),
-                                      "-o", out, "--no-time"] + argv)
-    with pytest.raises(SystemExit) as e:
-        m.main()
-    assert not [f for f in os.listdir(out) if f.endswith(".results.csv")]
-    assert isinstance(e.value.code, str), e.value.code
-    return e.value.code
 
 
 @pytest.mark.parametrize("flag,kw", FLAGS)
@@ -42,7 +16,7 @@ def test_command_line_refusals(exampledir, tmp_path, monkeypatch, flag, kw):
     path = _strata_file(exampledir, tmp_path)
     run = lambda argv: _run(argv, exampledir, tmp_path, monkeypatch)          # noqa: E731
     from scoary_amd import methods as m
-    rule = [r for r in m.FLAG_RULES if r[0] == flag][0]
+    rule = rule_of(flag)
     no_pairwise = ("Cannot use %s without --no_pairwise. The Westfall-Young minima are taken over the "
                    "Cochran-Mantel-Haenszel statistic of every gene" % flag)
     early_abort = ("Cannot use %s together with --permute-early-abort. Every gene has to see every permutation"
@@ -73,9 +47,8 @@ def test_rank_rule(exampledir, tmp_path, monkeypatch, flag, kw):
     # --cmh's own rank rule is met first (its row comes first); alone, the new flag's rule has the row's reason
     assert code.startswith("Cannot use --cmh under more than one rank"), code
     from scoary_amd import methods as m
-    rule = [r for r in m.FLAG_RULES if r[0] == flag][0]
-    why = {"--cmh-fwer": [r for r in m.FLAG_RULES if r[0] == "--cmh"][0][5],
-           "--cmh-fwer-stepdown": [r for r in m.FLAG_RULES if r[0] == "--permute-fwer-stepdown"][0][5]}[flag]
+    rule = rule_of(flag)
+    why = {"--cmh-fwer": rule_of("--cmh"), "--cmh-fwer-stepdown": rule_of("--permute-fwer-stepdown")}[flag].one_rank
     assert why and list(m._broken_rules(rule, True, 100, False, (), cmh=True)) == \
         ["Cannot use %s under more than one rank: %s" % (flag, why)]
     assert list(m._broken_rules(rule, True, 100, False, None, cmh=True)) == \
@@ -109,20 +82,17 @@ def test_flags_are_off_by_default_and_may_all_be_combined():
 
 def test_columns_and_rules_are_in_their_places():
     from scoary_amd import methods as m
-    names = [name for name, _key, _count in m.OPTIONAL_COLUMNS]
-    at = names.index("CMH_empirical_p")
-    assert names[at + 1:at + 3] == ["CMH_Westfall_Young_p", "CMH_Westfall_Young_stepdown_p"]
-    assert m.OPTIONAL_COLUMNS[at + 1][1:] == ("r_cmh_fwer", True) and m.OPTIONAL_COLUMNS[at + 2][1:] == \
-        ("r_cmh_fwer_sd", True)
-    assert names[:at + 1] == ["Westfall_Young_p", "Westfall_Young_stepdown_p", "CMH_p", "CMH_odds_ratio",
-                              "CMH_empirical_p"]
-    rules = {r[0]: r for r in m.FLAG_RULES}
+    assert m.OPTIONAL_COLUMNS == COLUMNS
+    at = COLUMNS.index(("CMH_empirical_p", "r_cmh", True))
+    assert COLUMNS[at + 1:at + 3] == (("CMH_Westfall_Young_p", "r_cmh_fwer", True),
+                                      ("CMH_Westfall_Young_stepdown_p", "r_cmh_fwer_sd", True))
     for flag, kw in FLAGS:
-        _flag, key, _sentence, needs_permutations, no_early_abort, one_rank, needs_cmh = rules[flag]
-        assert (key, needs_permutations, no_early_abort, needs_cmh) == (kw, True, True, True) and one_rank
-    assert rules["--cmh-fwer"][5] == rules["--cmh"][5]
-    assert rules["--cmh-fwer-stepdown"][5] == rules["--permute-fwer-stepdown"][5]
-    assert not any(r[6] for f, r in rules.items() if f not in dict(FLAGS))
+        rule = rule_of(flag)
+        assert (rule.kw, rule.needs_permutations, rule.no_early_abort, rule.needs_cmh) == (kw, True, True, "cmh")
+        assert rule.one_rank
+    assert rule_of("--cmh-fwer").one_rank == rule_of("--cmh").one_rank
+    assert rule_of("--cmh-fwer-stepdown").one_rank == rule_of("--permute-fwer-stepdown").one_rank
+    assert [r.flag for r in m.FLAG_RULES if r.needs_cmh == "cmh"] == [flag for flag, _kw in FLAGS]
 
 
 def test_table_kernels_compiled_without_scratch_or_spills_and_k_cmh_is_one_kernel_still():

@@ -239,8 +239,9 @@ def _run_cli(argv, outdir, trait):
     return text, list(csv.reader(io.StringIO(text)))
 
 
-def test_cli_columns_are_the_last_and_hold_the_engines_values(eng, tmp_path):
-    from scoary_amd import methods as m
+def _cli_files(tmp_path):
+    """A gene table of 40 genes x 90 isolates, one trait and a strata file of 4 strata under ``tmp_path``: (the three
+    paths, genes, trait, strata, the isolates' names)."""
     N, G, S = 90, 40, 4
     rng = np.random.default_rng(91)
     genes = (rng.random((G, N)) < rng.uniform(0.1, 0.9, (G, 1))).astype(np.uint8)
@@ -259,6 +260,12 @@ def test_cli_columns_are_the_last_and_hold_the_engines_values(eng, tmp_path):
         f.write(",resistance\n" + "".join("%s,%d\n" % (s, v) for s, v in zip(strains, trait)))
     with open(sf, "w") as f:
         f.write("Isolate,Lineage\n" + "".join("%s,L%d\n" % (s, v) for s, v in zip(strains, strata)))
+    return (gpa, tr, sf), genes, trait, strata, strains
+
+
+def test_cli_columns_are_the_last_and_hold_the_engines_values(eng, tmp_path):
+    from scoary_amd import methods as m
+    (gpa, tr, sf), genes, trait, _strata, strains = _cli_files(tmp_path)
     base = ["-g", gpa, "-t", tr, "--no_pairwise", "-p", "1.0", "--cmh", sf, "--cmh-exact"]
     old_text, old = _run_cli(base, tmp_path / "old", "resistance")
     names = ["CMH_exact_odds_ratio", "CMH_exact_odds_ratio_lower", "CMH_exact_odds_ratio_upper"]
@@ -283,3 +290,35 @@ def test_cli_columns_are_the_last_and_hold_the_engines_values(eng, tmp_path):
     assert [d[-3] for d in default[1:]] == [d[-3] for d in new[1:]] and default_text != _text      # the level is used
     again_text, _rows = _run_cli(base, tmp_path / "again", "resistance")
     assert again_text == old_text and "CMH_exact_odds" not in old_text
+
+
+def test_cli_every_optional_flag_at_once_writes_the_columns_of_each_flag_alone(eng, tmp_path):
+    """associate()'s "every other result is that of the same call without the option, bit for bit", seen at the file:
+    every column of a run with all six optional flags has the cell texts of the run that had only its flag."""
+    from scoary_amd import methods as m
+    (gpa, tr, sf), _genes, _trait, _strata, _strains = _cli_files(tmp_path)
+    base = ["-g", gpa, "-t", tr, "--no_pairwise", "-p", "1.0", "--cmh", sf, "-e", "100"]
+    flags = {"--permute-fwer": ["Westfall_Young_p"], "--permute-fwer-stepdown": ["Westfall_Young_stepdown_p"],
+             "--cmh-fwer": ["CMH_Westfall_Young_p"], "--cmh-fwer-stepdown": ["CMH_Westfall_Young_stepdown_p"],
+             "--cmh-exact": ["CMH_exact_p"],
+             "--cmh-exact-odds": ["CMH_exact_odds_ratio", "CMH_exact_odds_ratio_lower", "CMH_exact_odds_ratio_upper"]}
+    _text, plain = _run_cli(base, tmp_path / "plain", "resistance")
+    _text, full = _run_cli(base + list(flags), tmp_path / "full", "resistance")
+    # the header: the columns of the base run and the eight of the flags, the optional ones in OPTIONAL_COLUMNS' order
+    # (so the Westfall-Young columns of the Fisher statistic stand before --cmh's own, not behind the base header)
+    added = [name for names in flags.values() for name in names]
+    optional = [name for name, _key, _count in m.OPTIONAL_COLUMNS]
+    assert len(added) == 8 and [c for c in full[0] if c not in added] == plain[0]
+    assert full[0] == [c for c in plain[0] if c not in optional] + optional
+    assert len(full) == len(plain) > 10
+
+    def column(table, name):
+        return [row[table[0].index(name)] for row in table[1:]]
+    for name in plain[0]:
+        assert column(full, name) == column(plain, name), name
+    for flag, names in flags.items():
+        _text, alone = _run_cli(base + [flag], tmp_path / flag.strip("-"), "resistance")
+        assert [c for c in alone[0] if c not in names] == plain[0] and set(names) <= set(alone[0]), flag
+        for name in alone[0]:
+            assert column(full, name) == column(alone, name), (flag, name)
+        assert all(len(set(column(alone, name))) > 1 for name in names), flag       # (the cells are values)

@@ -1,24 +1,8 @@
 """--permute-fwer-stepdown: the argument checks (host only -- they exit before the engine is touched; the declarations
 of the step-down entry points: test_host_logic.py)."""
-import os
-import sys
-
 import pytest
 
-
-def _run(argv, exampledir, tmp_path, monkeypatch):
-    from scoary_amd import methods as m
-
-    def no_engine():
-        raise AssertionError("the engine was started before the arguments were refused")
-    monkeypatch.setattr(m, "get_engine", no_engine)
-    monkeypatch.setenv("SCOARY_OVERLAP_STARTUP", "0")
-    monkeypatch.setattr(sys, "argv", ["scoary", "-g", os.path.join(exampledir, "Gene_presence_absence.csv"),
-                                      "-t", os.path.join(exampledir, "Tetracycline_resistance.csv"),
-                                      "-o", str(tmp_path), "--no-time"] + argv)
-    with pytest.raises(SystemExit) as e:
-        m.main()
-    return e.value.code
+from args_cases import run_refused as _run
 
 
 @pytest.mark.parametrize("argv,message", [
@@ -33,7 +17,6 @@ def _run(argv, exampledir, tmp_path, monkeypatch):
 def test_permute_fwer_stepdown_refusals(exampledir, tmp_path, monkeypatch, argv, message):
     code = _run(argv, exampledir, tmp_path, monkeypatch)
     assert isinstance(code, str) and code.startswith(message), code
-    assert not [f for f in os.listdir(tmp_path) if f.endswith(".results.csv")]
 
 
 def test_permute_fwer_stepdown_refuses_more_than_one_rank(exampledir, tmp_path, monkeypatch):
@@ -42,7 +25,6 @@ def test_permute_fwer_stepdown_refuses_more_than_one_rank(exampledir, tmp_path, 
     code = _run(["--permute-fwer-stepdown", "--no_pairwise", "-e", "100"], exampledir, tmp_path, monkeypatch)
     assert isinstance(code, str) and code.startswith("Cannot use --permute-fwer-stepdown under more than one rank"), code
     assert "the successive minima run over all genes in one order; gene shards do not compose" in code
-    assert not [f for f in os.listdir(tmp_path) if f.endswith(".results.csv")]
 
 
 def test_flag_is_off_by_default():

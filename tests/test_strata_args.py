@@ -1,44 +1,18 @@
 """--permute-strata: the argument checks (host only -- they exit before the engine is touched; the declarations of
 the stratified entry points: test_host_logic.py)."""
 import os
-import sys
 
 import pytest
 
-
-def _strains(exampledir):
-    with open(os.path.join(exampledir, "Gene_presence_absence.csv")) as f:
-        return f.readline().rstrip("\n").split(",")[14:]
+from args_cases import good_rows, run_refused as _run, strains as _strains, strata_file
 
 
 def _strata_file(tmp_path, rows, name="strata.csv", header="Isolate,Stratum,Note"):
-    path = os.path.join(str(tmp_path), name)
-    with open(path, "w") as f:
-        f.write(header + "\n")
-        for r in rows:
-            f.write(",".join(r) + "\n")
-    return path
-
-
-def _run(argv, exampledir, tmp_path, monkeypatch):
-    from scoary_amd import methods as m
-
-    def no_engine():
-        raise AssertionError("the engine was started before the arguments were refused")
-    monkeypatch.setattr(m, "get_engine", no_engine)
-    monkeypatch.setenv("SCOARY_OVERLAP_STARTUP", "0")
-    out = os.path.join(str(tmp_path), "out")
-    monkeypatch.setattr(sys, "argv", ["scoary", "-g", os.path.join(exampledir, "Gene_presence_absence.csv"),
-                                      "-t", os.path.join(exampledir, "Tetracycline_resistance.csv"),
-                                      "-o", out, "--no-time"] + argv)
-    with pytest.raises(SystemExit) as e:
-        m.main()
-    assert not [f for f in os.listdir(out) if f.endswith(".results.csv")]
-    return e.value.code
+    return strata_file(tmp_path, rows, name, header)                        # (a third column: it is ignored)
 
 
 def _good_rows(exampledir):
-    return [(s, "L%d" % (i % 3), "x") for i, s in enumerate(_strains(exampledir))]
+    return good_rows(exampledir, "x")
 
 
 def test_refused_without_no_pairwise_or_permutations(exampledir, tmp_path, monkeypatch):

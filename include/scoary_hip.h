@@ -471,6 +471,26 @@ int scoary_cmh_exact_odds(scoary_handle h, const uint32_t *d_tiled, const uint32
                           const int32_t *d_a, const int64_t *d_off, const int32_t *d_lo, int64_t entries, double half,
                           double *d_or, double *d_or_lo, double *d_or_hi, void *d_scratch,
                           scoary_stream_t stream);
+/* ---- Homogeneity of the odds ratios over the strata (spec S14 of DESIGN.md; additive, ABI 11) -----------------
+ * The Breslow-Day test with Tarone's correction of the assumption every other CMH statistic makes: one common odds
+ * ratio in all strata.  Per (trait, gene), with psi = d_odds[t][g] as scoary_cmh wrote it (read, never recomputed,
+ * so the fitted tables belong to the printed odds ratio) and per stratum (k, n) = d_smargins, m = popc(gene & valid &
+ * stratum), a = popc(gene & label & stratum): over the informative strata (n > 0, 0 < k < n, 0 < m < n; L of them,
+ * ascending) x = the root of x (n - k - m + x) = psi (k - x) (m - x) inside the stratum's support,
+ * w = 1/x + 1/(k - x) + 1/(m - x) + 1/(n - k - m + x), d = a - x; fp64, every operation rounded on its own.
+ *   d_stat_bd     : double [T][G], sum d^2 w, the Breslow-Day statistic
+ *   d_stat_tarone : double [T][G], max(stat_bd - (sum d)^2 / sum (1 / w), 0), Tarone's
+ *   d_df          : int32 [T][G], L - 1
+ *   d_p           : double [T][G], the chi-square upper tail of stat_tarone at df degrees of freedom: within 1e-10
+ *                   relative of the true tail where that is >= 1e-290, any value in [0, 1e-290] below
+ *   psi nan, 0 or +inf, or L < 2: (nan, nan, 0, 1), scoary_cmh's convention for a gene without a test.
+ *   the strata plan, d_labels, d_masks, d_scratch: as scoary_cmh takes them (the segment table is rebuilt here)
+ * Asynchronous on `stream`, allocates nothing.  Limits and errors: scoary_cmh's. */
+int scoary_cmh_homogeneity(scoary_handle h, const uint32_t *d_tiled, const uint32_t *d_labels,
+                           const uint32_t *d_masks, const uint16_t *d_strata, const int32_t *d_members,
+                           const int32_t *d_offsets, const int32_t *d_smargins, int64_t G, int64_t T, int64_t N,
+                           int64_t S, const double *d_odds, double *d_stat_bd, double *d_stat_tarone, int32_t *d_df,
+                           double *d_p, void *d_scratch, scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

@@ -27,6 +27,12 @@
 //       are one contiguous run of the table.  u(x) = 1 / (1 + cmh_stat(x)) from d_e2 and d_var as scoary_cmh wrote
 //       them: a few flops per entry, no table list, 64-bit entry indices throughout.
 //
+// The homogeneity of the odds ratios over the strata (spec S14): the Breslow-Day statistic with Tarone's correction.
+//   k_cmh_homog : k_cmh's geometry (two traits per block) and cmh_walk once more, counting (a, m) per segment as k_cmh does; the fold fits
+//       every informative stratum's table to the common odds ratio scoary_cmh wrote to d_odds (read, never recomputed)
+//       and sums the three terms of the statistic; chi2_tail gives the upper tail at up to 1023 degrees of freedom.
+//       A kernel of its own, so that k_cmh, k_cmh_support and k_cmh_fill compile to what they compiled to before.
+//
 // The entry points check their arguments with strata_check / check_args and build the table through
 // scoary_cmh_segments_launch (both declared in scoary_common.hpp, shared with scoary_cmh_exact.hip).
 #include <cstddef>
@@ -291,6 +297,128 @@ __global__ __launch_bounds__(kCmhThreads) void k_cmh_fill(const double* __restri
   }
 }
 
+// ---- S14: the Breslow-Day test of homogeneity with Tarone's correction ----
+
+// traits per block: two -- 64 VGPRs, eight wavefronts per SIMD.  Measured at cfg3's shape against one, four and eight
+// (50 / 64 / 96 / 185 VGPRs): the fp64 sqrt and divisions of a fold want the wavefronts more than the walk wants the
+// gene quad shared by more traits (profiles/cmh_homog.txt)
+constexpr int kHomogTraits = 2;
+
+// S14: the upper tail Q(df / 2, stat / 2) of the chi-square distribution, 1 <= df <= 1023.  The finite sum of the
+// tail (all terms positive, plus erfc for an odd df) taken outward from its largest term, which is the one value
+// that goes through exp / log / lgamma; a value, not bits (within 1e-10 relative of the true tail above 1e-290).
+__device__ __forceinline__ double chi2_tail(double stat, int df) {
+  if (!(stat > 0.0)) return 1.0;
+  if (stat == __builtin_inf()) return 0.0;
+  const double y = stat / 2.0;
+  const int h = df >> 1;                                                  // the number of terms
+  const bool odd = df & 1;
+  const double base = odd ? erfc(sqrt(y)) : 0.0;
+  if (h == 0) return fmin(base, 1.0);
+  const double a0 = odd ? 0.5 : 0.0;                                      // term i: y^(a0 + i) e^-y / Gamma(a0 + i + 1)
+  const int top_i = (int)fmin(fmax(floor(y - a0), 0.0), (double)(h - 1));
+  const double top = exp(((a0 + (double)top_i) * log(y) - y) - lgamma((a0 + (double)top_i) + 1.0));
+  double sum = top, term = top;
+  for (int i = top_i; i > 0; --i) {
+    term = (term * (a0 + (double)i)) / y;
+    sum += term;
+    if (term < sum * 1e-20) break;
+  }
+  term = top;
+  for (int i = top_i + 1; i < h; ++i) {
+    term = (term * y) / (a0 + (double)i);
+    sum += term;
+    if (term < sum * 1e-20) break;
+  }
+  return fmin(base + sum, 1.0);
+}
+
+struct CmhHomogOut {
+  double *stat_bd, *stat_tarone, *p;
+  int32_t* df;
+};
+
+__global__ __launch_bounds__(kCmhThreads) void k_cmh_homog(const uint32_t* __restrict__ tiled,
+                                                           const uint32_t* __restrict__ labels,
+                                                           const uint32_t* __restrict__ masks,
+                                                           const int32_t* __restrict__ smargins,
+                                                           const CmhSegments* __restrict__ segs,
+                                                           const double* __restrict__ odds, int64_t G, int64_t Gp,
+                                                           int T, int N, int Wp, int S, CmhHomogOut out) {
+  const int64_t g = (int64_t)blockIdx.x * kCmhThreads + threadIdx.x;      // < Gp: the grid covers Gp exactly
+  const int t0 = blockIdx.y * kHomogTraits;
+
+  // trait j of the block, clamped for reading (the surplus traits of the last block are computed and dropped)
+  auto trait = [&](int j) { return min(t0 + j, T - 1); };
+  double psi[kHomogTraits], A1[kHomogTraits], BD[kHomogTraits], SD[kHomogTraits], SV[kHomogTraits];
+  int32_t L[kHomogTraits];
+  uint32_t a[kHomogTraits], m[kHomogTraits];
+#pragma unroll
+  for (int j = 0; j < kHomogTraits; ++j) {
+    const double o = odds[(int64_t)trait(j) * G + min(g, G - 1)];         // the lanes past G read gene G - 1
+    psi[j] = o > 0.0 && o < __builtin_inf() ? o : __builtin_nan("");      // nan: a row without a result
+    A1[j] = 1.0 - psi[j];
+    BD[j] = SD[j] = SV[j] = 0.0, L[j] = 0, a[j] = m[j] = 0;
+  }
+
+  // S14, steps 1-7: stratum s with this lane's (a, m) and the stratum's margins (k, n)
+  auto fold = [&](int s) {
+#pragma unroll
+    for (int j = 0; j < kHomogTraits; ++j) {
+      const int2 kn = reinterpret_cast<const int2*>(smargins)[(int64_t)trait(j) * S + s];
+      const int k = kn.x, n = kn.y, mm = (int)m[j], aa = (int)a[j];
+      a[j] = m[j] = 0;
+      if (!(n > 0 && 0 < k && k < n && 0 < mm && mm < n) || psi[j] != psi[j]) continue;
+      const double dk = (double)k, dm = (double)mm;
+      const int r = n - k - mm, km = k - mm;                              // (products of these stay below 2^31)
+      const double rest = (double)r;
+      const double B = rest + psi[j] * (double)(k + mm);
+      const double C = psi[j] * (dk * dm);
+      // the discriminant B B + 4 (1 - psi) C as a sum of non-negative terms: no cancellation at a large psi
+      const double root = sqrt(((double)(r * r) + (psi[j] * psi[j]) * (double)(km * km)) +
+                               (2.0 * psi[j]) * (double)(k * (n - k) + mm * (n - mm)));
+      const double x = B >= 0.0 ? (2.0 * C) / (B + root) : (root - B) / (2.0 * A1[j]);
+      const double w = ((1.0 / x + 1.0 / (dk - x)) + 1.0 / (dm - x)) + 1.0 / (rest + x);
+      const double d = (double)aa - x;
+      BD[j] += (d * d) * w;
+      SD[j] += d;
+      SV[j] += 1.0 / w;
+      L[j] += 1;
+    }
+  };
+
+  cmh_walk(
+      tiled, segs, Gp, g, N, Wp, S,
+      [&](int w, uint32_t gw) {
+#pragma unroll
+        for (int j = 0; j < kHomogTraits; ++j) {
+          const int64_t row = (int64_t)trait(j) * Wp + w;
+          bcnt_acc(m[j], gw & masks[row]);
+          bcnt_acc(a[j], gw & labels[row]);
+        }
+      },
+      fold, [](int, int) {});
+
+  if (g >= G) return;
+#pragma unroll
+  for (int j = 0; j < kHomogTraits; ++j) {
+    if (t0 + j >= T) continue;
+    const int64_t o = (int64_t)(t0 + j) * G + g;
+    double bd = __builtin_nan(""), tarone = __builtin_nan(""), p = 1.0;
+    int32_t df = 0;
+    if (L[j] >= 2) {
+      bd = BD[j];
+      tarone = fmax(BD[j] - (SD[j] * SD[j]) / SV[j], 0.0);
+      df = L[j] - 1;
+      p = chi2_tail(tarone, df);
+    }
+    out.stat_bd[o] = bd;
+    out.stat_tarone[o] = tarone;
+    out.df[o] = df;
+    out.p[o] = p;
+  }
+}
+
 }  // namespace
 
 int scoary_cmh_segments_launch(scoary_handle h, hipStream_t s, const uint16_t* d_strata, const int32_t* d_members,
@@ -383,6 +511,31 @@ int scoary_cmh_minp_fill(scoary_handle h, const double* d_e2, const double* d_va
                        0, s, d_e2, d_var, d_off, d_lo, r0, nrows, entries, d_tab);
     HIP_TRY(h, hipGetLastError());
   }
+  return SCOARY_OK;
+}
+
+int scoary_cmh_homogeneity(scoary_handle h, const uint32_t* d_tiled, const uint32_t* d_labels,
+                           const uint32_t* d_masks, const uint16_t* d_strata, const int32_t* d_members,
+                           const int32_t* d_offsets, const int32_t* d_smargins, int64_t G, int64_t T, int64_t N,
+                           int64_t S, const double* d_odds, double* d_stat_bd, double* d_stat_tarone, int32_t* d_df,
+                           double* d_p, void* d_scratch, scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (int rc = strata_check(h, "scoary_cmh_homogeneity",
+                            d_tiled && d_labels && d_masks && d_strata && d_members && d_offsets && d_smargins &&
+                                d_odds && d_stat_bd && d_stat_tarone && d_df && d_p && d_scratch && G >= 1, T, N, S))
+    return rc;
+  const int64_t Gp = scoary_tiled_genes(G);
+  if (Gp / kCmhThreads > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_cmh_homogeneity: grid too large");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = scoary_cmh_segments_launch(h, s, d_strata, d_members, N, S, d_scratch, "k_cmh_segments")) return rc;
+  const CmhHomogOut out{d_stat_bd, d_stat_tarone, d_p, d_df};
+  KernelTimer kt(h, s, "k_cmh_homog");
+  hipLaunchKernelGGL(k_cmh_homog, dim3((unsigned)(Gp / kCmhThreads), (unsigned)((T + kHomogTraits - 1) / kHomogTraits)),
+                     dim3(kCmhThreads), 0, s, d_tiled, d_labels, d_masks, d_smargins,
+                     static_cast<const CmhSegments*>(d_scratch), d_odds, G, Gp, (int)T, (int)N,
+                     (int)scoary_row_words(N), (int)S, out);
+  HIP_TRY(h, hipGetLastError());
   return SCOARY_OK;
 }
 

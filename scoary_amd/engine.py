@@ -651,6 +651,32 @@ class AssociationEngine:
             self._ptr(out["scounts"]) if scounts else None, self._ptr(scratch), self._stream()), "scoary_cmh")
         return out
 
+    def cmh_homogeneity(self, genes, traits, masks, strata, cmh_res):
+        """The Breslow-Day test of homogeneity of the odds ratios over the strata of ``strata``, with Tarone's
+        correction (spec S14; scoary_cmh_homogeneity): the test of the assumption cmh() makes, one common odds ratio.
+        ``traits`` / ``masks`` / ``strata``: as cmh() takes them; ``cmh_res``: cmh()'s result for them (its odds is
+        read, never recomputed: the fitted tables belong to the odds ratio that is reported).  Dict of device tensors:
+        stat_bd, stat_tarone and p (the chi-square upper tail of stat_tarone) float64 [T, G], df int32 [T, G] = the
+        informative strata less one.  Without a finite positive odds ratio or with fewer than two informative
+        strata: (nan, nan, 1, df 0)."""
+        torch = _torch()
+        T, G, N = int(traits.shape[0]), genes.G, genes.N
+        self._strata_fits(strata, T, N)
+        if int(masks.shape[0]) != T or not (traits.is_contiguous() and masks.is_contiguous()):
+            raise ValueError("cmh_homogeneity: label and validity rows must be contiguous [T, Wp] tensors of the "
+                             "same traits")
+        odds = cmh_res["odds"]
+        if not odds.is_contiguous() or tuple(odds.shape) != (T, G) or odds.dtype != torch.float64:
+            raise ValueError("cmh_homogeneity: cmh()'s odds [T, G] of the same traits, contiguous")
+        out = {k: self._empty((T, G), torch.float64) for k in ("stat_bd", "stat_tarone", "p")}
+        out["df"] = self._empty((T, G), torch.int32)
+        scratch = self._cmh_scratch(N)
+        self._check(self.lib.scoary_cmh_homogeneity(
+            self.h, self._ptr(genes.tiled), self._ptr(traits), self._ptr(masks), *self._strata_ptrs(strata),
+            G, T, N, strata.S, self._ptr(odds), *(self._ptr(out[k]) for k in ("stat_bd", "stat_tarone", "df", "p")),
+            self._ptr(scratch), self._stream()), "scoary_cmh_homogeneity")
+        return out
+
     def perm_generate(self, masks, margins, N, P, perm_base, seed, out=None, trait_base=0, strata=None):
         """Label rows [T, P, Wp] of the permutations perm_base .. perm_base + P - 1 (spec S4); with ``strata``
         (a StrataPlan of these traits) shuffled within its strata (spec S9)."""
@@ -1213,7 +1239,8 @@ class AssociationEngine:
     def associate(self, genes, traits, masks, permutations=0, seed=0, perm_buffer=None,
                   use_lists=None, workspace=None, plan=None, graph=None, records=None, fwer=False,
                   table_budget_bytes=8 << 30, stepdown=False, strata=None, cmh=False, cmh_fwer=False,
-                  cmh_stepdown=False, cmh_exact=False, cmh_exact_odds=False, cmh_exact_level=0.95):
+                  cmh_stepdown=False, cmh_exact=False, cmh_exact_odds=False, cmh_exact_level=0.95,
+                  cmh_homogeneity=False):
         """counts -> Fisher -> (optional) permutation exceedance counts.  Returns a dict of device tensors:
         counts [T, G, 4], margins [T, 2], p / odds [T, G], crit [T, G, 2], r [T, G] (uint32 bits in int32) or None.
         ``workspace``: the result tensors are the workspace's, overwritten by the next step that uses it.
@@ -1238,6 +1265,9 @@ class AssociationEngine:
         ``cmh_exact_odds`` (needs ``cmh``, not permutations; spec S13): the conditional maximum-likelihood odds ratio
         over the strata and its exact confidence limits at ``cmh_exact_level`` -- res["cmh_exact_odds"],
         res["cmh_exact_odds_lower"] and res["cmh_exact_odds_upper"] float64 [T, G] (cmh_exact_odds()).
+        ``cmh_homogeneity`` (needs ``cmh``, not permutations; spec S14): the Breslow-Day test of homogeneity of the odds
+        ratios over the strata with Tarone's correction -- res["cmh_homog_p"] and res["cmh_homog_stat"] (Tarone's)
+        float64 [T, G] and res["cmh_homog_df"] int32 [T, G] (cmh_homogeneity()).
         Every other result is that of the same call without the option, bit for bit."""
         if (fwer or stepdown) and permutations <= 0:
             raise ValueError("fwer=True / stepdown=True need permutations > 0")
@@ -1249,6 +1279,8 @@ class AssociationEngine:
             raise ValueError("cmh_exact_odds=True needs cmh=True (and its strata)")
         if cmh_exact_odds and not 0.0 < float(cmh_exact_level) < 1.0:
             raise ValueError("cmh_exact_level must lie inside (0, 1), not %r" % (cmh_exact_level,))
+        if cmh_homogeneity and not cmh:
+            raise ValueError("cmh_homogeneity=True needs cmh=True (and its strata)")
         if cmh and strata is None:
             raise ValueError("cmh=True needs strata (a StrataPlan of these traits)")
         if strata is not None and (permutations > 0 or cmh):
@@ -1269,6 +1301,10 @@ class AssociationEngine:
             odds = self.cmh_exact_odds(genes, masks, strata, self._cmh_of(res), level=cmh_exact_level)
             res = {**res, "cmh_exact_odds": odds["odds"], "cmh_exact_odds_lower": odds["lower"],
                    "cmh_exact_odds_upper": odds["upper"]}
+        if cmh_homogeneity:
+            homog = self.cmh_homogeneity(genes, traits, masks, strata, self._cmh_of(res))
+            res = {**res, "cmh_homog_p": homog["p"], "cmh_homog_stat": homog["stat_tarone"],
+                   "cmh_homog_df": homog["df"]}
         if records is not None:
             # the exchange records of the step, packed as its last kernel (inside a captured step:
             # one launch less per replay for a gene-sharded rank)

@@ -788,6 +788,8 @@ OPTIONAL_COLUMNS = (
     ("CMH_exact_odds_ratio_lower", "cmh_exact_odds_lower", False),
     ("CMH_exact_odds_ratio_upper", "cmh_exact_odds_upper", False),
 )
+# --cmh-homogeneity (spec S14): its column is written after every column above
+HOMOGENEITY_COLUMNS = (("CMH_homogeneity_p", "cmh_homog_p", False),)
 DEFAULT_EXACT_LEVEL = 0.95          # --cmh-exact-level
 
 # The rules of the flags behind them, in the order they are checked (which decides the message a faulty run sees
@@ -818,6 +820,14 @@ FLAG_RULES = (
              "Fisher's", False, False, "its results reach the host beside the gathered records of a single process",
              "cmh_exact"),
 )
+# --cmh-homogeneity: checked after every rule above; a single rank for --cmh's reason
+HOMOGENEITY_RULES = (
+    FlagRule("--cmh-homogeneity", "cmh_homogeneity", "The Breslow-Day test of homogeneity is a test of every gene over "
+             "the strata, beside Fisher's", False, False,
+             next(rule.one_rank for rule in FLAG_RULES if rule.flag == "--cmh"), "cmh_homogeneity"),
+)
+ALL_COLUMNS = OPTIONAL_COLUMNS + HOMOGENEITY_COLUMNS        # what every consumer of the two tables iterates
+ALL_RULES = FLAG_RULES + HOMOGENEITY_RULES
 # a broken rule as the command line reports it / as Setup_results raises it
 RULE_TEXT = {
     "no_pairwise": ("Cannot use %(flag)s without --no_pairwise. %(why)s", None),
@@ -830,12 +840,14 @@ RULE_TEXT = {
             "Cochran-Mantel-Haenszel test over the strata of FILE", "%(kw)s needs cmh (and its strata)"),
     "cmh_exact": ("Cannot use %(flag)s without --cmh FILE. The exact test is taken over the strata of FILE",
                   "%(kw)s needs cmh (and its strata)"),
+    "cmh_homogeneity": ("Cannot use %(flag)s without --cmh FILE. The odds ratios are compared across the strata of "
+                        "FILE", "%(kw)s needs cmh (and its strata)"),
     "ranks": ("Cannot use %(flag)s under more than one rank: %(why)s", "%(kw)s needs a single process: %(why)s"),
 }
 
 
 def _broken_rules(rule, no_pairwise, permutations, early_abort, files=None, cmh=False):
-    """The messages of the rules of one row of FLAG_RULES that a run breaks, in the order they are reported.
+    """The messages of the rules of one row of ALL_RULES that a run breaks, in the order they are reported.
     ``files``: the messages of the command line's checks of the flag's own file, which come before the rank rule
     (() for a flag without one); None: the run is Setup_results' and the messages are its ValueErrors.  ``cmh``: the
     run has --cmh FILE / cmh=True."""
@@ -880,10 +892,12 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
     ``cmh_exact_odds`` (needs ``cmh``, not permutations): the conditional maximum-likelihood odds ratio over the strata
     and its exact confidence limits at ``cmh_exact_level`` (spec S13): out["cmh_exact_odds"],
     out["cmh_exact_odds_lower"], out["cmh_exact_odds_upper"] [T, G].
-    How each of these arrays reaches the host: OPTIONAL_COLUMNS."""
+    ``cmh_homogeneity`` (needs ``cmh``, not permutations): the Breslow-Day test of homogeneity of the odds ratios over
+    the strata with Tarone's correction (spec S14): out["cmh_homog_p"] [T, G].
+    How each of these arrays reaches the host: ALL_COLUMNS."""
     import torch
     from . import dist
-    opt = {**dict.fromkeys((rule.kw for rule in FLAG_RULES), False), **(options or {})}
+    opt = {**dict.fromkeys((rule.kw for rule in ALL_RULES), False), **(options or {})}
     eng = get_engine()
     G, N, T = len(table), len(table.strains), tarr.shape[0]
     with _stage("device setup (H2D, tiling, trait plan)"):
@@ -951,9 +965,10 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         with _stage("kernels (counts, Fisher, permutations)"):
             res = eng.associate(gm, trv, mkv, permutations=permutations, seed=seed, plan=plan, strata=sp,
                                 cmh=opt["cmh"], cmh_exact=opt["cmh_exact"], cmh_exact_odds=opt["cmh_exact_odds"],
-                                cmh_exact_level=opt.get("cmh_exact_level", DEFAULT_EXACT_LEVEL))
+                                cmh_exact_level=opt.get("cmh_exact_level", DEFAULT_EXACT_LEVEL),
+                                cmh_homogeneity=opt["cmh_homogeneity"])
             torch.cuda.synchronize(eng.device)
-        beside.update({key: res[key] for _name, key, _count in OPTIONAL_COLUMNS if key in res})
+        beside.update({key: res[key] for _name, key, _count in ALL_COLUMNS if key in res})
         if opt["fwer"] or opt["fwer_stepdown"]:
             with _stage("Westfall-Young step-down minP (p tables, k_stepdown_minp)" if opt["fwer_stepdown"] else
                         "Westfall-Young minP (p tables, k_permute_minp)"):
@@ -973,7 +988,7 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
             torch.cuda.synchronize(eng.device)
         return rec
 
-    beside = {}         # the device arrays that reach the host beside the gathered records (OPTIONAL_COLUMNS)
+    beside = {}         # the device arrays that reach the host beside the gathered records (ALL_COLUMNS)
     rec = dist.associate_sharded(local, G)
     with _stage("results D2H"):
         # the stable p order for BH: numpy does 200 000 doubles in 25-40 ms, which beats the
@@ -989,7 +1004,7 @@ def _associate(table, tarr, permutations=0, seed=DEFAULT_SEED, early_abort=False
         out["r_fwer"], out["nstop"] = out["nstop"], np.zeros_like(out["nstop"])
     if opt["fwer_stepdown"]:
         out["r_fwer_sd"] = np.zeros((T, 0), dtype=np.int32)         # (a table without genes)
-    for key in ("minp",) + tuple(key for _name, key, _count in OPTIONAL_COLUMNS):
+    for key in ("minp",) + tuple(key for _name, key, _count in ALL_COLUMNS):
         if key in beside:
             out[key] = beside[key].cpu().numpy()
     return out
@@ -1050,7 +1065,8 @@ def _usable_cpus():
 
 def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEED,
                   early_abort=False, fwer=False, fwer_stepdown=False, strata=None, cmh=False, cmh_fwer=False,
-                  cmh_fwer_stepdown=False, cmh_exact=False, cmh_exact_odds=False, cmh_exact_level=0.95):
+                  cmh_fwer_stepdown=False, cmh_exact=False, cmh_exact_odds=False, cmh_exact_level=0.95,
+                  cmh_homogeneity=False):
     """Counts, Fisher's exact test and B/BH correction for every trait x gene
     (methods.py:757-928).  ``permutations`` >= 10 additionally attaches the
     Fisher-statistic ``Empirical_p`` (= (r+1)/(P+1), methods.py:1365) to every
@@ -1071,16 +1087,19 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
     ``cmh_exact_odds`` (with ``cmh``, not permutations; one process): also ``CMH_exact_odds_ratio``,
     ``CMH_exact_odds_ratio_lower`` and ``CMH_exact_odds_ratio_upper``, the conditional maximum-likelihood estimate of
     the common odds ratio and its exact confidence limits at ``cmh_exact_level`` (spec S13; the estimate and conf.int
-    of the same R test)."""
+    of the same R test).
+    ``cmh_homogeneity`` (with ``cmh``, not permutations; one process): also ``CMH_homogeneity_p``, the p of the
+    Breslow-Day test of homogeneity of the odds ratios over the strata with Tarone's correction (spec S14; R's
+    DescTools::BreslowDayTest(correct = TRUE)), written after every other column."""
     if cmh and strata is None:
         raise ValueError("cmh needs strata")
     # (permutations are 0 here whenever the run is not --no_pairwise; with cmh the strata are its own)
     active = {"fwer": fwer, "fwer_stepdown": fwer_stepdown, "cmh": cmh, "strata": strata is not None and not cmh,
               "cmh_fwer": cmh_fwer, "cmh_fwer_stepdown": cmh_fwer_stepdown, "cmh_exact": cmh_exact,
-              "cmh_exact_odds": cmh_exact_odds}
+              "cmh_exact_odds": cmh_exact_odds, "cmh_homogeneity": cmh_homogeneity}
     if cmh_exact_odds and not 0.0 < float(cmh_exact_level) < 1.0:
         raise ValueError("cmh_exact_level must lie inside (0, 1), not %r" % (cmh_exact_level,))
-    for rule in (rule for rule in FLAG_RULES if active[rule.kw]):
+    for rule in (rule for rule in ALL_RULES if active[rule.kw]):
         for text in _broken_rules(rule, True, permutations, early_abort, cmh=cmh):
             raise ValueError(text)
     table = _as_table(genedic)
@@ -1175,7 +1194,7 @@ def Setup_results(genedic, traitsdic, collapse, permutations=0, seed=DEFAULT_SEE
                 "B_p": B, "BH_p": BH}
         if emp is not None:
             cols["Empirical_p"] = emp[rows_idx]
-        for name, key, count in OPTIONAL_COLUMNS:
+        for name, key, count in ALL_COLUMNS:
             if key in dev:
                 v = dev[key][t][rows_idx]
                 cols[name] = (v.view(np.uint32).astype(np.float64) + 1.0) / (permutations + 1.0) if count else v
@@ -1525,7 +1544,7 @@ def StoreTraitResult(Trait, Traitname, max_hits, cutoffs, upgmatree, GTC, Pruned
     if not isinstance(Trait, TraitResults):
         Trait = _trait_results_from_dict(Trait)
     # (a count has its denominator from the permutations: without them it is not written)
-    optional = [name for name, _key, count in OPTIONAL_COLUMNS
+    optional = [name for name, _key, count in ALL_COLUMNS
                 if no_pairwise and name in Trait.cols and (with_emp or not count)]
     columns += optional
     columns += list(extracolstoprint)
@@ -1614,7 +1633,7 @@ def _trait_results_from_dict(rows):
     """Plain {gene: row dict} (the reference's Results[trait]) -> TraitResults."""
     genes = list(rows.keys())
     cols = {}
-    for k in TraitResults.FIELDS + ("Empirical_p",) + tuple(name for name, _key, _count in OPTIONAL_COLUMNS):
+    for k in TraitResults.FIELDS + ("Empirical_p",) + tuple(name for name, _key, _count in ALL_COLUMNS):
         if genes and k in rows[genes[0]]:
             cols[k] = np.array([rows[g][k] for g in genes])
     return TraitResults(genes, [rows[g]["NUGN"] for g in genes],
@@ -1761,6 +1780,11 @@ def ScoaryArgumentParser(argv=None):
                    "ratio over the strata of FILE and its exact confidence limits -- the estimate and conf.int of R's "
                    "mantelhaen.test(exact = TRUE); needs no permutations and not --cmh-exact; at most 8190 isolates "
                    "(single process; scoary_amd extension)")
+    a.add_argument("--cmh-homogeneity", dest="cmh_homogeneity", action="store_true", default=False,
+                   help="With --no_pairwise --cmh FILE: add the column CMH_homogeneity_p, the p of the Breslow-Day test of "
+                   "homogeneity of the odds ratios over the strata of FILE with Tarone's correction -- whether one "
+                   "common odds ratio, CMH_odds_ratio, describes every stratum; R's DescTools::BreslowDayTest(correct = "
+                   "TRUE); needs no permutations (single process; scoary_amd extension)")
     a.add_argument("--cmh-exact-level", dest="cmh_exact_level", type=float, default=None, metavar="FLOAT",
                    help="With --cmh-exact-odds: the confidence level of the limits, inside (0, 1) (default 0.95)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
@@ -1932,7 +1956,7 @@ def main(**kwargs):
                          % (len(labels), int(sizes.min()), int(sizes.max()), args.permute_strata or args.cmh))
         # the flags' keywords, by _validate's mapping; the two flags that name a file arrive as ``strata`` and a bool
         flags = {rule.kw: getattr(args, rule.flag[2:].replace("-", "_"), False)
-                 for rule in FLAG_RULES if rule.flag not in ("--cmh", "--permute-strata")}
+                 for rule in ALL_RULES if rule.flag not in ("--cmh", "--permute-strata")}
         res = Setup_results(genedic, traitsdic, args.collapse,
                             permutations=args.permute if args.no_pairwise else 0, seed=seed,
                             early_abort=getattr(args, "permute_early_abort", False), strata=strata,
@@ -2072,7 +2096,7 @@ def _validate(args, cutoffs):
                  "exactly as many as the number of correction methods and in corresponding "
                  "sequence. e.g. -c I EPW -p 0.1 0.05 will apply an individual p-value cutoff "
                  "of 0.1 AND a pairwise comparisons p-value cutoff of 0.05.")
-    for rule in FLAG_RULES:
+    for rule in ALL_RULES:
         value = getattr(args, rule.flag[2:].replace("-", "_"), None)
         if value:
             files = _strata_file_problems(args, rule.flag, value) if isinstance(value, str) else ()

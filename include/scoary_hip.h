@@ -517,7 +517,12 @@ int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_
  *       length, moved to a block count that fills whole rounds over the CUs.  block_start: HOST
  *       int64 [ceil(G/256) + 1] = index entries in front of every 256-slot block
  *       (32 * d_lstart[256 b]) and the entry count last
- *   scoary_permute_hybrid    : scoary_permute_lists with the slots [0, k_split) on the matrix cores;
+ *   scoary_mfma_plan         : host only, no handle -- the launch plan of k_permute_mfma for the slots
+ *       [0, k_split) of a (T, P) launch on num_cu CUs (the launch asks with the device's count):
+ *       out[0] = 256-slot gene blocks, out[1] = R, the ranges the T * ceil(P/64) stages of a gene
+ *       block are cut into, out[2] = L, the stages of a range (the last one may be shorter),
+ *       out[3] = blocks = out[0] * out[1].  SCOARY_ERR_ARG on a non-positive size or out = NULL
+ *   scoary_permute_hybrid   : scoary_permute_lists with the slots [0, k_split) on the matrix cores;
  *       routed_entries = index entries in front of slot k_split (32 * d_lstart[k_split]; sizes the
  *       list kernel's chunks).  k_split = 0 is scoary_permute_lists (d_panels / d_bfrag unused). */
 #define SCOARY_MFMA_ROUTE_NONE 0
@@ -533,6 +538,7 @@ int scoary_mfma_panels_build(scoary_handle h, const uint32_t *d_tiled, int64_t G
 int scoary_set_mfma_route(scoary_handle h, int mode);
 int64_t scoary_mfma_route(scoary_handle h, const int64_t *block_start, int64_t G, int64_t T,
                           int64_t N, int64_t P);
+int scoary_mfma_plan(int num_cu, int64_t k_split, int64_t T, int64_t P, int64_t *out);
 int scoary_permute_hybrid(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                           int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,
                           const int32_t *d_lorder, const uint8_t *d_lflipped,

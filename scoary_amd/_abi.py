@@ -85,6 +85,7 @@ SIGNATURES = {
     "scoary_mfma_panels_build": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "scoary_set_mfma_route": (_i32, [_vp, _i32]),
     "scoary_mfma_route": (_i64, [_vp, _vp, _i64, _i64, _i64, _i64]),
+    "scoary_mfma_plan": (_i32, [_i32, _i64, _i64, _i64, ctypes.POINTER(_i64)]),
     "scoary_permute_hybrid": (_i32, [_vp, _vp, _vp, _i64] + [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp,
                                                                         _i32, _vp, _vp, _i64, _i64, _vp]),
     "scoary_lists_scratch_bytes": (_i64, [_i64, _i64]),

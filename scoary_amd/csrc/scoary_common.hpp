@@ -39,10 +39,12 @@ struct scoary_ctx {
 };
 
 // scoary_mfma.hip: the matrix-core kernel of the slots [0, k_split) of a list launch (scoary_lists.hip calls it
-// between the region conversion and the list kernel); geometry = stages of 64 permutations, ranges per trait
-// (rp) of `per` stages each, 256-slot gene blocks, blocks in all
+// between the region conversion and the list kernel); geometry = stages of 64 permutations per trait, Q = T x
+// stages of them in all, cut into `ranges` ranges of L (the last one shorter), 256-slot gene blocks, blocks in
+// all, and the plan's model cost in stage-times of one CU
 struct MfmaGeom {
-  int64_t stages, rp, per, gene_blocks, blocks;
+  int64_t stages, Q, ranges, L, gene_blocks, blocks;
+  double cost;
 };
 MfmaGeom scoary_mfma_geom(int num_cu, int64_t k_split, int64_t T, int64_t P, int64_t ntiles);
 int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, const void* d_panels, void* d_bfrag,

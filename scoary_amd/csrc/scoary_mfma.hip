@@ -21,10 +21,15 @@
 // whatever its list holds, a listed gene kListNsPerEntry per padded list entry -- break-even list length
 // = their ratio (scoary_mfma_breakeven_entries).  Both per 100 000 tests of the gene (cfg3: 10 traits x
 // 10 000 permutations), chip-wide, on MI355X: k_permute_mfma + k_mfma_bfrag with every cfg3 gene routed,
-// k_permute_lists with none (profiles/r11_mfma_two_wave.txt).
-const double kMfmaNsPerGene = 62.0;
-const double kListNsPerEntry = 0.177;
-const double kMfmaPanelLoadStages = 10.0;  // a block's start (A panel: 256 KB from HBM) and end, in stages of its loop
+// k_permute_lists with none (profiles/mfma_ranges.txt: 57.1-59.4 and 0.179-0.184 in three sessions).
+const double kMfmaNsPerGene = 58.0;
+const double kListNsPerEntry = 0.18;
+// What a block costs beside its stages, in stage-times of its loop (scoary_mfma_geom; least squares over P and
+// trait count in profiles/mfma_ranges.txt: 5.7-6.1 and 1.9-2.3 at 2.14-2.19 us per stage): its start and end
+// (thresholds, the A panel: 256 KB from HBM, ring fill, epilogue), and every trait it enters after its first (the
+// segment's lane reduction and store, the thresholds out of the LDS; both wavefront groups pay it in turn).
+const double kMfmaBlockStartStages = 6.0;
+const double kMfmaTraitSwitchStages = 2.0;
 
 namespace {
 
@@ -42,7 +47,8 @@ constexpr int kRingSlots = 4;                     // 128 KB
 constexpr int kAhead = kRingSlots - 2;            // a half stage is issued this many ticks before its first read
 constexpr int kRingBytes = kRingSlots * kHalfBytes;
 constexpr int kDmaPerHalf = kHalfBytes / kBlockWaves / kFragBytes;   // LDS-DMA instructions per wavefront and half stage
-constexpr int kMfmaLds = kRingBytes;
+constexpr int kThrBytes = 32 * 8;                 // behind the ring: the (lo, hi1) pairs of a wavefront's 32 slots
+constexpr int kMfmaLds = kRingBytes + kBlockWaves * kThrBytes;
 static_assert(kRingSlots >= 4 && kMfmaLds <= 160 * 1024 && (kAhead - 1) * kDmaPerHalf < 64,
               "a half stage is issued at least two ticks ahead, within the LDS of a CU and the vmcnt field");
 
@@ -124,6 +130,16 @@ __device__ __forceinline__ void mfma_dma16(uint32_t lds, uint32_t lane_off, cons
                : "memory");
 }
 
+// The same for one dword per lane: src + lane_off -> LDS address lds + 4 * lane.
+__device__ __forceinline__ void mfma_dma4(uint32_t lds, uint32_t lane_off, const unsigned char* src) {
+  uint32_t m0_saved;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+               "global_load_lds_dword %2, %3\n\ts_mov_b32 m0, %0"
+               : "=&s"(m0_saved)
+               : "s"(lds), "v"(lane_off), "s"(src)
+               : "memory");
+}
+
 // Bijective XCD remap: consecutive work items land on ONE XCD (blocks are dealt to the eight XCDs
 // round-robin), so the blocks resident on an XCD at one time share their (trait, permutation range)
 // and stream the same B stages out of that XCD's L2.
@@ -132,20 +148,30 @@ __device__ __forceinline__ int xcd_item(int orig, int n) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (orig >> 3);
 }
 
-// Block = 256 list slots x one trait x `per` stages of 64 permutations; eight wavefronts, two per SIMD.
+// Block = 256 list slots x one range of the linear stage sequence q = t * S + s (S stages of 64 permutations per
+// trait, bfrag's own address order): stages [q0, q0 + ns), q0 = range * L.  A range may start and end inside a
+// trait and may hold several traits; the A panel and the ring are set up once per block whatever it holds.  A
+// SEGMENT is the part of one trait inside one range: its count goes to partial tile `range - first range that
+// meets the trait` (scoary_mfma_geom admits a range length only if every trait meets at most ntiles ranges), and the
+// block of the segment with the trait's last stage also writes, behind its loop, the zeros of the tiles behind that
+// segment's, so every (trait, tile) cell of a routed slot is written exactly once.  Eight wavefronts, two per SIMD.
 // Wavefront w owns 32 slots, row tile w & 1 of wave panel w >> 1: its A fragments of all 32 K-steps stay in
 // 128 registers, next to two column tiles of accumulators, minus the interval centre and the half width of
 // its 16 rows and 16 counters (no LDS beside the ring, at most 256 registers: two wavefronts per SIMD).
 // The accumulators start at minus the centre of the acceptance interval [lo, hi1) of the list count -- the C
 // operand of a stage's first K-step -- so "u outside the interval" is one compare, |acc| > half width; the two
-// column tiles of a row share one per-lane counter that lives across the stages, the 32 lanes of a row meet
-// once, at the end.
+// column tiles of a row share one per-lane counter that lives across the stages of a segment, the 32 lanes of a
+// row meet once per segment, at its end.
 //
 // Stagger.  Wavefronts 4..7, the SIMD partners of 0..3, run half a stage behind them: in tick n (one barrier
 // per tick, nh + 1 ticks for nh half stages) the early wavefronts read half n, the late ones half n - 1, so
 // one partner's region test, LDS-DMA issue and first fragment reads fall beside the other's MFMAs.  The region
 // test of a stage waits for the barrier that follows the stage (the partner is in mid-stage behind it, and
-// would only wait at that barrier for a test in front of it); the range's last one follows the loop.
+// would only wait at that barrier for a test in front of it); the range's last one follows the loop.  Where the
+// tested stage was its trait's last, the same place ends the segment (ragged column count, lane reduction,
+// stores, counters to zero) and takes the next trait's centres and half widths out of the LDS in front of the
+// stage's first MFMA, which takes the centres as C.  All of it is wave-local and sits between two barriers every wavefront
+// executes anyway, so the early and the late wavefronts still count the same ticks.
 // Measured and not built in, each within the kernel's run-to-run spread (profiles/r11_mfma_two_wave.txt):
 // s_setprio 1 for the late wavefronts; a fifth ring slot (issue three ticks ahead, 160 KB); with it, reading
 // the next half's first fragments in front of the barrier.
@@ -160,47 +186,87 @@ __device__ __forceinline__ int xcd_item(int orig, int n) {
 //     since; the slots of the halves n - 1 and n, which are being read, are other slots (kRingSlots >= 3).
 // Halves past the end re-read the last one into such a slot, which nobody reads any more, so the counts stay
 // the same to the end; ns = 1 and the late wavefronts' last half (tick nh, no early work beside it) need no
-// case of their own.  There is no ordinary global load inside the loop (the compiler would wait vmcnt(0) for
-// it and drain the ring).
+// case of their own.
+// Stores and the threshold DMA among the ring's LDS-DMAs.  A trait switch inside the loop stores the ended
+// segment's counts, and the stage before it fetches the next trait's thresholds, while halves are in flight.
+// Vector memory operations retire in the order they were issued and the counted wait only bounds how many are
+// outstanding, so an operation YOUNGER than the DMAs a wait is there for makes it retire more of the older DMAs,
+// never fewer: a store or a fetch can make a tick's wait longer, not early (a wait that leaves the one or two it
+// knows of outstanding as well measured the same and is not built in).  The fetch is one more LDS-DMA, issued
+// in tick n behind that tick's half and read in tick n + 2 behind that tick's wait, which leaves at most the four
+// DMAs of tick n + 1 outstanding: it has landed, with no wait of its own and without draining the ring (as a
+// register load it would: the compiler waits vmcnt(0) for one, and measured so a switch cost four to seven stages).
+// It lands in 256 bytes only its own wavefront reads, so no barrier is part of that.  No read of a ring slot
+// moves: every one stays behind the barrier that follows the wait retiring its half.  There is still no ordinary
+// global load inside the loop.
 __global__ __launch_bounds__(kBlockWaves * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_permute_mfma(const v4i* __restrict__ panels, const unsigned char* __restrict__ bfrag,
-                    const uint2* __restrict__ lcrit, int G, int64_t P, int S, int per, int rp, int nblk_genes,
+                    const uint2* __restrict__ lcrit, int G, int64_t P, int S, int64_t Q, int L, int nblk_genes,
                     int ntiles, int64_t gs, uint16_t* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int item = xcd_item(blockIdx.x, gridDim.x);
   const int gb = item % nblk_genes, rng = item / nblk_genes;
-  const int t = rng / rp, jr = rng % rp;
-  const int s0 = jr * per, ns = min(per, S - s0);
+  const int64_t q0 = (int64_t)rng * L;
+  const int ns = (int)min((int64_t)L, Q - q0);
+  // (t, s) of the stage the loop is at, and the partial tile of the segment it is in: all wave-uniform
+  int t = (int)(q0 / S), s = (int)(q0 % S);
+  int jt = rng - (int)((int64_t)t * S / L);
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool late = wave >= kBlockWaves / 2;
   // accumulator register r of a lane is row (r & 3) + 8 (r >> 2) + 4 half of the wavefront's 32 slots
-  const int64_t row0 = (int64_t)gb * kBlockGenes + wave * 32 + 4 * half;
+  const int wslot0 = gb * kBlockGenes + wave * 32;  // the wavefront's first slot
+  const int rows_mine = min(32, G - wslot0) - 4 * half;   // a lane's row (r & 3) + 8 (r >> 2) is a slot < G below this (<= 0: none is)
   v16f negc;
   float hw[16];
+  const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)lds;
+  const uint32_t lane_off = (uint32_t)lane * 16u;
+  // Thresholds.  The (lo, hi1) pairs of the wavefront's 32 slots are 256 contiguous bytes of lcrit[tt]: one LDS-DMA
+  // of a dword per lane copies them into the wavefront's own 256 bytes behind the ring (slots >= G: the last
+  // slot's pair again).  The lane's part of the addresses and conditions goes through an opaque copy, here and in
+  // end_segment: they are needed once per trait, and hoisted out of the stage loop they would take registers the
+  // loop has not got.
+  const int thr_slot0 = min(wslot0, G - 1);
+  const uint32_t thr_lds = kRingBytes + (uint32_t)wave * kThrBytes;
+  auto fetch_thresholds = [&](int tt) {
+    uint32_t l = lane_off;
+    asm volatile("" : "+v"(l));
+    l >>= 4;
+    const uint32_t off = (uint32_t)min((int)(l >> 1), G - 1 - thr_slot0) * 8u + (l & 1u) * 4u;
+    mfma_dma4(lds0 + thr_lds, off, reinterpret_cast<const unsigned char*>(lcrit + ((int64_t)tt * G + thr_slot0)));
+  };
+  // The centres and half widths from the pairs fetch_thresholds brought; the caller has waited for that DMA.  A
+  // wavefront reads only what it fetched itself: no barrier is involved.
+  auto take_thresholds = [&]() {
+    int h4 = 4 * half, mine = rows_mine;
+    asm volatile("" : "+v"(h4), "+v"(mine));
+    const uint2* thr = reinterpret_cast<const uint2*>(lds + thr_lds) + h4;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t slot = row0 + (r & 3) + 8 * (r >> 2);
-    const uint2 cr = lcrit[(int64_t)t * G + min(slot, (int64_t)G - 1)];
-    negc[r] = -0.5f * (float)((int)cr.x + (int)cr.y - 1);
-    hw[r] = slot < G ? 0.5f * (float)((int)cr.y - 1 - (int)cr.x) : 1e30f;   // slots >= G: never counted
-  }
-  v4i a[kKSteps];
-  {
-    const v4i* ap = panels + ((int64_t)gb * kBlockWaves + wave) * (kKSteps * 64) + lane;
-#pragma unroll
-    for (int k = 0; k < kKSteps; ++k) a[k] = ap[k * 64];
-    // every global load retired here, before the first LDS-DMA is issued: no compiler-placed wait in the loop
-#pragma unroll
-    for (int k = 0; k < kKSteps; ++k) asm volatile("" : "+v"(a[k]));
+    for (int r = 0; r < 16; ++r) {
+      const int row = (r & 3) + 8 * (r >> 2);
+      const uint2 cr = thr[row];
+      negc[r] = -0.5f * (float)((int)cr.x + (int)cr.y - 1);
+      hw[r] = row < mine ? 0.5f * (float)((int)cr.y - 1 - (int)cr.x) : 1e30f;   // slots >= G: never counted
+    }
+    // read and converted here: the next fetch may overwrite the pairs
     asm volatile("" : "+v"(negc));
 #pragma unroll
     for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(hw[r]));
+  };
+  v4i a[kKSteps];
+  {
+    fetch_thresholds(t);
+    const v4i* ap = panels + ((int64_t)gb * kBlockWaves + wave) * (kKSteps * 64) + lane;
+#pragma unroll
+    for (int k = 0; k < kKSteps; ++k) a[k] = ap[k * 64];
+    // every global load and the first thresholds retired here, before the ring's first LDS-DMA is issued
+#pragma unroll
+    for (int k = 0; k < kKSteps; ++k) asm volatile("" : "+v"(a[k]));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    take_thresholds();
   }
 
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)lds;
-  const uint32_t lane_off = (uint32_t)lane * 16u;
-  const unsigned char* bsrc = bfrag + ((int64_t)t * S + s0) * kStageBytes + wave * (kHalfBytes / kBlockWaves);
+  const unsigned char* bsrc = bfrag + q0 * kStageBytes + wave * (kHalfBytes / kBlockWaves);
   const int nh = 2 * ns;
   auto issue_half = [&](int n) {
     const unsigned char* src = bsrc + (int64_t)min(n, nh - 1) * kHalfBytes;
@@ -221,21 +287,43 @@ void k_permute_mfma(const v4i* __restrict__ panels, const unsigned char* __restr
   uint32_t ex[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) ex[r] = 0u;
-  const int64_t last_valid = P - (int64_t)s0 * 64;        // permutations of this range that exist
+  const int ragged = (int)(P - (int64_t)(S - 1) * 64);    // columns of a trait's last stage that exist: 1 .. 64
 
   v16f acc[2];
-  auto region_test = [&](int64_t nvalid) {
-    if (nvalid >= 64) {
+  auto region_test = [&](int nvalid) {
+    if (nvalid < 64) {                              // ragged last stage of a trait: columns >= P do not count --
+      const bool v0 = l31 < nvalid, v1 = l31 + 32 < nvalid;   // a NaN is outside no interval
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        ex[r] += (uint32_t)(__builtin_fabsf(acc[0][r]) > hw[r]) + (uint32_t)(__builtin_fabsf(acc[1][r]) > hw[r]);
-    } else {                                        // ragged last stage: columns >= P do not count
-      const bool v0 = l31 < nvalid, v1 = l31 + 32 < nvalid;
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        ex[r] += (uint32_t)(v0 && __builtin_fabsf(acc[0][r]) > hw[r]) +
-                 (uint32_t)(v1 && __builtin_fabsf(acc[1][r]) > hw[r]);
+      for (int r = 0; r < 16; ++r) {
+        acc[0][r] = v0 ? acc[0][r] : __builtin_nanf("");
+        acc[1][r] = v1 ? acc[1][r] : __builtin_nanf("");
+      }
     }
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      ex[r] += (uint32_t)(__builtin_fabsf(acc[0][r]) > hw[r]) + (uint32_t)(__builtin_fabsf(acc[1][r]) > hw[r]);
+  };
+  // The end of trait tt's segment in this range: partial[tt][jt][slot] takes its count and the counters start
+  // again.  Lanes 0 .. 15 of each half keep the sum of counter `lane` and store one row each: ONE store
+  // instruction, issued iff the wavefront owns a slot < G.  A trait the block enters after this one begins inside
+  // the range: tile 0.
+  const int jt0 = jt;
+  auto end_segment = [&](int tt) {
+    uint16_t* out = partial + ((int64_t)tt * ntiles + jt) * gs + wslot0;   // wave-uniform
+    int rl = l31, h4 = 4 * half, mine = rows_mine;
+    asm volatile("" : "+v"(rl), "+v"(h4), "+v"(mine));
+    uint32_t count = 0u;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      uint32_t v = ex[r];
+#pragma unroll
+      for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
+      ex[r] = 0u;
+      count = rl == r ? v : count;
+    }
+    const int row = (rl & 3) + 8 * (rl >> 2);
+    if (rl < 16 && row < mine) out[h4 + row] = (uint16_t)count;
+    jt = 0;
   };
   if (late) next_tick();                            // tick 0: the early wavefronts' first half
   int rslot = 0;                                    // ring slot of the half this wavefront reads next
@@ -258,7 +346,15 @@ void k_permute_mfma(const v4i* __restrict__ panels, const unsigned char* __restr
       read_b(1);
       if (h == 0) {
         __builtin_amdgcn_sched_barrier(0);
-        if (st > 0) region_test(64);                // stage st - 1, never the range's last: all 64 columns exist
+        if (st > 0) {                               // stage st - 1, never the range's last
+          const bool entered = s == 0;              // but the last of trait t - 1
+          region_test(entered ? ragged : 64);
+          if (entered) {
+            end_segment(t - 1);
+            take_thresholds();                      // fetched two ticks ago: retired by this tick's counted wait
+          }
+        }
+        if (s == S - 1 && st + 1 < ns) fetch_thresholds(t + 1);   // the trait's last stage: the next stage's trait
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
@@ -278,46 +374,79 @@ void k_permute_mfma(const v4i* __restrict__ panels, const unsigned char* __restr
         __builtin_amdgcn_sched_barrier(0);
       }
     }
+    if (++s == S) s = 0, ++t;
   }
   if (!late) next_tick();                           // tick nh: the late wavefronts' last half
-  region_test(last_valid - (int64_t)(ns - 1) * 64);
+  const bool trait_done = s == 0;                   // (t, s) is one past the range's last stage
+  region_test(trait_done ? ragged : 64);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last (redundant) transfers land before the LDS is given up
+  end_segment(trait_done ? t - 1 : t);
 
-  // partial[t][tile][slot]: the range's count goes to tile jr, zeros to the tiles jr + rp, jr + 2 rp, ...
-  // (k_lists_reduce sums every tile of every slot)
-  uint16_t* out = partial + ((int64_t)t * ntiles + jr) * gs + row0;
-  const int nrows = (int)min((int64_t)32, (int64_t)G - ((int64_t)gb * kBlockGenes + wave * 32));   // of the wavefront's slots, < G
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    uint32_t v = ex[r];
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    const int row = (r & 3) + 8 * (r >> 2);
-    if (l31 == 0 && 4 * half + row < nrows) {
-      out[row] = (uint16_t)v;
-      for (int tile = jr + rp; tile < ntiles; tile += rp) out[(int64_t)(tile - jr) * gs + row] = 0;
+  // The zeros of the tiles behind a trait's last segment, for every trait whose last stage this range held: traits
+  // t0 .. t - 1, the first in tile jt0, the others in tile 0 (k_lists_reduce sums every tile of every slot).  Out
+  // here they are no traffic among the ring's.
+  {
+    int rl = l31, h4 = 4 * half, mine = rows_mine;
+    asm volatile("" : "+v"(rl), "+v"(h4), "+v"(mine));
+    const int row = (rl & 3) + 8 * (rl >> 2);
+    const bool stores = rl < 16 && row < mine;
+    const int t0 = (int)(q0 / S);
+    for (int tt = t0; tt < t; ++tt) {
+      uint16_t* out = partial + (int64_t)tt * ntiles * gs + wslot0 + h4 + row;
+      for (int tile = (tt == t0 ? jt0 : 0) + 1; tile < ntiles; ++tile)
+        if (stores) out[(int64_t)tile * gs] = 0;
     }
   }
 }
 
 }  // namespace
 
-// Stages of 64 permutations per block (`per`) and ranges per trait (`rp`): the fewest rounds of blocks
-// over the CUs, a block long enough to pay for loading its A panel (~10 stages' worth), a range's count
-// within 16 bits and one range per partial tile at most.
-MfmaGeom scoary_mfma_geom(int num_cu, int64_t k_split, int64_t T, int64_t P, int64_t ntiles) {
+// The range lengths L a launch may use, longest first (one entry per distinct ceil(Q / R)): L <= 1023 keeps a
+// segment's count within 16 bits, and every trait meets at most ntiles ranges, so each of its segments has a
+// partial tile of its own (P <= 512, one tile: every cut on a trait boundary).  `switches` = the most traits any
+// range enters after its first.  L = min(S, 1023) always qualifies.
+struct MfmaRange {
+  int64_t L, ranges, switches;
+};
+static std::vector<MfmaRange> mfma_ranges(int64_t T, int64_t P, int64_t ntiles) {
+  std::vector<MfmaRange> out;
+  const int64_t S = (P + 63) / 64, Q = T * S;
+  for (int64_t L = std::min<int64_t>(Q, 1023); L >= 1; --L) {
+    const int64_t ranges = (Q + L - 1) / L;
+    if ((Q + ranges - 1) / ranges != L) continue;           // not ceil(Q / R) for any R
+    // where a trait (a range) starts inside a range (a trait) repeats after at most L traits (S ranges), and the
+    // short last range enters no more traits than a whole one that starts where it does
+    bool ok = true;
+    for (int64_t t = 0; t < std::min(T, L) && ok; ++t) ok = ((t + 1) * S - 1) / L - t * S / L + 1 <= ntiles;
+    if (!ok) continue;
+    MfmaRange c{L, ranges, 0};
+    for (int64_t r = 0; r < std::min(ranges, S); ++r)
+      c.switches = std::max(c.switches, (std::min(Q, (r + 1) * L) - 1) / S - r * L / S);
+    out.push_back(c);
+  }
+  return out;
+}
+
+// The cheapest of them for `gene_blocks` 256-slot blocks on num_cu CUs, in stage-times of one CU:
+//   rounds of blocks over the CUs x (L + kMfmaBlockStartStages + switches x kMfmaTraitSwitchStages).
+// The one-trait-per-block shapes (L = S / k) are candidates like any other; on a tie the longest range wins.
+static MfmaGeom mfma_pick(const std::vector<MfmaRange>& cands, int num_cu, int64_t gene_blocks, int64_t S,
+                          int64_t T) {
   MfmaGeom g{};
-  g.stages = (P + 63) / 64;
-  g.gene_blocks = (k_split + kBlockGenes - 1) / kBlockGenes;
-  const int64_t rp_min = (g.stages + 1022) / 1023, rp_max = std::min<int64_t>(std::min(ntiles, g.stages), 64);
-  double best = 0.0;
-  for (int64_t rp = rp_min; rp <= std::max(rp_min, rp_max); ++rp) {
-    const int64_t per = (g.stages + rp - 1) / rp, ranges = (g.stages + per - 1) / per;
-    const int64_t blocks = g.gene_blocks * T * ranges;
-    const double cost = (double)((blocks + num_cu - 1) / num_cu) * ((double)per + kMfmaPanelLoadStages);
-    if (g.rp == 0 || cost < best) best = cost, g.rp = ranges, g.per = per, g.blocks = blocks;
+  g.stages = S;
+  g.Q = T * S;
+  g.gene_blocks = gene_blocks;
+  for (const MfmaRange& c : cands) {
+    const int64_t blocks = gene_blocks * c.ranges;
+    const double cost = (double)((blocks + num_cu - 1) / num_cu) *
+                        ((double)c.L + kMfmaBlockStartStages + (double)c.switches * kMfmaTraitSwitchStages);
+    if (g.L == 0 || cost < g.cost) g.cost = cost, g.ranges = c.ranges, g.L = c.L, g.blocks = blocks;
   }
   return g;
+}
+
+MfmaGeom scoary_mfma_geom(int num_cu, int64_t k_split, int64_t T, int64_t P, int64_t ntiles) {
+  return mfma_pick(mfma_ranges(T, P, ntiles), num_cu, (k_split + kBlockGenes - 1) / kBlockGenes, (P + 63) / 64, T);
 }
 
 int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, const void* d_panels, void* d_bfrag,
@@ -340,7 +469,7 @@ int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, 
     KernelTimer kt(h, s, "k_permute_mfma");
     hipLaunchKernelGGL(k_permute_mfma, dim3((unsigned)g.blocks), dim3(kBlockWaves * 64), kMfmaLds, s,
                        static_cast<const v4i*>(d_panels), static_cast<const unsigned char*>(d_bfrag),
-                       reinterpret_cast<const uint2*>(d_lcrit), (int)G, P, (int)g.stages, (int)g.per, (int)g.rp,
+                       reinterpret_cast<const uint2*>(d_lcrit), (int)G, P, (int)g.stages, g.Q, (int)g.L,
                        (int)g.gene_blocks, (int)ntiles, gs, d_partial);
   }
   HIP_TRY(h, hipGetLastError());
@@ -377,6 +506,13 @@ int scoary_mfma_panels_build(scoary_handle h, const uint32_t* d_tiled, int64_t G
   return SCOARY_OK;
 }
 
+int scoary_mfma_plan(int num_cu, int64_t k_split, int64_t T, int64_t P, int64_t* out) {
+  if (num_cu < 1 || k_split < 1 || T < 1 || P < 1 || !out) return SCOARY_ERR_ARG;
+  const MfmaGeom g = scoary_mfma_geom(num_cu, k_split, T, P, (P + 511) / 512);
+  out[0] = g.gene_blocks, out[1] = g.ranges, out[2] = g.L, out[3] = g.blocks;
+  return SCOARY_OK;
+}
+
 int scoary_set_mfma_route(scoary_handle h, int mode) {
   if (!h) return SCOARY_ERR_ARG;
   if (mode < SCOARY_MFMA_ROUTE_NONE || mode > SCOARY_MFMA_ROUTE_AUTO)
@@ -385,8 +521,8 @@ int scoary_set_mfma_route(scoary_handle h, int mode) {
   return SCOARY_OK;
 }
 
-// AUTO: the whole number of 256-slot blocks that makes (rounds of MFMA blocks over the CUs) x (stages + panel
-// load) x (time of a stage) + (entries left to the lists) x kListNsPerEntry smallest.  Where a round of blocks
+// AUTO: the whole number of 256-slot blocks that makes (the cost of its cheapest plan, scoary_mfma_geom) x (time
+// of a stage) + (entries left to the lists) x kListNsPerEntry smallest.  Where a round of blocks
 // is short against the whole this is the break-even length; the rounds term keeps the split off block counts
 // that are a fraction over a multiple of the CU count (cfg3: 106 gene blocks x 10 traits = 4.1 rounds).
 int64_t scoary_mfma_route(scoary_handle h, const int64_t* block_start, int64_t G, int64_t T, int64_t N, int64_t P) {
@@ -399,11 +535,11 @@ int64_t scoary_mfma_route(scoary_handle h, const int64_t* block_start, int64_t G
   const double stage_ns = kMfmaNsPerGene * h->num_cu * kBlockGenes * 64 / 1e5;   // one block, one stage
   double best = kListNsPerEntry * (double)total * tests;
   int64_t best_nb = 0;
+  const std::vector<MfmaRange> cands = mfma_ranges(T, P, (P + 511) / 512);
   for (int64_t b = 1; b <= nb; ++b) {
-    const MfmaGeom g = scoary_mfma_geom(h->num_cu, b * kBlockGenes, T, P, (P + 511) / 512);
+    const MfmaGeom g = mfma_pick(cands, h->num_cu, b, (P + 63) / 64, T);
     if (g.blocks < h->num_cu) continue;            // less than one round of blocks over the CUs: lists
-    const double cost = (double)((g.blocks + h->num_cu - 1) / h->num_cu) * ((double)g.per + kMfmaPanelLoadStages) * stage_ns +
-                        kListNsPerEntry * (double)(total - block_start[b]) * tests;
+    const double cost = g.cost * stage_ns + kListNsPerEntry * (double)(total - block_start[b]) * tests;
     if (cost < best) best = cost, best_nb = b;
   }
   return best_nb * kBlockGenes;

@@ -3,7 +3,7 @@
 next to k_permute_lists on the same genes, and the two rates the break-even constants of
 scoary_mfma.hip (kMfmaNsPerGene, kListNsPerEntry) are derived from.  r is compared with the dense kernel.
 
-    python tools/mfma_route_bench.py [--config cfg3] [--gene-kind balanced] [--steps 5]
+    python tools/mfma_route_bench.py [--config cfg3] [--gene-kind balanced] [--steps 5] [--sweep P,P,...]
 """
 import argparse
 import json
@@ -23,6 +23,9 @@ def main():
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--gene-kind", default=None)
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--sweep", default=None, metavar="P,P,...",
+                    help="also time k_permute_mfma with every gene routed at these permutation counts and fit "
+                         "the plan's constants (e.g. 512,1024,2048,3072,4096,6144,8192,10000)")
     args = ap.parse_args()
     genes, traits, P, seed = synth.make_config(args.config, gene_kind=args.gene_kind)
     G, N = genes.shape
@@ -78,8 +81,57 @@ def main():
             row["list_ns_per_entry"] = med["k_permute_lists"] * 1e6 / (padded - routed) * scale
         out["modes"][mode] = row
         print(mode, json.dumps(row), flush=True)
+    if args.sweep:
+        out["sweep"] = sweep(eng, gm, trv, mkv, T, seed, [int(p) for p in args.sweep.split(",")])
     eng.set_mfma_route("auto")
     print(json.dumps(out))
+
+
+def sweep(eng, gm, trv, mkv, T, seed, perms):
+    """k_permute_mfma with every gene routed over a range of P: its launch plan (scoary_mfma_plan), its time, and
+    the least-squares fit of  time = rounds x (L + c_start + switches x c_switch) x tau  -- the constants
+    kMfmaBlockStartStages and kMfmaTraitSwitchStages of scoary_mfma.hip and the time of a stage."""
+    import ctypes
+
+    import torch
+    num_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    eng.set_mfma_route("all")
+    rows = []
+    # the first Tk traits as well: plans of one trait count tend to share their switches, which the fit cannot
+    # tell from the start of a block then
+    for Tk, P in [(Tk, P) for Tk in sorted({T, max(1, T // 2), min(T, 2), 1}, reverse=True) for P in perms]:
+        plan = (ctypes.c_int64 * 4)()
+        assert eng.lib.scoary_mfma_plan(num_cu, gm.G, Tk, P, plan) == 0
+        gene_blocks, R, L, blocks = (int(v) for v in plan)
+        S = -(-P // 64)
+        Q = Tk * S
+        switches = max((min(Q, (r + 1) * L) - 1) // S - r * L // S for r in range(R))
+        tr, mk = trv[:Tk].contiguous(), mkv[:Tk].contiguous()
+        ws = eng.workspace(gm, Tk, P, use_lists=True)
+        for _ in range(2):
+            eng.associate(gm, tr, mk, permutations=P, seed=seed, use_lists=True, workspace=ws, graph=False)
+        torch.cuda.synchronize()
+        eng.set_timing(True)
+        ms = []
+        for _ in range(5):
+            eng.associate(gm, tr, mk, permutations=P, seed=seed, use_lists=True, workspace=ws, graph=False)
+            torch.cuda.synchronize()
+            ms.append(eng.kernel_ms("k_permute_mfma"))
+        eng.set_timing(False)
+        row = {"T": Tk, "P": P, "R": R, "L": L, "blocks": blocks, "rounds": -(-blocks // num_cu),
+               "switches": switches, "k_permute_mfma_ms": float(np.median(ms))}
+        rows.append(row)
+        print("sweep", json.dumps(row), flush=True)
+    A = np.array([[r["rounds"] * r["L"], r["rounds"], r["rounds"] * r["switches"]] for r in rows], dtype=np.float64)
+    y = np.array([r["k_permute_mfma_ms"] for r in rows])
+    if np.linalg.matrix_rank(A) < 3:           # the plans' switches do not vary on their own: two unknowns
+        A = A[:, :2]
+    coef = np.linalg.lstsq(A, y, rcond=None)[0]
+    fit = {"tau_ms_per_stage": float(coef[0]), "c_start_stages": float(coef[1] / coef[0]),
+           "c_switch_stages": float(coef[2] / coef[0]) if len(coef) > 2 else None,
+           "max_rel_residual": float(np.max(np.abs(A @ coef - y) / y))}
+    print("fit", json.dumps(fit), flush=True)
+    return {"rows": rows, "fit": fit}
 
 
 if __name__ == "__main__":

@@ -1,10 +1,14 @@
 """Inputs and host-side references of the Cochran-Mantel-Haenszel tests (spec S10): deterministic, numpy only at
 import (Case touches the engine it is handed, nothing else does), so the CPU tests can build the same cases and show
 from the restatement (cmh_spec.py) alone that they reach the edges they are meant to reach.  A helper, not a test."""
+import math
 from fractions import Fraction
 
 import numpy as np
 
+import cmh_exact_odds_spec as S13
+import cmh_exact_spec as S12
+import cmh_homog_spec as S14
 import cmh_spec as S10
 
 P_NORMAL = 2.3e-308                  # just above the smallest normal double: below it p has no relative accuracy
@@ -258,3 +262,134 @@ def subsample_pairs(T, G, count=20):
     """About ``count`` (trait, gene) pairs spread evenly over [T, G]."""
     flat = np.unique(np.linspace(0, T * G - 1, count).astype(np.int64))
     return [(int(f) // G, int(f) % G) for f in flat]
+
+
+# -- what the device tests of S10, S12, S13 and S14 hold a result to: the fixed-shape files and the randomised corpus
+#    (strata_stress_cases.py) call the same functions, so both stand at the same bounds ------------------------------
+def check_cmh(out, want):
+    """cmh()'s result as numpy arrays against ``restate``'s of the same pairs: stat, e2, var and odds bit for bit,
+    the region, nan and p = 1 exactly where no stratum is informative, p within check_p."""
+    for key in ("stat", "e2", "var", "odds"):
+        assert np.array_equal(out[key], want[key], equal_nan=True), key
+    assert np.array_equal(out["crit"].view(np.uint32), want["crit"])
+    dead = want["var"] == 0
+    assert np.array_equal(np.isnan(out["stat"]), dead) and (out["p"][dead] == 1.0).all()
+    check_p(out["p"], want["p"])
+    return dead
+
+
+def check_exact_pairs(c, got, pairs, what, reference=S12.reference, allow_ties=0):
+    """The pairs ``pairs`` of a case against the reference: table, p (bit-identical to its table entry), p_region.
+    Near-tied pairs are dropped from the p comparison (at most ``allow_ties`` of them); returns how many were."""
+    a, m, k, n = c.recount()
+    tab_got, tab_want, p_got, p_want, r_got, r_want, ties = [], [], [], [], [], [], 0
+    for t, g in pairs:
+        tabs = tables(a, m, k, n, t, g)
+        ref = reference(tabs)
+        lo, tab, p, region = ref[:4]
+        o = got["off"][t * c.G + g]
+        row = got["tab"][o:got["off"][t * c.G + g + 1]]
+        assert got["lo"][t, g] == lo and len(row) == len(tab), (t, g)
+        assert got["a"][t, g] == S10.cmh(tabs)["a"] and tuple(got["crit"][t, g]) == tuple(S10.cmh(tabs)["crit"])
+        assert got["p"][t, g] == row[got["a"][t, g] - lo], (t, g)          # the gene's own entry, bit for bit
+        assert row.max() == 1.0 and row.min() >= 0.0
+        if len(ref) > 4 and ref[4]:
+            ties += 1
+            continue
+        tab_got.append(row), tab_want.append(tab), p_got.append(got["p"][t, g]), p_want.append(p)
+        r_got.append(got["p_region"][t, g]), r_want.append(region)
+    assert ties <= allow_ties, "%d near-tied pairs" % ties
+    if tab_got:
+        S12.check(np.concatenate(tab_got), np.concatenate(tab_want), what + ", tables")
+        S12.check(p_got, p_want, what + ", p")
+        S12.check(r_got, r_want, what + ", p_region")
+    return ties
+
+
+ODDS_EPS = 1e-12
+ODDS_EXACT_BUDGET = 1_000_000     # sum of L^2 over the pairs of a case that take the exact check (about a second)
+
+
+def check_odds_case(c, got, a_dev, level, what, pairs=None):
+    """cmh_exact_odds() as float64 [3, T, G] (odds, lower, upper): every pair of ``pairs`` (default: all) against the
+    references; returns {"special": counts of the exact values met, "L": the support sizes, "unspecified": pairs with
+    f(A) < 1e-290}."""
+    half = S13.half_of(level)
+    a, m, k, n = c.recount()
+    pairs = [(t, g) for t in range(c.T) for g in range(c.G)] if pairs is None else pairs
+    sampled = set(subsample_pairs(c.T, c.G, 200)) & set(pairs) if len(pairs) > 200 else set(pairs)
+    budget, exact, worst, seen = ODDS_EXACT_BUDGET, 0, 0.0, {"zero": 0, "inf": 0, "nan": 0, "L": [], "unspecified": 0}
+    for t, g in pairs:
+        tabs = tables(a, m, k, n, t, g)
+        lo, f = S12.float_pmf(tabs)
+        A, L = S10.cmh(tabs)["a"], len(f)
+        assert a_dev[t, g] == A
+        seen["L"].append(L)
+        mine = tuple(float(v) for v in got[:, t, g])
+        if L > 1 and f[A - lo] < S12.TINY:
+            seen["unspecified"] += 1
+            assert all(v >= 0 for v in mine), (what, t, g, mine)                # (nan >= 0 is False)
+            continue
+        if (t, g) in sampled and 1 < L <= 600 and budget >= L * L:
+            budget -= L * L
+            exact += 1
+            weights = S12.exact_weights(tabs)
+            for which, v in zip(S13.WHICH, mine):
+                want = S13.special(tabs, which)
+                if want is None:
+                    assert math.isfinite(v) and v > 0 and S13.brackets(tabs, half, v, which, ODDS_EPS, weights), \
+                        (what, t, g, which, v, S13.restate_pmf(f, A - lo, half))
+                else:
+                    assert v == want, (what, t, g, which, v, want)
+        else:
+            worst = max(worst, S13.check_values(mine, S13.restate_pmf(f, A - lo, half), (what, t, g)))
+        seen["zero"] += mine[0] == 0.0
+        seen["inf"] += mine[0] == math.inf
+        seen["nan"] += math.isnan(mine[0])
+        if L > 1:
+            assert mine[1] <= mine[0] <= mine[2], (what, t, g, mine)
+    print("cmh exact odds %s, level %s: %d pairs, %d by the exact check at 1e-12, the others within %.2e relative of "
+          "the restatement; supports of %d to %d entries; %d at 0, %d at inf, %d nan, %d unspecified"
+          % (what, level, len(pairs), exact, worst, min(seen["L"]), max(seen["L"]), seen["zero"], seen["inf"],
+             seen["nan"], seen["unspecified"]))
+    return seen, exact
+
+
+HOMOG_P_SPECIFIED = 1e-290           # S14: below it any p in [0, 1e-290] stands for the true one
+
+
+def check_homog_case(c, got, odds, what, pairs=None):
+    """cmh_homogeneity() as numpy arrays and the odds ratios of cmh() it read: the pairs of ``pairs`` (default: all)
+    against the restatement; returns (defined rows, undefined rows, the largest df)."""
+    a, m, k, n = c.recount()
+    pairs = [(t, g) for t in range(c.T) for g in range(c.G)] if pairs is None else pairs
+    defined = undefined = 0
+    worst_p, top_df = 0.0, 0
+    for t, g in pairs:
+        tabs = tables(a, m, k, n, t, g)
+        psi = float(odds[t, g])
+        want = S10.cmh(tabs)["odds"]
+        assert psi == want or (math.isnan(psi) and math.isnan(want)), (what, t, g, psi, want)
+        bd, tarone, df, _p = S14.homogeneity(tabs, psi)
+        mine = (float(got["stat_bd"][t, g]), float(got["stat_tarone"][t, g]), int(got["df"][t, g]),
+                float(got["p"][t, g]))
+        if df == 0:
+            undefined += 1
+            assert math.isnan(mine[0]) and math.isnan(mine[1]) and mine[2:] == (0, 1.0), (what, t, g, mine)
+            continue
+        defined += 1
+        top_df = max(top_df, df)
+        assert mine[:3] == (bd, tarone, df), (what, t, g, psi, mine, (bd, tarone, df))     # the restatement's bits
+        p_want = S14.chi2_sf(mine[1], mine[2])
+        assert 0.0 <= mine[3] <= 1.0
+        if p_want >= HOMOG_P_SPECIFIED:
+            err = abs(mine[3] - p_want) / p_want
+            worst_p = max(worst_p, err)
+            assert err <= 1e-10, (what, t, g, mine, p_want)
+        else:
+            assert mine[3] <= HOMOG_P_SPECIFIED, (what, t, g, mine, p_want)
+        if mine[1] == 0.0:
+            assert mine[3] == 1.0
+    print("cmh homogeneity %s: %d pairs, %d defined (bit for bit), %d undefined, df up to %d, p within %.2e relative"
+          % (what, len(pairs), defined, undefined, top_df, worst_p))
+    return defined, undefined, top_df

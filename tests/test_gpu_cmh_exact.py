@@ -12,7 +12,6 @@ import pytest
 
 import cmh_cases as C
 import cmh_exact_spec as S12
-import cmh_spec as S10
 import cmh_wy_spec as S11
 from cmh_cases import Case
 
@@ -44,30 +43,7 @@ def run_exact(eng, c, tables=True):
     return res, out
 
 
-def check_pairs(c, got, pairs, what, reference=S12.reference, allow_ties=0):
-    """The pairs ``pairs`` of a case against the reference: table, p (bit-identical to its table entry), p_region.
-    Near-tied pairs are dropped (at most ``allow_ties`` of them)."""
-    a, m, k, n = c.recount()
-    tab_got, tab_want, p_got, p_want, r_got, r_want, ties = [], [], [], [], [], [], 0
-    for t, g in pairs:
-        tabs = C.tables(a, m, k, n, t, g)
-        ref = reference(tabs)
-        lo, tab, p, region = ref[:4]
-        o = got["off"][t * c.G + g]
-        row = got["tab"][o:got["off"][t * c.G + g + 1]]
-        assert got["lo"][t, g] == lo and len(row) == len(tab), (t, g)
-        assert got["a"][t, g] == S10.cmh(tabs)["a"] and tuple(got["crit"][t, g]) == tuple(S10.cmh(tabs)["crit"])
-        assert got["p"][t, g] == row[got["a"][t, g] - lo], (t, g)          # the gene's own entry, bit for bit
-        assert row.max() == 1.0 and row.min() >= 0.0
-        if len(ref) > 4 and ref[4]:
-            ties += 1
-            continue
-        tab_got.append(row), tab_want.append(tab), p_got.append(got["p"][t, g]), p_want.append(p)
-        r_got.append(got["p_region"][t, g]), r_want.append(region)
-    assert ties <= allow_ties, "%d near-tied pairs" % ties
-    S12.check(np.concatenate(tab_got), np.concatenate(tab_want), what + ", tables")
-    S12.check(p_got, p_want, what + ", p")
-    S12.check(r_got, r_want, what + ", p_region")
+check_pairs = C.check_exact_pairs      # table, p (bit-identical to its table entry) and p_region against the reference
 
 
 def all_pairs(c):

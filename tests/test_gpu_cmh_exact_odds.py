@@ -5,7 +5,6 @@ of at most 600 entries to the exact bracketing check in integers at 1e-12 instea
 Pairs with f(A) < 1e-290 are outside the specification: there the values must be non-negative and not nan."""
 import csv
 import io
-import math
 import os
 import sys
 
@@ -13,14 +12,10 @@ import numpy as np
 import pytest
 
 import cmh_cases as C
-import cmh_exact_odds_spec as S13
 import cmh_exact_spec as S12
-import cmh_spec as S10
 from cmh_cases import Case
 
 pytestmark = pytest.mark.gpu
-EPS = 1e-12
-EXACT_BUDGET = 1_000_000          # sum of L^2 over the pairs of a case that take the exact check (about a second)
 
 
 @pytest.fixture(scope="module")
@@ -44,46 +39,8 @@ def run_odds(eng, c, level=0.95):
 
 
 def check_case(c, got, a_dev, level, what, pairs=None):
-    """Every pair of ``pairs`` (default: all) against the references; returns {"special": counts of the exact values
-    met, "L": the support sizes, "unspecified": pairs with f(A) < 1e-290}."""
-    half = S13.half_of(level)
-    a, m, k, n = c.recount()
-    pairs = [(t, g) for t in range(c.T) for g in range(c.G)] if pairs is None else pairs
-    sampled = set(C.subsample_pairs(c.T, c.G, 200)) & set(pairs) if len(pairs) > 200 else set(pairs)
-    budget, exact, worst, seen = EXACT_BUDGET, 0, 0.0, {"zero": 0, "inf": 0, "nan": 0, "L": [], "unspecified": 0}
-    for t, g in pairs:
-        tabs = C.tables(a, m, k, n, t, g)
-        lo, f = S12.float_pmf(tabs)
-        A, L = S10.cmh(tabs)["a"], len(f)
-        assert a_dev[t, g] == A
-        seen["L"].append(L)
-        mine = tuple(float(v) for v in got[:, t, g])
-        if L > 1 and f[A - lo] < S12.TINY:
-            seen["unspecified"] += 1
-            assert all(v >= 0 for v in mine), (what, t, g, mine)                # (nan >= 0 is False)
-            continue
-        if (t, g) in sampled and 1 < L <= 600 and budget >= L * L:
-            budget -= L * L
-            exact += 1
-            weights = S12.exact_weights(tabs)
-            for which, v in zip(S13.WHICH, mine):
-                want = S13.special(tabs, which)
-                if want is None:
-                    assert math.isfinite(v) and v > 0 and S13.brackets(tabs, half, v, which, EPS, weights), \
-                        (what, t, g, which, v, S13.restate_pmf(f, A - lo, half))
-                else:
-                    assert v == want, (what, t, g, which, v, want)
-        else:
-            worst = max(worst, S13.check_values(mine, S13.restate_pmf(f, A - lo, half), (what, t, g)))
-        seen["zero"] += mine[0] == 0.0
-        seen["inf"] += mine[0] == math.inf
-        seen["nan"] += math.isnan(mine[0])
-        if L > 1:
-            assert mine[1] <= mine[0] <= mine[2], (what, t, g, mine)
-    print("cmh exact odds %s, level %s: %d pairs, %d by the exact check at 1e-12, the others within %.2e relative of "
-          "the restatement; supports of %d to %d entries; %d at 0, %d at inf, %d nan, %d unspecified"
-          % (what, level, len(pairs), exact, worst, min(seen["L"]), max(seen["L"]), seen["zero"], seen["inf"],
-             seen["nan"], seen["unspecified"]))
+    """cmh_cases.check_odds_case, and that the exact check took part wherever a support allowed it."""
+    seen, exact = C.check_odds_case(c, got, a_dev, level, what, pairs)
     assert exact > 0 or min(seen["L"]) > 600 or max(seen["L"]) == 1
     return seen
 

@@ -4,7 +4,6 @@ with the per-stratum counts of numpy and the odds ratio the device itself wrote:
 p within 1e-10 relative of the restatement's tail at the device's own statistic and df."""
 import csv
 import io
-import math
 import os
 import sys
 
@@ -20,7 +19,6 @@ from conftest import golden_text, read_dense
 
 pytestmark = pytest.mark.gpu
 SEED = 1973
-P_SPECIFIED = 1e-290                 # S14: below it any p in [0, 1e-290] stands for the true one
 
 
 @pytest.fixture(scope="module")
@@ -45,41 +43,7 @@ def run_homog(eng, c):
     return got, res["odds"].cpu().numpy()
 
 
-def check_case(c, got, odds, what, pairs=None):
-    """The pairs of ``pairs`` (default: all) against the restatement; returns (defined rows, undefined rows, the
-    largest df)."""
-    a, m, k, n = c.recount()
-    pairs = [(t, g) for t in range(c.T) for g in range(c.G)] if pairs is None else pairs
-    defined = undefined = 0
-    worst_p, top_df = 0.0, 0
-    for t, g in pairs:
-        tabs = C.tables(a, m, k, n, t, g)
-        psi = float(odds[t, g])
-        want = S10.cmh(tabs)["odds"]
-        assert psi == want or (math.isnan(psi) and math.isnan(want)), (what, t, g, psi, want)
-        bd, tarone, df, _p = S14.homogeneity(tabs, psi)
-        mine = (float(got["stat_bd"][t, g]), float(got["stat_tarone"][t, g]), int(got["df"][t, g]),
-                float(got["p"][t, g]))
-        if df == 0:
-            undefined += 1
-            assert math.isnan(mine[0]) and math.isnan(mine[1]) and mine[2:] == (0, 1.0), (what, t, g, mine)
-            continue
-        defined += 1
-        top_df = max(top_df, df)
-        assert mine[:3] == (bd, tarone, df), (what, t, g, psi, mine, (bd, tarone, df))     # the restatement's bits
-        p_want = S14.chi2_sf(mine[1], mine[2])
-        assert 0.0 <= mine[3] <= 1.0
-        if p_want >= P_SPECIFIED:
-            err = abs(mine[3] - p_want) / p_want
-            worst_p = max(worst_p, err)
-            assert err <= 1e-10, (what, t, g, mine, p_want)
-        else:
-            assert mine[3] <= P_SPECIFIED, (what, t, g, mine, p_want)
-        if mine[1] == 0.0:
-            assert mine[3] == 1.0
-    print("cmh homogeneity %s: %d pairs, %d defined (bit for bit), %d undefined, df up to %d, p within %.2e relative"
-          % (what, len(pairs), defined, undefined, top_df, worst_p))
-    return defined, undefined, top_df
+check_case = C.check_homog_case      # both statistics and df bit for bit, p within 1e-10 relative of the restatement
 
 
 # ---- 1. the kernel against the restatement ----------------------------------------------------------------------

@@ -78,8 +78,22 @@ def test_bench_three_ranks_uneven_strong_shards():
     assert [r["exchange_bytes"] for r in d["per_rank"]] == [3334 * 40, 3333 * 40, 3333 * 40]
 
 
-@pytest.mark.parametrize("extra", [["--no_pairwise", "-e", "200", "--seed", "7"], ["--collapse", "-c", "I", "-p", "0.05"]],
-                         ids=["fisher-permutations", "pairwise-collapse"])
+def _three_strata_file(exampledir, tmp_path):
+    """A lineage file for the example data: three strata, the isolates in reverse order, a row that is in no table."""
+    from args_cases import strains
+    names = strains(exampledir)
+    path = os.path.join(str(tmp_path), "three.csv")
+    with open(path, "w") as f:
+        f.write("Isolate,Lineage,Comment\nnot_in_the_table,L9,\n")
+        for i, s in reversed(list(enumerate(names))):
+            f.write("%s,%s,whatever\n" % (s, ("clade A", "clade B", "7")[(i * 7 // len(names)) % 3]))
+    return path
+
+
+@pytest.mark.parametrize("extra", [["--no_pairwise", "-e", "200", "--seed", "7"], ["--collapse", "-c", "I", "-p", "0.05"],
+                                   ["--no_pairwise", "-e", "200", "--seed", "7", "--permute-fwer", "--permute-strata",
+                                    "FILE"]],
+                         ids=["fisher-permutations", "pairwise-collapse", "stratified-permutations"])
 def test_command_line_two_ranks_share_the_gpu(exampledir, tmp_path, extra):
     """`python -m scoary_amd` under torch.distributed.run with two ranks on the one GPU
     (SCOARY_SHARE_GPU=1, SCOARY_DIST_BACKEND=gloo): every rank parses one byte range of the
@@ -88,6 +102,7 @@ def test_command_line_two_ranks_share_the_gpu(exampledir, tmp_path, extra):
     run's (Tree.nwk included in default mode).  Reference analogue: scoary/methods.py:1076-1122."""
     inputs = ["-g", os.path.join(exampledir, "Gene_presence_absence.csv"),
               "-t", os.path.join(exampledir, "Tetracycline_resistance.csv")]
+    extra = [_three_strata_file(exampledir, tmp_path) if arg == "FILE" else arg for arg in extra]
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")

@@ -547,6 +547,39 @@ int scoary_permute_hybrid(scoary_handle h, const uint32_t *d_tiles, const uint32
                           int64_t G, int64_t T, int64_t N, int64_t P, uint32_t *d_r,
                           int accumulate, const void *d_panels, void *d_bfrag, int64_t k_split,
                           int64_t routed_entries, scoary_stream_t stream);
+/* ---- B fragments written by the label generator (additive, ABI 11) -----------------------------
+ * The generator holds a stage's label bits in LDS when it writes its tile rows, so it can write the
+ * stage's B fragments as well and the conversion pass (k_mfma_bfrag) goes.
+ *   scoary_perm_generate_tiles_bfrag_range / scoary_perm_generate_tiles_strata_bfrag_range : their
+ *       namesakes without _bfrag, which ALSO write into d_bfrag (scoary_mfma_bfrag_bytes(N, P, T)
+ *       bytes, of any content) the fragments of every stage of 64 permutations whose (trait, tile)
+ *       lies in the range -- the bytes scoary_permute_hybrid would make of these tiles; stages of
+ *       tiles outside the range are left as they are.  The tiles are those of the namesake, byte
+ *       for byte.  SCOARY_ERR_SIZE (nothing written) unless N <= scoary_mfma_max_isolates()
+ *   scoary_permute_hybrid_bfrag : scoary_permute_hybrid with bfrag_ready = 1 saying that d_bfrag
+ *       already holds the fragments of d_tiles (a generator call above, same N, P, T, every tile):
+ *       the conversion is skipped.  bfrag_ready = 0 is scoary_permute_hybrid. */
+int scoary_perm_generate_tiles_bfrag_range(scoary_handle h, const uint32_t *d_masks,
+                                           const int32_t *d_margins, int64_t T, int64_t N, int64_t P,
+                                           int64_t perm_base, int64_t trait_base, uint64_t seed,
+                                           int64_t first_tile, int64_t n_tiles, uint32_t *d_tiles,
+                                           void *d_bfrag, scoary_stream_t stream);
+int scoary_perm_generate_tiles_strata_bfrag_range(scoary_handle h, const uint32_t *d_masks,
+                                                  const uint16_t *d_strata, const int32_t *d_members,
+                                                  const int32_t *d_offsets, const int32_t *d_smargins,
+                                                  int64_t T, int64_t N, int64_t S, int64_t P,
+                                                  int64_t perm_base, int64_t trait_base, uint64_t seed,
+                                                  int64_t first_tile, int64_t n_tiles,
+                                                  uint32_t *d_tiles, void *d_bfrag,
+                                                  scoary_stream_t stream);
+int scoary_permute_hybrid_bfrag(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
+                                int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,
+                                const int32_t *d_lorder, const uint8_t *d_lflipped,
+                                const uint32_t *d_crit, const uint32_t *d_lcrit,
+                                const int32_t *d_margins, void *d_scratch,
+                                int64_t G, int64_t T, int64_t N, int64_t P, uint32_t *d_r,
+                                int accumulate, const void *d_panels, void *d_bfrag, int64_t k_split,
+                                int64_t routed_entries, int bfrag_ready, scoary_stream_t stream);
 
 /* ---- index lists of the list-driven kernel, built on the device -----------------
  * From the tiled gene matrix already in HBM (no host pass, no PCIe copy of the

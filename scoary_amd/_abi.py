@@ -61,12 +61,16 @@ SIGNATURES = {
                                           _vp]),
     "scoary_perm_generate_tiles_range": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _u64, _i64,
                                                 _i64, _vp, _vp]),
+    "scoary_perm_generate_tiles_bfrag_range": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _u64, _i64,
+                                                      _i64, _vp, _vp, _vp]),
     "scoary_perm_max_isolates": (_i64, []),
     "scoary_perm_max_strata": (_i32, []),
     "scoary_perm_strata_max_isolates": (_i64, []),
     "scoary_strata_margins": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "scoary_perm_generate_strata": (_i32, [_vp] * 6 + [_i64] * 6 + [_u64, _vp, _vp]),
     "scoary_perm_generate_tiles_strata_range": (_i32, [_vp] * 6 + [_i64] * 6 + [_u64, _i64, _i64, _vp, _vp]),
+    "scoary_perm_generate_tiles_strata_bfrag_range": (_i32, [_vp] * 6 + [_i64] * 6 + [_u64, _i64, _i64, _vp, _vp,
+                                                                                     _vp]),
     "scoary_cmh_scratch_bytes": (_i64, [_i64]),
     "scoary_cmh": (_i32, [_vp] * 8 + [_i64] * 4 + [_vp] * 10),
     "scoary_cmh_minp_plan": (_i32, [_vp] * 7 + [_i64] * 4 + [_vp] * 3 + [ctypes.POINTER(_i64), _vp]),
@@ -88,6 +92,8 @@ SIGNATURES = {
     "scoary_mfma_plan": (_i32, [_i32, _i64, _i64, _i64, ctypes.POINTER(_i64)]),
     "scoary_permute_hybrid": (_i32, [_vp, _vp, _vp, _i64] + [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp,
                                                                         _i32, _vp, _vp, _i64, _i64, _vp]),
+    "scoary_permute_hybrid_bfrag": (_i32, [_vp, _vp, _vp, _i64] + [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp,
+                                                                              _i32, _vp, _vp, _i64, _i64, _i32, _vp]),
     "scoary_lists_scratch_bytes": (_i64, [_i64, _i64]),
     "scoary_lists_slack_entries": (_i64, []),
     "scoary_lists_plan": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp,

@@ -49,7 +49,7 @@ struct MfmaGeom {
 MfmaGeom scoary_mfma_geom(int num_cu, int64_t k_split, int64_t T, int64_t P, int64_t ntiles);
 int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, const void* d_panels, void* d_bfrag,
                        const uint32_t* d_lcrit, uint16_t* d_partial, int64_t k_split, int64_t G, int64_t T,
-                       int64_t N, int64_t P, int64_t ntiles, int64_t gs);
+                       int64_t N, int64_t P, int64_t ntiles, int64_t gs, bool bfrag_ready);
 
 // scoary_cmh.hip: the strata plan as the segment table (CmhSegments, below) in d_scratch = scoary_cmh_scratch_bytes(N)
 // bytes -- THE launch of k_cmh_segments, for scoary_cmh, scoary_cmh_minp_plan and scoary_cmh_exact.  `event`: the
@@ -233,6 +233,61 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   out[1] = c1;
   out[2] = c2;
   out[3] = c3;
+}
+
+// ---- the B operand of k_permute_mfma (scoary_mfma.hip): THE definition of its layout, for the two kernels that
+// write it (k_mfma_bfrag from label tiles in HBM, the label generator from its rows in LDS) ----
+typedef int v4i __attribute__((ext_vector_type(4)));
+constexpr int kKSteps = 32;                       // K-steps of 64 isolates: N <= 2048
+constexpr int kFragBytes = 1024;                  // one operand fragment: 64 lanes x 16 bytes (32 E2M1 values)
+constexpr int kStageBytes = 2 * kKSteps * kFragBytes;   // B of (trait, 64 permutations): [K-step][column tile][lane]
+
+// 8 presence bits -> 8 E2M1 nibbles (bit i -> nibble i = 0b0010 = 1.0): pairs of bits select a byte
+// of the pool {0x00, 0x02, 0x20, 0x22} through v_perm_b32
+__device__ __forceinline__ uint32_t fp4_of_bits8(uint32_t b) {
+  uint32_t y = b | (b << 12);
+  y = (y | (y << 6)) & 0x03030303u;
+  return __builtin_amdgcn_perm(0u, 0x22200200u, y);
+}
+__device__ __forceinline__ v4i fp4_of_bits32(uint32_t w) {
+  return v4i{(int)fp4_of_bits8(w & 0xffu), (int)fp4_of_bits8((w >> 8) & 0xffu),
+             (int)fp4_of_bits8((w >> 16) & 0xffu), (int)fp4_of_bits8(w >> 24)};
+}
+
+// A 32 x 32 bit matrix held one row per lane by the 32 lanes of a wavefront half, transposed: bit c of lane i
+// becomes bit i of lane c.  Five butterfly stages; stage s swaps the off-diagonal s x s blocks of every 2s x 2s
+// block -- a lane takes its partner's word (lane ^ s, ds_swizzle) rotated by s towards the bits it gives away and
+// keeps the bits of its own diagonal block.
+__device__ __forceinline__ uint32_t bit_transpose32(uint32_t x) {
+  const uint32_t lane = threadIdx.x;
+#define SCOARY_TRANSPOSE_STAGE(S, M)                                                                     \
+  {                                                                                                      \
+    const uint32_t p = (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, ((S) << 10) | 0x1f);                \
+    const bool up = lane & (S);                                                                          \
+    const uint32_t r = __builtin_amdgcn_alignbit(p, p, up ? (S) : 32 - (S)), keep = up ? ~(M) : (M);     \
+    x = (x & keep) | (r & ~keep);                                                                        \
+  }
+  SCOARY_TRANSPOSE_STAGE(16, 0x0000ffffu)
+  SCOARY_TRANSPOSE_STAGE(8, 0x00ff00ffu)
+  SCOARY_TRANSPOSE_STAGE(4, 0x0f0f0f0fu)
+  SCOARY_TRANSPOSE_STAGE(2, 0x33333333u)
+  SCOARY_TRANSPOSE_STAGE(1, 0x55555555u)
+#undef SCOARY_TRANSPOSE_STAGE
+  return x;
+}
+
+// Column tile j of stage s of trait t: bfrag[t][s][K-step k][j][lane] x 16 bytes, S stages per trait.  Lane l
+// holds permutation 64 s + 32 j + (l & 31), isolates 64 k + 32 (l >> 5) .. + 31.  row_word(row) = the 32
+// permutation bits of isolate `row` in this column tile (bit c = permutation 64 s + 32 j + c), zero for rows >= N:
+// a wavefront takes 64 rows (lane = isolate) and each of its halves transposes its 32 x 32 bits.  Every one of the
+// kKSteps K-steps is written, zeros included (k_permute_mfma masks columns, not rows).  Called by whole
+// wavefronts, wavefront `wave` of the `nwaves` that share the work.
+template <class RowWord>
+__device__ __forceinline__ void mfma_bfrag_emit(v4i* __restrict__ bfrag, int S, int t, int s, int j, int wave,
+                                                int nwaves, RowWord row_word) {
+  const int lane = threadIdx.x & 63;
+  v4i* out = bfrag + ((int64_t)t * S + s) * (kStageBytes / 16) + j * 64 + lane;
+  for (int k = wave; k < kKSteps; k += nwaves) out[k * 128] = fp4_of_bits32(bit_transpose32(row_word(k * 64 + lane)));
 }
 
 struct CmhSegments {                 // the layout of scoary_cmh's d_scratch (k_cmh_segments)

@@ -18,8 +18,10 @@
 //            on K the marked set is uniform among K-subsets, and adding / removing uniformly
 //            chosen isolates keeps it uniform -- the result is exactly uniform under ideal
 //            random words;
-//   output   isolate-major LDS tiles (scoary_perm_generate_tiles) or permutation-major bit rows
-//            (scoary_perm_generate, through 32 ballots per 64 isolates).
+//   output   isolate-major LDS tiles (scoary_perm_generate_tiles), the same tiles together with the E2M1 B
+//            fragments of k_permute_mfma (scoary_perm_generate_tiles_bfrag_range: a block's columns are one
+//            stage of that kernel, or half of one) or permutation-major bit rows (scoary_perm_generate); the
+//            last two through 32 ballots per 64 isolates.
 //
 // A block = (trait, NB dword columns of 32 permutations); its rows live in LDS until the fix-up is
 // done: N * NB * 4 bytes (NB = 1 or 2 by how many blocks the launch has).  Beyond N = 40 000 a
@@ -107,6 +109,7 @@ struct LabelArgs {
   int ntiles, TW;
   int64_t first_flat, nflat; // flat (trait, tile) range of this launch
   uint32_t* out;
+  v4i* bfrag;                // tiles + fragments: [trait][stage][K-step][column tile][lane], mfma_bfrag_emit
 };
 
 // What a block produces: (trait, NB dword columns of 32 permutations), or with sub-dword rows the bits
@@ -116,6 +119,7 @@ struct LabelBlock {
   int t, bit0;
   uint32_t Bglob;            // Philox block of column 0
   uint32_t* tile_base;       // tiles: row 0, column `col` of the block's tile
+  int stage, jcol;           // tiles + fragments: column w is column tile jcol + w of this stage (< 0: none to write)
   uint32_t live[NB];         // permutations of column w that exist, as a mask over the 32 bits of the Philox block
 };
 // The block map of both kernels.  SUB: rows may keep fewer than 32 permutations of a dword (a.elt_log2 < 5;
@@ -127,7 +131,8 @@ __device__ __forceinline__ bool label_block(const LabelArgs& a, LabelBlock<NB>& 
   const int subs = 32 >> elt_log2;                   // blocks that share one dword column
   int64_t lc0 = 0;                                   // tiles: dword column among this launch's permutations
   b.tile_base = nullptr;
-  if constexpr (OUT == 0) {
+  b.stage = -1, b.jcol = 0;
+  if constexpr (OUT != 1) {
     // block id -> (flat tile, unit): the units of one tile get ids that are equal mod 8, i.e. run
     // on one XCD (observed placement: block b on XCD b % 8), so the 4 * NB-byte pieces they
     // write into the same tile rows meet in one L2 and leave it as whole lines
@@ -146,6 +151,12 @@ __device__ __forceinline__ bool label_block(const LabelArgs& a, LabelBlock<NB>& 
     b.Bglob = (uint32_t)((a.perm_base >> 5) + lc0);
     // (more than one segment means N > 20479, hence TW == kSegTW; below that this is list_tile_dwords)
     b.tile_base = a.out + f * list_tile_dwords_seg(a.N, a.TW) + col;
+    if constexpr (OUT == 2) {
+      // sixteen-dword tiles of whole dwords (the entry point checks): a stage of 64 permutations is two columns,
+      // and the buffer ends at the last stage that holds a permutation
+      const int stage = tile * 8 + (col >> 1);
+      if ((int64_t)stage * 64 < a.P) b.stage = stage, b.jcol = col & 1;
+    }
   } else {
     b.t = blockIdx.y;
     b.Bglob = (uint32_t)((a.perm_base >> 5) + blockIdx.x / subs);
@@ -154,7 +165,7 @@ __device__ __forceinline__ bool label_block(const LabelArgs& a, LabelBlock<NB>& 
 #pragma unroll
   for (int w = 0; w < NB; ++w) {
     int64_t lo, hi;                                  // bits [lo, hi) of the block exist
-    if constexpr (OUT == 0) {
+    if constexpr (OUT != 1) {
       lo = 0;
       hi = a.P - (lc0 + w) * 32;
     } else {
@@ -339,9 +350,9 @@ template <int NB, int OUT, class RowField>
 __device__ __forceinline__ void emit_labels(const LabelArgs& a, const LabelBlock<NB>& b, RowField row_field) {
   const int tid = threadIdx.x, lane = tid & 63, tpb = blockDim.x, nwaves = tpb >> 6;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int N = a.N, elt = 1 << a.elt_log2, bit0 = b.bit0;
+  const int N = a.N, elt = OUT == 2 ? 32 : 1 << a.elt_log2, bit0 = b.bit0;
   uint32_t* tile_base = b.tile_base;
-  if constexpr (OUT == 0) {
+  if constexpr (OUT != 1) {
     const bool seg = a.TW == kSegTW;                  // two-dword tiles: segmented above N = 20479
     auto row_off = [&](int64_t row) -> int64_t { return seg ? list_row_dword(N, row) : row * a.TW; };
     if (elt == 32) {
@@ -374,8 +385,17 @@ __device__ __forceinline__ void emit_labels(const LabelArgs& a, const LabelBlock
         else *dst = 0;
       }
     }
+    if constexpr (OUT == 2) {
+      // the same bits once more as the stage's B fragments: the K-steps go round the wavefronts of the block
+      if (b.stage >= 0) {
+#pragma unroll
+        for (int w = 0; w < NB; ++w)
+          mfma_bfrag_emit(a.bfrag, (int)((a.P + 63) >> 6), b.t, b.stage, b.jcol + w, wave, nwaves,
+                          [&](int row) { return row < N ? row_field(row, w) : 0u; });
+      }
+    }
   } else {
-    static_assert(OUT == 0 || NB == 1, "bit rows: one dword column per block");
+    static_assert(OUT != 1 || NB == 1, "bit rows: one dword column per block");
     // permutation-major rows: 64 isolates per wavefront step, one ballot per permutation
     const int nchunks = (N + 63) >> 6;
     const int64_t pl = (int64_t)b.Bglob * 32 + bit0 + lane - a.perm_base;   // lane < elt: its permutation
@@ -399,15 +419,35 @@ __device__ __forceinline__ void emit_labels(const LabelArgs& a, const LabelBlock
   }
 }
 
-// NB dword columns per block (NB > 1 only with all 32 permutations per dword); OUT 0: tiles, 1: rows
+// tiles + fragments: a block none of whose permutations exists (the columns of the last tile beyond P) has zero
+// rows to write, and zero fragments where its stage still holds permutations -- nothing to draw
+template <int NB, int OUT>
+__device__ __forceinline__ bool emit_dead_block(const LabelArgs& a, const LabelBlock<NB>& b) {
+  if constexpr (OUT == 2) {
+    uint32_t any = 0u;
+#pragma unroll
+    for (int w = 0; w < NB; ++w) any |= b.live[w];
+    if (any == 0u) {
+      emit_labels<NB, OUT>(a, b, [](int, int) { return 0u; });
+      return true;
+    }
+  }
+  return false;
+}
+
+// NB dword columns per block (NB > 1 only with all 32 permutations per dword); OUT 0: tiles, 1: rows, 2: tiles and
+// the B fragments of k_permute_mfma
 template <int NB, int OUT>   // NB = 1, 2
 __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const int tid = threadIdx.x, lane = tid & 63, tpb = blockDim.x;
   const int N = a.N;
-  const int elt = 1 << a.elt_log2;                  // permutation bits a row keeps per column
+  constexpr bool SUB = OUT != 2;                    // rows of fewer than 32 permutations: never with fragments
+  const int elt_log2 = SUB ? a.elt_log2 : 5;
+  const int elt = 1 << elt_log2;                    // permutation bits a row keeps per column
   LabelBlock<NB> blk;
-  if (!label_block<NB, OUT, true>(a, blk)) return;
+  if (!label_block<NB, OUT, SUB>(a, blk)) return;
+  if (emit_dead_block<NB, OUT>(a, blk)) return;
   const int t = blk.t, bit0 = blk.bit0;
   const uint32_t Bglob = blk.Bglob;
   const uint32_t (&live)[NB] = blk.live;
@@ -456,7 +496,7 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
           carry = nc;
         }
     }
-    store_row0<NB>(xs, row, x, a.elt_log2);
+    store_row0<NB>(xs, row, x, elt_log2);
   }
   // ---- marks per permutation: butterfly over the wavefront, then one LDS atomic per wavefront ----
 #pragma unroll
@@ -511,7 +551,7 @@ __global__ __launch_bounds__(1024) void k_labels(const LabelArgs a) {
     if (elt == 32) {
       f = xs[(int64_t)row * NB + w];
     } else {
-      const uint32_t bp = (uint32_t)row << a.elt_log2;
+      const uint32_t bp = (uint32_t)row << elt_log2;
       f = (xs[bp >> 5] >> (bp & 31u)) & fieldmask;
     }
     if (plan.flip) {
@@ -540,7 +580,7 @@ struct StrataArgs {
   int S;
 };
 
-// NB dword columns of 32 permutations per block; OUT 0: tiles, 1: rows.  The block shape of k_labels.
+// NB dword columns of 32 permutations per block; OUT as for k_labels.  The block shape of k_labels.
 template <int NB, int OUT>   // NB = 1, 2
 __global__ __launch_bounds__(1024) void k_labels_strata(const LabelArgs a, const StrataArgs sa) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -548,6 +588,7 @@ __global__ __launch_bounds__(1024) void k_labels_strata(const LabelArgs a, const
   const int N = a.N, S = sa.S;
   LabelBlock<NB> blk;
   if (!label_block<NB, OUT, false>(a, blk)) return;
+  if (emit_dead_block<NB, OUT>(a, blk)) return;
   const int t = blk.t;
   const uint32_t Bglob = blk.Bglob;
   const uint32_t (&live)[NB] = blk.live;
@@ -708,16 +749,22 @@ int launch_block(scoary_handle h, hipStream_t s, void (*kernel)(Args...), int op
 int launch_labels(scoary_handle h, hipStream_t s, const LabelArgs& a, int NB, int OUT, dim3 grid, int tpb) {
   // the per-lane mark counters would wrap (labels_threads never picks such a geometry)
   const bool fits = (int64_t)tpb * kMaxRowsPerThread >= a.N;
-  return launch_block(h, s, OUT ? k_labels<1, 1> : (NB == 2 ? k_labels<2, 0> : k_labels<1, 0>),
-                      1 << (NB + 8 * OUT) /* 2, 4 | 512 */, labels_lds<int64_t>(a.N, 1 << a.elt_log2, NB).bytes(), fits,
+  return launch_block(h, s,
+                      OUT == 1 ? k_labels<1, 1>
+                               : (OUT == 2 ? (NB == 2 ? k_labels<2, 2> : k_labels<1, 2>)
+                                           : (NB == 2 ? k_labels<2, 0> : k_labels<1, 0>)),
+                      1 << (NB + 4 * OUT) /* 2, 4 | 32 | 512, 1024 */, labels_lds<int64_t>(a.N, 1 << a.elt_log2, NB).bytes(), fits,
                       "k_labels: more than 1023 isolates per thread (or a block size that is no power of two in "
                       "64..1024)", grid, tpb, a);
 }
 int launch_labels_strata(scoary_handle h, hipStream_t s, const LabelArgs& a, const StrataArgs& sa, int NB, int OUT,
                          dim3 grid, int tpb) {
   const int64_t lds_bytes = strata_lds<int64_t>(a.N, NB, sa.S).bytes();
-  return launch_block(h, s, OUT ? k_labels_strata<1, 1> : (NB == 2 ? k_labels_strata<2, 0> : k_labels_strata<1, 0>),
-                      1 << (16 + NB + 8 * OUT), lds_bytes, lds_bytes <= kLabelsMaxLds,
+  return launch_block(h, s,
+                      OUT == 1 ? k_labels_strata<1, 1>
+                               : (OUT == 2 ? (NB == 2 ? k_labels_strata<2, 2> : k_labels_strata<1, 2>)
+                                           : (NB == 2 ? k_labels_strata<2, 0> : k_labels_strata<1, 0>)),
+                      1 << (16 + NB + 4 * OUT), lds_bytes, lds_bytes <= kLabelsMaxLds,
                       "k_labels_strata: rows, members and the stratum table do not fit LDS (or a block size that is "
                       "no power of two in 64..1024)", grid, tpb, a, sa);
 }
@@ -776,8 +823,16 @@ int tile_shape(scoary_handle h, const char* what, int64_t T, int64_t N, int64_t 
   ts.tpb = labels_threads(n_tiles * units, N, h->num_cu);
   return SCOARY_OK;
 }
-void tile_args(LabelArgs& a, const TileShape& ts, int64_t first_tile, int64_t n_tiles) {
+void tile_args(LabelArgs& a, const TileShape& ts, int64_t first_tile, int64_t n_tiles, void* d_bfrag) {
   a.ntiles = (int)ts.ntiles, a.TW = ts.TW, a.first_flat = first_tile, a.nflat = n_tiles;
+  a.bfrag = static_cast<v4i*>(d_bfrag);
+}
+// tiles + fragments: the shapes whose tiles are cut the way k_permute_mfma's stages are -- sixteen-dword tiles of
+// whole dwords, at most kKSteps K-steps of isolates (elt: what labels_elt gives for N)
+int check_bfrag_shape(scoary_handle h, const char* what, int64_t N, int elt) {
+  return (N > scoary_mfma_max_isolates() || list_tw(N) != 16 || elt != 32)
+             ? fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more isolates than scoary_mfma_max_isolates()")
+             : SCOARY_OK;
 }
 
 }  // namespace
@@ -814,19 +869,24 @@ int scoary_perm_generate(scoary_handle h, const uint32_t* d_masks, const int32_t
   return launch_labels(h, s, a, 1, 1, dim3((unsigned)gx, (unsigned)T), labels_threads(gx * T, N, h->num_cu));
 }
 
-int scoary_perm_generate_tiles_range(scoary_handle h, const uint32_t* d_masks, const int32_t* d_margins,
-                                     int64_t T, int64_t N, int64_t P, int64_t perm_base,
-                                     int64_t trait_base, uint64_t seed, int64_t first_tile,
-                                     int64_t n_tiles, uint32_t* d_tiles, scoary_stream_t stream) {
-  const char* what = "scoary_perm_generate_tiles";
+extern "C++" {
+// the tile-range generator, plain; d_bfrag (`fragments`): the B fragments of the range's stages as well
+static int generate_tiles(scoary_handle h, const uint32_t* d_masks, const int32_t* d_margins, int64_t T, int64_t N,
+                          int64_t P, int64_t perm_base, int64_t trait_base, uint64_t seed, int64_t first_tile,
+                          int64_t n_tiles, uint32_t* d_tiles, bool fragments, void* d_bfrag,
+                          scoary_stream_t stream) {
+  const char* what = fragments ? "scoary_perm_generate_tiles_bfrag_range" : "scoary_perm_generate_tiles";
   if (!h) return SCOARY_ERR_ARG;
   if (int rc = check_args(h, what, d_masks && d_margins && d_tiles && T >= 1 && N >= 1 && P >= 1 && perm_base >= 0 &&
-                                       trait_base >= 0 && first_tile >= 0 && n_tiles >= 0))
+                                       trait_base >= 0 && first_tile >= 0 && n_tiles >= 0 &&
+                                       (d_bfrag || !fragments)))
     return rc;
   if (int rc = check_tile_base(h, what, perm_base)) return rc;
   if (T > 65535 || perm_base + P > 0xffffffffLL)
     return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles: T > 65535 or permutation index >= 2^32");
   const int elt = labels_elt(N, 8);
+  if (fragments)
+    if (int rc = check_bfrag_shape(h, what, N, elt)) return rc;
   TileShape ts;
   if (int rc = tile_shape(h, what, T, N, P, first_tile, n_tiles, elt,
                           [&](int nb) { return labels_lds(N, 32, nb); }, ts))
@@ -835,9 +895,27 @@ int scoary_perm_generate_tiles_range(scoary_handle h, const uint32_t* d_masks, c
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   LabelArgs a = label_args(d_masks, d_margins, N, P, perm_base, trait_base, seed, elt, d_tiles);
-  tile_args(a, ts, first_tile, n_tiles);
-  KernelTimer kt(h, s, "k_perm_generate_tiles");
-  return launch_labels(h, s, a, ts.NB, 0, dim3((unsigned)ts.gx), ts.tpb);
+  tile_args(a, ts, first_tile, n_tiles, d_bfrag);
+  KernelTimer kt(h, s, "k_perm_generate_tiles");   // either output mode: the step's generator
+  return launch_labels(h, s, a, ts.NB, fragments ? 2 : 0, dim3((unsigned)ts.gx), ts.tpb);
+}
+}  // extern "C++"
+
+int scoary_perm_generate_tiles_range(scoary_handle h, const uint32_t* d_masks, const int32_t* d_margins,
+                                     int64_t T, int64_t N, int64_t P, int64_t perm_base,
+                                     int64_t trait_base, uint64_t seed, int64_t first_tile,
+                                     int64_t n_tiles, uint32_t* d_tiles, scoary_stream_t stream) {
+  return generate_tiles(h, d_masks, d_margins, T, N, P, perm_base, trait_base, seed, first_tile, n_tiles, d_tiles,
+                        false, nullptr, stream);
+}
+
+int scoary_perm_generate_tiles_bfrag_range(scoary_handle h, const uint32_t* d_masks, const int32_t* d_margins,
+                                           int64_t T, int64_t N, int64_t P, int64_t perm_base,
+                                           int64_t trait_base, uint64_t seed, int64_t first_tile,
+                                           int64_t n_tiles, uint32_t* d_tiles, void* d_bfrag,
+                                           scoary_stream_t stream) {
+  return generate_tiles(h, d_masks, d_margins, T, N, P, perm_base, trait_base, seed, first_tile, n_tiles, d_tiles,
+                        true, d_bfrag, stream);
 }
 
 int scoary_perm_generate_tiles(scoary_handle h, const uint32_t* d_masks, const int32_t* d_margins,
@@ -892,21 +970,25 @@ int scoary_perm_generate_strata(scoary_handle h, const uint32_t* d_masks, const 
                               labels_threads(gx * T, N, h->num_cu));
 }
 
-int scoary_perm_generate_tiles_strata_range(scoary_handle h, const uint32_t* d_masks, const uint16_t* d_strata,
-                                            const int32_t* d_members, const int32_t* d_offsets,
-                                            const int32_t* d_smargins, int64_t T, int64_t N, int64_t S, int64_t P,
-                                            int64_t perm_base, int64_t trait_base, uint64_t seed,
-                                            int64_t first_tile, int64_t n_tiles, uint32_t* d_tiles,
-                                            scoary_stream_t stream) {
-  const char* what = "scoary_perm_generate_tiles_strata_range";
+extern "C++" {
+// the tile-range generator within strata; d_bfrag (`fragments`): the B fragments of the range's stages as well
+static int generate_tiles_strata(scoary_handle h, const uint32_t* d_masks, const uint16_t* d_strata,
+                                 const int32_t* d_members, const int32_t* d_offsets, const int32_t* d_smargins,
+                                 int64_t T, int64_t N, int64_t S, int64_t P, int64_t perm_base, int64_t trait_base,
+                                 uint64_t seed, int64_t first_tile, int64_t n_tiles, uint32_t* d_tiles,
+                                 bool fragments, void* d_bfrag, scoary_stream_t stream) {
+  const char* what = fragments ? "scoary_perm_generate_tiles_strata_bfrag_range"
+                               : "scoary_perm_generate_tiles_strata_range";
   if (!h) return SCOARY_ERR_ARG;
   if (int rc = strata_check(h, what, d_masks && d_strata && d_members && d_offsets && d_smargins && d_tiles &&
                                          P >= 1 && perm_base >= 0 && trait_base >= 0 && first_tile >= 0 &&
-                                         n_tiles >= 0, T, N, S))
+                                         n_tiles >= 0 && (d_bfrag || !fragments), T, N, S))
     return rc;
   if (int rc = check_tile_base(h, what, perm_base)) return rc;
   if (trait_base + T > 0x7fffffffLL || perm_base + P > 0xffffffffLL)
-    return fail(h, SCOARY_ERR_SIZE, "scoary_perm_generate_tiles_strata_range: permutation index >= 2^32");
+    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": permutation index >= 2^32");
+  if (fragments)
+    if (int rc = check_bfrag_shape(h, what, N, 32)) return rc;
   TileShape ts;
   if (int rc = tile_shape(h, what, T, N, P, first_tile, n_tiles, 32,
                           [&](int nb) { return strata_lds(N, nb, S); }, ts))
@@ -915,10 +997,31 @@ int scoary_perm_generate_tiles_strata_range(scoary_handle h, const uint32_t* d_m
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   LabelArgs a = label_args(d_masks, nullptr, N, P, perm_base, trait_base, seed, 32, d_tiles);
-  tile_args(a, ts, first_tile, n_tiles);
+  tile_args(a, ts, first_tile, n_tiles, d_bfrag);
   const StrataArgs sa{d_strata, d_members, d_offsets, d_smargins, (int)S};
   KernelTimer kt(h, s, "k_perm_generate_tiles_strata");
-  return launch_labels_strata(h, s, a, sa, ts.NB, 0, dim3((unsigned)ts.gx), ts.tpb);
+  return launch_labels_strata(h, s, a, sa, ts.NB, fragments ? 2 : 0, dim3((unsigned)ts.gx), ts.tpb);
+}
+}  // extern "C++"
+
+int scoary_perm_generate_tiles_strata_range(scoary_handle h, const uint32_t* d_masks, const uint16_t* d_strata,
+                                            const int32_t* d_members, const int32_t* d_offsets,
+                                            const int32_t* d_smargins, int64_t T, int64_t N, int64_t S, int64_t P,
+                                            int64_t perm_base, int64_t trait_base, uint64_t seed,
+                                            int64_t first_tile, int64_t n_tiles, uint32_t* d_tiles,
+                                            scoary_stream_t stream) {
+  return generate_tiles_strata(h, d_masks, d_strata, d_members, d_offsets, d_smargins, T, N, S, P, perm_base,
+                               trait_base, seed, first_tile, n_tiles, d_tiles, false, nullptr, stream);
+}
+
+int scoary_perm_generate_tiles_strata_bfrag_range(scoary_handle h, const uint32_t* d_masks, const uint16_t* d_strata,
+                                                  const int32_t* d_members, const int32_t* d_offsets,
+                                                  const int32_t* d_smargins, int64_t T, int64_t N, int64_t S,
+                                                  int64_t P, int64_t perm_base, int64_t trait_base, uint64_t seed,
+                                                  int64_t first_tile, int64_t n_tiles, uint32_t* d_tiles,
+                                                  void* d_bfrag, scoary_stream_t stream) {
+  return generate_tiles_strata(h, d_masks, d_strata, d_members, d_offsets, d_smargins, T, N, S, P, perm_base,
+                               trait_base, seed, first_tile, n_tiles, d_tiles, true, d_bfrag, stream);
 }
 
 }  // extern "C"

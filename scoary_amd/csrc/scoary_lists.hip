@@ -592,7 +592,7 @@ static int launch_lists(scoary_handle h, hipStream_t s, Kernel kernel, const cha
                         const uint8_t* d_lflipped, const uint32_t* d_crit, const uint32_t* d_lcrit_in,
                         const int32_t* d_margins, uint32_t* d_scratch, int64_t G, int64_t T, int64_t N,
                         int64_t P, uint32_t* d_r, int accumulate, const void* d_panels, void* d_bfrag,
-                        int64_t k_split, int64_t routed_entries, Extra... extra) {
+                        int64_t k_split, int64_t routed_entries, bool bfrag_ready, Extra... extra) {
   uint32_t* d_lcrit_sc = d_scratch;                    // [T][G][2]
   uint16_t* d_partial = reinterpret_cast<uint16_t*>(d_scratch + 2 * T * G);   // [T][ntiles][gs]
   const uint32_t* d_lcrit = d_lcrit_in ? d_lcrit_in : d_lcrit_sc;
@@ -609,7 +609,7 @@ static int launch_lists(scoary_handle h, hipStream_t s, Kernel kernel, const cha
   const ListGeom g = list_geom(h->num_cu, G, T, N, P, entries - routed_entries, q_first);
   if (k_split > 0) {
     const int rc = scoary_mfma_launch(h, s, d_tiles, d_panels, d_bfrag, d_lcrit, d_partial, k_split, G, T, N, P,
-                                      g.ntiles, g.gs);
+                                      g.ntiles, g.gs, bfrag_ready);
     if (rc != SCOARY_OK) return rc;
   }
   if (T * g.ntiles > 0x7fffffffLL || g.chunks > 65535)
@@ -667,7 +667,21 @@ int scoary_permute_hybrid(scoary_handle h, const uint32_t* d_tiles, const uint32
                           void* d_scratch, int64_t G, int64_t T, int64_t N, int64_t P,
                           uint32_t* d_r, int accumulate, const void* d_panels, void* d_bfrag,
                           int64_t k_split, int64_t routed_entries, scoary_stream_t stream) {
+  return scoary_permute_hybrid_bfrag(h, d_tiles, d_lidx, entries, d_lstart, d_lngroups, d_lorder, d_lflipped, d_crit,
+                                     d_lcrit, d_margins, d_scratch, G, T, N, P, d_r, accumulate, d_panels, d_bfrag,
+                                     k_split, routed_entries, 0, stream);
+}
+
+int scoary_permute_hybrid_bfrag(scoary_handle h, const uint32_t* d_tiles, const uint32_t* d_lidx,
+                                int64_t entries, const int32_t* d_lstart, const int32_t* d_lngroups,
+                                const int32_t* d_lorder, const uint8_t* d_lflipped,
+                                const uint32_t* d_crit, const uint32_t* d_lcrit, const int32_t* d_margins,
+                                void* d_scratch, int64_t G, int64_t T, int64_t N, int64_t P,
+                                uint32_t* d_r, int accumulate, const void* d_panels, void* d_bfrag,
+                                int64_t k_split, int64_t routed_entries, int bfrag_ready, scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
+  if (bfrag_ready != 0 && bfrag_ready != 1)
+    return fail(h, SCOARY_ERR_ARG, "scoary_permute_hybrid_bfrag: bfrag_ready is 0 or 1");
   if (k_split < 0 || k_split > G || routed_entries < 0 || routed_entries > entries ||
       (k_split > 0 && (!d_panels || !d_bfrag || N > scoary_mfma_max_isolates() ||
                        (k_split % 256 != 0 && k_split != G))))
@@ -688,13 +702,14 @@ int scoary_permute_hybrid(scoary_handle h, const uint32_t* d_tiles, const uint32
   if (list_segments(N) > 1)
     return launch_lists(h, s, &k_permute_seglists<16>, "k_permute_seglists", (size_t)kSegStride * sizeof(uint32_t),
                         32, d_tiles, d_lidx, entries, d_lstart, d_lngroups, d_lorder, d_lflipped, d_crit, d_lcrit,
-                        d_margins, sc, G, T, N, P, d_r, accumulate, nullptr, nullptr, 0, 0, list_segments(N));
+                        d_margins, sc, G, T, N, P, d_r, accumulate, nullptr, nullptr, 0, 0, false, list_segments(N));
   // counter planes KC: lists hold <= N/2 entries, N/2 < 2^KC (and N + 1 < 2^(KC+1))
 #define LAUNCH(TWV, KCV)                                                                             \
   return launch_lists(h, s, &k_permute_lists<list_lpg(TWV), list_nw(TWV), KCV>, "k_permute_lists",  \
                       (size_t)list_tile_dwords(N, TWV) * sizeof(uint32_t), TWV, d_tiles, d_lidx,     \
                       entries, d_lstart, d_lngroups, d_lorder, d_lflipped, d_crit, d_lcrit, d_margins, \
                       sc, G, T, N, P, d_r, accumulate, d_panels, d_bfrag, k_split, routed_entries,       \
+                      bfrag_ready != 0,                                                              \
                       (int)((k_split + kWave / list_lpg(TWV) - 1) / (kWave / list_lpg(TWV))))
   if (TW == 16) LAUNCH(16, 11);
   if (TW == 8) LAUNCH(8, 12);

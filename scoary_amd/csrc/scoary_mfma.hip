@@ -9,8 +9,14 @@
 //
 //   k_mfma_panels  (once per data set)  minority rows of the list slots as E2M1 (0 = 0x0, 1.0 = 0x2)
 //                                       A fragments of v_mfma_scale_f32_32x32x64_f8f6f4, 1 KB per slot
-//   k_mfma_bfrag   (per label batch)    the label tiles of k_labels as E2M1 B fragments, 64 KB per
-//                                       (trait, 64 permutations): the SAME draws the list kernel reads
+//   B fragments    (per label batch)    the labels as E2M1 B fragments, 64 KB per (trait, 64 permutations): the
+//                                       SAME draws the list kernel reads.  The label generator writes them next
+//                                       to its tile rows, out of the rows it holds in LDS (scoary_labels.hip,
+//                                       output mode "tiles + fragments"; the layout is mfma_bfrag_emit's,
+//                                       scoary_common.hpp), and scoary_permute_hybrid_bfrag(bfrag_ready = 1)
+//                                       takes them as they are;
+//   k_mfma_bfrag                        the same fragments from label tiles that come from elsewhere (gathered
+//                                       from other ranks, or a caller's own): scoary_permute_hybrid
 //   k_permute_mfma                      gene operand stationary in registers (128 per lane), two wavefronts
 //                                       per SIMD half a stage apart, B streamed through a four-slot LDS
 //                                       ring by LDS-DMA, region test on the accumulators, 16-bit counts
@@ -21,7 +27,10 @@
 // whatever its list holds, a listed gene kListNsPerEntry per padded list entry -- break-even list length
 // = their ratio (scoary_mfma_breakeven_entries).  Both per 100 000 tests of the gene (cfg3: 10 traits x
 // 10 000 permutations), chip-wide, on MI355X: k_permute_mfma + k_mfma_bfrag with every cfg3 gene routed,
-// k_permute_lists with none (profiles/mfma_ranges.txt: 57.1-59.4 and 0.179-0.184 in three sessions).
+// k_permute_lists with none (profiles/mfma_ranges.txt: 57.1-59.4 and 0.179-0.184 in three sessions).  With the
+// fragments written by the label generator k_mfma_bfrag is no part of the step (1.0 of the 58); one session of
+// that step gave 56.3 and 0.175 (profiles/labels_bfrag.txt), both inside or next to the ranges above: the
+// constants stay until more than one session says otherwise (cfg3's split with them: 32 768 slots, as before).
 const double kMfmaNsPerGene = 58.0;
 const double kListNsPerEntry = 0.18;
 // What a block costs beside its stages, in stage-times of its loop (scoary_mfma_geom; least squares over P and
@@ -34,14 +43,11 @@ const double kMfmaTraitSwitchStages = 2.0;
 namespace {
 
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 
-constexpr int kKSteps = 32;                       // K-steps of 64 isolates: N <= 2048
+// (kKSteps, kFragBytes, kStageBytes and the E2M1 conversion: scoary_common.hpp, with the B-fragment layout)
 constexpr int kBlockGenes = 256;                  // list slots of a block: eight wavefronts x 32
 constexpr int kBlockWaves = 8;                    // two per SIMD
-constexpr int kFragBytes = 1024;                  // one operand fragment: 64 lanes x 16 bytes (32 E2M1 values)
-constexpr int kStageBytes = 2 * kKSteps * kFragBytes;   // B of (trait, 64 permutations): [K-step][column tile][lane]
 constexpr int kHalfBytes = kStageBytes / 2;       // the unit of the LDS ring: 16 K-steps
 constexpr int kRingSlots = 4;                     // 128 KB
 constexpr int kAhead = kRingSlots - 2;            // a half stage is issued this many ticks before its first read
@@ -51,18 +57,6 @@ constexpr int kThrBytes = 32 * 8;                 // behind the ring: the (lo, h
 constexpr int kMfmaLds = kRingBytes + kBlockWaves * kThrBytes;
 static_assert(kRingSlots >= 4 && kMfmaLds <= 160 * 1024 && (kAhead - 1) * kDmaPerHalf < 64,
               "a half stage is issued at least two ticks ahead, within the LDS of a CU and the vmcnt field");
-
-// 8 presence bits -> 8 E2M1 nibbles (bit i -> nibble i = 0b0010 = 1.0): pairs of bits select a byte
-// of the pool {0x00, 0x02, 0x20, 0x22} through v_perm_b32
-__device__ __forceinline__ uint32_t fp4_of_bits8(uint32_t b) {
-  uint32_t y = b | (b << 12);
-  y = (y | (y << 6)) & 0x03030303u;
-  return __builtin_amdgcn_perm(0u, 0x22200200u, y);
-}
-__device__ __forceinline__ v4i fp4_of_bits32(uint32_t w) {
-  return v4i{(int)fp4_of_bits8(w & 0xffu), (int)fp4_of_bits8((w >> 8) & 0xffu),
-             (int)fp4_of_bits8((w >> 16) & 0xffu), (int)fp4_of_bits8(w >> 24)};
-}
 
 // A panels: [wave panel of 64 slots][row tile i][K-step k][lane] x 16 bytes.  Lane l of fragment (i, k)
 // holds slot 64 * panel + 32 i + (l & 31), isolates 64 k + 32 (l >> 5) .. + 31: one 32-bit word of the
@@ -89,34 +83,18 @@ __global__ __launch_bounds__(256) void k_mfma_panels(const uint32_t* __restrict_
   panels[idx] = fp4_of_bits32(bits);
 }
 
-// B fragments from the label tiles (tiles[t][tile][row 0..N][16 dwords], dword j of a row = permutations
-// 512 tile + 32 j .. + 31): bfrag[t][stage s][K-step k][column tile j][lane] x 16 bytes, lane l = permutation
-// 64 s + 32 j + (l & 31), isolates 64 k + 32 (l >> 5) .. + 31.  A wavefront reads dword 2 (s % 8) + j of
-// 64 rows (lane = isolate) and transposes 64 x 32 bits with one ballot per permutation.  Rows >= N are
-// zero; permutations >= P hold whatever the tile holds and are masked by the kernel.
+// B fragments from label tiles that come from elsewhere (tiles[t][tile][row 0..N][16 dwords], dword j of a row =
+// permutations 512 tile + 32 j .. + 31): stage s of trait t is dwords 2 (s % 8) + j of tile s / 8, in the layout of
+// mfma_bfrag_emit (scoary_common.hpp).  Rows >= N are zero; permutations >= P hold whatever the tile holds and are
+// masked by the kernel.
 __global__ __launch_bounds__(256) void k_mfma_bfrag(const uint32_t* __restrict__ tiles, int N, int ntiles,
                                                     int64_t tile_dwords, int S, v4i* __restrict__ bfrag) {
   const int s = blockIdx.x, t = blockIdx.y;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t* tile = tiles + ((int64_t)t * ntiles + (s >> 3)) * tile_dwords + 2 * (s & 7);
-  v4i* out = bfrag + ((int64_t)t * S + s) * (kStageBytes / 16);
-  for (int k = wave; k < kKSteps; k += 4) {
-    const int row = k * 64 + lane;
-    uint2 w = make_uint2(0u, 0u);
-    if (row < N) w = *reinterpret_cast<const uint2*>(tile + (int64_t)row * 16);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const uint32_t x = j ? w.y : w.x;
-      uint32_t mine = 0u;
-#pragma unroll
-      for (int c = 0; c < 32; ++c) {
-        const uint64_t bal = __ballot((x >> c) & 1u);
-        const uint32_t v = (lane >> 5) ? (uint32_t)(bal >> 32) : (uint32_t)bal;
-        if ((lane & 31) == c) mine = v;
-      }
-      out[(k * 2 + j) * 64 + lane] = fp4_of_bits32(mine);
-    }
-  }
+  for (int j = 0; j < 2; ++j)
+    mfma_bfrag_emit(bfrag, S, t, s, j, wave, 4, [&](int row) { return row < N ? tile[(int64_t)row * 16 + j] : 0u; });
 }
 
 // One 16-byte vector per lane, src + 16 * lane -> LDS address lds + 16 * lane, by LDS-DMA: wave-uniform
@@ -451,7 +429,7 @@ MfmaGeom scoary_mfma_geom(int num_cu, int64_t k_split, int64_t T, int64_t P, int
 
 int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, const void* d_panels, void* d_bfrag,
                        const uint32_t* d_lcrit, uint16_t* d_partial, int64_t k_split, int64_t G, int64_t T,
-                       int64_t N, int64_t P, int64_t ntiles, int64_t gs) {
+                       int64_t N, int64_t P, int64_t ntiles, int64_t gs, bool bfrag_ready) {
   const MfmaGeom g = scoary_mfma_geom(h->num_cu, k_split, T, P, ntiles);
   if (g.blocks > 0x7fffffffLL || g.stages > 0x7fffffffLL / 64)
     return fail(h, SCOARY_ERR_SIZE, "scoary_permute_hybrid: grid too large");
@@ -460,7 +438,7 @@ int scoary_mfma_launch(scoary_handle h, hipStream_t s, const uint32_t* d_tiles, 
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     h->mfma_lds_optin = 1;
   }
-  {
+  if (!bfrag_ready) {                               // tiles from elsewhere: the generator did not write d_bfrag
     KernelTimer kt(h, s, "k_mfma_bfrag");
     hipLaunchKernelGGL(k_mfma_bfrag, dim3((unsigned)g.stages, (unsigned)T), dim3(256), 0, s, d_tiles, (int)N,
                        (int)ntiles, list_tile_dwords(N, 16), (int)g.stages, static_cast<v4i*>(d_bfrag));

@@ -239,6 +239,9 @@ class AssociationEngine:
         # dist.LabelShards: generate one share of every batch of label tiles and all-gather the
         # rest (multi-GPU, opt-in); None: every rank generates all tiles (the default)
         self.label_shards = None
+        # the label generator writes the matrix-core kernel's B fragments next to its tiles (_label_tiles);
+        # False: the tiles alone, and every permute_lists converts them (k_mfma_bfrag) -- for comparisons
+        self.fuse_bfrag = True
 
     def close(self):
         if getattr(self, "h", None):
@@ -425,17 +428,33 @@ class AssociationEngine:
         return int(N) <= int(self.lib.scoary_list_max_isolates())
 
     def perm_generate_tiles(self, masks, margins, N, P, perm_base, seed, out=None, trait_base=0,
-                            tile_range=None, strata=None):
+                            tile_range=None, strata=None, bfrag=None):
         """Label tiles of permutations perm_base .. perm_base + P - 1 (perm_base a multiple of
         32).  ``tile_range`` = (first, count): only these flat (trait, tile) indices of the
         [T][tiles] array are written (scoary_perm_generate_tiles_range) -- one rank's share of a
         run that all-gathers the rest (dist.LabelShards).  ``strata``: a StrataPlan of these traits --
-        the labels are shuffled within its strata (spec S9)."""
+        the labels are shuffled within its strata (spec S9).  ``bfrag``: a buffer of scoary_mfma_bfrag_bytes(N, P, T)
+        bytes that also takes the B fragments of the written tiles' stages (N <= 2048), ready for
+        permute_lists(..., bfrag=bfrag, bfrag_ready=True)."""
         torch = _torch()
         T = masks.shape[0]
         if out is None:
             out = self._empty((int(self.lib.scoary_list_tiles_words(N, P, T)),), torch.int32)
-        if strata is not None:
+        if bfrag is not None:
+            if tile_range is None:
+                tile_range = (0, self.tiles_per_batch(N, P, T)[0])
+            if strata is not None:
+                self._strata_fits(strata, T, N)
+                self._check(self.lib.scoary_perm_generate_tiles_strata_bfrag_range(
+                    self.h, self._ptr(masks), *self._strata_ptrs(strata), T, N, strata.S, P, perm_base, trait_base,
+                    ctypes.c_uint64(seed), int(tile_range[0]), int(tile_range[1]), self._ptr(out), self._ptr(bfrag),
+                    self._stream()), "scoary_perm_generate_tiles_strata_bfrag_range")
+            else:
+                self._check(self.lib.scoary_perm_generate_tiles_bfrag_range(
+                    self.h, self._ptr(masks), self._ptr(margins), T, N, P, perm_base, trait_base,
+                    ctypes.c_uint64(seed), int(tile_range[0]), int(tile_range[1]), self._ptr(out), self._ptr(bfrag),
+                    self._stream()), "scoary_perm_generate_tiles_bfrag_range")
+        elif strata is not None:
             self._strata_fits(strata, T, N)
             if tile_range is None:
                 tile_range = (0, self.tiles_per_batch(N, P, T)[0])
@@ -466,10 +485,11 @@ class AssociationEngine:
         return self._empty(((nbytes + 3) // 4,), torch.int32)
 
     def permute_lists(self, genes, tiles, crit, margins, P, r, scratch=None, lcrit=None,
-                      accumulate=True, bfrag=None):
+                      accumulate=True, bfrag=None, bfrag_ready=False):
         """r (+)= exceedance counts of P permutations (label tiles ``tiles``).  The regions
         come in gene order (``crit`` from fisher) or, one launch cheaper, in slot order
-        (``lcrit`` from fisher(..., lists=...)); accumulate=False overwrites r."""
+        (``lcrit`` from fisher(..., lists=...)); accumulate=False overwrites r.  ``bfrag_ready``: ``bfrag`` already
+        holds the B fragments of ``tiles`` (perm_generate_tiles(..., bfrag=bfrag) of the same N, P, T)."""
         L = genes.lists
         T = (lcrit if lcrit is not None else crit).shape[0]
         if scratch is None:
@@ -482,15 +502,15 @@ class AssociationEngine:
             if bfrag is None:
                 bfrag = self._empty((int(self.lib.scoary_mfma_bfrag_bytes(genes.N, P, T)) // 4,), _torch().int32)
             routed = int(L.block_start[-1 if k_split >= genes.G else k_split // 256])
-        self._check(self.lib.scoary_permute_hybrid(
+        self._check(self.lib.scoary_permute_hybrid_bfrag(
             self.h, self._ptr(tiles), self._ptr(L.idx), L.entries, self._ptr(L.start),
             self._ptr(L.ngroups), self._ptr(L.order), self._ptr(L.flipped),
             self._ptr(crit) if lcrit is None else None,
             self._ptr(lcrit) if lcrit is not None else None,
             self._ptr(margins), self._ptr(scratch), genes.G, T, genes.N, P, self._ptr(r),
             1 if accumulate else 0, self._ptr(L.panels) if k_split > 0 else None,
-            self._ptr(bfrag) if k_split > 0 else None, k_split, routed, self._stream()),
-            "scoary_permute_hybrid")
+            self._ptr(bfrag) if k_split > 0 else None, k_split, routed, 1 if bfrag_ready and k_split > 0 else 0,
+            self._stream()), "scoary_permute_hybrid_bfrag")
         return r
 
     # -- a3: counts -----------------------------------------------------------
@@ -1204,7 +1224,7 @@ class AssociationEngine:
         # (a graph recorded without strata is never replayed for a step with strata, or the reverse: the strata
         # plan and its tensors are among the references, and the flag among the scalars)
         scalars = (genes.G, genes.N, int(traits.shape[0]), int(permutations), int(seed), bool(use_lists),
-                   getattr(self, "_mfma_mode", "auto"), strata is not None,
+                   getattr(self, "_mfma_mode", "auto"), bool(self.fuse_bfrag), strata is not None,
                    tuple(getattr(x, "_version", 0) for x in refs))
         st = ws.auto
         same = st is not None and st["scalars"] == scalars and len(st["refs"]) == len(refs) and \
@@ -1223,18 +1243,24 @@ class AssociationEngine:
         st["graph"].launch()
         return st["res"]
 
-    def _label_tiles(self, ws, masks, margins, N, nb, base, seed, strata=None):
+    def _label_tiles(self, ws, masks, margins, N, nb, base, seed, strata=None, genes=None):
         """One batch of label tiles into ws.tiles: all of them, or -- with label shards -- this
-        rank's share followed by the all-gather of the others'."""
+        rank's share followed by the all-gather of the others'.  Returns True if ws.bfrag holds the batch's B
+        fragments as well: the workspace has the buffer, the tiles are generated here (gathered tiles go through
+        k_mfma_bfrag), and the matrix-core kernel takes slots of this launch (``genes``: the step's matrix)."""
         sh = ws.label_shards
         if sh is None or sh.world == 1:
-            self.perm_generate_tiles(masks, margins, N, nb, base, seed, out=ws.tiles, strata=strata)
-            return
+            fuse = self.fuse_bfrag and ws.bfrag is not None and genes is not None and \
+                N <= int(self.lib.scoary_mfma_max_isolates()) and self.mfma_split(genes, masks.shape[0], nb) > 0
+            self.perm_generate_tiles(masks, margins, N, nb, base, seed, out=ws.tiles, strata=strata,
+                                     bfrag=ws.bfrag if fuse else None)
+            return fuse
         nflat, tile_words = self.tiles_per_batch(N, nb, masks.shape[0])
         _per, first, count = sh.share(nflat)
         self.perm_generate_tiles(masks, margins, N, nb, base, seed, out=ws.tiles,
                                  tile_range=(first, count), strata=strata)
         sh.all_gather(ws.tiles, nflat, tile_words)
+        return False
 
     def associate(self, genes, traits, masks, permutations=0, seed=0, perm_buffer=None,
                   use_lists=None, workspace=None, plan=None, graph=None, records=None, fwer=False,
@@ -1349,7 +1375,8 @@ class AssociationEngine:
             side = self._side_stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                self._label_tiles(ws, masks, margins, genes.N, min(ws.batch, permutations), 0, seed, strata)
+                ready = self._label_tiles(ws, masks, margins, genes.N, min(ws.batch, permutations), 0, seed, strata,
+                                          genes)
             p, odds, crit, lcrit = self.fisher(counts, out=(ws.p, ws.odds, ws.crit),
                                                lists=genes.lists, lcrit=ws.lcrit)
         else:
@@ -1366,10 +1393,10 @@ class AssociationEngine:
             while done < permutations:
                 nb = min(ws.batch, permutations - done)
                 if done > 0:
-                    self._label_tiles(ws, masks, margins, genes.N, nb, done, seed, strata)
+                    ready = self._label_tiles(ws, masks, margins, genes.N, nb, done, seed, strata, genes)
                 for regions, r in counted:
                     self.permute_lists(genes, ws.tiles, margins=margins, P=nb, r=r, scratch=ws.scratch,
-                                       accumulate=done > 0, bfrag=ws.bfrag, **regions)
+                                       accumulate=done > 0, bfrag=ws.bfrag, bfrag_ready=ready, **regions)
                 done += nb
         elif permutations > 0:
             ws.r.zero_()

@@ -1,4 +1,5 @@
-"""Time the label-tile generator alone: python tools/gen_time.py N T P [reps]  (events around reps launches)."""
+"""Time the label-tile generator alone: python tools/gen_time.py N T P [reps]  (events around reps launches).
+For N <= 2048 both output modes: the tiles alone, and the tiles with the B fragments of k_permute_mfma."""
 import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np, torch
@@ -15,15 +16,21 @@ def main():
     masks, trv = eng.vecrows(mb, N), eng.vecrows(tb, N)
     _, margins = eng.counts(eng.pack_dense(np.ones((1, N), dtype=np.uint8)), trv, masks)
     out = eng.perm_generate_tiles(masks, margins, N, P, 0, 7)
-    torch.cuda.synchronize()
+    modes = [("tiles", None)]
+    if N <= int(eng.lib.scoary_mfma_max_isolates()):
+        modes.append(("tiles + fragments", eng._empty((int(eng.lib.scoary_mfma_bfrag_bytes(N, P, T)) // 4,), torch.int32)))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    best = 1e9
-    for _ in range(3):
-        e0.record()
-        for _ in range(reps):
-            eng.perm_generate_tiles(masks, margins, N, P, 0, 7, out=out)
-        e1.record(); torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) / reps)
-    print("N=%d T=%d P=%d frac=%.2f: %.4f ms per launch" % (N, T, P, frac, best))
+    for name, bfrag in modes * 2:                     # each mode twice, alternating
+        eng.perm_generate_tiles(masks, margins, N, P, 0, 7, out=out, bfrag=bfrag)
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(3):
+            e0.record()
+            for _ in range(reps):
+                eng.perm_generate_tiles(masks, margins, N, P, 0, 7, out=out, bfrag=bfrag)
+            e1.record(); torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) / reps)
+        print("N=%d T=%d P=%d frac=%.2f %s: %.4f ms per launch (best of %s)"
+              % (N, T, P, frac, name, min(times), " ".join("%.4f" % t for t in times)))
 
 main()

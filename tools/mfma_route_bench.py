@@ -1,9 +1,11 @@
 """Per-kernel times of the permutation step under the three routing modes of the matrix-core kernel
-(none / all / auto), on a BASELINE config's shape: what k_permute_mfma and its B-operand conversion cost
-next to k_permute_lists on the same genes, and the two rates the break-even constants of
-scoary_mfma.hip (kMfmaNsPerGene, kListNsPerEntry) are derived from.  r is compared with the dense kernel.
+(none / all / auto), on a BASELINE config's shape: what k_permute_mfma costs next to k_permute_lists on the same
+genes, and the two rates the break-even constants of scoary_mfma.hip (kMfmaNsPerGene, kListNsPerEntry) are derived
+from.  The step is the engine's: the label generator writes the B fragments itself (k_mfma_bfrag does not run and
+counts as 0; the generator's time is listed beside it); --unfused puts the conversion pass back (tiles from
+elsewhere).  r is compared with the dense kernel.
 
-    python tools/mfma_route_bench.py [--config cfg3] [--gene-kind balanced] [--steps 5] [--sweep P,P,...]
+    python tools/mfma_route_bench.py [--config cfg3] [--gene-kind balanced] [--steps 5] [--unfused] [--sweep P,P,...]
 """
 import argparse
 import json
@@ -26,11 +28,14 @@ def main():
     ap.add_argument("--sweep", default=None, metavar="P,P,...",
                     help="also time k_permute_mfma with every gene routed at these permutation counts and fit "
                          "the plan's constants (e.g. 512,1024,2048,3072,4096,6144,8192,10000)")
+    ap.add_argument("--unfused", action="store_true",
+                    help="generate the tiles alone and convert them with k_mfma_bfrag (engine.fuse_bfrag = False)")
     args = ap.parse_args()
     genes, traits, P, seed = synth.make_config(args.config, gene_kind=args.gene_kind)
     G, N = genes.shape
     T = traits.shape[0]
     eng = AssociationEngine(0)
+    eng.fuse_bfrag = not args.unfused
     gm = eng.pack_dense(genes)
     eng.build_lists(gm)
     L = gm.lists
@@ -41,7 +46,7 @@ def main():
     ws = eng.workspace(gm, T, P, use_lists=True)
     padded = int(L.block_start[-1])
     out = {"config": args.config, "gene_kind": args.gene_kind or "config", "G": G, "N": N, "T": T, "P": P,
-           "padded_entries": padded,
+           "padded_entries": padded, "fused_bfrag": eng.fuse_bfrag,
            "breakeven_entries": int(eng.lib.scoary_mfma_breakeven_entries()), "modes": {}}
     names = ("k_permute_lists", "k_permute_mfma", "k_mfma_bfrag", "k_lists_reduce", "k_perm_generate_tiles")
     for mode in ("none", "all", "auto"):

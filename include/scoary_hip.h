@@ -167,6 +167,32 @@ int scoary_fisher_lists(scoary_handle h, const int32_t *d_tables, int64_t T, int
                         const int32_t *d_lorder, const uint8_t *d_lflipped,
                         double *d_p, double *d_or, uint32_t *d_crit, uint32_t *d_lcrit,
                         scoary_stream_t stream);
+/* scoary_fisher_lists with one weight chain per margin class: the hypergeometric weights a table's walk passes
+ * through depend on (trait, canonical gene count) alone, so a first kernel (k_fisher_chains) walks every class of
+ * the step once -- both sides of the mode, weights and running sums, up to scoary_fisher_chains_capacity() entries
+ * per side or until a weight falls below scoary_fisher_chains_floor() of the mode's -- and the table kernel
+ * (k_fisher_tables) reads a weight where scoary_fisher_lists divides; past the end of a stored chain it walks on by
+ * itself.  Every output is scoary_fisher_lists' own, bit for bit.
+ *   N        : the isolates of the matrix the tables were counted on (every a + b + c + d <= N)
+ *   d_chains : scoary_fisher_chains_bytes(T, N) bytes of caller-owned scratch, rewritten by every call (nothing
+ *              is kept between calls); chains_bytes = its size.  scoary_fisher_chains_bytes returns 0 when the
+ *              slabs would exceed 256 MiB (T * floor(N / 2) > 65536): then, with d_chains = NULL, or with
+ *              scoary_set_fisher_route(h, SCOARY_FISHER_ROUTE_WALK), the call is scoary_fisher_lists.
+ *   scoary_set_fisher_route : for this handle, WALK (scoary_fisher_lists' kernel), CHAINS (the two kernels whenever
+ *              d_chains is given) or AUTO (the default): the two kernels for launches of at least four table
+ *              wavefronts per SIMD of the device (T * G >= 128 per SIMD) -- below that the one kernel is a single
+ *              short round and the chain kernel's serial walks would only be added to it */
+#define SCOARY_FISHER_ROUTE_WALK 0
+#define SCOARY_FISHER_ROUTE_CHAINS 1
+#define SCOARY_FISHER_ROUTE_AUTO 2
+int64_t scoary_fisher_chains_bytes(int64_t T, int64_t N);
+int64_t scoary_fisher_chains_capacity(void);
+double scoary_fisher_chains_floor(void);
+int scoary_set_fisher_route(scoary_handle h, int mode);
+int scoary_fisher_lists_chained(scoary_handle h, const int32_t *d_tables, int64_t T, int64_t G, int64_t N,
+                                const int32_t *d_lorder, const uint8_t *d_lflipped,
+                                double *d_p, double *d_or, uint32_t *d_crit, uint32_t *d_lcrit,
+                                void *d_chains, int64_t chains_bytes, scoary_stream_t stream);
 
 /* ---- a8: PermuteGTC (scoary/methods.py:1371-1384) ----------------------
  * Label permutations pi = perm_base .. perm_base+P-1 of the T traits whose

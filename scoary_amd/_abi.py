@@ -39,6 +39,11 @@ SIGNATURES = {
     "scoary_counts_planned": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "scoary_fisher": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "scoary_fisher_lists": (_i32, [_vp, _vp, _i64, _i64] + [_vp] * 7),
+    "scoary_fisher_chains_bytes": (_i64, [_i64, _i64]),
+    "scoary_fisher_chains_capacity": (_i64, []),
+    "scoary_fisher_chains_floor": (ctypes.c_double, []),
+    "scoary_set_fisher_route": (_i32, [_vp, _i32]),
+    "scoary_fisher_lists_chained": (_i32, [_vp, _vp, _i64, _i64, _i64] + [_vp] * 7 + [_i64, _vp]),
     "scoary_fisher_scipy": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "scoary_fisher_scipy_max_isolates": (_i64, []),
     "scoary_perm_generate": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _u64, _vp, _vp]),

@@ -516,18 +516,29 @@ __device__ __noinline__ double scipy_small_p(int a, int b, int c, int d) {
 // list kernel wants -- (lo, hi1) of the LIST count u, in slot order -- which saves the
 // separate conversion launch (k_lists_crit):
 //   ones-list : u in [base, base + span);  zeros-list: u in [npos - base - span + 1, npos - base + 1)
+//
+// The kernels of the pass (k_fisher here, k_fisher_tables below) differ only in where a weight comes from: what
+// they share -- the table of a lane pair, its canonical orientation and support (fisher_table), and everything
+// after the two walks (fisher_finish) -- is written once.
+struct FisherOut {
+  double* __restrict__ p;
+  double* __restrict__ odds;
+  uint2* __restrict__ crit;
+  uint2* __restrict__ lcrit;
+};
+struct FisherTable {
+  int4 c;                            // the table as counted
+  int64_t idx, lidx;                 // where its results go: gene order, list-slot order
+  bool zeros_list, mirrored;
+  int n1, n2, a, n, lo, hi, mode;    // canonical margins and count, the support and its mode
+};
+
+// The table of lane pair `pid` (M = tables, or genes per trait with SLOTS).  False: a table the reference never
+// tests; its results are written and the pair is done.
 template <bool SLOTS>
-__global__ __launch_bounds__(64) void k_fisher(const int4* __restrict__ tables, int64_t M,
-                                               double* __restrict__ p_out,
-                                               double* __restrict__ or_out,
-                                               uint2* __restrict__ crit,
-                                               const int32_t* __restrict__ order,
-                                               const uint8_t* __restrict__ flipped,
-                                               uint2* __restrict__ lcrit) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t pid = tid >> 1;
-  const bool down = tid & 1;
-  if (pid >= M) return;            // M = tables (SLOTS = false) or genes per trait (true)
+__device__ __forceinline__ bool fisher_table(FisherTable& tb, const int4* __restrict__ tables, int64_t M, int64_t pid,
+                                             bool down, const int32_t* __restrict__ order,
+                                             const uint8_t* __restrict__ flipped, const FisherOut& out) {
   int64_t idx = pid, lidx = 0;
   bool zeros_list = false;
   if constexpr (SLOTS) {
@@ -539,15 +550,16 @@ __global__ __launch_bounds__(64) void k_fisher(const int4* __restrict__ tables, 
   const int4 c = tables[idx];
   const int b = c.y, cc = c.z, d = c.w;
   const int n0 = c.x + cc;
+  tb.c = c, tb.idx = idx, tb.lidx = lidx, tb.zeros_list = zeros_list;
   if (c.x + b == 0 || cc + d == 0 || n0 == 0 || b + d == 0) {
     if (down) {
-      or_out[idx] = __longlong_as_double(0x7ff8000000000000LL);
+      out.odds[idx] = __longlong_as_double(0x7ff8000000000000LL);
     } else {
-      p_out[idx] = 1.0;
-      if (crit) crit[idx] = make_uint2(0u, 0u);
-      if constexpr (SLOTS) lcrit[lidx] = make_uint2(0u, 0u);
+      out.p[idx] = 1.0;
+      if (out.crit) out.crit[idx] = make_uint2(0u, 0u);
+      if constexpr (SLOTS) out.lcrit[lidx] = make_uint2(0u, 0u);
     }
-    return;
+    return false;
   }
   // Canonical orientation (round 6): a gene and the gene with the complementary pattern -- the tables
   // [[a, b], [c, d]] and [[b, a], [d, c]] -- have the same p, and SciPy returns the same double for both
@@ -564,6 +576,71 @@ __global__ __launch_bounds__(64) void k_fisher(const int4* __restrict__ tables, 
   const int lo = max(0, n - n2), hi = min(n, n1);
   int mode = (int)(((double)(n + 1) * (double)(n1 + 1)) / (double)(n1 + n2 + 2));
   mode = min(max(mode, lo), hi);
+  tb.mirrored = mirrored, tb.n1 = n1, tb.n2 = n2, tb.a = a, tb.n = n, tb.lo = lo, tb.hi = hi, tb.mode = mode;
+  return true;
+}
+
+// What follows the two walks of a pair: tot = the weights a lane summed, inc = those inside the rejection region,
+// first = its first term inside the region (own coordinate; -1: none).
+template <bool SLOTS>
+__device__ __forceinline__ void fisher_finish(const FisherTable& tb, bool down, double tot, double inc, int first,
+                                              const FisherOut& out) {
+  const int4 c = tb.c;
+  const int b = c.y, cc = c.z, d = c.w;
+  const int n1 = tb.n1, n2 = tb.n2, n = tb.n, lo = tb.lo, hi = tb.hi, mode = tb.mode;
+  const bool mirrored = tb.mirrored;
+  const int64_t idx = tb.idx;
+  tot += __shfl_xor(tot, 1);
+  inc += __shfl_xor(inc, 1);
+  const int other = __shfl_xor(first, 1);
+  if (down) {
+    out.odds[idx] = (cc > 0 && b > 0) ? ((double)c.x * (double)d) / ((double)cc * (double)b)
+                                      : __longlong_as_double(0x7ff0000000000000LL);
+    return;
+  }
+  const int Hc = first >= 0 ? first : hi + 1;          // region bounds in the canonical coordinate
+  const int Lc = other >= 0 ? n - other : lo - 1;
+  const bool all = (Hc == mode);
+  double p = all ? 1.0 : inc / tot;
+  if (n1 + n2 <= kSciPySmallN) p = scipy_small_p(c.x, b, cc, d);   // the reference's own double (above)
+  out.p[idx] = p < 1.0 ? p : 1.0;
+  const int L = mirrored ? n1 - Hc : Lc, H = mirrored ? n1 - Lc : Hc;   // ... and in the table's own a
+  const uint32_t base = (uint32_t)(L + 1), span = all ? 0u : (uint32_t)(H - L - 1);
+  if (out.crit) out.crit[idx] = all ? make_uint2(0u, 0u) : make_uint2(base, span);
+  if constexpr (SLOTS) {
+    const uint32_t npos = (uint32_t)n1;                // the trait's positives among the valid isolates
+    uint2 o = make_uint2(0u, 0u);                      // span 0: every permutation is in the region
+    if (span != 0u)
+      o = tb.zeros_list ? make_uint2(npos - base - span + 1u, npos - base + 1u)
+                        : make_uint2(base, base + span);
+    out.lcrit[tb.lidx] = o;
+  }
+}
+
+// The region predicate of one term: certain outside kAmbig of a tie, hg_tie inside it
+struct FisherRegion {
+  double sure_in, sure_out, tiny;
+  __device__ __forceinline__ explicit FisherRegion(double wobs)
+      : sure_in(wobs * (1.0 - kAmbig)), sure_out(wobs * (1.0 + kAmbig)),
+        tiny(5.421010862427522e-20 * (wobs < 1.0 ? wobs : 1.0)) {}   // 2^-64 * w_obs
+};
+
+template <bool SLOTS>
+__global__ __launch_bounds__(64) void k_fisher(const int4* __restrict__ tables, int64_t M,
+                                               double* __restrict__ p_out,
+                                               double* __restrict__ or_out,
+                                               uint2* __restrict__ crit,
+                                               const int32_t* __restrict__ order,
+                                               const uint8_t* __restrict__ flipped,
+                                               uint2* __restrict__ lcrit) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t pid = tid >> 1;
+  const bool down = tid & 1;
+  if (pid >= M) return;            // M = tables (SLOTS = false) or genes per trait (true)
+  const FisherOut out{p_out, or_out, crit, lcrit};
+  FisherTable tb;
+  if (!fisher_table<SLOTS>(tb, tables, M, pid, down, order, flipped, out)) return;
+  const int n1 = tb.n1, n2 = tb.n2, a = tb.a, n = tb.n, lo = tb.lo, hi = tb.hi, mode = tb.mode;
 
   // weight of the observed table, walking from the mode towards a
   double w = 1.0;
@@ -585,8 +662,8 @@ __global__ __launch_bounds__(64) void k_fisher(const int4* __restrict__ tables, 
   // The body is predicated rather than branched (a lone wavefront issues an instruction
   // every ~6 cycles, so the instruction count is the latency of a small problem): only the
   // comparisons inside the 1e-9 band around a tie -- rare -- leave the straight line.
-  const double tiny = 5.421010862427522e-20 * (wobs < 1.0 ? wobs : 1.0);   // 2^-64 * w_obs
-  const double sure_in = wobs * (1.0 - kAmbig), sure_out = wobs * (1.0 + kAmbig);
+  const FisherRegion rg(wobs);
+  const double tiny = rg.tiny, sure_in = rg.sure_in, sure_out = rg.sure_out;
   const int xend = down ? n - lo : hi;
   int x = down ? n - mode : mode;          // own (mirrored, for the odd lane) coordinate
   int first = -1;                          // first term inside the region, own coordinate
@@ -606,31 +683,214 @@ __global__ __launch_bounds__(64) void k_fisher(const int4* __restrict__ tables, 
     w = wk.step(w);
     ++x;
   }
-  tot += __shfl_xor(tot, 1);
-  inc += __shfl_xor(inc, 1);
-  const int other = __shfl_xor(first, 1);
-  if (down) {
-    or_out[idx] = (cc > 0 && b > 0) ? ((double)c.x * (double)d) / ((double)cc * (double)b)
-                                    : __longlong_as_double(0x7ff0000000000000LL);
+  fisher_finish<SLOTS>(tb, down, tot, inc, first, out);
+}
+
+// ---- the list path's pass with one weight chain per margin class (scoary_fisher_lists_chained) ----
+// The weights k_fisher walks -- w(mode) = 1 outwards, both sides -- depend on the canonical margins (n1, n2, n)
+// alone: on the trait and the gene's canonical count, not on the observed a.  A step's tables of one trait fall
+// into at most floor((n1 + n2) / 2) such classes (cfg3: 475 000 live tables, 9696 classes), so the division of a
+// step is done once per class instead of once per table: k_fisher_chains stores, per (class, side), the weights
+// w[i] at distance i from the mode and the running sums pre[i] k_fisher's `tot` passes through, and
+// k_fisher_tables runs k_fisher's loop with a weight read where one is stored.  The stored doubles come from the
+// same HgWalk::step in the same order, so every p, odds and region is k_fisher's bit for bit; past the end of a
+// stored chain (capacity, floor) a lane goes on with HgWalk itself -- the same arithmetic again.
+//
+// The slabs (scoary_fisher_chains_bytes): len int32 [T][C][2], then w double [T][C][kChainCap / 4][2][4] and pre
+// double [T][C][2][kChainCap], C = floor(N / 2) classes per trait (class n - 1 of canonical count n), side 0 =
+// upwards.  The weights are kept four terms of the upward side, then the same four of the downward side: the two
+// lanes of a pair read 64 consecutive bytes, 32 each, for four terms of their loop.  (Against one row per side it
+// measured the same in k_fisher_tables, whose time is its instruction count, and 33 -> 26 us in k_fisher_chains.)
+constexpr int kChainCap = 128;                  // entries per (class, side): cfg3's longest table needs 115
+constexpr double kChainFloor = 0x1p-96;         // a chain ends below this (the mode is 1): cfg3's tables stop by 2^-81
+constexpr int64_t kChainBudget = (int64_t)256 << 20;   // larger slabs: scoary_fisher_chains_bytes = 0, k_fisher runs
+// AUTO takes the chains from this many table wavefronts per SIMD on.  The chain kernel is one round of serial walks
+// (26 us at cfg3, whatever the number of tables) and the table kernel saves about half of k_fisher's time per
+// wavefront: cfg3 (15 per SIMD) 109 -> 26 + 61..100 us, cfg4 (6) a step inside its spread, cfg2 (0.3: k_fisher is one
+// short round) 0.069 -> 0.078 ms per step with the chains.  Not measured between 0.3 and 6.
+constexpr int kChainMinWavesPerSimd = 4;
+struct ChainSlabs {
+  int32_t* len;
+  double *w, *pre;
+  int C;
+  static __host__ __device__ int64_t len_bytes(int64_t T, int64_t C) { return (T * C * 2 * 4 + 255) / 256 * 256; }
+  static __host__ __device__ int64_t bytes(int64_t T, int64_t C) {
+    return len_bytes(T, C) + T * C * 2 * kChainCap * 16;
+  }
+  // weight i of a side of class `cls`
+  static __host__ __device__ int64_t w_index(int64_t cls, int side, int i) {
+    return cls * (2 * kChainCap) + (i >> 2) * 8 + side * 4 + (i & 3);
+  }
+  __host__ ChainSlabs(void* base, int64_t T, int64_t C_)
+      : len(static_cast<int32_t*>(base)),
+        w(reinterpret_cast<double*>(static_cast<char*>(base) + len_bytes(T, C_))),
+        pre(w + T * C_ * 2 * kChainCap), C((int)C_) {}
+};
+
+// A lane pair per class (trait blockIdx.y, canonical count n = 1 .. C): k_fisher's two walks from the mode, every
+// weight and running sum stored.  The margins are those of the trait's tables (a + b and c + d are the same for
+// all of them); classes past floor((n1 + n2) / 2) and traits with an empty margin have no tables: length 0.
+__global__ __launch_bounds__(64) void k_fisher_chains(const int4* __restrict__ tables, int64_t G, ChainSlabs ch) {
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int cls = tid >> 1;
+  const bool down = tid & 1;
+  if (cls >= ch.C) return;
+  const int4 c0 = tables[(int64_t)blockIdx.y * G];
+  const int n1 = c0.x + c0.y, n2 = c0.z + c0.w, n = cls + 1;
+  const int64_t slot = ((int64_t)blockIdx.y * ch.C + cls) * 2 + down;
+  if (n1 < 1 || n2 < 1 || n > (n1 + n2) / 2) {
+    ch.len[slot] = 0;
     return;
   }
-  const int Hc = first >= 0 ? first : hi + 1;          // region bounds in the canonical coordinate
-  const int Lc = other >= 0 ? n - other : lo - 1;
-  const bool all = (Hc == mode);
-  double p = all ? 1.0 : inc / tot;
-  if (n1 + n2 <= kSciPySmallN) p = scipy_small_p(c.x, b, cc, d);   // the reference's own double (above)
-  p_out[idx] = p < 1.0 ? p : 1.0;
-  const int L = mirrored ? n1 - Hc : Lc, H = mirrored ? n1 - Lc : Hc;   // ... and in the table's own a
-  const uint32_t base = (uint32_t)(L + 1), span = all ? 0u : (uint32_t)(H - L - 1);
-  if (crit) crit[idx] = all ? make_uint2(0u, 0u) : make_uint2(base, span);
-  if constexpr (SLOTS) {
-    const uint32_t npos = (uint32_t)n1;                // the trait's positives among the valid isolates
-    uint2 o = make_uint2(0u, 0u);                      // span 0: every permutation is in the region
-    if (span != 0u)
-      o = zeros_list ? make_uint2(npos - base - span + 1u, npos - base + 1u)
-                     : make_uint2(base, base + span);
-    lcrit[lidx] = o;
+  const int lo = max(0, n - n2), hi = min(n, n1);
+  int mode = (int)(((double)(n + 1) * (double)(n1 + 1)) / (double)(n1 + n2 + 2));
+  mode = min(max(mode, lo), hi);
+  const int xend = down ? n - lo : hi;
+  int x = down ? n - mode : mode;
+  double* __restrict__ cw = ch.w;
+  const int64_t wcls = slot >> 1;
+  double* __restrict__ cpre = ch.pre + slot * kChainCap;
+  bool take = !down;                       // as in k_fisher: the mode's term belongs to the upward lane
+  double w = 1.0, pre = 0.0;
+  HgWalk wk(x, down ? n2 : n1, down ? n1 : n2, n);
+  int i = 0;
+  for (;;) {
+    pre += take ? w : 0.0;
+    cw[ChainSlabs::w_index(wcls, down, i)] = w;
+    cpre[i] = pre;
+    if (x >= xend || i + 1 >= kChainCap || w < kChainFloor) break;
+    take = true;
+    w = wk.step(w);
+    ++x;
+    ++i;
   }
+  ch.len[slot] = i + 1;
+}
+
+// k_fisher<true> with the chains of k_fisher_chains: the observed weight is one read (no walk from the mode to a),
+// and the loop takes weight i of its side from the slab while i < len, from HgWalk afterwards (positioned at the
+// last stored term).  `tot` is not summed over stored terms: it is pre[] at the index the loop ends on.  The
+// region predicate is evaluated per term, as in k_fisher.  A table whose class is not in the slabs (n > C, or
+// margins that are not those of the trait's first table) has length 0 on both sides and is walked as k_fisher does.
+__global__ __launch_bounds__(64) void k_fisher_tables(const int4* __restrict__ tables, int64_t M,
+                                                      double* __restrict__ p_out,
+                                                      double* __restrict__ or_out,
+                                                      uint2* __restrict__ crit,
+                                                      const int32_t* __restrict__ order,
+                                                      const uint8_t* __restrict__ flipped,
+                                                      uint2* __restrict__ lcrit, ChainSlabs ch) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t pid = tid >> 1;
+  const bool down = tid & 1;
+  if (pid >= M) return;
+  const FisherOut out{p_out, or_out, crit, lcrit};
+  FisherTable tb;
+  if (!fisher_table<true>(tb, tables, M, pid, down, order, flipped, out)) return;
+  const int n1 = tb.n1, n2 = tb.n2, a = tb.a, n = tb.n, lo = tb.lo, hi = tb.hi, mode = tb.mode;
+  const int4 c0 = tables[(int64_t)blockIdx.y * M];
+  const bool stored = n <= ch.C && c0.x + c0.y == n1 && c0.z + c0.w == n2;
+  const int64_t cls = stored ? ((int64_t)blockIdx.y * ch.C + (n - 1)) * 2 : 0;
+
+  const int2 lens = stored ? reinterpret_cast<const int2*>(ch.len)[cls >> 1] : make_int2(0, 0);
+
+  // weight of the observed table: entry |a - mode| of a's side, or walked on from that chain's last entry
+  double w;
+  {
+    const bool below = a < mode;
+    const int j = below ? mode - a : a - mode;
+    const int len = below ? lens.y : lens.x;
+    if (j < len) {
+      w = ch.w[ChainSlabs::w_index(cls >> 1, below, j)];
+    } else {
+      int k = len > 0 ? len - 1 : 0;
+      w = len > 0 ? ch.w[ChainSlabs::w_index(cls >> 1, below, k)] : 1.0;
+      HgWalk wk((below ? n - mode : mode) + k, below ? n2 : n1, below ? n1 : n2, n);
+      for (; k < j; ++k) w = wk.step(w);
+    }
+  }
+  const FisherRegion rg(w);
+  const double tiny = rg.tiny, sure_in = rg.sure_in, sure_out = rg.sure_out;
+
+  const int len = down ? lens.y : lens.x;
+  const double* __restrict__ cw = ch.w + ChainSlabs::w_index(cls >> 1, down, 0);   // term i: cw[(i >> 2) * 8 + (i & 3)]
+  const double* __restrict__ cpre = ch.pre + (cls + down) * kChainCap;
+  const int xend = down ? n - lo : hi;
+  int x = down ? n - mode : mode;          // own (mirrored, for the odd lane) coordinate
+  int i = 0;                               // distance from the mode: the term (x, i) is the next one
+  int first = -1;
+  bool take = !down;
+  double tot = 0.0, inc = 0.0;
+  // one term of k_fisher's loop; true: the loop ends on it (and i stays its index)
+  auto term = [&](double wt) -> bool {
+    bool in = wt <= sure_in;
+    if (!in && !(wt > sure_out)) in = hg_tie(n1, n2, n, down ? n - x : x, a);
+    in = in && take;
+    if (i >= len) tot += take ? wt : 0.0;
+    inc += in ? wt : 0.0;
+    first = (in && first < 0) ? x : first;
+    w = wt;
+    if ((in && wt < tiny) || x >= xend) return true;
+    take = true;
+    ++x;
+    ++i;
+    return false;
+  };
+  // Stored terms in front of the end of the support (i < lim), four at a time (i is a multiple of four here): two
+  // 16-byte reads, then term() for the four written without branches -- as in k_fisher the instruction count is
+  // the time, and term() as it stands compiles to ~60 instructions of mask bookkeeping.  The same predicates in the
+  // same order: `in` per term, the weights inside the region added in ascending order up to the term the loop ends
+  // on (in and below tiny; x >= xend cannot hold here).  Only a term in the kAmbig band leaves the straight line.
+  const int lim = min(len, xend - x);
+  bool done = false;
+  while (!done && i + 4 <= lim) {
+    const double2* __restrict__ q = reinterpret_cast<const double2*>(cw + i * 2);
+    const double2 wa = q[0], wb = q[1];
+    const double wq[4] = {wa.x, wa.y, wb.x, wb.y};
+    bool inq[4], band = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      inq[j] = wq[j] <= sure_in;
+      band |= !inq[j] & !(wq[j] > sure_out);
+    }
+    if (band) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (!inq[j] && !(wq[j] > sure_out)) inq[j] = hg_tie(n1, n2, n, down ? n - (x + j) : x + j, a);
+    }
+    inq[0] = inq[0] & take;
+    int stop = 4;                          // the first of the four that is in the region and below tiny
+#pragma unroll
+    for (int j = 3; j >= 0; --j) stop = (inq[j] & (wq[j] < tiny)) ? j : stop;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool use = inq[j] & (j <= stop);
+      inc += use ? wq[j] : 0.0;
+      first = (use & (first < 0)) ? x + j : first;
+    }
+    done = stop < 4;
+    const int adv = done ? stop : 4;       // i stays the index of the term the loop ends on
+    i += adv;
+    x += adv;
+    w = wq[3];
+    take = true;
+  }
+  // the last stored terms, then the lane's own walk from the last stored term (or from the mode: no chain)
+  HgWalk wk(x, down ? n2 : n1, down ? n1 : n2, n);
+  while (!done) {
+    double wt = 1.0;
+    if (i < len) {
+      wt = cw[(i >> 2) * 8 + (i & 3)];
+    } else if (i > 0) {
+      if (i == len) {                      // leaving the chain: the sum so far, the walk at the last stored term
+        tot = cpre[i - 1];
+        wk = HgWalk(x - 1, down ? n2 : n1, down ? n1 : n2, n);
+      }
+      wt = wk.step(w);
+    }
+    done = term(wt);
+  }
+  if (i < len) tot = cpre[i];
+  fisher_finish<true>(tb, down, tot, inc, first, out);
 }
 
 // ----------------------------------------------------------------------------
@@ -961,18 +1221,62 @@ int scoary_fisher_lists(scoary_handle h, const int32_t* d_tables, int64_t T, int
                         const int32_t* d_lorder, const uint8_t* d_lflipped, double* d_p,
                         double* d_or, uint32_t* d_crit, uint32_t* d_lcrit,
                         scoary_stream_t stream) {
+  return scoary_fisher_lists_chained(h, d_tables, T, G, 0, d_lorder, d_lflipped, d_p, d_or, d_crit, d_lcrit,
+                                     nullptr, 0, stream);
+}
+
+int64_t scoary_fisher_chains_capacity(void) { return kChainCap; }
+double scoary_fisher_chains_floor(void) { return kChainFloor; }
+int64_t scoary_fisher_chains_bytes(int64_t T, int64_t N) {
+  if (T < 1 || N < 2) return 0;
+  const int64_t C = N / 2;
+  if (C > kChainBudget / (2 * kChainCap * 16) / T) return 0;      // also keeps the product below from overflowing
+  const int64_t b = ChainSlabs::bytes(T, C);
+  return b <= kChainBudget ? b : 0;
+}
+
+int scoary_set_fisher_route(scoary_handle h, int mode) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (mode < SCOARY_FISHER_ROUTE_WALK || mode > SCOARY_FISHER_ROUTE_AUTO)
+    return fail(h, SCOARY_ERR_ARG, "scoary_set_fisher_route: mode is 0 (walk), 1 (chains) or 2 (auto)");
+  h->fisher_route = mode;
+  return SCOARY_OK;
+}
+
+int scoary_fisher_lists_chained(scoary_handle h, const int32_t* d_tables, int64_t T, int64_t G, int64_t N,
+                                const int32_t* d_lorder, const uint8_t* d_lflipped, double* d_p,
+                                double* d_or, uint32_t* d_crit, uint32_t* d_lcrit, void* d_chains,
+                                int64_t chains_bytes, scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
   if (!d_tables || !d_lorder || !d_lflipped || !d_p || !d_or || !d_lcrit || T < 1 || G < 1)
     return fail(h, SCOARY_ERR_ARG, "scoary_fisher_lists: bad argument");
   if (T > 65535 || (2 * G + kWave - 1) / kWave > 0x7fffffffLL)
     return fail(h, SCOARY_ERR_SIZE, "scoary_fisher_lists: T > 65535 or G too large");
+  const int64_t need = d_chains ? scoary_fisher_chains_bytes(T, N) : 0;
+  if (d_chains && (need == 0 || chains_bytes < need))
+    return fail(h, SCOARY_ERR_ARG, "scoary_fisher_lists_chained: d_chains must hold scoary_fisher_chains_bytes(T, N) "
+                                   "> 0 bytes");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  KernelTimer kt(h, s, "k_fisher");
-  hipLaunchKernelGGL(k_fisher<true>, dim3((unsigned)((2 * G + kWave - 1) / kWave), (unsigned)T),
-                     dim3(kWave), 0, s, reinterpret_cast<const int4*>(d_tables), G, d_p, d_or,
-                     reinterpret_cast<uint2*>(d_crit), d_lorder, d_lflipped,
-                     reinterpret_cast<uint2*>(d_lcrit));
+  KernelTimer kt(h, s, "k_fisher");                    // the Fisher pass, whichever kernels run it
+  const dim3 grid((unsigned)((2 * G + kWave - 1) / kWave), (unsigned)T);
+  const int64_t waves = grid.x * (int64_t)T;
+  if (d_chains && (h->fisher_route == SCOARY_FISHER_ROUTE_CHAINS ||
+                   (h->fisher_route == SCOARY_FISHER_ROUTE_AUTO &&
+                    waves >= (int64_t)kChainMinWavesPerSimd * 4 * h->num_cu))) {
+    const int64_t C = N / 2;
+    const ChainSlabs ch(d_chains, T, C);
+    hipLaunchKernelGGL(k_fisher_chains, dim3((unsigned)((2 * C + kWave - 1) / kWave), (unsigned)T), dim3(kWave), 0, s,
+                       reinterpret_cast<const int4*>(d_tables), G, ch);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(k_fisher_tables, grid, dim3(kWave), 0, s, reinterpret_cast<const int4*>(d_tables), G, d_p,
+                       d_or, reinterpret_cast<uint2*>(d_crit), d_lorder, d_lflipped,
+                       reinterpret_cast<uint2*>(d_lcrit), ch);
+  } else {
+    hipLaunchKernelGGL(k_fisher<true>, grid, dim3(kWave), 0, s, reinterpret_cast<const int4*>(d_tables), G, d_p,
+                       d_or, reinterpret_cast<uint2*>(d_crit), d_lorder, d_lflipped,
+                       reinterpret_cast<uint2*>(d_lcrit));
+  }
   HIP_TRY(h, hipGetLastError());
   return SCOARY_OK;
 }

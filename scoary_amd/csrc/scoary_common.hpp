@@ -28,6 +28,7 @@ struct scoary_ctx {
   int cmh_exact_lds_optin = 0;   // k_cmh_exact with it
   int cmh_exact_odds_lds_optin = 0;   // k_cmh_odds_exact with it
   int mfma_route = SCOARY_MFMA_ROUTE_AUTO;   // scoary_set_mfma_route: which list slots take the matrix-core kernel
+  int fisher_route = SCOARY_FISHER_ROUTE_AUTO;     // scoary_set_fisher_route: the kernels of scoary_fisher_lists_chained
   uint32_t* scipy_primes = nullptr;  // scoary_fisher_scipy's prime table and reciprocals (device,
   float* scipy_inv = nullptr;        // built on the handle's first call, freed by scoary_destroy)
   int scipy_nprimes = 0;

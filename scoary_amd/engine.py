@@ -63,11 +63,11 @@ class GeneLists:
     start / ngroups: int32 [G] per list slot, or [segments, G] for N > 20479.
     panels: the slots' minority rows as matrix-core operands (scoary_mfma_panels_build; N <= 2048), or
     None; block_start: host int64 array, index entries in front of every 256-slot block (and the
-    total last); routes: k_split per (routing mode, T, P), a host-side cache."""
+    total last); routes: k_split per (routing mode, T, P), a host-side cache; N: the isolates of the matrix."""
 
-    def __init__(self, idx, start, ngroups, order, flipped, entries):
+    def __init__(self, idx, start, ngroups, order, flipped, entries, N):
         self.idx, self.start, self.ngroups = idx, start, ngroups
-        self.order, self.flipped, self.entries = order, flipped, entries
+        self.order, self.flipped, self.entries, self.N = order, flipped, entries, int(N)
         self.panels, self.block_start, self.routes = None, None, {}
 
 
@@ -169,6 +169,7 @@ class Workspace:
             self.label_shards = eng.label_shards
             self.scratch = eng.permute_lists_scratch(G, T, N, nb0)
             self.lcrit = eng._empty((T, G, 2), torch.int32)
+            eng.fisher_chains(T, N)           # the Fisher pass's slabs: allocated here, not inside a captured step
             # B operand of the matrix-core kernel, one label batch
             if genes.lists is not None and genes.lists.panels is not None:
                 self.bfrag = eng._empty((int(eng.lib.scoary_mfma_bfrag_bytes(N, nb0, T)) // 4,), torch.int32)
@@ -377,7 +378,7 @@ class AssociationEngine:
         self._check(self.lib.scoary_lists_fill(
             self.h, self._ptr(genes.tiled), G, N, self._ptr(scratch), self._ptr(order),
             self._ptr(flipped), total, self._ptr(idx), self._stream()), "scoary_lists_fill")
-        genes.lists = GeneLists(idx, start, ngroups, order, flipped, total)
+        genes.lists = GeneLists(idx, start, ngroups, order, flipped, total, N)
         self._build_panels(genes, budget_bytes - need)
         return genes.lists
 
@@ -549,7 +550,10 @@ class AssociationEngine:
         """tables: int32 device tensor [..., 4] -> (p, odds, crit) shaped [...].
         With ``lists`` (the GeneLists of the matrix the [T, G, 4] tables were counted on):
         scoary_fisher_lists -- tables visited in list-slot order, and the regions also
-        written in the list kernel's form; returns (p, odds, crit, lcrit)."""
+        written in the list kernel's form; returns (p, odds, crit, lcrit).  Where the weight chains of the
+        tables' margin classes fit their budget (fisher_chains) the pass is scoary_fisher_lists_chained: the same
+        bits from two kernels that divide once per class, not once per table, for launches large enough to pay
+        for the chain kernel (set_fisher_route)."""
         torch = _torch()
         tables = tables.contiguous()
         shape = tables.shape[:-1]
@@ -565,17 +569,44 @@ class AssociationEngine:
                 raise ValueError("fisher(lists=...) wants tables shaped [T, G, 4]")
             if lcrit is None:
                 lcrit = self._empty(tuple(shape) + (2,), torch.int32)
-            self._check(self.lib.scoary_fisher_lists(
-                self.h, self._ptr(tables), shape[0], shape[1], self._ptr(lists.order),
+            chains = self.fisher_chains(shape[0], lists.N)
+            self._check(self.lib.scoary_fisher_lists_chained(
+                self.h, self._ptr(tables), shape[0], shape[1], lists.N, self._ptr(lists.order),
                 self._ptr(lists.flipped), self._ptr(p), self._ptr(odds),
                 self._ptr(crit) if crit is not None else None, self._ptr(lcrit),
-                self._stream()), "scoary_fisher_lists")
+                self._ptr(chains) if chains is not None else None,
+                chains.numel() * 4 if chains is not None else 0, self._stream()), "scoary_fisher_lists_chained")
             return p, odds, crit, lcrit
         self._check(self.lib.scoary_fisher(self.h, self._ptr(tables), M, self._ptr(p),
                                            self._ptr(odds),
                                            self._ptr(crit) if crit is not None else None,
                                            self._stream()), "scoary_fisher")
         return p, odds, crit
+
+    def fisher_chains(self, T, N):
+        """The scratch of scoary_fisher_lists_chained for T traits of an N-isolate matrix (None: the slabs exceed
+        the library's budget and the pass runs the one-kernel walk).  Cached on the engine by size and rewritten
+        by every pass; never replaced, because a captured step holds its address.  A capture must find it there
+        (a Workspace allocates it)."""
+        torch = _torch()
+        need = int(self.lib.scoary_fisher_chains_bytes(int(T), int(N)))
+        if need == 0:
+            return None
+        cache = self.__dict__.setdefault("_fisher_chains", {})
+        buf = cache.get(need)
+        if buf is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError("fisher(lists=...) inside a graph capture needs its chain slabs allocated before "
+                                 "the capture: make the step's Workspace (or call fisher_chains(T, N)) first")
+            buf = cache[need] = self._empty((need // 4,), torch.int32)
+        return buf
+
+    def set_fisher_route(self, mode):
+        """The kernels of fisher(lists=...): "walk" (every table walks its own weights: the kernel of
+        scoary_fisher_lists), "chains" (one weight chain per margin class, whenever the slabs fit) or "auto" (the
+        default: the chains for launches large enough to pay for the chain kernel) -- scoary_set_fisher_route."""
+        self._check(self.lib.scoary_set_fisher_route(self.h, {"walk": 0, "chains": 1, "auto": 2}[mode]),
+                    "scoary_set_fisher_route")
 
     def fisher_scipy(self, tables, p):
         """SciPy's own double for every table of 171 ... fisher_scipy_max_isolates() isolates, written over the

@@ -74,6 +74,12 @@ def main():
     sha_path = os.path.join(src, "kernel_source_sha256.txt")
     if os.path.exists(sha_path):
         sha = open(sha_path).read().strip()
+    # the Fisher pass of the list path is two kernels under one timer scope (k_fisher): their per-launch counters
+    # added up under that name, which is the one bench.py's roofline_k2 looks up
+    parts = [pmc[k] for k in ("k_fisher_chains", "k_fisher_tables") if k in pmc]
+    if len(parts) == 2 and "k_fisher" not in pmc:
+        pmc["k_fisher"] = {f: parts[0][f] + parts[1][f] for f in parts[0]
+                           if f in parts[1] and all(isinstance(p[f], (int, float)) for p in parts)}
     pmc["_meta"] = {"workload": sys.argv[3] if len(sys.argv) > 3 else "cfg3",
                     # sha256 over scoary_amd/csrc/{bench.KERNEL_SOURCES} at profile time
                     "kernel_source_sha256": sha,

@@ -148,22 +148,29 @@ def test_minp_bits_equal_the_oracle(eng, G, N, T, P):
 
 # ---- 2. bit-exact above 170 (and at the ragged edges), against the engine's own scoary_fisher --------------------
 # tiled row size (quads) of every N used below: which k_permute_minp instance the case reaches.  With 100 (test 1) the
-# cases cover every register row size -- 1, 2, 4, 6, 8, 12, 16, 20, 24 quads -- and the chunked kernel (> 24)
-ROW_QUADS = {100: 1, 131: 2, 200: 2, 333: 4, 400: 4, 700: 6, 900: 8, 1300: 12, 1800: 16, 2300: 20, 2600: 24, 3300: 32,
-             7000: 56}
+# cases cover every register row size -- 1, 2, 4, 6, 8, 12, 16, 20, 24 quads -- and the chunked kernel (> 24); 2000 is
+# test_gpu_wy_scale.py's
+ROW_QUADS = {100: 1, 131: 2, 200: 2, 333: 4, 400: 4, 700: 6, 900: 8, 1300: 12, 1800: 16, 2000: 16, 2300: 20, 2600: 24,
+             3300: 32, 7000: 56}
 
 
 @pytest.mark.parametrize("G,N,T,P", [(150, 333, 2, 96), (130, 2600, 1, 40), (70, 131, 2, 33), (130, 3300, 1, 40),
-                                     (70, 7000, 2, 33)]
+                                     (70, 7000, 2, 33), (603, 3300, 2, 40), (300, 7000, 1, 33)]
                          + [(70, N, 1, 33) for N in (200, 400, 700, 900, 1300, 1800, 2300)])
 def test_minp_bits_equal_fisher_of_the_permuted_tables(eng, G, N, T, P):
     """Tables from the oracle's labels and numpy counts, pushed through eng.fisher: the minimum per (trait,
     permutation) must be minp bit for bit.  N = 2600 is the largest register-resident instance (24 quads, up to 3072
     isolates); N = 3300 and N = 7000 (32 and 56 quads) run k_permute_minp_chunked; N = 131 / P = 33 / G = 70 are
     ragged at the quad, lane and block edges; the (70, N, 1, 33) cases walk the remaining register row sizes: a wrong
-    instance reads the label rows at the wrong stride."""
+    instance reads the label rows at the wrong stride.  G = 603 and G = 300 give k_permute_minp_chunked several gene
+    chunks: blocks that start at a gene above 0, and a last chunk that ends inside a pass of eight genes."""
     assert eng.quads(N) == ROW_QUADS[N]                 # which instance the shape reaches
     assert (eng.quads(N) > 24) == (N > 3072)            # ... of which kernel
+    if G > 256:
+        # the launch shape is the step-down's (one function of the library serves both entry points)
+        nch = eng.stepdown_chunks(G, T, P)
+        gchunk = -(-(-(-G // nch)) // 64) * 64          # a chunk is ceil(G / nch) rounded up to 64 genes
+        assert eng.quads(N) > 24 and nch > 1 and (nch - 1) * gchunk < G and (G % gchunk) % 8 != 0
     import torch
     genes, traits = make_data(G, N, T, 2000 + N)
     tabs = permuted_tables(genes, traits, oracle_labels(traits, P, SEED))

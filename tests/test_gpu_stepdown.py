@@ -140,10 +140,28 @@ def test_stepdown_equals_the_oracle(eng, G, N, T, P, seed):
 # ---- 2. the kernel alone over synthetic tables: every position informative ---------------------------------------
 # tiled row size (quads) of every N used below: which k_stepdown_minp instance the case reaches -- every register row
 # size (1, 2, 4, 6, 8, 12, 16, 20, 24 quads) and the chunked kernel (> 24)
-ROW_QUADS = {100: 1, 131: 2, 200: 2, 400: 4, 700: 6, 900: 8, 1300: 12, 1800: 16, 2300: 20, 2600: 24, 3300: 32}
+ROW_QUADS = {100: 1, 131: 2, 200: 2, 400: 4, 700: 6, 900: 8, 1300: 12, 1800: 16, 2300: 20, 2600: 24, 3300: 32,
+             7000: 56}
+# the fewest chunks of the rank order the cases that are there for the walk over several chunks must reach; those
+# with N > 3072 are the chunked instances
+MIN_CHUNKS = {(1100, 100, 2, 70): 3, (1100, 131, 2, 33): 3, (603, 3300, 2, 40): 3, (300, 7000, 1, 33): 2,
+              (603, 3300, 1, 40): 3}
 
 
-@pytest.mark.parametrize("G,N,T,P", [(1100, 100, 2, 70), (1100, 131, 2, 33), (130, 2600, 1, 40), (130, 3300, 1, 40)]
+def several_chunks(eng, G, N, T, P, least):
+    """Asserts that the launch shape walks the G genes / rank positions in at least ``least`` chunks with a ragged
+    last one -- for the chunked instances (groups of eight) one that also ends inside a group; -> (chunks, chunk
+    length)."""
+    nch = eng.stepdown_chunks(G, T, P)
+    gchunk = -(-(-(-G // nch)) // 64) * 64                         # a chunk is ceil(G / nch) rounded up to 64 positions
+    assert nch >= least and (nch - 1) * gchunk < G and G % gchunk != 0
+    if N > 3072:
+        assert eng.quads(N) > 24 and (G % gchunk) % 8 != 0
+    return nch, gchunk
+
+
+@pytest.mark.parametrize("G,N,T,P", [(1100, 100, 2, 70), (1100, 131, 2, 33), (130, 2600, 1, 40), (130, 3300, 1, 40),
+                                     (603, 3300, 2, 40), (300, 7000, 1, 33)]
                          + [(130, N, 1, 40) for N in (200, 400, 700, 900, 1300, 1800, 2300)])
 def test_raw_counts_over_synthetic_tables(eng, G, N, T, P):
     """The real CSR layout of the p tables filled with random doubles, random label rows (they may leave a gene's
@@ -151,7 +169,10 @@ def test_raw_counts_over_synthetic_tables(eng, G, N, T, P):
     successive minima themselves: counts in mid-range at most positions, exact equalities, a tie run of 40.
     G = 1100 is walked in >= 3 chunks with a ragged last one (both passes); N = 131 / P = 33 are ragged at the quad
     and the lane; N = 2600 and N = 3300 are the largest register-resident row and the chunked instance; the other
-    (130, N, 1, 40) cases walk the remaining register row sizes, both passes' instances of each."""
+    (130, N, 1, 40) cases walk the remaining register row sizes, both passes' instances of each.  (603, 3300, 2, 40)
+    and (300, 7000, 1, 33) walk the chunked instance in >= 3 and >= 2 chunks whose last one ends inside a group of
+    eight positions: pass A of the chunked kernel, the carry into its pass B, the rank-ordered copy of the rows read
+    from a position above 0."""
     import torch
     from scoary_amd.engine import MinpTables, pack_bits_rows
     assert eng.quads(N) == ROW_QUADS[N]                 # which instance the shape reaches
@@ -191,10 +212,8 @@ def test_raw_counts_over_synthetic_tables(eng, G, N, T, P):
     assert ((want_c > 0) & (want_c < P)).mean() > 0.5
     assert sum(int((q[t] == ps[t][None, :]).sum()) for t in range(T)) >= 10
 
-    if G == 1100:
-        nch = eng.stepdown_chunks(1100, 2, 70)
-        gchunk = -(-(-(-G // nch)) // 64) * 64                      # a chunk is ceil(G / nch) rounded up to 64 positions
-        assert nch >= 3 and (nch - 1) * gchunk < G and G % gchunk != 0
+    if (G, N, T, P) in MIN_CHUNKS:
+        several_chunks(eng, G, N, T, P, MIN_CHUNKS[(G, N, T, P)])
     c = torch.zeros((T, G), dtype=torch.int32, device=eng.device)
     minp = torch.ones((T, P), dtype=torch.float64, device=eng.device)
     out = eng.permute_stepdown(gm, perms, tables, torch.from_numpy(order).to(eng.device),
@@ -213,8 +232,11 @@ def test_raw_counts_over_synthetic_tables(eng, G, N, T, P):
 
 
 # ---- 3. above 170 isolates, against the engine's own scoary_fisher ----------------------------------------------
-@pytest.mark.parametrize("G,N,T,P", [(150, 333, 2, 96), (130, 3300, 1, 40)])
+@pytest.mark.parametrize("G,N,T,P", [(150, 333, 2, 96), (130, 3300, 1, 40), (603, 3300, 1, 40)])
 def test_stepdown_equals_fisher_of_the_permuted_tables(eng, G, N, T, P):
+    """(603, 3300, 1, 40): the chunked instance over three chunks, the last one ragged, through the whole step."""
+    if (G, N, T, P) in MIN_CHUNKS:
+        several_chunks(eng, G, N, T, P, MIN_CHUNKS[(G, N, T, P)])
     genes, traits = make_sd_data(G, N, T, 3)
     p, pperm, sd = reference(genes, traits, P, SEED, engine_fisher(eng))
     gm, trv, mkv = device_inputs(eng, genes, traits)

@@ -517,6 +517,40 @@ int scoary_cmh_homogeneity(scoary_handle h, const uint32_t *d_tiled, const uint3
                            const int32_t *d_offsets, const int32_t *d_smargins, int64_t G, int64_t T, int64_t N,
                            int64_t S, const double *d_odds, double *d_stat_bd, double *d_stat_tarone, int32_t *d_df,
                            double *d_p, void *d_scratch, scoary_stream_t stream);
+/* ---- Quantitative traits: the rank-sum test with value permutations (spec S15 of DESIGN.md; additive, ABI 11) ----
+ * A trait is a row of centred doubled midranks of a measured value, d_rc int16 [T][N] (Rc_i = R_i - (n + 1), 0 for
+ * an isolate without a value), its validity bits d_valid uint32 [T][Wp] (vecrows, bits >= N ignored) and
+ * d_tiesum int64 [T] = sum (tau^3 - tau) over its tie groups; the host ranks (exact double comparisons).  Per
+ * (trait, gene): m = popc(gene & valid), D = sum of Rc over the isolates of the gene.
+ *   scoary_ranksum_max_isolates()  16320: |Rc| <= 16319 splits into two signed bytes, Rc = 128 hi + lo
+ *   scoary_ranksum        d_d, d_m int32 [T][G]; d_auc = 0.5 + D / (2 m (n - m)); d_p = erfc(z / sqrt 2),
+ *                         z = max(0, |D| / 2 - 1/2) / sqrt(m (n - m) / 12 * f), f = n + 1 - tiesum / (n (n - 1)),
+ *                         fp64, every operation rounded on its own (scipy.stats.mannwhitneyu, asymptotic, with
+ *                         continuity).  n < 2, m = 0, m = n or f <= 0: (auc 0.5, p 1), and D is 0 by itself.
+ *   scoary_ranksum_perm_generate   d_rows int16 [T][P][N]: the Rc rows of the permutations perm_base .. + P - 1 of
+ *                         the traits trait_base .. + T - 1 under `seed`: the values shuffled over the valid isolates
+ *                         by the order of 50 Philox bits | isolate (counter (i, pi, t, "SCOQ")), 0 where invalid
+ *   scoary_ranksum_bfrag_bytes     bytes of the same rows as the B operand of scoary_permute_ranksum (0: bad size)
+ *   scoary_ranksum_perm_generate_bfrag   d_bfrag: those rows in that form, hi and lo digit planes, permutation
+ *                         p of the call in column p; K padded with zeros to whole chunks of 256 isolates
+ *   scoary_permute_ranksum  d_r[t][g] += #{p < P : |D_p| >= |d_dobs[t][g]|}, int32 [T][G], D_p the gene's sum over
+ *                         permuted row p of d_bfrag (T traits, P permutations as generated), exact in integers on the
+ *                         int8 matrix cores; the caller zeroes d_r before the first batch, batches add up
+ * Asynchronous on `stream`, nothing is allocated.  SCOARY_ERR_ARG: null pointer, size < 1 or negative base;
+ * SCOARY_ERR_SIZE, with nothing written: N > scoary_ranksum_max_isolates(), T > 65535, G or P >= 2^31. */
+int64_t scoary_ranksum_max_isolates(void);
+int scoary_ranksum(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_rc, const uint32_t *d_valid,
+                   const int64_t *d_tiesum, int64_t G, int64_t T, int64_t N, int32_t *d_d, int32_t *d_m,
+                   double *d_auc, double *d_p, scoary_stream_t stream);
+int scoary_ranksum_perm_generate(scoary_handle h, const int16_t *d_rc, const uint32_t *d_valid, int64_t T, int64_t N,
+                                 int64_t P, int64_t perm_base, int64_t trait_base, uint64_t seed, int16_t *d_rows,
+                                 scoary_stream_t stream);
+int64_t scoary_ranksum_bfrag_bytes(int64_t N, int64_t P, int64_t T);
+int scoary_ranksum_perm_generate_bfrag(scoary_handle h, const int16_t *d_rc, const uint32_t *d_valid, int64_t T,
+                                       int64_t N, int64_t P, int64_t perm_base, int64_t trait_base, uint64_t seed,
+                                       void *d_bfrag, scoary_stream_t stream);
+int scoary_permute_ranksum(scoary_handle h, const uint32_t *d_tiled, const void *d_bfrag, const int32_t *d_dobs,
+                           int64_t G, int64_t T, int64_t N, int64_t P, int32_t *d_r, scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

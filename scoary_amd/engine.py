@@ -139,6 +139,42 @@ class StrataPlan:
                           checked=True)
 
 
+class RankPlan:
+    """The quantitative traits of a rank-sum step (spec S15; AssociationEngine.ranksum_plan): ``rc`` int16 [T, N]
+    = the centred doubled midranks (0 where the value is missing), ``valid`` the validity rows (vecrows, int32
+    [T, Wp]) and ``tiesum`` int64 [T] on the device; ``n``, ``tiesum_host`` and ``tie_groups`` (groups of two or
+    more equal values) per trait and ``rc_host`` / ``valid_host`` (bool [T, N]) on the host."""
+
+    def __init__(self, rc, valid, tiesum, rc_host, valid_host, n, tiesum_host, tie_groups):
+        self.rc, self.valid, self.tiesum = rc, valid, tiesum
+        self.rc_host, self.valid_host = rc_host, valid_host
+        self.n, self.tiesum_host, self.tie_groups = n, tiesum_host, tie_groups
+        self.T, self.N = (int(x) for x in rc_host.shape)
+
+
+def rank_rows(values):
+    """Host ranking of spec S15, exact double comparisons: float64 [T, N] with NaN for missing -> (rc int16 [T, N],
+    valid bool [T, N], n int64 [T], tiesum int64 [T], tie groups int64 [T])."""
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    if values.ndim != 2:
+        raise ValueError("ranksum_plan: values must be a [T, N] array")
+    T, N = values.shape
+    valid = ~np.isnan(values)
+    rc = np.zeros((T, N), dtype=np.int16)
+    n, tiesum, groups = (np.zeros(T, dtype=np.int64) for _ in range(3))
+    for t in range(T):
+        x = values[t, valid[t]]
+        srt = np.sort(x)
+        less = np.searchsorted(srt, x, side="left").astype(np.int64)
+        equal = np.searchsorted(srt, x, side="right").astype(np.int64) - less
+        n[t] = x.size
+        rc[t, valid[t]] = 2 * less + equal + 1 - (x.size + 1)
+        tau = np.unique(srt, return_counts=True)[1].astype(np.int64)
+        tiesum[t] = int(np.sum(tau ** 3 - tau))
+        groups[t] = int(np.sum(tau > 1))
+    return rc, valid, n, tiesum, groups
+
+
 class Workspace:
     """Device buffers of one associate() step (engine.workspace)."""
 
@@ -1591,6 +1627,74 @@ class AssociationEngine:
                                                  self._ptr(obs.contiguous()), self._ptr(out),
                                                  self._stream()), "scoary_tree_permute")
         return out
+
+    # -- quantitative traits: the rank-sum test (spec S15) ---------------------------
+    def ranksum_max_isolates(self):
+        return int(self.lib.scoary_ranksum_max_isolates())
+
+    def ranksum_plan(self, values):
+        """values: float64 [T, N], NaN = missing.  The host ranking of spec S15 as a RankPlan."""
+        torch = _torch()
+        rc, valid, n, tiesum, groups = rank_rows(values)
+        if rc.shape[1] > self.ranksum_max_isolates():
+            raise ValueError("ranksum_plan: %d isolates, the rank-sum kernels take at most %d"
+                             % (rc.shape[1], self.ranksum_max_isolates()))
+        return RankPlan(torch.from_numpy(rc).to(self.device),
+                        self.vecrows(pack_bits_rows(valid.astype(np.uint8)), rc.shape[1]),
+                        torch.from_numpy(tiesum).to(self.device), rc, valid, n, tiesum, groups)
+
+    def _ranksum_fits(self, what, genes, plan):
+        if genes is not None and genes.N != plan.N:
+            raise ValueError("%s: the plan has %d isolates, the gene matrix %d" % (what, plan.N, genes.N))
+
+    def ranksum(self, genes, plan):
+        """The observed rank-sum statistic of every (trait, gene): dict of device tensors d (the centred doubled
+        rank sum) and m (isolates with the gene and a value) int32 [T, G], auc and p float64 [T, G]; an untestable
+        gene has (d 0, auc 0.5, p 1)."""
+        torch = _torch()
+        self._ranksum_fits("ranksum", genes, plan)
+        T, G = plan.T, genes.G
+        out = {"d": self._empty((T, G), torch.int32), "m": self._empty((T, G), torch.int32),
+               "auc": self._empty((T, G), torch.float64), "p": self._empty((T, G), torch.float64)}
+        self._check(self.lib.scoary_ranksum(
+            self.h, self._ptr(genes.tiled), self._ptr(plan.rc), self._ptr(plan.valid), self._ptr(plan.tiesum),
+            G, T, plan.N, *(self._ptr(out[k]) for k in ("d", "m", "auc", "p")), self._stream()), "scoary_ranksum")
+        return out
+
+    def ranksum_values(self, plan, perm_base, P, seed):
+        """The permuted centred ranks of the permutations perm_base .. perm_base + P - 1: int16 [T, P, N]."""
+        out = self._empty((plan.T, int(P), plan.N), _torch().int16)
+        self._check(self.lib.scoary_ranksum_perm_generate(
+            self.h, self._ptr(plan.rc), self._ptr(plan.valid), plan.T, plan.N, int(P), int(perm_base), 0,
+            ctypes.c_uint64(seed), self._ptr(out), self._stream()), "scoary_ranksum_perm_generate")
+        return out
+
+    def ranksum_batch(self, T, N, permutations, budget_bytes=8 << 30):
+        """Permutations per batch of ranksum_permute (a multiple of 64): the B operand stays under budget_bytes."""
+        per = max(int(self.lib.scoary_ranksum_bfrag_bytes(N, 64, T)), 1)
+        return int(max(64, min(-(-permutations // 64) * 64, budget_bytes // per * 64)))
+
+    def ranksum_permute(self, genes, plan, d_obs, permutations, seed, budget_bytes=8 << 30):
+        """r_q int32 [T, G] = #{pi < permutations : |D_pi| >= |d_obs|} under value shuffles (spec S15), in batches
+        of ranksum_batch() permutations: the generator writes a batch as the matrix-core kernel's B operand and
+        k_permute_ranksum adds its counts."""
+        torch = _torch()
+        self._ranksum_fits("ranksum_permute", genes, plan)
+        T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
+        if tuple(d_obs.shape) != (T, G) or d_obs.dtype != torch.int32 or not d_obs.is_contiguous():
+            raise ValueError("ranksum_permute: d_obs is ranksum()'s d, int32 [T, G], contiguous")
+        r = torch.zeros((T, G), dtype=torch.int32, device=self.device)
+        batch = self.ranksum_batch(T, N, P, budget_bytes)
+        bfrag = self._empty((int(self.lib.scoary_ranksum_bfrag_bytes(N, min(batch, P), T)),), torch.uint8)
+        for base in range(0, P, batch):
+            nb = min(batch, P - base)
+            self._check(self.lib.scoary_ranksum_perm_generate_bfrag(
+                self.h, self._ptr(plan.rc), self._ptr(plan.valid), T, N, nb, base, 0, ctypes.c_uint64(seed),
+                self._ptr(bfrag), self._stream()), "scoary_ranksum_perm_generate_bfrag")
+            self._check(self.lib.scoary_permute_ranksum(
+                self.h, self._ptr(genes.tiled), self._ptr(bfrag), self._ptr(d_obs), G, T, N, nb, self._ptr(r),
+                self._stream()), "scoary_permute_ranksum")
+        return r
 
     # -- timing (bench.py) ------------------------------------------------------
     def set_timing(self, on):

@@ -532,7 +532,12 @@ int scoary_cmh_homogeneity(scoary_handle h, const uint32_t *d_tiled, const uint3
  *                         by the order of 50 Philox bits | isolate (counter (i, pi, t, "SCOQ")), 0 where invalid
  *   scoary_ranksum_bfrag_bytes     bytes of the same rows as the B operand of scoary_permute_ranksum (0: bad size)
  *   scoary_ranksum_perm_generate_bfrag   d_bfrag: those rows in that form, hi and lo digit planes, permutation
- *                         p of the call in column p; K padded with zeros to whole chunks of 256 isolates
+ *                         p of the call in column p; K padded with zeros to whole chunks of 256 isolates.  Byte
+ *                         order: [t][stage of 64 columns][K-step of 32 isolates][plane hi, lo][column tile of 32]
+ *                         [lane of 64] x 16 bytes; lane l of a fragment = column 64 stage + 32 tile + (l & 31),
+ *                         isolates 32 K-step + 16 (l >> 5) .. + 15, one signed byte each; every stage has all its
+ *                         K-steps, 8 per chunk.  What the columns from P to the end of the last stage hold is not
+ *                         specified, and scoary_permute_ranksum does not count them
  *   scoary_permute_ranksum  d_r[t][g] += #{p < P : |D_p| >= |d_dobs[t][g]|}, int32 [T][G], D_p the gene's sum over
  *                         permuted row p of d_bfrag (T traits, P permutations as generated), exact in integers on the
  *                         int8 matrix cores; the caller zeroes d_r before the first batch, batches add up

@@ -1,8 +1,11 @@
 """Spec S15 in plain Python: the rank-sum test of a measured value against gene presence and
 its value permutations.  A helper, not a test; written from the specification, independently of the kernels and of
-the engine's host ranking, on top of the oracle's Philox block function only (the shape of strata_spec.py)."""
+the engine's host ranking, on top of the oracle's Philox block function only (the shape of strata_spec.py).  The
+bfrag_* functions restate the byte order of scoary_permute_ranksum's B operand from the words of the public header."""
 import bisect
 import math
+
+import numpy as np
 
 from oracle import oracle as orc
 
@@ -70,6 +73,59 @@ def digits(rc):
     """Rc = 128 hi + lo with lo in [-64, 63]."""
     lo = ((rc + 64) % 128) - 64
     return (rc - lo) // 128, lo
+
+
+def chunks(N):
+    """Chunks of 256 isolates that cover N: the B operand's K is padded to that many."""
+    return -(-N // 256)
+
+
+def bfrag_bytes(N, P, T):
+    """Bytes of the B operand of T traits x P permutations: a chunk of a stage of 64 permutations is 32 KB."""
+    return T * -(-P // 64) * chunks(N) * 32768
+
+
+def bfrag_pack(dig):
+    """dig: int8 [T][64 S][256 chunks][2] -- the (hi, lo) digits of every (trait, column, isolate) of whole stages
+    and whole chunks -> the bytes, in the order include/scoary_hip.h states:
+    [t][stage of 64][K-step of 32 isolates][plane hi, lo][column tile of 32][lane of 64] x 16 bytes, lane l of a
+    fragment = column 64 stage + 32 tile + (l & 31), isolates 32 K-step + 16 (l >> 5) .. + 15, one per byte."""
+    dig = np.asarray(dig, dtype=np.int8)
+    T, C, K, _ = dig.shape
+    assert C % 64 == 0 and K % 256 == 0
+    x = dig.reshape(T, C // 64, 2, 32, K // 32, 2, 16, 2)        # t, stage, tile, l & 31, K-step, l >> 5, byte, plane
+    x = x.transpose(0, 1, 4, 7, 2, 5, 3, 6)                      # t, stage, K-step, plane, tile, l >> 5, l & 31, byte
+    return np.ascontiguousarray(x).reshape(-1).view(np.uint8)
+
+
+def bfrag_unpack(buf, T, P, N):
+    """The inverse of bfrag_pack: the bytes of a B operand of (T, P, N) -> int8 [T][64 S][256 chunks][2]."""
+    S, W = -(-P // 64), 8 * chunks(N)
+    buf = np.asarray(buf).reshape(-1).view(np.int8)
+    assert buf.size == bfrag_bytes(N, P, T), (buf.size, bfrag_bytes(N, P, T))
+    x = buf.reshape(T, S, W, 2, 2, 2, 32, 16).transpose(0, 1, 4, 6, 2, 5, 7, 3)
+    return np.ascontiguousarray(x).reshape(T, 64 * S, 32 * W, 2)
+
+
+def bfrag_encode(rows, N):
+    """rows[T][P][N] of ints, |Rc| <= 16 319 -> the bytes of the B operand: permutation p in column p, the columns
+    from P to the end of the last stage and the isolates from N to the end of the last chunk zero."""
+    rows = np.asarray(rows, dtype=np.int64)
+    T, P, n = rows.shape
+    assert n == N and np.abs(rows).max(initial=0) < MAX_ISOLATES
+    lo = (rows + 64) % 128 - 64                                   # digits(), on arrays
+    dig = np.zeros((T, 64 * -(-P // 64), 256 * chunks(N), 2), dtype=np.int8)
+    dig[:, :P, :N, 0] = (rows - lo) // 128
+    dig[:, :P, :N, 1] = lo
+    return bfrag_pack(dig)
+
+
+def bfrag_decode(buf, T, P, N):
+    """-> (rows int64 [T][P][N] = 128 hi + lo, digits int8 [T][P][N][2], the K pad int8 [T][P][256 chunks - N][2],
+    the columns at and past P int8 [T][64 S - P][256 chunks][2])."""
+    dig = bfrag_unpack(buf, T, P, N)
+    d = dig[:, :P, :N].astype(np.int64)
+    return 128 * d[..., 0] + d[..., 1], dig[:, :P, :N], dig[:, :P, N:], dig[:, P:]
 
 
 def r_q(genes, rows, d_obs):

@@ -128,3 +128,30 @@ def test_r_q_composes_over_batches_and_rows_are_functions_of_seed_trait_permutat
     assert whole == [u + v for u, v in zip(a, b)]
     assert whole[0] == P                                                            # untestable: r = P
     assert max(whole) <= P and any(0 < r < P for r in whole[1:])
+
+
+@pytest.mark.parametrize("N", (1, 33, 256, 257))
+def test_b_operand_decodes_to_what_was_encoded(N):
+    """bfrag_encode / bfrag_decode, the byte order of include/scoary_hip.h in numpy: a round trip over random rows
+    with |Rc| up to 16 319, the size formula, and single entries at byte offsets worked out by hand from the
+    header's sentence (so that a transposition the two functions share would show)."""
+    rng = np.random.default_rng(N)
+    T, P = 3, 70
+    rows = rng.integers(-16319, 16320, (T, P, N))
+    rows[0, 0, :] = 16319
+    rows[1, P - 1, :] = -16319
+    buf = rs.bfrag_encode(rows, N)
+    chunks = (N + 255) // 256
+    assert buf.dtype == np.uint8 and buf.size == T * ((P + 63) // 64) * chunks * 32768 == rs.bfrag_bytes(N, P, T)
+    got, dig, pad, past = rs.bfrag_decode(buf, T, P, N)
+    assert np.array_equal(got, rows)
+    assert dig.shape == (T, P, N, 2) and pad.shape == (T, P, 256 * chunks - N, 2)
+    assert past.shape == (T, 128 - P, 256 * chunks, 2) and not pad.any() and not past.any()
+    for t, p, i in ((0, 0, 0), (2, 69, N - 1), (1, 31, N // 2), (1, 32, N - 1), (2, 63, 0), (0, 64, N // 3)):
+        hi, lo = rs.digits(int(rows[t, p, i]))
+        assert (int(dig[t, p, i, 0]), int(dig[t, p, i, 1])) == (hi, lo)
+        stage, tile, lane = p // 64, (p % 64) // 32, p % 32 + 32 * ((i % 32) // 16)
+        at = ((t * 2 + stage) * 8 * chunks + i // 32) * 4096 + tile * 1024 + lane * 16 + i % 16
+        assert buf[at] == hi % 256 and buf[at + 2048] == lo % 256, (t, p, i)
+    with pytest.raises(AssertionError):
+        rs.bfrag_encode(np.full((1, 1, N), 16320), N)

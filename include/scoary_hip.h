@@ -556,6 +556,47 @@ int scoary_ranksum_perm_generate_bfrag(scoary_handle h, const int16_t *d_rc, con
                                        void *d_bfrag, scoary_stream_t stream);
 int scoary_permute_ranksum(scoary_handle h, const uint32_t *d_tiled, const void *d_bfrag, const int32_t *d_dobs,
                            int64_t G, int64_t T, int64_t N, int64_t P, int32_t *d_r, scoary_stream_t stream);
+/* ---- Quantitative traits over strata: the van Elteren test with value permutations within the strata (spec S16 of
+ * DESIGN.md; additive, ABI 11) ----
+ * The strata are d_strata uint16 [N] (the stratum of every isolate, in [0, S)) and d_members int32 [N] (the isolates
+ * by (stratum, isolate)), as the CMH entry points take them.  The host ranks inside every stratum: a trait is its row
+ * of scores d_score int16 [T][N], a_i = w_s Rc_i with Rc the centred doubled midrank inside the stratum and w_s =
+ * max(1, floor(16319 / (n_s + 1))) (0 for an isolate without a value; |a| <= 16319), its validity bits d_valid
+ * uint32 [T][Wp], d_wn int32 [T][S][2] = (w_s, n_s), d_c double [T][S] = w_s^2 f_s / 12 with f_s = n_s + 1 -
+ * tiesum_s / (n_s (n_s - 1)) (0 for n_s < 2), and d_l int16 [T][N] = the scores of the valid isolates in (stratum,
+ * isolate) order, the rest of the row 0.  Per (trait, gene): m_s = popc(gene & valid) inside stratum s, D = the sum
+ * of the scores over the isolates of the gene.
+ *   scoary_vanelteren     d_d, d_m int32 [T][G] (m = sum m_s); d_var = sum_s c_s (m_s (n_s - m_s)), fp64 in ascending
+ *                         s, every operation rounded on its own; d_p = erfc(z / sqrt 2), z = (|D| / 2) / sqrt(var)
+ *                         (no continuity correction); d_auc = 0.5 + D / (2 sum_s w_s m_s (n_s - m_s)).  var <= 0:
+ *                         (auc 0.5, p 1), and D is 0 by itself.  d_scratch: scoary_cmh_scratch_bytes(N) bytes, the
+ *                         segment table of the strata, built by the call
+ *   scoary_vanelteren_perm_generate   d_rows int16 [T][P][N]: the score rows of the permutations perm_base .. + P - 1
+ *                         of the traits trait_base .. + T - 1 under `seed`: the valid isolate whose composite
+ *                         (stratum << (64 - b)) | (((key64 >> 14) >> b) << 14) | isolate has rank rho takes d_l[rho];
+ *                         key64 = Philox words 0 and 1 of counter (i, pi, t, "SCOQ"), b = 0 for S = 1, else the bit
+ *                         length of S - 1.  A shuffle within the strata; 0 where invalid
+ *   scoary_vanelteren_perm_generate_bfrag   d_bfrag: those rows as the B operand of scoary_permute_ranksum, in
+ *                         exactly the bytes scoary_ranksum_perm_generate_bfrag writes for the same rows
+ *                         (scoary_ranksum_bfrag_bytes(N, P, T) of them), and the columns from P to the end of the
+ *                         last stage as zeros: every byte of d_bfrag is written.  The exceedance counts are
+ *                         scoary_permute_ranksum's, on d_d
+ * Every index read from d_strata, d_members and the segment table is clamped: a bad plan gives wrong numbers, never
+ * a wild access.  Asynchronous on `stream`, nothing is allocated.  SCOARY_ERR_ARG: null pointer, size < 1 or negative
+ * base; SCOARY_ERR_SIZE, with nothing written: S > scoary_perm_max_strata(), N > scoary_ranksum_max_isolates(),
+ * T > 65535, G or P >= 2^31. */
+int scoary_vanelteren(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_score, const uint32_t *d_valid,
+                      const uint16_t *d_strata, const int32_t *d_members, const int32_t *d_wn, const double *d_c,
+                      int64_t G, int64_t T, int64_t N, int64_t S, int32_t *d_d, int32_t *d_m, double *d_var,
+                      double *d_auc, double *d_p, void *d_scratch, scoary_stream_t stream);
+int scoary_vanelteren_perm_generate(scoary_handle h, const int16_t *d_l, const uint32_t *d_valid,
+                                    const uint16_t *d_strata, int64_t T, int64_t N, int64_t S, int64_t P,
+                                    int64_t perm_base, int64_t trait_base, uint64_t seed, int16_t *d_rows,
+                                    scoary_stream_t stream);
+int scoary_vanelteren_perm_generate_bfrag(scoary_handle h, const int16_t *d_l, const uint32_t *d_valid,
+                                          const uint16_t *d_strata, int64_t T, int64_t N, int64_t S, int64_t P,
+                                          int64_t perm_base, int64_t trait_base, uint64_t seed, void *d_bfrag,
+                                          scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

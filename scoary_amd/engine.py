@@ -175,6 +175,57 @@ def rank_rows(values):
     return rc, valid, n, tiesum, groups
 
 
+class VanElterenPlan:
+    """The quantitative traits of a stratified rank-sum step (spec S16; AssociationEngine.vanelteren_plan).  On the
+    device: ``score`` int16 [T, N] = w_s Rc_i with Rc the centred doubled midrank inside the stratum (0 where the
+    value is missing), ``l`` int16 [T, N] = the scores of the valid isolates by (stratum, isolate), ``valid`` the
+    validity rows (vecrows, int32 [T, Wp]), ``wn`` int32 [T, S, 2] = (w_s, n_s), ``c`` float64 [T, S], ``strata``
+    int16 [N] (uint16 bit pattern) and ``members`` int32 [N].  On the host: score_host, valid_host (bool [T, N]),
+    strata_host int64 [N], w, n, tiesum, tie_groups int64 [T, S] and c_host float64 [T, S]."""
+
+    def __init__(self, dev, score_host, valid_host, strata_host, S, w, n, tiesum, tie_groups, c_host):
+        self.score, self.l, self.valid, self.wn, self.c, self.strata, self.members = dev
+        self.score_host, self.valid_host, self.strata_host = score_host, valid_host, strata_host
+        self.w, self.n, self.tiesum, self.tie_groups, self.c_host = w, n, tiesum, tie_groups, c_host
+        self.S = int(S)
+        self.T, self.N = (int(x) for x in score_host.shape)
+
+
+VANELTEREN_MAX_SCORE = 16319                      # |w_s Rc_i| <= 16319: the hi digit of S15's split fits a signed byte
+
+
+def vanelteren_rows(values, strata, S):
+    """Host ranking of spec S16, exact double comparisons: float64 [T, N] with NaN for missing and the stratum of
+    every isolate -> (score int16 [T, N], l int16 [T, N], valid bool [T, N], w, n, tiesum, tie groups int64 [T, S],
+    c float64 [T, S])."""
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    if values.ndim != 2:
+        raise ValueError("vanelteren_plan: values must be a [T, N] array")
+    T, N = values.shape
+    valid = ~np.isnan(values)
+    score, l = np.zeros((T, N), dtype=np.int16), np.zeros((T, N), dtype=np.int16)
+    w, n, tiesum, groups = (np.zeros((T, S), dtype=np.int64) for _ in range(4))
+    c = np.zeros((T, S), dtype=np.float64)
+    members = [np.flatnonzero(strata == s) for s in range(S)]
+    for t in range(T):
+        k = 0
+        for s in range(S):
+            who = members[s][valid[t, members[s]]]
+            ns = who.size
+            if ns == 0:
+                continue
+            rc, _valid, _n, ts, gr = rank_rows(values[t:t + 1, who])
+            ws = max(1, VANELTEREN_MAX_SCORE // (ns + 1))
+            score[t, who] = ws * rc[0].astype(np.int64)
+            l[t, k:k + ns] = score[t, who]
+            k += ns
+            w[t, s], n[t, s], tiesum[t, s], groups[t, s] = ws, ns, ts[0], gr[0]
+            if ns >= 2:
+                f = float(ns + 1) - float(ts[0]) / (float(ns) * float(ns - 1))
+                c[t, s] = float(ws * ws) * f / 12.0
+    return score, l, valid, w, n, tiesum, groups, c
+
+
 class Workspace:
     """Device buffers of one associate() step (engine.workspace)."""
 
@@ -1674,27 +1725,102 @@ class AssociationEngine:
         per = max(int(self.lib.scoary_ranksum_bfrag_bytes(N, 64, T)), 1)
         return int(max(64, min(-(-permutations // 64) * 64, budget_bytes // per * 64)))
 
-    def ranksum_permute(self, genes, plan, d_obs, permutations, seed, budget_bytes=8 << 30):
-        """r_q int32 [T, G] = #{pi < permutations : |D_pi| >= |d_obs|} under value shuffles (spec S15), in batches
-        of ranksum_batch() permutations: the generator writes a batch as the matrix-core kernel's B operand and
-        k_permute_ranksum adds its counts."""
+    def _rank_permute(self, what, genes, plan, d_obs, permutations, budget_bytes, generate):
+        """The permutation loop of ranksum_permute and vanelteren_permute: batches of ranksum_batch() permutations,
+        ``generate(nb, base, bfrag)`` writes a batch as the matrix-core kernel's B operand and k_permute_ranksum adds
+        its counts."""
         torch = _torch()
-        self._ranksum_fits("ranksum_permute", genes, plan)
+        self._ranksum_fits(what, genes, plan)
         T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
         if tuple(d_obs.shape) != (T, G) or d_obs.dtype != torch.int32 or not d_obs.is_contiguous():
-            raise ValueError("ranksum_permute: d_obs is ranksum()'s d, int32 [T, G], contiguous")
+            raise ValueError("%s: d_obs is the observed d, int32 [T, G], contiguous" % what)
         r = torch.zeros((T, G), dtype=torch.int32, device=self.device)
         batch = self.ranksum_batch(T, N, P, budget_bytes)
         bfrag = self._empty((int(self.lib.scoary_ranksum_bfrag_bytes(N, min(batch, P), T)),), torch.uint8)
         for base in range(0, P, batch):
             nb = min(batch, P - base)
-            self._check(self.lib.scoary_ranksum_perm_generate_bfrag(
-                self.h, self._ptr(plan.rc), self._ptr(plan.valid), T, N, nb, base, 0, ctypes.c_uint64(seed),
-                self._ptr(bfrag), self._stream()), "scoary_ranksum_perm_generate_bfrag")
+            generate(nb, base, bfrag)
             self._check(self.lib.scoary_permute_ranksum(
                 self.h, self._ptr(genes.tiled), self._ptr(bfrag), self._ptr(d_obs), G, T, N, nb, self._ptr(r),
                 self._stream()), "scoary_permute_ranksum")
         return r
+
+    def ranksum_permute(self, genes, plan, d_obs, permutations, seed, budget_bytes=8 << 30):
+        """r_q int32 [T, G] = #{pi < permutations : |D_pi| >= |d_obs|} under value shuffles (spec S15), in batches
+        of ranksum_batch() permutations: the generator writes a batch as the matrix-core kernel's B operand and
+        k_permute_ranksum adds its counts."""
+        def generate(nb, base, bfrag):
+            self._check(self.lib.scoary_ranksum_perm_generate_bfrag(
+                self.h, self._ptr(plan.rc), self._ptr(plan.valid), plan.T, plan.N, nb, base, 0,
+                ctypes.c_uint64(seed), self._ptr(bfrag), self._stream()), "scoary_ranksum_perm_generate_bfrag")
+        return self._rank_permute("ranksum_permute", genes, plan, d_obs, permutations, budget_bytes, generate)
+
+    # -- quantitative traits over strata: the van Elteren test (spec S16) --------------
+    def vanelteren_plan(self, values, strata):
+        """values: float64 [T, N], NaN = missing; strata: N integers in [0, S), S = the largest + 1.  The host
+        ranking, weights, scores and L of spec S16 as a VanElterenPlan."""
+        torch = _torch()
+        values = np.asarray(values, dtype=np.float64)
+        st = np.asarray(strata)
+        if values.ndim != 2 or st.ndim != 1 or st.shape[0] != values.shape[1] or st.shape[0] < 1 \
+                or not np.issubdtype(st.dtype, np.integer):
+            raise ValueError("vanelteren_plan: values must be [T, N] and strata N integers, one per isolate")
+        st = st.astype(np.int64)
+        N, S = st.shape[0], int(st.max()) + 1
+        if st.min() < 0:
+            raise ValueError("vanelteren_plan: stratum indices must not be negative")
+        if S > self.strata_max()[0]:
+            raise ValueError("vanelteren_plan: %d strata, the kernels take %d (scoary_perm_max_strata)"
+                             % (S, self.strata_max()[0]))
+        if N > self.ranksum_max_isolates():
+            raise ValueError("vanelteren_plan: %d isolates, the rank-sum kernels take at most %d"
+                             % (N, self.ranksum_max_isolates()))
+        score, l, valid, w, n, tiesum, groups, c = vanelteren_rows(values, st, S)
+        wn = np.stack([w, n], axis=2).astype(np.int32)
+        members = np.argsort(st, kind="stable").astype(np.int32)
+        dev = [torch.from_numpy(np.ascontiguousarray(x)).to(self.device) for x in
+               (score, l, wn, c, st.astype(np.uint16).view(np.int16), members)]
+        dev.insert(2, self.vecrows(pack_bits_rows(valid.astype(np.uint8)), N))
+        return VanElterenPlan(dev, score, valid, st, S, w, n, tiesum, groups, c)
+
+    def vanelteren(self, genes, plan):
+        """The observed van Elteren statistic of every (trait, gene): dict of device tensors d (the weighted sum of
+        the centred doubled within-stratum ranks) and m (isolates with the gene and a value) int32 [T, G], var, auc
+        and p float64 [T, G]; an untestable gene has (d 0, var 0, auc 0.5, p 1)."""
+        torch = _torch()
+        self._ranksum_fits("vanelteren", genes, plan)
+        T, G = plan.T, genes.G
+        out = {"d": self._empty((T, G), torch.int32), "m": self._empty((T, G), torch.int32),
+               "var": self._empty((T, G), torch.float64), "auc": self._empty((T, G), torch.float64),
+               "p": self._empty((T, G), torch.float64)}
+        scratch = self._cmh_scratch(plan.N)
+        self._check(self.lib.scoary_vanelteren(
+            self.h, self._ptr(genes.tiled), self._ptr(plan.score), self._ptr(plan.valid), self._ptr(plan.strata),
+            self._ptr(plan.members), self._ptr(plan.wn), self._ptr(plan.c), G, T, plan.N, plan.S,
+            *(self._ptr(out[k]) for k in ("d", "m", "var", "auc", "p")), self._ptr(scratch), self._stream()),
+            "scoary_vanelteren")
+        return out
+
+    def vanelteren_values(self, plan, perm_base, P, seed):
+        """The score rows of the permutations perm_base .. perm_base + P - 1, shuffled within strata: int16
+        [T, P, N]."""
+        out = self._empty((plan.T, int(P), plan.N), _torch().int16)
+        self._check(self.lib.scoary_vanelteren_perm_generate(
+            self.h, self._ptr(plan.l), self._ptr(plan.valid), self._ptr(plan.strata), plan.T, plan.N, plan.S, int(P),
+            int(perm_base), 0, ctypes.c_uint64(seed), self._ptr(out), self._stream()),
+            "scoary_vanelteren_perm_generate")
+        return out
+
+    def vanelteren_permute(self, genes, plan, d_obs, permutations, seed, budget_bytes=8 << 30):
+        """r int32 [T, G] = #{pi < permutations : |D_pi| >= |d_obs|} under value shuffles within the strata (spec
+        S16), in ranksum_permute's batches: the stratified generator writes a batch as the B operand and
+        k_permute_ranksum adds its counts."""
+        def generate(nb, base, bfrag):
+            self._check(self.lib.scoary_vanelteren_perm_generate_bfrag(
+                self.h, self._ptr(plan.l), self._ptr(plan.valid), self._ptr(plan.strata), plan.T, plan.N, plan.S, nb,
+                base, 0, ctypes.c_uint64(seed), self._ptr(bfrag), self._stream()),
+                "scoary_vanelteren_perm_generate_bfrag")
+        return self._rank_permute("vanelteren_permute", genes, plan, d_obs, permutations, budget_bytes, generate)
 
     # -- timing (bench.py) ------------------------------------------------------
     def set_timing(self, on):

@@ -1793,6 +1793,12 @@ def ScoaryArgumentParser(argv=None):
                    "against every gene with the Wilcoxon-Mann-Whitney rank-sum test (normal approximation with tie and "
                    "continuity corrections) and written to <trait>.ranksum.results.csv; --permute adds Empirical_p "
                    "from shuffles of the values over the isolates (single process; scoary_amd extension)")
+    a.add_argument("--quantitative-strata", dest="quantitative_strata", metavar="FILE", default=None,
+                   help="With --quantitative: FILE names a stratum (lineage, cluster) for every isolate, in the format "
+                   "of --permute-strata's file.  Every measured trait is additionally tested with the van Elteren "
+                   "stratified rank-sum test -- ranks inside the strata, weights 1 / (n_s + 1) -- and written to "
+                   "<trait>.vanelteren.results.csv; --permute adds Empirical_p from shuffles of the values within "
+                   "the strata; at most 1024 strata (single process; scoary_amd extension)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1982,6 +1988,12 @@ def main(**kwargs):
             with _stage("rank-sum test of the quantitative traits"):
                 StoreRanksumResults(Ranksum_results(genedic, names, values, permutations=args.permute, seed=seed),
                                     genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
+            if getattr(args, "quantitative_strata", None):
+                qstrata = strata_indices(args.quantitative_strata_map, strains)[0]
+                with _stage("van Elteren test of the quantitative traits"):
+                    StoreVanElterenResults(VanElteren_results(genedic, names, values, qstrata,
+                                                              permutations=args.permute, seed=seed),
+                                           genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
         log.info("Stage seconds: load (+tree) %.2f, association (+permutations) %.2f, pairwise stage and "
                  "output %.2f" % (t_loaded - start, t_stats - t_loaded, _time.time() - t_stats))
         gene_bytes = os.path.getsize(args.genes) if os.path.isfile(args.genes) else 0
@@ -2131,17 +2143,17 @@ def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, n
     return out
 
 
-def StoreRanksumResults(results, genedic, max_hits, outdir, time="", delimiter=","):
-    """Write ``<outdir><trait><time>.ranksum.results.csv`` for every trait of Ranksum_results: the testable genes in
-    ascending Rank_sum_p (ties in file order), Bonferroni and Benjamini-Hochberg over them, every cell
-    double-quoted.  Returns the file names."""
+def _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, test_columns, suffix, what):
+    """The result files of a rank test's stage (StoreRanksumResults, StoreVanElterenResults): per trait the testable
+    genes in ascending p (ties in file order), Bonferroni and Benjamini-Hochberg over them, every cell
+    double-quoted."""
     table = _as_table(genedic)
     files = []
     for name, res in results.items():
         with_emp = "r" in res
-        columns = ROARY_HEAD + list(RANKSUM_COLUMNS) + (["Empirical_p"] if with_emp else [])
+        columns = ROARY_HEAD + list(test_columns) + (["Empirical_p"] if with_emp else [])
         idx = np.flatnonzero(res["testable"])
-        fname = outdir + name + time + ".ranksum.results.csv"
+        fname = outdir + name + time + suffix
         with open(fname, "w") as out:
             out.write(delimiter.join('"' + c + '"' for c in columns) + "\n")
             if len(idx):
@@ -2160,9 +2172,83 @@ def StoreRanksumResults(results, genedic, max_hits, outdir, time="", delimiter="
                     if with_emp:
                         cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
                     out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
-        log.info("Storing rank-sum results: " + fname)
+        log.info("Storing %s results: %s" % (what, fname))
         files.append(fname)
     return files
+
+
+def StoreRanksumResults(results, genedic, max_hits, outdir, time="", delimiter=","):
+    """Write ``<outdir><trait><time>.ranksum.results.csv`` for every trait of Ranksum_results: the testable genes in
+    ascending Rank_sum_p (ties in file order), Bonferroni and Benjamini-Hochberg over them, every cell
+    double-quoted.  Returns the file names."""
+    return _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, RANKSUM_COLUMNS,
+                               ".ranksum.results.csv", "rank-sum")
+
+
+# ---------------------------------------------------------------------------
+# --quantitative-strata FILE: the van Elteren test of the measured traits over strata (spec S16), next to the
+# rank-sum stage: result files of its own, and nothing of the rank-sum files changes.
+# ---------------------------------------------------------------------------
+VANELTEREN_COLUMNS = ("Number_with_gene", "Number_without_gene", "Van_Elteren_AUC", "Van_Elteren_p", "Bonferroni_p",
+                      "Benjamini_H_p")
+VANELTEREN_TEXT = {
+    "quantitative": "Cannot use --quantitative-strata without --quantitative. Its strata are those of the van Elteren "
+                    "test of the measured traits",
+    "file": "Could not find the strata file of --quantitative-strata: %s",
+    "strata": "The strata file %s names %d strata for the analysed isolates; --quantitative-strata takes at most %d",
+}
+
+
+def VanElteren_results(genedic, names, values, strata, permutations=0, seed=DEFAULT_SEED, no_pairwise=True,
+                       collapse=False):
+    """The van Elteren stage (spec S16) of the traits ``names`` with the values float64 [T, N] (nan = missing) and
+    the stratum index of every isolate ``strata`` (N integers) over the isolates of ``genedic``: {name: dict(n,
+    strata (those with a value), m, auc, p, var, testable [G]; r [G] with permutations >= 10)}, arrays in the gene
+    table's order.  Raises ValueError where the command line refuses --quantitative."""
+    for text in _ranksum_refusals(no_pairwise, collapse, False):
+        raise ValueError(text)
+    table = _as_table(genedic)
+    eng = get_engine()
+    values = np.asarray(values, dtype=np.float64)
+    strata = np.asarray(strata)
+    if values.ndim != 2 or values.shape != (len(names), len(table.strains)):
+        raise ValueError("quantitative traits: values must be [%d traits, %d isolates]"
+                         % (len(names), len(table.strains)))
+    if strata.shape != (len(table.strains),) or not np.issubdtype(strata.dtype, np.integer) or strata.min() < 0:
+        raise ValueError("quantitative traits: strata must be %d stratum indices, one per isolate"
+                         % len(table.strains))
+    if values.shape[1] > eng.ranksum_max_isolates():
+        raise ValueError("quantitative traits take at most %d isolates; this analysis has %d"
+                         % (eng.ranksum_max_isolates(), values.shape[1]))
+    from . import _abi
+    if int(strata.max()) + 1 > _abi.PERM_MAX_STRATA:
+        raise ValueError("quantitative traits take at most %d strata; these are %d"
+                         % (_abi.PERM_MAX_STRATA, int(strata.max()) + 1))
+    genes = table.on_device(eng)
+    plan = eng.vanelteren_plan(values, strata)
+    res = eng.vanelteren(genes, plan)
+    permutations = int(permutations)
+    r = (eng.vanelteren_permute(genes, plan, res["d"], permutations, seed).cpu().numpy()
+         if permutations >= 10 else None)
+    m, auc, p, var = (res[k].cpu().numpy() for k in ("m", "auc", "p", "var"))
+    out = {}
+    for t, name in enumerate(names):
+        out[name] = dict(n=int(plan.n[t].sum()), strata=int((plan.n[t] > 0).sum()), m=m[t], auc=auc[t], p=p[t],
+                         var=var[t], testable=var[t] > 0)
+        if r is not None:
+            out[name]["r"] = r[t]
+            out[name]["permutations"] = permutations
+        log.info("Van Elteren test of %s: %d isolates with a value in %d strata, %d genes tested"
+                 % (name, out[name]["n"], out[name]["strata"], int(out[name]["testable"].sum())))
+    return out
+
+
+def StoreVanElterenResults(results, genedic, max_hits, outdir, time="", delimiter=","):
+    """Write ``<outdir><trait><time>.vanelteren.results.csv`` for every trait of VanElteren_results, by
+    StoreRanksumResults' rules: the testable genes in ascending Van_Elteren_p (ties in file order), Bonferroni and
+    Benjamini-Hochberg over them, every cell double-quoted.  Returns the file names."""
+    return _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, VANELTEREN_COLUMNS,
+                               ".vanelteren.results.csv", "van Elteren")
 
 
 class _LevelCounter(logging.Handler):
@@ -2268,6 +2354,17 @@ def _validate(args, cutoffs):
             sys.exit(text)
         if not os.path.isfile(args.quantitative):
             sys.exit("Could not find the quantitative traits file: %s" % args.quantitative)
+    qstrata = getattr(args, "quantitative_strata", None)
+    if qstrata:
+        if not getattr(args, "quantitative", None):
+            sys.exit(VANELTEREN_TEXT["quantitative"])
+        if not os.path.isfile(qstrata):
+            sys.exit(VANELTEREN_TEXT["file"] % qstrata)
+        args.quantitative_strata_map = read_strata_file(qstrata, args.delimiter)
+        from . import _abi
+        labels = strata_indices(args.quantitative_strata_map, _analysed_isolates(args))[1]
+        if len(labels) > _abi.PERM_MAX_STRATA:
+            sys.exit(VANELTEREN_TEXT["strata"] % (qstrata, len(labels), _abi.PERM_MAX_STRATA))
     level = getattr(args, "cmh_exact_level", None)
     if level is not None and not getattr(args, "cmh_exact_odds", False):
         sys.exit("Cannot use --cmh-exact-level without --cmh-exact-odds. It is the confidence level of the limits "

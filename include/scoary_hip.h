@@ -597,6 +597,31 @@ int scoary_vanelteren_perm_generate_bfrag(scoary_handle h, const int16_t *d_l, c
                                           const uint16_t *d_strata, int64_t T, int64_t N, int64_t S, int64_t P,
                                           int64_t perm_base, int64_t trait_base, uint64_t seed, void *d_bfrag,
                                           scoary_stream_t stream);
+/* ---- Quantitative traits: Westfall-Young single-step maxT over the rank statistics (spec S17 of DESIGN.md; additive,
+ * ABI 11) ----
+ * One statistic for the rank-sum test (S15, cc = 1) and the van Elteren test (S16, cc = 0).  A cell (gene, row) with
+ * the integer D has s = ((double)E * (double)E) * iv, E = max(0, |D| - cc), iv = 1 / var of the gene where it is
+ * testable and 0 where not; fp64, every operation rounded on its own; 4 z^2 in the reals.
+ *   scoary_ranksum_var      d_var double [T][G]: S15's var = (m (n - m) / 12) f of scoary_ranksum, operations in its
+ *                           order, from d_m (scoary_ranksum's), the validity bits and the tie sums; 0 where the gene
+ *                           is untestable.  (S16's var is scoary_vanelteren's d_var.)
+ *   scoary_rank_wy_prepare  d_iv double [T][G] = 1 / var where var > 0, else 0; d_sobs double [T][G] = s of d_dobs
+ *   scoary_permute_rank_wy  scoary_permute_ranksum with the family-wise maxima in the same pass: d_r as there, bit
+ *                           for bit, and d_maxs[t * maxs_stride + p] = max(what it held, max over g < G of s of the
+ *                           cell (g, p)) for p < P -- d_maxs points at the batch's first column inside a double
+ *                           [T][maxs_stride] array that the caller fills with zeros before the first batch; columns
+ *                           at and past P are not written, whatever d_bfrag holds there.  The maximum is exact and
+ *                           does not depend on the order the blocks run in
+ * Asynchronous on `stream`, nothing is allocated.  SCOARY_ERR_ARG: null pointer, size < 1, cc not 0 or 1,
+ * maxs_stride < P; SCOARY_ERR_SIZE, with nothing written: N > scoary_ranksum_max_isolates(), T > 65535, G or
+ * P >= 2^31. */
+int scoary_ranksum_var(scoary_handle h, const int32_t *d_m, const uint32_t *d_valid, const int64_t *d_tiesum,
+                       int64_t G, int64_t T, int64_t N, double *d_var, scoary_stream_t stream);
+int scoary_rank_wy_prepare(scoary_handle h, const double *d_var, const int32_t *d_dobs, int64_t cc, int64_t G,
+                           int64_t T, double *d_iv, double *d_sobs, scoary_stream_t stream);
+int scoary_permute_rank_wy(scoary_handle h, const uint32_t *d_tiled, const void *d_bfrag, const int32_t *d_dobs,
+                           const double *d_iv, int64_t cc, int64_t G, int64_t T, int64_t N, int64_t P, int32_t *d_r,
+                           double *d_maxs, int64_t maxs_stride, scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

@@ -1725,10 +1725,11 @@ class AssociationEngine:
         per = max(int(self.lib.scoary_ranksum_bfrag_bytes(N, 64, T)), 1)
         return int(max(64, min(-(-permutations // 64) * 64, budget_bytes // per * 64)))
 
-    def _rank_permute(self, what, genes, plan, d_obs, permutations, budget_bytes, generate):
+    def _rank_permute(self, what, genes, plan, d_obs, permutations, budget_bytes, generate, maxt=None):
         """The permutation loop of ranksum_permute and vanelteren_permute: batches of ranksum_batch() permutations,
         ``generate(nb, base, bfrag)`` writes a batch as the matrix-core kernel's B operand and k_permute_ranksum adds
-        its counts."""
+        its counts.  ``maxt`` = (iv float64 [T, G], cc, maxs float64 [T, P] of zeros) picks k_rank_maxt instead (spec
+        S17): the same counts, and a batch's maxima into its columns of maxs."""
         torch = _torch()
         self._ranksum_fits(what, genes, plan)
         T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
@@ -1740,20 +1741,82 @@ class AssociationEngine:
         for base in range(0, P, batch):
             nb = min(batch, P - base)
             generate(nb, base, bfrag)
-            self._check(self.lib.scoary_permute_ranksum(
-                self.h, self._ptr(genes.tiled), self._ptr(bfrag), self._ptr(d_obs), G, T, N, nb, self._ptr(r),
-                self._stream()), "scoary_permute_ranksum")
+            if maxt is None:
+                self._check(self.lib.scoary_permute_ranksum(
+                    self.h, self._ptr(genes.tiled), self._ptr(bfrag), self._ptr(d_obs), G, T, N, nb, self._ptr(r),
+                    self._stream()), "scoary_permute_ranksum")
+            else:
+                iv, cc, maxs = maxt
+                self._check(self.lib.scoary_permute_rank_wy(
+                    self.h, self._ptr(genes.tiled), self._ptr(bfrag), self._ptr(d_obs), self._ptr(iv), cc, G, T, N,
+                    nb, self._ptr(r), self._ptr(maxs[:, base:]), P, self._stream()), "scoary_permute_rank_wy")
         return r
+
+    def rank_wy_prepare(self, var, d_obs, cc):
+        """(iv, s_obs) float64 [T, G] of spec S17 from a rank test's var (0 where untestable) and observed d."""
+        torch = _torch()
+        T, G = (int(x) for x in d_obs.shape)
+        if tuple(var.shape) != (T, G) or var.dtype != torch.float64 or not var.is_contiguous():
+            raise ValueError("rank_wy_prepare: var is float64 [T, G], contiguous")
+        iv, sobs = self._empty((T, G), torch.float64), self._empty((T, G), torch.float64)
+        self._check(self.lib.scoary_rank_wy_prepare(self.h, self._ptr(var), self._ptr(d_obs), int(cc), G, T,
+                                                    self._ptr(iv), self._ptr(sobs), self._stream()),
+                    "scoary_rank_wy_prepare")
+        return iv, sobs
+
+    @staticmethod
+    def r_fwer_max(maxs, s_obs):
+        """r_fwer[t, g] = #{pi : maxs[t, pi] >= s_obs[t, g]} (int32 [T, G]), doubles compared exactly: a sort of
+        every trait's maxima and a search for every gene's statistic (r_fwer()'s counterpart for a maximum)."""
+        torch = _torch()
+        srt = torch.sort(maxs, dim=1).values.contiguous()
+        below = torch.searchsorted(srt, s_obs.contiguous(), right=False)
+        return (maxs.shape[1] - below).to(torch.int32)
+
+    def _rank_westfall_young(self, what, genes, plan, res, var, cc, permutations, budget_bytes, generate):
+        """Spec S17 over one rank test: (r, r_fwer, maxs) from one pass over the permutations."""
+        torch = _torch()
+        self._ranksum_fits(what, genes, plan)
+        d_obs = res["d"]
+        if tuple(d_obs.shape) != (plan.T, genes.G) or d_obs.dtype != torch.int32 or not d_obs.is_contiguous():
+            raise ValueError("%s: res is the observed result of these genes and this plan" % what)
+        iv, sobs = self.rank_wy_prepare(var, d_obs, cc)
+        maxs = torch.zeros((plan.T, int(permutations)), dtype=torch.float64, device=self.device)
+        r = self._rank_permute(what, genes, plan, d_obs, permutations, budget_bytes, generate, maxt=(iv, cc, maxs))
+        return r, self.r_fwer_max(maxs, sobs), maxs
 
     def ranksum_permute(self, genes, plan, d_obs, permutations, seed, budget_bytes=8 << 30):
         """r_q int32 [T, G] = #{pi < permutations : |D_pi| >= |d_obs|} under value shuffles (spec S15), in batches
         of ranksum_batch() permutations: the generator writes a batch as the matrix-core kernel's B operand and
         k_permute_ranksum adds its counts."""
+        return self._rank_permute("ranksum_permute", genes, plan, d_obs, permutations, budget_bytes,
+                                  self._ranksum_generator(plan, seed))
+
+    def _ranksum_generator(self, plan, seed):
         def generate(nb, base, bfrag):
             self._check(self.lib.scoary_ranksum_perm_generate_bfrag(
                 self.h, self._ptr(plan.rc), self._ptr(plan.valid), plan.T, plan.N, nb, base, 0,
                 ctypes.c_uint64(seed), self._ptr(bfrag), self._stream()), "scoary_ranksum_perm_generate_bfrag")
-        return self._rank_permute("ranksum_permute", genes, plan, d_obs, permutations, budget_bytes, generate)
+        return generate
+
+    def ranksum_var(self, plan, m):
+        """S15's var float64 [T, G] of the observed m (ranksum()'s), 0 where the gene is untestable."""
+        torch = _torch()
+        T, G = (int(x) for x in m.shape)
+        if T != plan.T or m.dtype != torch.int32 or not m.is_contiguous():
+            raise ValueError("ranksum_var: m is the observed m, int32 [T, G], contiguous")
+        var = self._empty((T, G), torch.float64)
+        self._check(self.lib.scoary_ranksum_var(self.h, self._ptr(m), self._ptr(plan.valid), self._ptr(plan.tiesum),
+                                                G, T, plan.N, self._ptr(var), self._stream()), "scoary_ranksum_var")
+        return var
+
+    def ranksum_westfall_young(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
+        """Westfall-Young single-step maxT over the rank-sum statistic (spec S17, cc = 1) of the step ``res`` =
+        ranksum(genes, plan): (r_q, r_fwer, maxs) -- r_q int32 [T, G] as ranksum_permute returns it, r_fwer int32
+        [T, G] = #{pi : maxs[t, pi] >= s_obs[t, g]}, maxs float64 [T, permutations] -- from one pass of k_rank_maxt
+        over ranksum_permute's batches."""
+        return self._rank_westfall_young("ranksum_westfall_young", genes, plan, res, self.ranksum_var(plan, res["m"]),
+                                         1, permutations, budget_bytes, self._ranksum_generator(plan, seed))
 
     # -- quantitative traits over strata: the van Elteren test (spec S16) --------------
     def vanelteren_plan(self, values, strata):
@@ -1815,12 +1878,23 @@ class AssociationEngine:
         """r int32 [T, G] = #{pi < permutations : |D_pi| >= |d_obs|} under value shuffles within the strata (spec
         S16), in ranksum_permute's batches: the stratified generator writes a batch as the B operand and
         k_permute_ranksum adds its counts."""
+        return self._rank_permute("vanelteren_permute", genes, plan, d_obs, permutations, budget_bytes,
+                                  self._vanelteren_generator(plan, seed))
+
+    def _vanelteren_generator(self, plan, seed):
         def generate(nb, base, bfrag):
             self._check(self.lib.scoary_vanelteren_perm_generate_bfrag(
                 self.h, self._ptr(plan.l), self._ptr(plan.valid), self._ptr(plan.strata), plan.T, plan.N, plan.S, nb,
                 base, 0, ctypes.c_uint64(seed), self._ptr(bfrag), self._stream()),
                 "scoary_vanelteren_perm_generate_bfrag")
-        return self._rank_permute("vanelteren_permute", genes, plan, d_obs, permutations, budget_bytes, generate)
+        return generate
+
+    def vanelteren_westfall_young(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
+        """Westfall-Young single-step maxT over the van Elteren statistic (spec S17, cc = 0) of the step ``res`` =
+        vanelteren(genes, plan): (r, r_fwer, maxs) as ranksum_westfall_young returns them, the rows shuffled within
+        the strata."""
+        return self._rank_westfall_young("vanelteren_westfall_young", genes, plan, res, res["var"], 0, permutations,
+                                         budget_bytes, self._vanelteren_generator(plan, seed))
 
     # -- timing (bench.py) ------------------------------------------------------
     def set_timing(self, on):

@@ -1799,6 +1799,11 @@ def ScoaryArgumentParser(argv=None):
                    "stratified rank-sum test -- ranks inside the strata, weights 1 / (n_s + 1) -- and written to "
                    "<trait>.vanelteren.results.csv; --permute adds Empirical_p from shuffles of the values within "
                    "the strata; at most 1024 strata (single process; scoary_amd extension)")
+    a.add_argument("--quantitative-fwer", dest="quantitative_fwer", action="store_true", default=False,
+                   help="With --quantitative and --permute X (X >= 10): add the column Westfall_Young_p to the rank-sum "
+                   "results -- and, with --quantitative-strata, to the van Elteren results -- the single-step maxT "
+                   "family-wise p over all genes of the table, from the same permutations that give Empirical_p "
+                   "(single process; scoary_amd extension)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1985,14 +1990,17 @@ def main(**kwargs):
                          gd["Firstcolnames"], time=stamp, delimiter=args.delimiter, seed=seed)
         if getattr(args, "quantitative", None) and rank == 0:
             names, values = read_quantitative_file(args.quantitative, args.delimiter, strains)
+            qfwer = bool(getattr(args, "quantitative_fwer", False))
             with _stage("rank-sum test of the quantitative traits"):
-                StoreRanksumResults(Ranksum_results(genedic, names, values, permutations=args.permute, seed=seed),
+                StoreRanksumResults(Ranksum_results(genedic, names, values, permutations=args.permute, seed=seed,
+                                                    fwer=qfwer),
                                     genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
             if getattr(args, "quantitative_strata", None):
                 qstrata = strata_indices(args.quantitative_strata_map, strains)[0]
                 with _stage("van Elteren test of the quantitative traits"):
                     StoreVanElterenResults(VanElteren_results(genedic, names, values, qstrata,
-                                                              permutations=args.permute, seed=seed),
+                                                              permutations=args.permute, seed=seed,
+                                                              fwer=qfwer),
                                            genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
         log.info("Stage seconds: load (+tree) %.2f, association (+permutations) %.2f, pairwise stage and "
                  "output %.2f" % (t_loaded - start, t_stats - t_loaded, _time.time() - t_stats))
@@ -2108,11 +2116,14 @@ def read_quantitative_file(path, delimiter, strains):
 
 
 def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False,
-                    strata=None):
+                    strata=None, fwer=False):
     """The rank-sum stage (spec S15) of the traits ``names`` with the values float64 [T, N] (nan = missing) over the
-    isolates of ``genedic``: {name: dict(n, tie_groups, m, auc, p, testable [G]; r [G] with permutations >= 10)},
-    arrays in the gene table's order.  Raises ValueError where the command line refuses --quantitative."""
+    isolates of ``genedic``: {name: dict(n, tie_groups, m, auc, p, testable [G]; r [G] with permutations >= 10;
+    r_fwer [G] with ``fwer``, spec S17)}, arrays in the gene table's order.  Raises ValueError where the command line
+    refuses --quantitative or --quantitative-fwer."""
     for text in _ranksum_refusals(no_pairwise, collapse, strata is not None):
+        raise ValueError(text)
+    for text in _rank_wy_refusals(fwer, True, permutations):
         raise ValueError(text)
     table = _as_table(genedic)
     eng = get_engine()
@@ -2127,7 +2138,11 @@ def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, n
     plan = eng.ranksum_plan(values)
     res = eng.ranksum(genes, plan)
     permutations = int(permutations)
-    r = eng.ranksum_permute(genes, plan, res["d"], permutations, seed).cpu().numpy() if permutations >= 10 else None
+    r = r_fwer = None
+    if fwer:                     # one pass over the permutations gives both counts
+        r, r_fwer = (x.cpu().numpy() for x in eng.ranksum_westfall_young(genes, plan, res, permutations, seed)[:2])
+    elif permutations >= 10:
+        r = eng.ranksum_permute(genes, plan, res["d"], permutations, seed).cpu().numpy()
     m, auc, p = (res[k].cpu().numpy() for k in ("m", "auc", "p"))
     out = {}
     for t, name in enumerate(names):
@@ -2138,6 +2153,8 @@ def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, n
         if r is not None:
             out[name]["r"] = r[t]
             out[name]["permutations"] = permutations
+        if r_fwer is not None:
+            out[name]["r_fwer"] = r_fwer[t]
         log.info("Rank-sum test of %s: %d isolates with a value, %d tie groups, %d genes tested"
                  % (name, n, out[name]["tie_groups"], int(testable.sum())))
     return out
@@ -2151,7 +2168,9 @@ def _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, tes
     files = []
     for name, res in results.items():
         with_emp = "r" in res
-        columns = ROARY_HEAD + list(test_columns) + (["Empirical_p"] if with_emp else [])
+        with_fwer = with_emp and "r_fwer" in res
+        columns = ROARY_HEAD + list(test_columns) + (["Empirical_p"] if with_emp else []) + \
+            (["Westfall_Young_p"] if with_fwer else [])
         idx = np.flatnonzero(res["testable"])
         fname = outdir + name + time + suffix
         with open(fname, "w") as out:
@@ -2171,6 +2190,8 @@ def _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, tes
                               _fmt(bh[k])]
                     if with_emp:
                         cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
+                    if with_fwer:
+                        cells.append(_fmt((int(res["r_fwer"][g]) + 1.0) / (res["permutations"] + 1.0)))
                     out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
         log.info("Storing %s results: %s" % (what, fname))
         files.append(fname)
@@ -2200,12 +2221,15 @@ VANELTEREN_TEXT = {
 
 
 def VanElteren_results(genedic, names, values, strata, permutations=0, seed=DEFAULT_SEED, no_pairwise=True,
-                       collapse=False):
+                       collapse=False, fwer=False):
     """The van Elteren stage (spec S16) of the traits ``names`` with the values float64 [T, N] (nan = missing) and
     the stratum index of every isolate ``strata`` (N integers) over the isolates of ``genedic``: {name: dict(n,
-    strata (those with a value), m, auc, p, var, testable [G]; r [G] with permutations >= 10)}, arrays in the gene
-    table's order.  Raises ValueError where the command line refuses --quantitative."""
+    strata (those with a value), m, auc, p, var, testable [G]; r [G] with permutations >= 10; r_fwer [G] with
+    ``fwer``, spec S17)}, arrays in the gene table's order.  Raises ValueError where the command line refuses
+    --quantitative or --quantitative-fwer."""
     for text in _ranksum_refusals(no_pairwise, collapse, False):
+        raise ValueError(text)
+    for text in _rank_wy_refusals(fwer, True, permutations):
         raise ValueError(text)
     table = _as_table(genedic)
     eng = get_engine()
@@ -2228,8 +2252,11 @@ def VanElteren_results(genedic, names, values, strata, permutations=0, seed=DEFA
     plan = eng.vanelteren_plan(values, strata)
     res = eng.vanelteren(genes, plan)
     permutations = int(permutations)
-    r = (eng.vanelteren_permute(genes, plan, res["d"], permutations, seed).cpu().numpy()
-         if permutations >= 10 else None)
+    r = r_fwer = None
+    if fwer:
+        r, r_fwer = (x.cpu().numpy() for x in eng.vanelteren_westfall_young(genes, plan, res, permutations, seed)[:2])
+    elif permutations >= 10:
+        r = eng.vanelteren_permute(genes, plan, res["d"], permutations, seed).cpu().numpy()
     m, auc, p, var = (res[k].cpu().numpy() for k in ("m", "auc", "p", "var"))
     out = {}
     for t, name in enumerate(names):
@@ -2238,6 +2265,8 @@ def VanElteren_results(genedic, names, values, strata, permutations=0, seed=DEFA
         if r is not None:
             out[name]["r"] = r[t]
             out[name]["permutations"] = permutations
+        if r_fwer is not None:
+            out[name]["r_fwer"] = r_fwer[t]
         log.info("Van Elteren test of %s: %d isolates with a value in %d strata, %d genes tested"
                  % (name, out[name]["n"], out[name]["strata"], int(out[name]["testable"].sum())))
     return out
@@ -2249,6 +2278,28 @@ def StoreVanElterenResults(results, genedic, max_hits, outdir, time="", delimite
     Benjamini-Hochberg over them, every cell double-quoted.  Returns the file names."""
     return _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, VANELTEREN_COLUMNS,
                                ".vanelteren.results.csv", "van Elteren")
+
+
+# ---------------------------------------------------------------------------
+# --quantitative-fwer: Westfall-Young single-step maxT over the rank statistics (spec S17): one more column,
+# Westfall_Young_p, behind Empirical_p in the rank-sum file and -- with --quantitative-strata -- the van Elteren
+# file.  Nothing of the binary step's option tables (FLAG_RULES, OPTIONAL_COLUMNS) knows of it.
+# ---------------------------------------------------------------------------
+# a refusal, worded alike on the command line and in Ranksum_results / VanElteren_results (fwer=True)
+RANK_WY_TEXT = {
+    "quantitative": "Cannot use --quantitative-fwer without --quantitative. It is the family-wise p of the rank tests "
+                    "of the measured traits",
+    "permute": "Cannot use --quantitative-fwer without --permute X, X >= 10. The family-wise p is counted over the "
+               "permutations of the values",
+}
+
+
+def _rank_wy_refusals(fwer, quantitative, permutations):
+    """The messages of the --quantitative-fwer rules that a run breaks, in the order they are reported."""
+    if fwer and not quantitative:
+        yield RANK_WY_TEXT["quantitative"]
+    if fwer and int(permutations or 0) < 10:
+        yield RANK_WY_TEXT["permute"]
 
 
 class _LevelCounter(logging.Handler):
@@ -2365,6 +2416,9 @@ def _validate(args, cutoffs):
         labels = strata_indices(args.quantitative_strata_map, _analysed_isolates(args))[1]
         if len(labels) > _abi.PERM_MAX_STRATA:
             sys.exit(VANELTEREN_TEXT["strata"] % (qstrata, len(labels), _abi.PERM_MAX_STRATA))
+    for text in _rank_wy_refusals(getattr(args, "quantitative_fwer", False),
+                                  bool(getattr(args, "quantitative", None)), args.permute):
+        sys.exit(text)
     level = getattr(args, "cmh_exact_level", None)
     if level is not None and not getattr(args, "cmh_exact_odds", False):
         sys.exit("Cannot use --cmh-exact-level without --cmh-exact-odds. It is the confidence level of the limits "

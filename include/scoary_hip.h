@@ -622,6 +622,37 @@ int scoary_rank_wy_prepare(scoary_handle h, const double *d_var, const int32_t *
 int scoary_permute_rank_wy(scoary_handle h, const uint32_t *d_tiled, const void *d_bfrag, const int32_t *d_dobs,
                            const double *d_iv, int64_t cc, int64_t G, int64_t T, int64_t N, int64_t P, int32_t *d_r,
                            double *d_maxs, int64_t maxs_stride, scoary_stream_t stream);
+/* ---- Quantitative traits: Westfall-Young step-down maxT over the rank statistics (spec S18 of DESIGN.md; additive,
+ * ABI 11) ----
+ * S17's statistic s with the genes of a trait walked in rank order: order[t][k] = the gene at rank k of trait t, ranks
+ * by descending s_obs and ascending gene index among equals (one stable descending sort of scoary_rank_wy_prepare's
+ * d_sobs, made by the caller).  u[k] of a permuted row = the maximum of s over the genes at the ranks k and behind.
+ *   scoary_rank_stepdown_scratch_bytes  the size of d_scratch for batches of up to P permutations.  With Gp =
+ *       scoary_tiled_genes(G), Qp = scoary_tiled_quads(N), in this order: rows uint32 [T][Qp][Gp][4] (a tiled matrix
+ *       per trait, position k where the tiled matrix has gene k), ss double [T][Gp], iv double [T][Gp], |D_obs| int32
+ *       [T][Gp], gmax double [T][Gp / 64][64 ceil(P / 64)].  Everything before gmax does not depend on P.
+ *   scoary_rank_stepdown_gather         once per analysis: rows, ss, iv and |D_obs| from d_tiled, d_order int32 [T][G],
+ *       d_sobs and d_iv (scoary_rank_wy_prepare's) and d_dobs.  The positions k >= G hold zero rows, iv 0, ss 0 and a
+ *       threshold no |D| reaches; an entry of d_order outside [0, G) makes such a position too.
+ *   scoary_permute_rank_stepdown        one batch of P permutations, the columns perm_base .. perm_base + P - 1, in
+ *       three launches on `stream`: d_r_rank[t * G + k] += #{columns < P : |D| >= |D_obs|} of the gene at rank k
+ *       (scoary_permute_ranksum's count by rank position), d_c_rank[t * G + k] += #{columns < P : u[k] >= ss[k]},
+ *       doubles compared exactly, and d_maxs[t * maxs_stride + perm_base + p] = u[0] of column p < P -- written, not
+ *       combined, and equal to scoary_permute_rank_wy's maximum bit for bit.  d_maxs is the whole double
+ *       [T][maxs_stride] array.  The caller zeroes d_r_rank and d_c_rank (int32 [T][G]) before the first batch.
+ *       Columns at and past P reach none of the three, whatever d_bfrag holds there; their cells of gmax hold anything.
+ * No block waits for another and gmax has one writer per cell; the counts are integer atomic additions, as d_r's are.
+ * Asynchronous on `stream`, nothing is allocated.  SCOARY_ERR_ARG: null pointer, size < 1, cc not 0 or 1, perm_base
+ * < 0, maxs_stride < perm_base + P; SCOARY_ERR_SIZE, with nothing written: N > scoary_ranksum_max_isolates(),
+ * T > 65535, G or P >= 2^31, a grid past 2^31 - 1 blocks.  scoary_rank_stepdown_scratch_bytes returns 0 for a
+ * null handle or a size < 1. */
+int64_t scoary_rank_stepdown_scratch_bytes(scoary_handle h, int64_t G, int64_t T, int64_t N, int64_t P);
+int scoary_rank_stepdown_gather(scoary_handle h, const uint32_t *d_tiled, const int32_t *d_order,
+                                const double *d_sobs, const double *d_iv, const int32_t *d_dobs, int64_t G, int64_t T,
+                                int64_t N, void *d_scratch, scoary_stream_t stream);
+int scoary_permute_rank_stepdown(scoary_handle h, void *d_scratch, const void *d_bfrag, int64_t cc, int64_t G,
+                                 int64_t T, int64_t N, int64_t P, int64_t perm_base, int32_t *d_r_rank,
+                                 int32_t *d_c_rank, double *d_maxs, int64_t maxs_stride, scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

@@ -96,6 +96,9 @@ SIGNATURES = {
     "scoary_ranksum_var": (_i32, [_vp] * 4 + [_i64] * 3 + [_vp, _vp]),
     "scoary_rank_wy_prepare": (_i32, [_vp] * 3 + [_i64] * 3 + [_vp] * 3),
     "scoary_permute_rank_wy": (_i32, [_vp] * 5 + [_i64] * 5 + [_vp, _vp, _i64, _vp]),
+    "scoary_rank_stepdown_scratch_bytes": (_i64, [_vp] + [_i64] * 4),
+    "scoary_rank_stepdown_gather": (_i32, [_vp] * 6 + [_i64] * 3 + [_vp, _vp]),
+    "scoary_permute_rank_stepdown": (_i32, [_vp] * 3 + [_i64] * 6 + [_vp] * 3 + [_i64, _vp]),
     "scoary_permute_lists_scratch_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "scoary_permute_lists": (_i32, [_vp, _vp, _vp, _i64] + [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp,
                                                                        _i32, _vp]),

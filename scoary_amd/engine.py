@@ -1896,6 +1896,102 @@ class AssociationEngine:
         return self._rank_westfall_young("vanelteren_westfall_young", genes, plan, res, res["var"], 0, permutations,
                                          budget_bytes, self._vanelteren_generator(plan, seed))
 
+    # -- quantitative traits: step-down maxT over the rank statistics (spec S18) --------
+    def rank_stepdown_batch(self, G, T, N, permutations, budget_bytes=8 << 30):
+        """Permutations per batch of the step-down passes (a multiple of 64): the B operand and gmax -- 8 bytes per
+        (trait, group of 64 ranks, column) -- stay under budget_bytes together."""
+        per = max(int(self.lib.scoary_ranksum_bfrag_bytes(N, 64, T)), 1) + 8 * int(T) * (self.padded_genes(G) // 64) * 64
+        return int(max(64, min(-(-permutations // 64) * 64, budget_bytes // per * 64)))
+
+    @staticmethod
+    def rank_stepdown_order(s_obs):
+        """Step 1 of spec S18: (order int32 [T, G], ss float64 [T, G]) -- the genes descending by s_obs, ties by
+        ascending gene index: one stable descending device sort."""
+        torch = _torch()
+        ss, order = torch.sort(s_obs.contiguous(), dim=1, descending=True, stable=True)
+        return order.to(torch.int32).contiguous(), ss.contiguous()
+
+    def rank_stepdown_gather(self, genes, order32, s_obs, iv, d_obs, N, batch):
+        """The scratch of the step-down passes for batches of up to ``batch`` permutations, with every trait's gene
+        rows, s_obs, iv and |d_obs| gathered into rank order (k_rank_sd_gather: once per analysis)."""
+        torch = _torch()
+        T, G = (int(x) for x in d_obs.shape)
+        for x, dt, name in ((order32, torch.int32, "order32"), (s_obs, torch.float64, "s_obs"),
+                            (iv, torch.float64, "iv"), (d_obs, torch.int32, "d_obs")):
+            if tuple(x.shape) != (T, G) or x.dtype != dt or not x.is_contiguous():
+                raise ValueError("rank_stepdown_gather: %s is %s [T, G], contiguous" % (name, dt))
+        if genes.G != G or genes.N != int(N):
+            raise ValueError("rank_stepdown_gather: the gene matrix is not the one of d_obs")
+        need = int(self.lib.scoary_rank_stepdown_scratch_bytes(self.h, G, T, int(N), int(batch)))
+        scratch = self._empty((need,), torch.uint8)
+        self._check(self.lib.scoary_rank_stepdown_gather(
+            self.h, self._ptr(genes.tiled), self._ptr(order32), self._ptr(s_obs), self._ptr(iv), self._ptr(d_obs), G, T,
+            int(N), self._ptr(scratch), self._stream()), "scoary_rank_stepdown_gather")
+        return scratch
+
+    def permute_rank_stepdown(self, scratch, bfrag, cc, G, T, N, P, perm_base, r_rank, c_rank, maxs):
+        """One batch of the three step-down launches: the columns perm_base .. perm_base + P - 1 of ``bfrag`` add to
+        r_rank and c_rank (int32 [T, G], by rank position) and write their columns of maxs (float64 [T, stride])."""
+        self._check(self.lib.scoary_permute_rank_stepdown(
+            self.h, self._ptr(scratch), self._ptr(bfrag), int(cc), int(G), int(T), int(N), int(P), int(perm_base),
+            self._ptr(r_rank), self._ptr(c_rank), self._ptr(maxs), int(maxs.shape[1]), self._stream()),
+            "scoary_permute_rank_stepdown")
+
+    @staticmethod
+    def rank_stepdown_tail(c_rank, ss, order32):
+        """Steps 4 and 5 of spec S18, minp_stepdown's tail with the comparison mirrored: every position of a group of
+        equal ss takes the count of the group's first position, then the running maximum along the ranks, scattered
+        to gene order: r_sd int32 [T, G]."""
+        torch = _torch()
+        T, G = (int(x) for x in c_rank.shape)
+        pos = torch.arange(G, device=c_rank.device).expand(T, G)
+        first = torch.ones((T, G), dtype=torch.bool, device=c_rank.device)
+        first[:, 1:] = ss[:, 1:] != ss[:, :-1]
+        head = torch.cummax(torch.where(first, pos, torch.zeros_like(pos)), dim=1).values
+        r_rank = torch.cummax(c_rank.gather(1, head), dim=1).values
+        r_sd = torch.empty_like(c_rank)
+        r_sd.scatter_(1, order32.to(torch.int64), r_rank)
+        return r_sd
+
+    def _rank_stepdown(self, what, genes, plan, res, var, cc, permutations, budget_bytes, generate):
+        """Spec S18 over one rank test: (r, r_fwer, r_sd, maxs) from one run -- the sort and the gather, the batch
+        loop with the test's generator, then the host tail.  k_rank_maxt is not launched: maxs is u[0]."""
+        torch = _torch()
+        self._ranksum_fits(what, genes, plan)
+        d_obs = res["d"]
+        T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
+        if tuple(d_obs.shape) != (T, G) or d_obs.dtype != torch.int32 or not d_obs.is_contiguous():
+            raise ValueError("%s: res is the observed result of these genes and this plan" % what)
+        iv, sobs = self.rank_wy_prepare(var, d_obs, cc)
+        order32, ss = self.rank_stepdown_order(sobs)
+        batch = self.rank_stepdown_batch(G, T, N, P, budget_bytes)
+        scratch = self.rank_stepdown_gather(genes, order32, sobs, iv, d_obs, N, min(batch, P))
+        bfrag = self._empty((int(self.lib.scoary_ranksum_bfrag_bytes(N, min(batch, P), T)),), torch.uint8)
+        r_rank = torch.zeros((T, G), dtype=torch.int32, device=self.device)
+        c_rank = torch.zeros((T, G), dtype=torch.int32, device=self.device)
+        maxs = torch.zeros((T, P), dtype=torch.float64, device=self.device)
+        for base in range(0, P, batch):
+            nb = min(batch, P - base)
+            generate(nb, base, bfrag)
+            self.permute_rank_stepdown(scratch, bfrag, cc, G, T, N, nb, base, r_rank, c_rank, maxs)
+        r = torch.empty_like(r_rank)
+        r.scatter_(1, order32.to(torch.int64), r_rank)
+        return r, self.r_fwer_max(maxs, sobs), self.rank_stepdown_tail(c_rank, ss, order32), maxs
+
+    def ranksum_stepdown(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
+        """Westfall-Young step-down maxT over the rank-sum statistic (spec S18, cc = 1) of the step ``res`` =
+        ranksum(genes, plan): (r_q, r_fwer, r_sd, maxs) -- r_q, r_fwer and maxs as ranksum_westfall_young returns
+        them, bit for bit, and r_sd int32 [T, G] with r_q <= r_sd <= r_fwer; (r_sd + 1) / (permutations + 1) is the
+        adjusted p.  The step-down is over all genes of the matrix: gene shards do not compose."""
+        return self._rank_stepdown("ranksum_stepdown", genes, plan, res, self.ranksum_var(plan, res["m"]), 1,
+                                   permutations, budget_bytes, self._ranksum_generator(plan, seed))
+
+    def vanelteren_stepdown(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
+        """ranksum_stepdown over the van Elteren statistic (spec S18, cc = 0) of the step ``res`` =
+        vanelteren(genes, plan), the rows shuffled within the strata."""
+        return self._rank_stepdown("vanelteren_stepdown", genes, plan, res, res["var"], 0, permutations, budget_bytes,
+                                   self._vanelteren_generator(plan, seed))
+
     # -- timing (bench.py) ------------------------------------------------------
     def set_timing(self, on):
         self._check(self.lib.scoary_set_timing(self.h, 1 if on else 0), "scoary_set_timing")

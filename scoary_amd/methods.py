@@ -1804,6 +1804,12 @@ def ScoaryArgumentParser(argv=None):
                    "results -- and, with --quantitative-strata, to the van Elteren results -- the single-step maxT "
                    "family-wise p over all genes of the table, from the same permutations that give Empirical_p "
                    "(single process; scoary_amd extension)")
+    a.add_argument("--quantitative-fwer-stepdown", dest="quantitative_fwer_stepdown", action="store_true",
+                   default=False,
+                   help="With --quantitative and --permute X (X >= 10): add the column Westfall_Young_stepdown_p to the "
+                   "rank-sum results -- and, with --quantitative-strata, to the van Elteren results -- the step-down "
+                   "maxT family-wise p: a gene is compared with the genes at its rank and behind, so the p is never "
+                   "above Westfall_Young_p (single process; scoary_amd extension)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1991,16 +1997,17 @@ def main(**kwargs):
         if getattr(args, "quantitative", None) and rank == 0:
             names, values = read_quantitative_file(args.quantitative, args.delimiter, strains)
             qfwer = bool(getattr(args, "quantitative_fwer", False))
+            qsd = bool(getattr(args, "quantitative_fwer_stepdown", False))
             with _stage("rank-sum test of the quantitative traits"):
                 StoreRanksumResults(Ranksum_results(genedic, names, values, permutations=args.permute, seed=seed,
-                                                    fwer=qfwer),
+                                                    fwer=qfwer, stepdown=qsd),
                                     genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
             if getattr(args, "quantitative_strata", None):
                 qstrata = strata_indices(args.quantitative_strata_map, strains)[0]
                 with _stage("van Elteren test of the quantitative traits"):
                     StoreVanElterenResults(VanElteren_results(genedic, names, values, qstrata,
                                                               permutations=args.permute, seed=seed,
-                                                              fwer=qfwer),
+                                                              fwer=qfwer, stepdown=qsd),
                                            genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
         log.info("Stage seconds: load (+tree) %.2f, association (+permutations) %.2f, pairwise stage and "
                  "output %.2f" % (t_loaded - start, t_stats - t_loaded, _time.time() - t_stats))
@@ -2116,14 +2123,17 @@ def read_quantitative_file(path, delimiter, strains):
 
 
 def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False,
-                    strata=None, fwer=False):
+                    strata=None, fwer=False, stepdown=False):
     """The rank-sum stage (spec S15) of the traits ``names`` with the values float64 [T, N] (nan = missing) over the
     isolates of ``genedic``: {name: dict(n, tie_groups, m, auc, p, testable [G]; r [G] with permutations >= 10;
-    r_fwer [G] with ``fwer``, spec S17)}, arrays in the gene table's order.  Raises ValueError where the command line
-    refuses --quantitative or --quantitative-fwer."""
+    r_fwer [G] with ``fwer``, spec S17; r_sd [G] with ``stepdown``, spec S18)}, arrays in the gene table's order.
+    Raises ValueError where the command line refuses --quantitative, --quantitative-fwer or
+    --quantitative-fwer-stepdown."""
     for text in _ranksum_refusals(no_pairwise, collapse, strata is not None):
         raise ValueError(text)
     for text in _rank_wy_refusals(fwer, True, permutations):
+        raise ValueError(text)
+    for text in _rank_sd_refusals(stepdown, True, permutations):
         raise ValueError(text)
     table = _as_table(genedic)
     eng = get_engine()
@@ -2138,8 +2148,11 @@ def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, n
     plan = eng.ranksum_plan(values)
     res = eng.ranksum(genes, plan)
     permutations = int(permutations)
-    r = r_fwer = None
-    if fwer:                     # one pass over the permutations gives both counts
+    r = r_fwer = r_sd = None
+    if stepdown:                 # the step-down run gives all three counts; the single-step one costs nothing extra
+        r, r_fwer, r_sd = (x.cpu().numpy() for x in eng.ranksum_stepdown(genes, plan, res, permutations, seed)[:3])
+        r_fwer = r_fwer if fwer else None
+    elif fwer:                   # one pass over the permutations gives both counts
         r, r_fwer = (x.cpu().numpy() for x in eng.ranksum_westfall_young(genes, plan, res, permutations, seed)[:2])
     elif permutations >= 10:
         r = eng.ranksum_permute(genes, plan, res["d"], permutations, seed).cpu().numpy()
@@ -2155,6 +2168,8 @@ def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, n
             out[name]["permutations"] = permutations
         if r_fwer is not None:
             out[name]["r_fwer"] = r_fwer[t]
+        if r_sd is not None:
+            out[name]["r_sd"] = r_sd[t]
         log.info("Rank-sum test of %s: %d isolates with a value, %d tie groups, %d genes tested"
                  % (name, n, out[name]["tie_groups"], int(testable.sum())))
     return out
@@ -2169,8 +2184,9 @@ def _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, tes
     for name, res in results.items():
         with_emp = "r" in res
         with_fwer = with_emp and "r_fwer" in res
+        with_sd = with_emp and "r_sd" in res
         columns = ROARY_HEAD + list(test_columns) + (["Empirical_p"] if with_emp else []) + \
-            (["Westfall_Young_p"] if with_fwer else [])
+            (["Westfall_Young_p"] if with_fwer else []) + (["Westfall_Young_stepdown_p"] if with_sd else [])
         idx = np.flatnonzero(res["testable"])
         fname = outdir + name + time + suffix
         with open(fname, "w") as out:
@@ -2192,6 +2208,8 @@ def _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, tes
                         cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
                     if with_fwer:
                         cells.append(_fmt((int(res["r_fwer"][g]) + 1.0) / (res["permutations"] + 1.0)))
+                    if with_sd:
+                        cells.append(_fmt((int(res["r_sd"][g]) + 1.0) / (res["permutations"] + 1.0)))
                     out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
         log.info("Storing %s results: %s" % (what, fname))
         files.append(fname)
@@ -2221,15 +2239,17 @@ VANELTEREN_TEXT = {
 
 
 def VanElteren_results(genedic, names, values, strata, permutations=0, seed=DEFAULT_SEED, no_pairwise=True,
-                       collapse=False, fwer=False):
+                       collapse=False, fwer=False, stepdown=False):
     """The van Elteren stage (spec S16) of the traits ``names`` with the values float64 [T, N] (nan = missing) and
     the stratum index of every isolate ``strata`` (N integers) over the isolates of ``genedic``: {name: dict(n,
     strata (those with a value), m, auc, p, var, testable [G]; r [G] with permutations >= 10; r_fwer [G] with
-    ``fwer``, spec S17)}, arrays in the gene table's order.  Raises ValueError where the command line refuses
-    --quantitative or --quantitative-fwer."""
+    ``fwer``, spec S17; r_sd [G] with ``stepdown``, spec S18)}, arrays in the gene table's order.  Raises ValueError
+    where the command line refuses --quantitative, --quantitative-fwer or --quantitative-fwer-stepdown."""
     for text in _ranksum_refusals(no_pairwise, collapse, False):
         raise ValueError(text)
     for text in _rank_wy_refusals(fwer, True, permutations):
+        raise ValueError(text)
+    for text in _rank_sd_refusals(stepdown, True, permutations):
         raise ValueError(text)
     table = _as_table(genedic)
     eng = get_engine()
@@ -2252,8 +2272,11 @@ def VanElteren_results(genedic, names, values, strata, permutations=0, seed=DEFA
     plan = eng.vanelteren_plan(values, strata)
     res = eng.vanelteren(genes, plan)
     permutations = int(permutations)
-    r = r_fwer = None
-    if fwer:
+    r = r_fwer = r_sd = None
+    if stepdown:
+        r, r_fwer, r_sd = (x.cpu().numpy() for x in eng.vanelteren_stepdown(genes, plan, res, permutations, seed)[:3])
+        r_fwer = r_fwer if fwer else None
+    elif fwer:
         r, r_fwer = (x.cpu().numpy() for x in eng.vanelteren_westfall_young(genes, plan, res, permutations, seed)[:2])
     elif permutations >= 10:
         r = eng.vanelteren_permute(genes, plan, res["d"], permutations, seed).cpu().numpy()
@@ -2267,6 +2290,8 @@ def VanElteren_results(genedic, names, values, strata, permutations=0, seed=DEFA
             out[name]["permutations"] = permutations
         if r_fwer is not None:
             out[name]["r_fwer"] = r_fwer[t]
+        if r_sd is not None:
+            out[name]["r_sd"] = r_sd[t]
         log.info("Van Elteren test of %s: %d isolates with a value in %d strata, %d genes tested"
                  % (name, out[name]["n"], out[name]["strata"], int(out[name]["testable"].sum())))
     return out
@@ -2300,6 +2325,31 @@ def _rank_wy_refusals(fwer, quantitative, permutations):
         yield RANK_WY_TEXT["quantitative"]
     if fwer and int(permutations or 0) < 10:
         yield RANK_WY_TEXT["permute"]
+
+
+# ---------------------------------------------------------------------------
+# --quantitative-fwer-stepdown: Westfall-Young step-down maxT over the rank statistics (spec S18): the column
+# Westfall_Young_stepdown_p, the last of the rank-sum file and -- with --quantitative-strata -- the van Elteren file,
+# behind Westfall_Young_p where --quantitative-fwer is given too.  Either flag works without the other.
+# ---------------------------------------------------------------------------
+RANK_SD_TEXT = {
+    "quantitative": "Cannot use --quantitative-fwer-stepdown without --quantitative. It is the step-down family-wise "
+                    "p of the rank tests of the measured traits",
+    "permute": "Cannot use --quantitative-fwer-stepdown without --permute X, X >= 10. The family-wise p is counted "
+               "over the permutations of the values",
+}
+# (rule, the run breaks it): in the order they are reported
+RANK_SD_FLAG_RULES = (
+    ("quantitative", lambda quantitative, permutations: not quantitative),
+    ("permute", lambda quantitative, permutations: int(permutations or 0) < 10),
+)
+
+
+def _rank_sd_refusals(stepdown, quantitative, permutations):
+    """The messages of the --quantitative-fwer-stepdown rules that a run breaks, in the order they are reported."""
+    for key, broken in RANK_SD_FLAG_RULES:
+        if stepdown and broken(quantitative, permutations):
+            yield RANK_SD_TEXT[key]
 
 
 class _LevelCounter(logging.Handler):
@@ -2417,6 +2467,9 @@ def _validate(args, cutoffs):
         if len(labels) > _abi.PERM_MAX_STRATA:
             sys.exit(VANELTEREN_TEXT["strata"] % (qstrata, len(labels), _abi.PERM_MAX_STRATA))
     for text in _rank_wy_refusals(getattr(args, "quantitative_fwer", False),
+                                  bool(getattr(args, "quantitative", None)), args.permute):
+        sys.exit(text)
+    for text in _rank_sd_refusals(getattr(args, "quantitative_fwer_stepdown", False),
                                   bool(getattr(args, "quantitative", None)), args.permute):
         sys.exit(text)
     level = getattr(args, "cmh_exact_level", None)

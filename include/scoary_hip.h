@@ -653,6 +653,29 @@ int scoary_rank_stepdown_gather(scoary_handle h, const uint32_t *d_tiled, const 
 int scoary_permute_rank_stepdown(scoary_handle h, void *d_scratch, const void *d_bfrag, int64_t cc, int64_t G,
                                  int64_t T, int64_t N, int64_t P, int64_t perm_base, int32_t *d_r_rank,
                                  int32_t *d_c_rank, double *d_maxs, int64_t maxs_stride, scoary_stream_t stream);
+/* ---- Quantitative traits: the Hodges-Lehmann shift of the rank-sum test and its confidence limits (spec S19 of
+ * DESIGN.md; additive, ABI 11) ----
+ * The K = m (n - m) differences fl(x_i - x_j), carrier i minus non-carrier j over the isolates with a value, are never
+ * written: their order statistics are selected exactly, by counting.
+ *   scoary_ranksum_shift     d_xs double [T][N]: a trait's valid values ascending in its first n places (no NaN, no
+ *                            -0.0, |x| <= 1e150; the places behind hold anything); d_pos int32 [T][N]: the isolate at
+ *                            each sorted place (an entry outside [0, N) is clamped into it); d_valid, d_m, d_var:
+ *                            scoary_ranksum's validity rows and m, scoary_ranksum_var's var; zq = the normal quantile
+ *                            of 0.5 + level / 2.  Writes, [T][G]: d_ca int64 = floor(0.5 K - zq sqrt(var)) (at most
+ *                            K / 2), d_shift = (d_(floor((K-1)/2)+1) + d_(floor(K/2)+1)) 0.5, d_lower = d_(ca) and
+ *                            d_upper = d_(K+1-ca) where ca >= 1, else -inf and +inf.  An untestable gene (var = 0)
+ *                            has (0, -inf, +inf, ca 0); a gene whose bits at d_pos do not count to its d_m -- a plan
+ *                            of other values or genes -- has NaN in all three and ca 0.  A zero is +0.0.
+ *   scoary_rank_shift_waves  the wavefronts of a block at N isolates (a trait's d_xs and every wavefront's lists
+ *                            share the LDS): 16 while they fit, then 8, 4, 2, 1; 0 for an N the stage does not take
+ * No block waits for another.  Asynchronous on `stream`, nothing is allocated.  SCOARY_ERR_ARG: null pointer, size
+ * < 1, zq not positive and finite; SCOARY_ERR_SIZE, with nothing written: N > scoary_ranksum_max_isolates(),
+ * T > 65535, G >= 2^31. */
+int64_t scoary_rank_shift_waves(int64_t N);
+int scoary_ranksum_shift(scoary_handle h, const uint32_t *d_tiled, const double *d_xs, const int32_t *d_pos,
+                         const uint32_t *d_valid, const int32_t *d_m, const double *d_var, double zq, int64_t G,
+                         int64_t T, int64_t N, double *d_shift, double *d_lower, double *d_upper, int64_t *d_ca,
+                         scoary_stream_t stream);
 int64_t scoary_permute_lists_scratch_bytes(int64_t G, int64_t T, int64_t N, int64_t P);
 int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_t *d_lidx,
                          int64_t entries, const int32_t *d_lstart, const int32_t *d_lngroups,

@@ -99,6 +99,8 @@ SIGNATURES = {
     "scoary_rank_stepdown_scratch_bytes": (_i64, [_vp] + [_i64] * 4),
     "scoary_rank_stepdown_gather": (_i32, [_vp] * 6 + [_i64] * 3 + [_vp, _vp]),
     "scoary_permute_rank_stepdown": (_i32, [_vp] * 3 + [_i64] * 6 + [_vp] * 3 + [_i64, _vp]),
+    "scoary_rank_shift_waves": (_i64, [_i64]),
+    "scoary_ranksum_shift": (_i32, [_vp] * 7 + [ctypes.c_double] + [_i64] * 3 + [_vp] * 5),
     "scoary_permute_lists_scratch_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "scoary_permute_lists": (_i32, [_vp, _vp, _vp, _i64] + [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp,
                                                                        _i32, _vp]),

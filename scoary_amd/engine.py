@@ -145,11 +145,13 @@ class RankPlan:
     [T, Wp]) and ``tiesum`` int64 [T] on the device; ``n``, ``tiesum_host`` and ``tie_groups`` (groups of two or
     more equal values) per trait and ``rc_host`` / ``valid_host`` (bool [T, N]) on the host."""
 
-    def __init__(self, rc, valid, tiesum, rc_host, valid_host, n, tiesum_host, tie_groups):
+    def __init__(self, rc, valid, tiesum, rc_host, valid_host, n, tiesum_host, tie_groups, values_host=None):
         self.rc, self.valid, self.tiesum = rc, valid, tiesum
         self.rc_host, self.valid_host = rc_host, valid_host
         self.n, self.tiesum_host, self.tie_groups = n, tiesum_host, tie_groups
         self.T, self.N = (int(x) for x in rc_host.shape)
+        self.values_host = values_host      # the values themselves, for the sorted rows of spec S19
+        self.shift_plan = None              # ranksum_shift's RankShiftPlan, made when it is first asked for
 
 
 def rank_rows(values):
@@ -173,6 +175,43 @@ def rank_rows(values):
         tiesum[t] = int(np.sum(tau ** 3 - tau))
         groups[t] = int(np.sum(tau > 1))
     return rc, valid, n, tiesum, groups
+
+
+SHIFT_MAX_ABS = 1e150          # spec S19's magnitude rule: no difference of two values overflows
+
+
+class RankShiftPlan:
+    """The sorted values of a rank-sum step for the Hodges-Lehmann shift (spec S19;
+    AssociationEngine.ranksum_shift_plan): ``xs`` float64 [T, N] = a trait's valid values ascending in its first n
+    places (zeros behind) and ``pos`` int32 [T, N] = the isolate at each sorted place, on the device; ``xs_host`` /
+    ``pos_host`` the same on the host."""
+
+    def __init__(self, xs, pos, xs_host, pos_host):
+        self.xs, self.pos, self.xs_host, self.pos_host = xs, pos, xs_host, pos_host
+        self.T, self.N = (int(x) for x in xs_host.shape)
+
+
+def shift_rows(values):
+    """Host sort of spec S19: float64 [T, N] with NaN for missing -> (xs float64 [T, N], pos int32 [T, N]); a stable
+    sort, -0.0 stored as +0.0.  Raises ValueError for a value above SHIFT_MAX_ABS in magnitude."""
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    if values.ndim != 2:
+        raise ValueError("ranksum_shift_plan: values must be a [T, N] array")
+    valid = ~np.isnan(values)
+    if np.any(np.abs(values[valid]) > SHIFT_MAX_ABS):
+        raise ValueError(shift_magnitude_text())
+    xs, pos = np.zeros(values.shape, dtype=np.float64), np.zeros(values.shape, dtype=np.int32)
+    for t in range(values.shape[0]):
+        iso = np.flatnonzero(valid[t])
+        x = values[t, iso] + 0.0
+        order = np.argsort(x, kind="stable")
+        xs[t, :iso.size], pos[t, :iso.size] = x[order], iso[order]
+    return xs, pos
+
+
+def shift_magnitude_text():
+    return ("the Hodges-Lehmann shift takes values up to 1e150 in magnitude: beyond it a difference of two values "
+            "could overflow")
 
 
 class VanElterenPlan:
@@ -1692,7 +1731,8 @@ class AssociationEngine:
                              % (rc.shape[1], self.ranksum_max_isolates()))
         return RankPlan(torch.from_numpy(rc).to(self.device),
                         self.vecrows(pack_bits_rows(valid.astype(np.uint8)), rc.shape[1]),
-                        torch.from_numpy(tiesum).to(self.device), rc, valid, n, tiesum, groups)
+                        torch.from_numpy(tiesum).to(self.device), rc, valid, n, tiesum, groups,
+                        values_host=np.array(values, dtype=np.float64))
 
     def _ranksum_fits(self, what, genes, plan):
         if genes is not None and genes.N != plan.N:
@@ -1817,6 +1857,45 @@ class AssociationEngine:
         over ranksum_permute's batches."""
         return self._rank_westfall_young("ranksum_westfall_young", genes, plan, res, self.ranksum_var(plan, res["m"]),
                                          1, permutations, budget_bytes, self._ranksum_generator(plan, seed))
+
+    # -- quantitative traits: the Hodges-Lehmann shift and its limits (spec S19) --------
+    def ranksum_shift_plan(self, values):
+        """values: float64 [T, N], NaN = missing (ranksum_plan's).  The sorted values of spec S19 as a RankShiftPlan;
+        ValueError for a value above 1e150 in magnitude."""
+        torch = _torch()
+        xs, pos = shift_rows(values)
+        if xs.shape[1] > self.ranksum_max_isolates():
+            raise ValueError("ranksum_shift_plan: %d isolates, the rank-sum kernels take at most %d"
+                             % (xs.shape[1], self.ranksum_max_isolates()))
+        return RankShiftPlan(torch.from_numpy(xs).to(self.device), torch.from_numpy(pos).to(self.device), xs, pos)
+
+    def ranksum_shift(self, genes, plan, res, level=0.95):
+        """The Hodges-Lehmann shift of every (trait, gene) of the step ``res`` = ranksum(genes, plan) and its
+        confidence limits at ``level`` (spec S19): dict of device tensors shift, lower, upper float64 [T, G] and ca
+        int64 [T, G].  The plan's values are sorted once (ranksum_shift_plan) and kept with the plan; ValueError for
+        a value above 1e150 in magnitude.  An untestable gene has (0, -inf, +inf, ca 0), and a gene with ca < 1 has
+        the limits -inf and +inf."""
+        import statistics
+        torch = _torch()
+        self._ranksum_fits("ranksum_shift", genes, plan)
+        if not 0.0 < float(level) < 1.0:
+            raise ValueError("ranksum_shift: the confidence level must be inside (0, 1)")
+        if plan.shift_plan is None:
+            plan.shift_plan = self.ranksum_shift_plan(plan.values_host)
+        shift_plan = plan.shift_plan
+        T, G = plan.T, genes.G
+        m = res["m"]
+        if tuple(m.shape) != (T, G) or m.dtype != torch.int32 or not m.is_contiguous():
+            raise ValueError("ranksum_shift: res is the observed result of these genes and this plan")
+        var = self.ranksum_var(plan, m)
+        zq = statistics.NormalDist().inv_cdf(0.5 + float(level) / 2.0)
+        out = {k: self._empty((T, G), torch.float64) for k in ("shift", "lower", "upper")}
+        out["ca"] = self._empty((T, G), torch.int64)
+        self._check(self.lib.scoary_ranksum_shift(
+            self.h, self._ptr(genes.tiled), self._ptr(shift_plan.xs), self._ptr(shift_plan.pos),
+            self._ptr(plan.valid), self._ptr(m), self._ptr(var), zq, G, T, plan.N,
+            *(self._ptr(out[k]) for k in ("shift", "lower", "upper", "ca")), self._stream()), "scoary_ranksum_shift")
+        return out
 
     # -- quantitative traits over strata: the van Elteren test (spec S16) --------------
     def vanelteren_plan(self, values, strata):

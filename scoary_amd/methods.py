@@ -1810,6 +1810,15 @@ def ScoaryArgumentParser(argv=None):
                    "rank-sum results -- and, with --quantitative-strata, to the van Elteren results -- the step-down "
                    "maxT family-wise p: a gene is compared with the genes at its rank and behind, so the p is never "
                    "above Westfall_Young_p (single process; scoary_amd extension)")
+    a.add_argument("--quantitative-shift", dest="quantitative_shift", action="store_true", default=False,
+                   help="With --quantitative: add the columns Rank_sum_shift, Rank_sum_shift_lower and "
+                   "Rank_sum_shift_upper to the rank-sum results -- the Hodges-Lehmann estimate of the shift of the "
+                   "trait with the gene (the median of all differences isolate with the gene minus isolate without, "
+                   "in the trait's units) and its distribution-free confidence limits; R's wilcox.test(conf.int = "
+                   "TRUE); needs no permutations (single process; scoary_amd extension)")
+    a.add_argument("--quantitative-shift-level", dest="quantitative_shift_level", type=float, default=None,
+                   metavar="FLOAT",
+                   help="With --quantitative-shift: the confidence level of the limits, inside (0, 1) (default 0.95)")
     a.add_argument("--no_pairwise", action="store_true", default=False,
                    help="Population-structure-naive analysis only (Fisher's test, odds ratios)")
     a.add_argument("--collapse", action="store_true", default=False,
@@ -1998,9 +2007,13 @@ def main(**kwargs):
             names, values = read_quantitative_file(args.quantitative, args.delimiter, strains)
             qfwer = bool(getattr(args, "quantitative_fwer", False))
             qsd = bool(getattr(args, "quantitative_fwer_stepdown", False))
+            qshift = bool(getattr(args, "quantitative_shift", False))
+            for text in _rank_shift_refusals(qshift, True, None, values):
+                sys.exit(text)
             with _stage("rank-sum test of the quantitative traits"):
                 StoreRanksumResults(Ranksum_results(genedic, names, values, permutations=args.permute, seed=seed,
-                                                    fwer=qfwer, stepdown=qsd),
+                                                    fwer=qfwer, stepdown=qsd, shift=qshift,
+                                                    shift_level=_shift_level(args)),
                                     genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
             if getattr(args, "quantitative_strata", None):
                 qstrata = strata_indices(args.quantitative_strata_map, strains)[0]
@@ -2123,17 +2136,20 @@ def read_quantitative_file(path, delimiter, strains):
 
 
 def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False,
-                    strata=None, fwer=False, stepdown=False):
+                    strata=None, fwer=False, stepdown=False, shift=False, shift_level=0.95):
     """The rank-sum stage (spec S15) of the traits ``names`` with the values float64 [T, N] (nan = missing) over the
     isolates of ``genedic``: {name: dict(n, tie_groups, m, auc, p, testable [G]; r [G] with permutations >= 10;
-    r_fwer [G] with ``fwer``, spec S17; r_sd [G] with ``stepdown``, spec S18)}, arrays in the gene table's order.
-    Raises ValueError where the command line refuses --quantitative, --quantitative-fwer or
-    --quantitative-fwer-stepdown."""
+    r_fwer [G] with ``fwer``, spec S17; r_sd [G] with ``stepdown``, spec S18; shift, shift_lower, shift_upper [G] with
+    ``shift``, the Hodges-Lehmann shift and its limits at ``shift_level``, spec S19)}, arrays in the gene table's
+    order.  Raises ValueError where the command line refuses --quantitative, --quantitative-fwer,
+    --quantitative-fwer-stepdown or --quantitative-shift."""
     for text in _ranksum_refusals(no_pairwise, collapse, strata is not None):
         raise ValueError(text)
     for text in _rank_wy_refusals(fwer, True, permutations):
         raise ValueError(text)
     for text in _rank_sd_refusals(stepdown, True, permutations):
+        raise ValueError(text)
+    for text in _rank_shift_refusals(shift, True, shift_level if shift else None, values):
         raise ValueError(text)
     table = _as_table(genedic)
     eng = get_engine()
@@ -2156,6 +2172,9 @@ def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, n
         r, r_fwer = (x.cpu().numpy() for x in eng.ranksum_westfall_young(genes, plan, res, permutations, seed)[:2])
     elif permutations >= 10:
         r = eng.ranksum_permute(genes, plan, res["d"], permutations, seed).cpu().numpy()
+    hl = None
+    if shift:
+        hl = {k: v.cpu().numpy() for k, v in eng.ranksum_shift(genes, plan, res, level=shift_level).items()}
     m, auc, p = (res[k].cpu().numpy() for k in ("m", "auc", "p"))
     out = {}
     for t, name in enumerate(names):
@@ -2170,6 +2189,8 @@ def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, n
             out[name]["r_fwer"] = r_fwer[t]
         if r_sd is not None:
             out[name]["r_sd"] = r_sd[t]
+        if hl is not None:
+            out[name].update(shift=hl["shift"][t], shift_lower=hl["lower"][t], shift_upper=hl["upper"][t])
         log.info("Rank-sum test of %s: %d isolates with a value, %d tie groups, %d genes tested"
                  % (name, n, out[name]["tie_groups"], int(testable.sum())))
     return out
@@ -2185,7 +2206,10 @@ def _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, tes
         with_emp = "r" in res
         with_fwer = with_emp and "r_fwer" in res
         with_sd = with_emp and "r_sd" in res
-        columns = ROARY_HEAD + list(test_columns) + (["Empirical_p"] if with_emp else []) + \
+        with_shift = all(key in res for _column, key in RANK_SHIFT_COLUMNS)
+        columns = ROARY_HEAD + list(test_columns) + \
+            ([column for column, _key in RANK_SHIFT_COLUMNS] if with_shift else []) + \
+            (["Empirical_p"] if with_emp else []) + \
             (["Westfall_Young_p"] if with_fwer else []) + (["Westfall_Young_stepdown_p"] if with_sd else [])
         idx = np.flatnonzero(res["testable"])
         fname = outdir + name + time + suffix
@@ -2204,6 +2228,8 @@ def _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, tes
                     m = int(res["m"][g])
                     cells += [_fmt(m), _fmt(res["n"] - m), _fmt(res["auc"][g]), _fmt(res["p"][g]), _fmt(bonf[k]),
                               _fmt(bh[k])]
+                    if with_shift:           # an infinite limit is _fmt's "inf" / "-inf", as in the odds ratio's limits
+                        cells += [_fmt(res[key][g]) for _column, key in RANK_SHIFT_COLUMNS]
                     if with_emp:
                         cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
                     if with_fwer:
@@ -2352,6 +2378,52 @@ def _rank_sd_refusals(stepdown, quantitative, permutations):
             yield RANK_SD_TEXT[key]
 
 
+# ---------------------------------------------------------------------------
+# --quantitative-shift: the Hodges-Lehmann shift of the rank-sum test and its confidence limits (spec S19): three
+# columns of the rank-sum file, behind Benjamini_H_p and in front of Empirical_p, so that the Westfall-Young columns
+# stay last.  No permutations; nothing of the van Elteren file changes.
+# ---------------------------------------------------------------------------
+RANK_SHIFT_LEVEL = 0.95
+# (column, key of Ranksum_results' dict), in file order
+RANK_SHIFT_COLUMNS = (("Rank_sum_shift", "shift"), ("Rank_sum_shift_lower", "shift_lower"),
+                      ("Rank_sum_shift_upper", "shift_upper"))
+RANK_SHIFT_TEXT = {
+    "quantitative": "Cannot use --quantitative-shift without --quantitative. It is the shift of the measured traits "
+                    "with a gene, next to the rank-sum test",
+    "level_flag": "Cannot use --quantitative-shift-level without --quantitative-shift. It is the confidence level of "
+                  "the limits of the Hodges-Lehmann shift",
+    "level": "The confidence level of --quantitative-shift-level must be between 0.0 and 1.0 (both excluded)",
+    "magnitude": "Cannot use --quantitative-shift with a value above 1e150 in magnitude: the difference of two such "
+                 "values could overflow",
+}
+# (rule, the run breaks it): in the order they are reported.  ``level`` is None where none was given.
+RANK_SHIFT_FLAG_RULES = (
+    ("quantitative", lambda shift, quantitative, level, values: shift and not quantitative),
+    ("level_flag", lambda shift, quantitative, level, values: level is not None and not shift),
+    ("level", lambda shift, quantitative, level, values: level is not None and not 0.0 < float(level) < 1.0),
+    ("magnitude", lambda shift, quantitative, level, values: shift and values is not None and _beyond_shift(values)),
+)
+
+
+def _beyond_shift(values):
+    from .engine import SHIFT_MAX_ABS
+    values = np.asarray(values, dtype=np.float64)
+    return bool(np.any(np.abs(values[~np.isnan(values)]) > SHIFT_MAX_ABS))
+
+
+def _rank_shift_refusals(shift, quantitative, level, values=None):
+    """The messages of the --quantitative-shift rules that a run breaks, in the order they are reported, worded alike
+    on the command line and in Ranksum_results (shift=True).  ``values``: the measured values, once they are read."""
+    for key, broken in RANK_SHIFT_FLAG_RULES:
+        if broken(shift, quantitative, level, values):
+            yield RANK_SHIFT_TEXT[key]
+
+
+def _shift_level(args):
+    level = getattr(args, "quantitative_shift_level", None)
+    return RANK_SHIFT_LEVEL if level is None else level
+
+
 class _LevelCounter(logging.Handler):
     def __init__(self):
         super().__init__(logging.WARNING)
@@ -2471,6 +2543,10 @@ def _validate(args, cutoffs):
         sys.exit(text)
     for text in _rank_sd_refusals(getattr(args, "quantitative_fwer_stepdown", False),
                                   bool(getattr(args, "quantitative", None)), args.permute):
+        sys.exit(text)
+    for text in _rank_shift_refusals(getattr(args, "quantitative_shift", False),
+                                     bool(getattr(args, "quantitative", None)),
+                                     getattr(args, "quantitative_shift_level", None)):
         sys.exit(text)
     level = getattr(args, "cmh_exact_level", None)
     if level is not None and not getattr(args, "cmh_exact_odds", False):

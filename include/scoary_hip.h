@@ -688,7 +688,7 @@ int scoary_permute_lists(scoary_handle h, const uint32_t *d_tiles, const uint32_
 /* ---- matrix-core kernel for the long-list slots (N <= scoary_mfma_max_isolates() = 2048) ----
  * The list count is a 0/1 GEMM whose cost does not depend on the list length, so the slots with
  * the longest lists -- slots [0, k_split), the slot order is by descending length -- can take
- * v_mfma_scale_f32_32x32x64_f8f6f4 (E2M1 operands, exact in fp32) instead of the list walk; d_r
+ * v_mfma_f32_16x16x128_f8f6f4 (E2M1 operands, exact in fp32) instead of the list walk; d_r
  * stays bit-identical.
  *   scoary_mfma_panels_build : once per data set, after scoary_lists_plan: d_panels =
  *       scoary_mfma_panels_bytes(G, N) bytes, the minority rows of all list slots as A fragments

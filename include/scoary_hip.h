@@ -584,7 +584,7 @@ int scoary_permute_ranksum(scoary_handle h, const uint32_t *d_tiled, const void 
  * Every index read from d_strata, d_members and the segment table is clamped: a bad plan gives wrong numbers, never
  * a wild access.  Asynchronous on `stream`, nothing is allocated.  SCOARY_ERR_ARG: null pointer, size < 1 or negative
  * base; SCOARY_ERR_SIZE, with nothing written: S > scoary_perm_max_strata(), N > scoary_ranksum_max_isolates(),
- * T > 65535, G or P >= 2^31. */
+ * T > 65535, G or P >= 2^31, perm_base + P or trait_base + T > 2^32 (the last counter words are those sums - 1). */
 int scoary_vanelteren(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_score, const uint32_t *d_valid,
                       const uint16_t *d_strata, const int32_t *d_members, const int32_t *d_wn, const double *d_c,
                       int64_t G, int64_t T, int64_t N, int64_t S, int32_t *d_d, int32_t *d_m, double *d_var,

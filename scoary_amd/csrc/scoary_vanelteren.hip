@@ -257,7 +257,8 @@ int ve_generate(scoary_handle h, const char* what, const int16_t* d_l, const uin
   if (int rc = ve_check(h, what, d_l && d_valid && d_strata && (d_rows || d_bfrag) && P >= 1 && perm_base >= 0 &&
                                      trait_base >= 0, T, N, S))
     return rc;
-  if (P > 0x7fffffffLL - 64 || perm_base + P > 0xffffffffLL || trait_base + T > 0xffffffffLL)
+  // (the last counter words are perm_base + P - 1 and trait_base + T - 1: both sums may be 2^32 itself)
+  if (P > 0x7fffffffLL - 64 || perm_base + P > 0x100000000LL || trait_base + T > 0x100000000LL)
     return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": P >= 2^31 or a counter word past 2^32");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);

@@ -8,7 +8,10 @@ n - 1; genes next to their complements; N = 16 320 with m = 8 160 (K = 66 585 60
 untestable genes and traits.
 
 ca: the device takes sqrt and floor itself.  No cell of these cases has the spec's unfloored value within 1e-9
-(relative, of at least 1) of an integer -- asserted for every cell -- so ca is held exactly, and the limits with it."""
+(relative, of at least 1) of an integer -- asserted for every cell -- so ca is held exactly, and the limits with it.
+
+test_gpu_rank_shift_limits.py goes on where these stop: several genes per wavefront, values from subnormals to 1e150,
+traits of no, one and two values."""
 import ctypes
 import math
 

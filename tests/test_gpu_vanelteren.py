@@ -1,7 +1,8 @@
 """The van Elteren kernels (spec S16) on the GPU, through the raw entry points and the engine, against the plain
 Python restatement vanelteren_spec.py: the stratified generator's rows and B operand bit for bit, the stratum bits
 up to 1024 strata, the size limit N = 16 320, one stratum against the S15 kernels, the observed statistic, and the
-exceedance counts over batches."""
+exceedance counts over batches.  test_gpu_vanelteren_limits.py holds the same kernels at their size edges, at every
+width of the stratum field, at the ends of the counter words, over a full segment table and in the deep tail of p."""
 import ctypes
 import math
 

@@ -21,8 +21,9 @@
 //   k_permute_mfma                      v_mfma_f32_16x16x128_f8f6f4 on those pieces (the chip holds a higher
 //                                       clock on this shape than on 32x32x64: profiles/mfma_16x16.txt); gene
 //                                       operand stationary in registers (128 per lane), two wavefronts
-//                                       per SIMD half a stage apart, B streamed through a four-slot LDS
-//                                       ring by LDS-DMA, region test on the accumulators, 16-bit counts
+//                                       per SIMD half a stage apart in the data and a quarter in time, B
+//                                       streamed through a four-slot LDS ring by LDS-DMA, region test on the
+//                                       accumulators, 16-bit counts
 //                                       into the list path's `partial`
 #include "scoary_common.hpp"
 
@@ -147,42 +148,64 @@ __device__ __forceinline__ int xcd_item(int orig, int n) {
 // column tiles of a row share one per-lane counter that lives across the stages of a segment, the 16 lanes of a
 // row meet once per segment, at its end.
 //
-// Stagger.  Wavefronts 4..7, the SIMD partners of 0..3, run half a stage behind them: in tick n (one barrier
-// per tick, nh + 1 ticks for nh half stages) the early wavefronts read half n, the late ones half n - 1, so
-// one partner's region test, LDS-DMA issue and first fragment reads fall beside the other's MFMAs.  The region
-// test of a stage waits for the barrier that follows the stage (the partner is in mid-stage behind it, and
-// would only wait at that barrier for a test in front of it); the range's last one follows the loop.  Where the
-// tested stage was its trait's last, the same place ends the segment (ragged column count, lane reduction,
-// stores, counters to zero) and takes the next trait's centres and half widths out of the LDS in front of the
-// stage's first MFMA, which takes the centres as C.  All of it is wave-local and sits between two barriers every wavefront
-// executes anyway, so the early and the late wavefronts still count the same ticks.
+// Stagger.  Wavefronts 4..7, the SIMD partners of 0..3, run half a stage behind them in the data AND half a half
+// stage apart in time.  A block executes nh + 1 barriers for nh half stages; INTERVAL n is what a wavefront does
+// between barrier n and barrier n + 1:
+//   early (0..3)  half n whole, fragments 0..31: the barrier stands in front of a half;
+//   late  (4..7)  fragments 16..31 of half n - 1, the half boundary WITHOUT a barrier, fragments 0..15 of half n:
+//                 the barrier stands in the middle of a half, in front of fragment 16.  Interval 0 holds only
+//                 fragments 0..15 of half 0 -- that sets the offset -- and interval nh is the tail, fragments
+//                 16..31 of half nh - 1 behind the last barrier, with nothing of the early wavefronts beside it.
+// So at a barrier the early wavefronts are between two halves (first fragment reads; every other time the region
+// test) while their partners are in mid-half with fragments in the register ring and go on with MFMAs at once; and
+// the late wavefronts' own boundary lies beside the early partners' fragments 16..: their fragment ring runs across
+// it (fragments 0..2 of half n are read in front of the last MFMAs of half n - 1: half n has been whole since
+// barrier n), and their region test, end of segment, threshold traffic and LDS-DMA issue stand there.  What the
+// partners still share is the barrier's own skew.  The region test of a stage stands at the boundary behind it, in
+// front of the next stage's first MFMA (which takes the centres as C); the range's last one follows the loop.
+// Where the tested stage was its trait's last, the same place ends the segment (ragged column count, lane
+// reduction, stores, counters to zero) and takes the next trait's centres and half widths out of the LDS.  All of
+// it is wave-local.
+// The two groups are two instances of one loop body (`run`), chosen by the wave-uniform `late`; they differ in
+// where the barrier and the LDS-DMA issue stand.
 // Measured and not built in, each within the kernel's run-to-run spread (profiles/r11_mfma_two_wave.txt):
-// s_setprio 1 for the late wavefronts; a fifth ring slot (issue three ticks ahead, 160 KB); with it, reading
-// the next half's first fragments in front of the barrier.
+// s_setprio 1 for the late wavefronts; a fifth ring slot (issue three intervals ahead, 160 KB); with it, reading
+// the next half's first fragments in front of a barrier both partners took between halves.  Measured against this
+// schedule and slower (profiles/mfma_time_stagger.txt): the four pieces of an interval issued one by one among its
+// MFMAs instead of together, with the barriers where they were and with this stagger (0.07 and 0.08 ms off the cfg3
+// step in the session in which this schedule took 0.10).
 //
 // Ring.  B moves HBM/L2 -> LDS by LDS-DMA in half stages of 32 KB (8 K-steps), half n into slot
-// n % kRingSlots, every wavefront 4 KB of it.  Invariant, for every tick n:
-//   * before the barrier of tick n a wavefront has issued halves 0 .. n + kAhead - 1 and waits with the
-//     counted vmcnt(kAhead - 1 halves) until its pieces of half n have landed; behind the barrier half n is
-//     whole (and half n - 1 has been since the barrier before);
-//   * behind that barrier it issues half n + kAhead into slot (n + kAhead) % kRingSlots = (n - 2) % kRingSlots:
-//     half n - 2 was last read in tick n - 1, by the late wavefronts, and every wavefront has passed a barrier
-//     since; the slots of the halves n - 1 and n, which are being read, are other slots (kRingSlots >= 3).
-// Halves past the end re-read the last one into such a slot, which nobody reads any more, so the counts stay
-// the same to the end; ns = 1 and the late wavefronts' last half (tick nh, no early work beside it) need no
-// case of their own.
+// n % kRingSlots, every wavefront 4 KB of it in kDmaPerHalf pieces.  Halves 0 and 1 are issued in front of the
+// loop.  Invariant, for every n:
+//   * in front of barrier n a wavefront has issued every piece of the halves 0 .. n + kAhead - 1 and waits with
+//     the counted vmcnt(kAhead - 1 halves) until its pieces of half n have landed: barrier n makes half n whole.
+//     Every read of half n lies behind barrier n (early: interval n; late: intervals n and n + 1);
+//   * the kDmaPerHalf pieces of half n + kAhead = n + 2 are issued in interval n, together: by an early wavefront
+//     right behind barrier n, by a late one at its boundary into half n (in interval 0: right behind barrier 0, which
+//     is that boundary) -- in both cases in front of the interval's counted wait, which so means what the line above
+//     says;
+//   * they go into slot (n + 2) % kRingSlots = (n - 2) % kRingSlots.  Half n - 2 is read by the early wavefronts in
+//     interval n - 2 and by the late ones in n - 2 and n - 1, the last read retired by the MFMA that uses it: all of
+//     it in front of barrier n.  In interval n the halves n - 1 and n are read and n + 1, n + 2 are in flight: four
+//     distinct slots, kRingSlots = 4, kAhead = 2.
+// Halves past the end re-read the last one into such a slot, which nobody reads any more (the late wavefronts'
+// look-ahead reads of "half nh" behind barrier nh find that copy and use nothing of it), so the counts stay the same
+// to the end; ns = 1 needs no case of its own.  (tests/test_mfma_ring_schedule.py walks these statements.)
 // Stores and the threshold DMA among the ring's LDS-DMAs.  A trait switch inside the loop stores the ended
-// segment's counts, and the stage before it fetches the next trait's thresholds, while halves are in flight.
-// Vector memory operations retire in the order they were issued and the counted wait only bounds how many are
-// outstanding, so an operation YOUNGER than the DMAs a wait is there for makes it retire more of the older DMAs,
-// never fewer: a store or a fetch can make a tick's wait longer, not early (a wait that leaves the one or two it
-// knows of outstanding as well measured the same and is not built in).  The fetch is one more LDS-DMA, issued
-// in tick n behind that tick's half and read in tick n + 2 behind that tick's wait, which leaves at most the four
-// DMAs of tick n + 1 outstanding: it has landed, with no wait of its own and without draining the ring (as a
-// register load it would: the compiler waits vmcnt(0) for one, and measured so a switch cost four to seven stages).
-// It lands in 256 bytes only its own wavefront reads, so no barrier is part of that.  No read of a ring slot
-// moves: every one stays behind the barrier that follows the wait retiring its half.  There is still no ordinary
-// global load inside the loop.
+// segment's counts, and the boundary one stage before it fetches the next trait's thresholds, while halves are in
+// flight.  Vector memory operations retire in the order they were issued and the counted wait only bounds how many
+// are outstanding, so an operation YOUNGER than the DMAs a wait is there for makes it retire more of the older DMAs,
+// never fewer: a store or a fetch can make a wait longer, not early.  The fetch is one more LDS-DMA, issued at the
+// boundary into a trait's last stage.  A late wavefront issues it IN FRONT of that boundary's half pieces, so the
+// next barrier's counted wait, which leaves only those four outstanding, retires it.  An early wavefront issues it
+// behind the pieces of its interval n; the wait in front of barrier n + 1 may leave it outstanding, the one in front
+// of barrier n + 2 has the four pieces of interval n + 1 behind it and retires it.  take_thresholds stands one stage
+// later, at the boundary into the next stage: for an early wavefront behind barrier n + 2, for a late one behind
+// the two barriers it takes in between.  Either way the fetch has landed, with no wait of its own and without
+// draining the ring (as a register load it would: the compiler waits vmcnt(0) for one, and measured so a switch
+// cost four to seven stages).  It lands in 256 bytes only its own wavefront reads, so no barrier is part of that,
+// and the next fetch is issued behind the take.  There is still no ordinary global load inside the loop.
 __global__ __launch_bounds__(kBlockWaves * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_permute_mfma(const v4i* __restrict__ panels, const unsigned char* __restrict__ bfrag,
                     const uint2* __restrict__ lcrit, int G, int64_t P, int S, int64_t Q, int L, int nblk_genes,
@@ -265,12 +288,9 @@ void k_permute_mfma(const v4i* __restrict__ panels, const unsigned char* __restr
   };
 #pragma unroll
   for (int n = 0; n < kAhead; ++n) issue_half(n);
-  int tick = 0;
-  auto next_tick = [&]() {
+  auto barrier = [&]() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kAhead - 1) * kDmaPerHalf) : "memory");
     __builtin_amdgcn_s_barrier();
-    issue_half(tick + kAhead);
-    ++tick;
   };
 
   uint32_t ex[8];
@@ -315,65 +335,87 @@ void k_permute_mfma(const v4i* __restrict__ panels, const unsigned char* __restr
     if (rl < 8 && row < mine) out[q4 + row] = (uint16_t)count;
     jt = 0;
   };
-  if (late) next_tick();                            // tick 0: the early wavefronts' first half
-  int rslot = 0;                                    // ring slot of the half this wavefront reads next
-  for (int st = 0; st < ns; ++st) {
+  // B fragment (K-step k, column tile j) holds in lane l the piece of column 16 j + (l & 15), isolates 128 k +
+  // 32 (l >> 4) .. + 31, which the stage keeps in its K-step 2 k + (l >> 5), column tile j >> 1, lane
+  // 16 (j & 1) + (l & 15) + 32 ((l >> 4) & 1): every 16 lanes read 256 contiguous bytes.
+  const unsigned char* lbase = lds + ((quad >> 1) * 128 + (quad & 1) * 32 + l15) * 16;
+  // A half stage is 32 B fragments, f = 4 (K-step) + column tile, two MFMAs each (one per row tile).  Fragment
+  // f + kBLead is read in front of the MFMAs of fragment f through a register ring of kBLead + 1: one
+  // ds_read_b128 per pair of MFMAs, three pairs ahead of its use.  The scheduling barriers keep the reads where
+  // they are written (left alone, the compiler reads each fragment right before its MFMAs).  Measured
+  // (profiles/mfma_16x16.txt section 3): whole K-steps read two K-steps ahead, as the 32x32x64 body did, cost
+  // 0.13 ms of the cfg3 step against this, leads of 2, 4, 5 and 6 fragments 0.01-0.03 ms.
+  constexpr int kBLead = 3, kFrags = 4 * (kKSteps128 / 2);
+  // The loop of one wavefront group (see "Stagger" above): the early wavefronts take their barrier in front of a
+  // half, the late ones behind its fragment kFrags / 2 - 1, and only that differs between the two instances.
+  auto run = [&](auto group) {
+    constexpr bool kLate = decltype(group)::value;
+    v4i bq[kBLead + 1];
+    auto read_b = [&](const unsigned char* buf, int f) {
+      bq[f % (kBLead + 1)] =
+          *reinterpret_cast<const v4i*>(buf + (f >> 2) * kKStepBytes + ((f >> 1) & 1) * kFragBytes + (f & 1) * 256);
+    };
+    int rslot = 0;                                  // ring slot of the half this wavefront is reading
+    int nx = kAhead;                                // the half it issues next
+    const unsigned char* bbuf = lbase;
+    if (kLate) {                                    // interval 0: fragments 0 .. 15 of half 0
+      barrier();
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      next_tick();
-      // B fragment (K-step k, column tile j) holds in lane l the piece of column 16 j + (l & 15), isolates 128 k +
-      // 32 (l >> 4) .. + 31, which the stage keeps in its K-step 2 k + (l >> 5), column tile j >> 1, lane
-      // 16 (j & 1) + (l & 15) + 32 ((l >> 4) & 1): every 16 lanes read 256 contiguous bytes.
-      const unsigned char* bbuf = lds + rslot * kHalfBytes + ((quad >> 1) * 128 + (quad & 1) * 32 + l15) * 16;
-      rslot = rslot == kRingSlots - 1 ? 0 : rslot + 1;
-      // A half stage is 32 B fragments, f = 4 (K-step) + column tile, two MFMAs each (one per row tile).  Fragment
-      // f + kBLead is read in front of the MFMAs of fragment f through a register ring of kBLead + 1: one
-      // ds_read_b128 per pair of MFMAs, three pairs ahead of its use.  The scheduling barriers keep the reads where
-      // they are written (left alone, the compiler reads each fragment right before its MFMAs).  Measured
-      // (profiles/mfma_16x16.txt section 3): whole K-steps read two K-steps ahead, as the 32x32x64 body did, cost
-      // 0.13 ms of the cfg3 step against this, leads of 2, 4, 5 and 6 fragments 0.01-0.03 ms.
-      constexpr int kBLead = 3, kFrags = 4 * (kKSteps128 / 2);
-      v4i bq[kBLead + 1];
-      auto read_b = [&](int f) {
-        bq[f % (kBLead + 1)] =
-            *reinterpret_cast<const v4i*>(bbuf + (f >> 2) * kKStepBytes + ((f >> 1) & 1) * kFragBytes + (f & 1) * 256);
-      };
-#pragma unroll
-      for (int f = 0; f < kBLead; ++f) read_b(f);
-      if (h == 0) {
-        __builtin_amdgcn_sched_barrier(0);
-        if (st > 0) {                               // stage st - 1, never the range's last
-          const bool entered = s == 0;              // but the last of trait t - 1
-          region_test(entered ? ragged : 64);
-          if (entered) {
-            end_segment(t - 1);
-            take_thresholds();                      // fetched two ticks ago: retired by this tick's counted wait
-          }
-        }
-        if (s == S - 1 && st + 1 < ns) fetch_thresholds(t + 1);   // the trait's last stage: the next stage's trait
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int f = 0; f < kFrags; ++f) {
-        const int k = h * (kKSteps128 / 2) + (f >> 2), j = f & 3;
-        if (f + kBLead < kFrags) read_b(f + kBLead);
-        __builtin_amdgcn_sched_barrier(0);
-        const v4i x = bq[f % (kBLead + 1)];
-        const v8i bb = v8i{x.x, x.y, x.z, x.w, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-          // The stage's first K-step takes minus the centre as C: no accumulator set-up.  Scale operands 0 select
-          // the instruction without block scales (v_mfma_f32_16x16x128_f8f6f4: every scale 1, half the code bytes):
-          // the same counts, and 0.14 ms of the cfg3 step less than the form that reads 0x7f scales from a VGPR.
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-              v8i{a[i][k].x, a[i][k].y, a[i][k].z, a[i][k].w, 0, 0, 0, 0}, bb, k == 0 ? negc[i] : acc[i][j], 4, 4, 0, 0,
-              0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      for (int f = 0; f < kBLead; ++f) read_b(bbuf, f);
     }
-    if (++s == S) s = 0, ++t;
-  }
-  if (!late) next_tick();                           // tick nh: the late wavefronts' last half
+    for (int st = 0; st < ns; ++st) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (!kLate) {
+          barrier();
+          issue_half(nx++);
+#pragma unroll
+          for (int f = 0; f < kBLead; ++f) read_b(bbuf, f);
+        }
+        if (h == 0) {
+          __builtin_amdgcn_sched_barrier(0);
+          if (st > 0) {                             // stage st - 1, never the range's last
+            const bool entered = s == 0;            // but the last of trait t - 1
+            region_test(entered ? ragged : 64);
+            if (entered) {
+              end_segment(t - 1);
+              take_thresholds();                    // fetched a stage ago: two counted waits lie between
+            }
+          }
+          if (s == S - 1 && st + 1 < ns) fetch_thresholds(t + 1);   // the trait's last stage: the next stage's trait
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (kLate) issue_half(nx++);                // at the boundary, behind the fetch, in front of the counted wait
+        rslot = rslot == kRingSlots - 1 ? 0 : rslot + 1;
+        const unsigned char* nbuf = lbase + rslot * kHalfBytes;
+#pragma unroll
+        for (int f = 0; f < kFrags; ++f) {
+          const int k = h * (kKSteps128 / 2) + (f >> 2), j = f & 3;
+          if (kLate && f == kFrags / 2) barrier();
+          if (f + kBLead < kFrags) read_b(bbuf, f + kBLead);
+          else if (kLate) read_b(nbuf, f + kBLead - kFrags);   // whole since this interval's barrier
+          __builtin_amdgcn_sched_barrier(0);
+          const v4i x = bq[f % (kBLead + 1)];
+          const v8i bb = v8i{x.x, x.y, x.z, x.w, 0, 0, 0, 0};
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+            // The stage's first K-step takes minus the centre as C: no accumulator set-up.  Scale operands 0 select
+            // the instruction without block scales (v_mfma_f32_16x16x128_f8f6f4: every scale 1, half the code
+            // bytes): the same counts, and 0.14 ms of the cfg3 step less than the form that reads 0x7f scales from
+            // a VGPR.
+            acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+                v8i{a[i][k].x, a[i][k].y, a[i][k].z, a[i][k].w, 0, 0, 0, 0}, bb, k == 0 ? negc[i] : acc[i][j], 4, 4, 0,
+                0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        bbuf = nbuf;
+      }
+      if (++s == S) s = 0, ++t;
+    }
+    if (!kLate) barrier();                          // barrier nh: the late wavefronts' tail is behind it
+  };
+  if (late) run(std::true_type{});
+  else run(std::false_type{});
   const bool trait_done = s == 0;                   // (t, s) is one past the range's last stage
   region_test(trait_done ? ragged : 64);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last (redundant) transfers land before the LDS is given up

@@ -556,6 +556,37 @@ int scoary_ranksum_perm_generate_bfrag(scoary_handle h, const int16_t *d_rc, con
                                        void *d_bfrag, scoary_stream_t stream);
 int scoary_permute_ranksum(scoary_handle h, const uint32_t *d_tiled, const void *d_bfrag, const int32_t *d_dobs,
                            int64_t G, int64_t T, int64_t N, int64_t P, int32_t *d_r, scoary_stream_t stream);
+/* ---- Categorical traits: the gene x K-class chi-square test with label permutations (spec S20 of DESIGN.md;
+ * additive, ABI 11) ----
+ * A trait is a row of class codes d_codes int16 [T][N] (1 .. K, 0 for an isolate without a label; the host numbers
+ * the classes) and its class sizes d_nk int32 [T][8] over the isolates with a code (entries from K on are 0).  Per
+ * (trait, gene): a_k = |gene & class k|, m = sum a_k, n = sum n_k, K' = #{k : n_k > 0}.
+ *   scoary_categorical_max_classes()  8: eight 16-bit count fields in two 64-bit words
+ *   scoary_categorical    d_a int32 [T][G][8] (the entries from K on are 0 for a sound row); d_m int32 [T][G];
+ *                         d_x2 = (sum over n_k > 0, ascending k, of (double)(c_k c_k) / (double)n_k) /
+ *                         ((double)m (double)(n - m)), c_k = n a_k - m n_k in int64 -- the Pearson chi-square of the
+ *                         2 x K table without cancellation, fp64, every operation rounded on its own; d_p = the
+ *                         chi-square upper tail of it at K' - 1 degrees of freedom (scoary_cmh_homogeneity's tail:
+ *                         within 1e-10 relative of the true tail where that is >= 1e-290); d_v = sqrt(x2 / n),
+ *                         Cramer's V.  n < 2, m = 0, m = n or K' < 2: (x2 0, p 1, v 0).
+ *   scoary_permute_categorical  d_r[t][g] += #{p < P : S_p >= S_obs}, int32 [T][G], S = sum a_k^2 / n_k (X2 is
+ *                         increasing in it), a^p the gene's table under row p of d_rows int16 [T][P][N] -- the code
+ *                         rows shuffled by scoary_ranksum_perm_generate with d_codes in the place of d_rc -- and
+ *                         a^obs = d_a as scoary_categorical wrote it.  Decided in integers: with d_w uint64 [T][8][2]
+ *                         = the limbs (low, high) of w_k = lcm{n_k > 0} / n_k (0 where n_k = 0), the permutation
+ *                         counts iff sum (a^p_k^2 - a^obs_k^2) w_k >= 0.  The caller zeroes d_r before the first
+ *                         batch, batches add up.
+ * A code read from a row is clamped into [0, 8] before it indexes anything (scoary_permute_categorical only compares
+ * it with the classes): a bad row gives wrong numbers, never an access outside the buffers.  Asynchronous on `stream`, nothing is allocated.  SCOARY_ERR_ARG: null pointer or a size < 1;
+ * SCOARY_ERR_SIZE, with nothing written: K outside [1, 8], N > scoary_ranksum_max_isolates() (the rows are the
+ * rank-sum generator's), T > 65535, G or P >= 2^31. */
+int64_t scoary_categorical_max_classes(void);
+int scoary_categorical(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_codes, const int32_t *d_nk, int64_t G,
+                       int64_t T, int64_t N, int64_t K, int32_t *d_a, int32_t *d_m, double *d_x2, double *d_p,
+                       double *d_v, scoary_stream_t stream);
+int scoary_permute_categorical(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_rows, const int32_t *d_a,
+                               const int32_t *d_nk, const uint64_t *d_w, int64_t G, int64_t T, int64_t N, int64_t P,
+                               int32_t *d_r, scoary_stream_t stream);
 /* ---- Quantitative traits over strata: the van Elteren test with value permutations within the strata (spec S16 of
  * DESIGN.md; additive, ABI 11) ----
  * The strata are d_strata uint16 [N] (the stratum of every isolate, in [0, S)) and d_members int32 [N] (the isolates

@@ -16,6 +16,8 @@ ABI_VERSION = 11
 # here so that the command line can refuse a strata file before the library is loaded (load() compares)
 PERM_MAX_STRATA = 1024
 PERM_STRATA_MAX_ISOLATES = 20479
+# scoary_categorical_max_classes(): the classes a categorical trait may have (spec S20), known here for the same reason
+CATEGORICAL_MAX_CLASSES = 8
 
 _i64, _u64, _i32, _vp, _cp = (ctypes.c_int64, ctypes.c_uint64, ctypes.c_int,
                               ctypes.c_void_p, ctypes.c_char_p)
@@ -90,6 +92,9 @@ SIGNATURES = {
     "scoary_ranksum_bfrag_bytes": (_i64, [_i64, _i64, _i64]),
     "scoary_ranksum_perm_generate_bfrag": (_i32, [_vp] * 3 + [_i64] * 5 + [_u64, _vp, _vp]),
     "scoary_permute_ranksum": (_i32, [_vp] * 4 + [_i64] * 4 + [_vp, _vp]),
+    "scoary_categorical_max_classes": (_i64, []),
+    "scoary_categorical": (_i32, [_vp] * 4 + [_i64] * 4 + [_vp] * 6),
+    "scoary_permute_categorical": (_i32, [_vp] * 6 + [_i64] * 4 + [_vp, _vp]),
     "scoary_vanelteren": (_i32, [_vp] * 8 + [_i64] * 4 + [_vp] * 7),
     "scoary_vanelteren_perm_generate": (_i32, [_vp] * 4 + [_i64] * 6 + [_u64, _vp, _vp]),
     "scoary_vanelteren_perm_generate_bfrag": (_i32, [_vp] * 4 + [_i64] * 6 + [_u64, _vp, _vp]),
@@ -171,5 +176,7 @@ def load():
     if (lib.scoary_perm_max_strata(), lib.scoary_perm_strata_max_isolates()) != \
             (PERM_MAX_STRATA, PERM_STRATA_MAX_ISOLATES):
         raise ScoaryHipError("the library's strata limits differ from the binding's")
+    if lib.scoary_categorical_max_classes() != CATEGORICAL_MAX_CLASSES:
+        raise ScoaryHipError("the library's class limit differs from the binding's")
     _lib = lib
     return lib

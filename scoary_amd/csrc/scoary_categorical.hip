@@ -1,0 +1,308 @@
+// scoary_categorical.hip -- categorical traits: the Pearson chi-square test of a gene against a label of up to eight
+// classes (a 2 x K table per gene), with label permutations (spec S20 of DESIGN.md).
+//
+// The host numbers a trait's classes 1 .. K (0 = missing): a trait is its row of class codes (int16), the class sizes
+// n_k over the isolates with a code, and the weights w_k = lcm{n_k > 0} / n_k as two 64-bit limbs.  Everything per
+// gene is the vector a_k = |gene & class k|; the permutation null shuffles the codes over the isolates that have one
+// -- spec S15's value shuffle, made by scoary_ranksum_perm_generate with the codes in the place of the ranks.
+//
+//   k_cat_observed  (observed)      a[8], m, X2, p and Cramer's V of every (trait, gene): k_ranksum's shape, a bit
+//                                   walk over the tiled matrix with the trait's code row in LDS; not the hot path
+//   k_cat_permute   (the hot path)  block = one stage of 64 permutations of one trait x a strided share of the gene
+//                                   groups.  The stage's 64 code rows stand in LDS as class bit planes, a word per
+//                                   (class, 32 isolates, permutation); a lane is a permutation, a wavefront takes four
+//                                   genes at a time and adds popc(gene word & plane word) per class -- the gene words
+//                                   are wave-uniform, a plane word is read once for the four genes; behind a gene's
+//                                   last chunk of isolates the permuted table is compared exactly with the observed
+//                                   one and the lanes' verdicts are counted
+#include "scoary_chi2.hpp"
+#include "scoary_common.hpp"
+
+namespace {
+
+constexpr int kCatMaxClasses = 8;
+constexpr int kCatThreads = 1024;                 // sixteen wavefronts
+constexpr int kCatWaves = kCatThreads / 64;
+constexpr int kCatHold = 4;                       // genes a wavefront counts at a time: one read of a plane word serves four
+constexpr int kCatGroup = kCatWaves * kCatHold;   // genes of a block's step
+constexpr int kCatPlanes = kCatMaxClasses - 1;    // the last non-empty class needs no plane: its count is m - the others
+// words (of 32 isolates) of a chunk: whole quads of the tiled matrix whose seven class planes x 64 permutations stay
+// under the 160 KB of a CU (133 KB).  A matrix of up to 2432 isolates is loaded once per block; beyond that a block
+// reloads the chunks for every gene group.
+constexpr int kCatChunkWords = 76;
+constexpr int kCatChunk = 32 * kCatChunkWords;
+static_assert(kCatChunkWords % 4 == 0 && kCatPlanes * kCatChunkWords * 256 <= 160 * 1024,
+              "a chunk is whole quads and its planes fit the LDS");
+
+// d w as a signed 128-bit integer, d signed and w unsigned
+__device__ __forceinline__ __int128 cat_mul(int64_t d, uint64_t w) {
+  const uint64_t ud = (uint64_t)d;
+  const uint64_t hi = __umul64hi(ud, w) - (d < 0 ? w : 0ull);
+  return (__int128)(((unsigned __int128)hi << 64) | (unsigned __int128)(ud * w));
+}
+
+// Observed table and statistic.  Block = 256 genes of one trait, a gene per lane; the trait's code row in LDS, a byte
+// per isolate.  A lane counts the classes 1 .. 8 of its gene's isolates in eight 16-bit fields of two 64-bit words.
+__global__ __launch_bounds__(256) void k_cat_observed(const uint4* __restrict__ tiled, int64_t Gp, int G, int N, int K,
+                                                      const int16_t* __restrict__ codes,
+                                                      const int32_t* __restrict__ nk, int32_t* __restrict__ d_a,
+                                                      int32_t* __restrict__ d_m, double* __restrict__ d_x2,
+                                                      double* __restrict__ d_p, double* __restrict__ d_v) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const int t = blockIdx.y, tid = threadIdx.x;
+  for (int i = tid; i < N; i += 256)
+    lds[i] = (unsigned char)min(max((int)codes[(int64_t)t * N + i], 0), kCatMaxClasses);
+  __syncthreads();
+  const int g = blockIdx.x * 256 + tid;
+  if (g >= G) return;
+  const int nw = (N + 31) / 32;
+  uint64_t lo = 0, hi = 0;
+  for (int q = 0; 4 * q < nw; ++q) {
+    const uint4 x = tiled[(int64_t)q * Gp + g];
+    const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int w = 4 * q + j;
+      if (w >= nw) break;
+      uint32_t bits = xs[j];
+      if (32 * w + 32 > N) bits &= (1u << (N - 32 * w)) - 1u;
+      while (bits) {
+        const int c = lds[32 * w + __builtin_ctz(bits)];
+        bits &= bits - 1u;
+        if (c >= 5) hi += 1ull << (16 * (c - 5));
+        else if (c >= 1) lo += 1ull << (16 * (c - 1));
+      }
+    }
+  }
+  int a[kCatMaxClasses], m = 0;
+#pragma unroll
+  for (int k = 0; k < kCatMaxClasses; ++k) {
+    a[k] = (int)(((k < 4 ? lo : hi) >> (16 * (k & 3))) & 0xffffull);
+    m += a[k];
+  }
+  int64_t n = 0;
+  int kp = 0;
+#pragma unroll
+  for (int k = 0; k < kCatMaxClasses; ++k) {
+    const int nkk = k < K ? nk[t * kCatMaxClasses + k] : 0;
+    if (nkk > 0) n += nkk, ++kp;
+  }
+  // X2 in the form of spec S20: c_k = n a_k - m n_k exact, the sum in ascending k, every operation rounded on its own
+  double x2 = 0.0, p = 1.0, v = 0.0;
+  if (n >= 2 && m > 0 && m < n && kp >= 2) {
+    double sum = 0.0;
+#pragma unroll
+    for (int k = 0; k < kCatMaxClasses; ++k) {
+      const int nkk = k < K ? nk[t * kCatMaxClasses + k] : 0;
+      if (nkk > 0) {
+        const int64_t c = n * (int64_t)a[k] - (int64_t)m * (int64_t)nkk;
+        sum += (double)(c * c) / (double)nkk;
+      }
+    }
+    x2 = sum / ((double)m * (double)(n - m));
+    p = chi2_tail(x2, kp - 1);
+    v = sqrt(x2 / (double)n);
+  }
+  const int64_t o = (int64_t)t * G + g;
+  int4* ao = reinterpret_cast<int4*>(d_a + o * kCatMaxClasses);
+  ao[0] = int4{a[0], a[1], a[2], a[3]};
+  ao[1] = int4{a[4], a[5], a[6], a[7]};
+  d_m[o] = m;
+  d_x2[o] = x2;
+  d_p[o] = p;
+  d_v[o] = v;
+}
+
+// The walk of one gene group over the chunks, for NF class planes (3 while the trait's last non-empty class is at most
+// the fourth, else 7).  LDS holds planes[k][w][lane]: bit b of the word = isolate 32 w + b of the chunk has class k + 1
+// under the lane's permutation.  cnt[j][k] += popc(gene j's word & plane k's word): a plane word is read once for the
+// wavefront's four genes, whose words of a quad are 64 contiguous bytes of the tiled matrix (wave-uniform).
+template <int NF>
+__device__ __forceinline__ void cat_count(const uint32_t* __restrict__ planes, int lds_words, const uint4* __restrict__ tq,
+                                          int64_t Gp, int nquads, uint32_t (&cnt)[kCatHold][kCatPlanes]) {
+  for (int q = 0; q < nquads; ++q) {
+    uint4 gw[kCatHold];
+#pragma unroll
+    for (int j = 0; j < kCatHold; ++j) gw[j] = tq[(int64_t)q * Gp + j];
+#pragma unroll
+    for (int w4 = 0; w4 < 4; ++w4) {
+      uint32_t pl[NF];
+#pragma unroll
+      for (int k = 0; k < NF; ++k) pl[k] = planes[(k * lds_words + 4 * q + w4) * 64];
+#pragma unroll
+      for (int j = 0; j < kCatHold; ++j) {
+        const uint32_t g = w4 == 0 ? gw[j].x : w4 == 1 ? gw[j].y : w4 == 2 ? gw[j].z : gw[j].w;
+#pragma unroll
+        for (int k = 0; k < NF; ++k) bcnt_acc(cnt[j][k], g & pl[k]);
+      }
+    }
+  }
+}
+
+// Block = stage blockIdx.x % S (64 permutations) of trait blockIdx.y x the gene groups rng, rng + ranges, .. of
+// kCatGroup genes; wavefront w of a group counts its genes kCatHold w .. + kCatHold - 1; a lane is a permutation.
+// Per group and chunk of kCatChunk isolates: the chunk of the 64 code rows goes to LDS as class planes (a wavefront
+// reads 64 isolates of one row, coalesced, and a ballot per class gives two plane words; with one chunk in all the
+// planes are built once per block), and every wavefront counts its genes against them (cat_count).  Isolates past N
+// and permutations past P have no class, and a code that is none of 1 .. 8 matches no plane: no mask is needed and a
+// bad row gives wrong numbers only.  Behind the last chunk, per gene and lane: a_k = the count, the last non-empty
+// class a = m - the others, d_k = a_k^2 - a_obs,k^2, H = sum d_k w_hi,k, Lo = sum d_k w_lo,k, and the permutation
+// counts iff H + (Lo >> 64) >= 0 (spec S20: the sign of sum d_k L / n_k in integers).
+__global__ __launch_bounds__(kCatThreads) void k_cat_permute(const uint32_t* __restrict__ tiled, int64_t Gp, int G,
+                                                             int N, const int16_t* __restrict__ rows, int64_t P, int S,
+                                                             const int32_t* __restrict__ aobs,
+                                                             const int32_t* __restrict__ nk,
+                                                             const uint64_t* __restrict__ wt, int ranges,
+                                                             int lds_words, int32_t* __restrict__ d_r) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  uint32_t* planes = reinterpret_cast<uint32_t*>(lds);
+  const int t = blockIdx.y, s = blockIdx.x % S, rng = blockIdx.x / S;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int32_t* nkt = nk + t * kCatMaxClasses;
+  int klast = 0;
+#pragma unroll
+  for (int k = 0; k < kCatMaxClasses; ++k)
+    if (nkt[k] > 0) klast = k + 1;
+  const bool wide = klast > 4;
+  const int nf = wide ? kCatPlanes : 3;
+  const uint64_t* w = wt + (int64_t)t * 2 * kCatMaxClasses;
+  const int nw = (N + 31) / 32;
+  const int nchunks = (nw + kCatChunkWords - 1) / kCatChunkWords;
+  const int ngroups = (G + kCatGroup - 1) / kCatGroup;
+  const bool counted = (int64_t)s * 64 + lane < P;
+
+  // chunk c -> LDS: wavefront iteration = (permutation p, word pair wp); lanes 0 and 1 write the two words of a plane
+  auto load = [&](int c) {
+    const int npairs = lds_words / 2;
+    for (int it = wave; it < 64 * npairs; it += kCatWaves) {
+      const int p = it / npairs, wp = it - p * npairs;
+      const int64_t col = (int64_t)s * 64 + p;
+      const int i = (c * kCatChunkWords + 2 * wp) * 32 + lane;
+      int code = 0;
+      if (i < N && col < P) code = rows[((int64_t)t * P + col) * N + i];
+      for (int k = 0; k < nf; ++k) {
+        const uint64_t m64 = __ballot(code == k + 1);
+        if (lane < 2) planes[(k * lds_words + 2 * wp + lane) * 64 + p] = lane ? (uint32_t)(m64 >> 32) : (uint32_t)m64;
+      }
+    }
+  };
+
+  bool loaded = false;
+  for (int grp = rng; grp < ngroups; grp += ranges) {
+    const int g0 = grp * kCatGroup + wave * kCatHold;
+    uint32_t cnt[kCatHold][kCatPlanes];
+#pragma unroll
+    for (int j = 0; j < kCatHold; ++j)
+#pragma unroll
+      for (int k = 0; k < kCatPlanes; ++k) cnt[j][k] = 0u;
+    for (int c = 0; c < nchunks; ++c) {
+      if (!loaded || nchunks > 1) {
+        __syncthreads();
+        load(c);
+        __syncthreads();
+        loaded = true;
+      }
+      const int nquads = (min(kCatChunkWords, nw - c * kCatChunkWords) + 3) / 4;
+      const uint4* tq = reinterpret_cast<const uint4*>(tiled) + (int64_t)c * (kCatChunkWords / 4) * Gp + g0;
+      if (wide) cat_count<kCatPlanes>(planes + lane, lds_words, tq, Gp, nquads, cnt);
+      else cat_count<3>(planes + lane, lds_words, tq, Gp, nquads, cnt);
+    }
+#pragma unroll
+    for (int j = 0; j < kCatHold; ++j) {
+      const int g = g0 + j;
+      if (g >= G) break;
+      const int32_t* ao = aobs + ((int64_t)t * G + g) * kCatMaxClasses;
+      int m = 0;
+#pragma unroll
+      for (int k = 0; k < kCatMaxClasses; ++k) m += ao[k];
+      __int128 H = 0, Lo = 0;
+      int sum = 0;
+#pragma unroll 1                                   // (unrolled, the sixteen limbs wait in SGPRs across the count)
+      for (int k = 0; k < klast; ++k) {
+        int a;
+        if (k < klast - 1) {
+          a = (int)cnt[j][0];
+#pragma unroll
+          for (int x = 1; x < kCatPlanes; ++x) a = k == x ? (int)cnt[j][x] : a;
+          sum += a;
+        } else {
+          a = m - sum;
+        }
+        const int64_t o = ao[k];
+        const int64_t d = (int64_t)a * a - o * o;
+        H += cat_mul(d, w[2 * k + 1]);
+        Lo += cat_mul(d, w[2 * k]);
+      }
+      const bool ge = H + (Lo >> 64) >= 0;
+      const int hits = __popcll(__ballot(ge && counted));
+      if (lane == 0 && hits) atomicAdd(d_r + (int64_t)t * G + g, hits);
+    }
+  }
+}
+
+int cat_check(scoary_handle h, const char* what, bool ok, int64_t G, int64_t T, int64_t N, int64_t K, int64_t P) {
+  if (int rc = check_args(h, what, ok && G >= 1 && T >= 1 && N >= 1 && P >= 1)) return rc;
+  if (K < 1 || K > kCatMaxClasses)
+    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": K outside [1, scoary_categorical_max_classes()]");
+  if (N > scoary_ranksum_max_isolates())
+    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more isolates than scoary_ranksum_max_isolates()");
+  if (T > 65535 || G > 0x7fffffffLL - 256 || P > 0x7fffffffLL)
+    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": T > 65535, G >= 2^31 or P >= 2^31");
+  return SCOARY_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t scoary_categorical_max_classes(void) { return kCatMaxClasses; }
+
+int scoary_categorical(scoary_handle h, const uint32_t* d_tiled, const int16_t* d_codes, const int32_t* d_nk, int64_t G,
+                       int64_t T, int64_t N, int64_t K, int32_t* d_a, int32_t* d_m, double* d_x2, double* d_p,
+                       double* d_v, scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (int rc = cat_check(h, "scoary_categorical", d_tiled && d_codes && d_nk && d_a && d_m && d_x2 && d_p && d_v, G, T,
+                         N, K, 1))
+    return rc;
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  KernelTimer kt(h, s, "k_cat_observed");
+  hipLaunchKernelGGL(k_cat_observed, dim3((unsigned)((G + 255) / 256), (unsigned)T), dim3(256),
+                     (size_t)round_up(N, 16), s, reinterpret_cast<const uint4*>(d_tiled), scoary_tiled_genes(G), (int)G,
+                     (int)N, (int)K, d_codes, d_nk, d_a, d_m, d_x2, d_p, d_v);
+  HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+
+int scoary_permute_categorical(scoary_handle h, const uint32_t* d_tiled, const int16_t* d_rows, const int32_t* d_a,
+                               const int32_t* d_nk, const uint64_t* d_w, int64_t G, int64_t T, int64_t N, int64_t P,
+                               int32_t* d_r, scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (int rc = cat_check(h, "scoary_permute_categorical", d_tiled && d_rows && d_a && d_nk && d_w && d_r, G, T, N, 1,
+                         P))
+    return rc;
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // (the trait's classes are on the device: the LDS is sized for the seven planes of eight classes)
+  const int64_t lds_words = round_up(std::min<int64_t>((N + 31) / 32, kCatChunkWords), 4);
+  const int64_t lds = kCatPlanes * lds_words * 256;
+  if (lds > 64 * 1024 && !h->categorical_lds_optin) {
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cat_permute),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kCatPlanes * kCatChunkWords * 256));
+    h->categorical_lds_optin = 1;
+  }
+  // gene ranges per stage: enough blocks for four rounds over the CUs, where the gene groups allow it; a range is
+  // every ranges-th group, so that a table sorted by gene frequency spreads evenly
+  const int64_t S = (P + 63) / 64, ngroups = (G + kCatGroup - 1) / kCatGroup;
+  const int64_t ranges = std::min<int64_t>(ngroups, std::max<int64_t>(1, (4 * (int64_t)h->num_cu + S * T - 1) / (S * T)));
+  if (S * ranges > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_permute_categorical: grid too large");
+  KernelTimer kt(h, s, "k_cat_permute");
+  hipLaunchKernelGGL(k_cat_permute, dim3((unsigned)(S * ranges), (unsigned)T), dim3(kCatThreads), (size_t)lds, s,
+                     d_tiled, scoary_tiled_genes(G), (int)G, (int)N, d_rows, P, (int)S, d_a, d_nk, d_w, (int)ranges,
+                     (int)lds_words, d_r);
+  HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+
+}  // extern "C"

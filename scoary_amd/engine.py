@@ -154,6 +154,49 @@ class RankPlan:
         self.shift_plan = None              # ranksum_shift's RankShiftPlan, made when it is first asked for
 
 
+class CategoricalPlan:
+    """The categorical traits of a chi-square step (spec S20; AssociationEngine.categorical_plan): ``codes`` int16
+    [T, N] (class 1 .. K, 0 = missing), ``valid`` the validity rows (vecrows), ``nk`` int32 [T, 8] and ``w`` (the
+    limbs (low, high) of lcm{n_k > 0} / n_k, uint64 [T, 8, 2] held as int64) on the device; ``codes_host``,
+    ``valid_host`` (bool [T, N]), ``n`` int64 [T], ``nk_host`` int64 [T, 8], ``classes`` (K' per trait, int64 [T]),
+    ``weights`` (Python ints, [T][8]) and ``K`` (the largest code) on the host."""
+
+    def __init__(self, codes, valid, nk, w, codes_host, valid_host, n, nk_host, classes, weights, K):
+        self.codes, self.valid, self.nk, self.w = codes, valid, nk, w
+        self.codes_host, self.valid_host = codes_host, valid_host
+        self.n, self.nk_host, self.classes, self.weights, self.K = n, nk_host, classes, weights, K
+        self.T, self.N = (int(x) for x in codes_host.shape)
+
+
+CATEGORICAL_MAX_CLASSES = _abi.CATEGORICAL_MAX_CLASSES
+
+
+def categorical_host(codes):
+    """Host side of spec S20: integer codes [T, N] (0 = missing, classes from 1) -> (codes int16 [T, N], valid bool
+    [T, N], n int64 [T], nk int64 [T, 8], K' int64 [T], weights [T][8] of Python ints = lcm{n_k > 0} / n_k, 0 for an
+    empty class, and the same as limbs uint64 [T, 8, 2] (low, high))."""
+    import math
+    codes = np.ascontiguousarray(codes)
+    if codes.ndim != 2 or codes.dtype.kind not in "iu":
+        raise ValueError("categorical_plan: codes must be a [T, N] array of integers")
+    if codes.size and (codes.min() < 0 or codes.max() > CATEGORICAL_MAX_CLASSES):
+        raise ValueError("categorical_plan: a code is 0 (missing) or a class 1 .. %d" % CATEGORICAL_MAX_CLASSES)
+    codes = codes.astype(np.int16)
+    T = codes.shape[0]
+    nk = np.stack([np.bincount(row, minlength=CATEGORICAL_MAX_CLASSES + 1)[1:] for row in codes]).astype(np.int64) \
+        if T else np.zeros((0, CATEGORICAL_MAX_CLASSES), dtype=np.int64)
+    weights, limbs = [], np.zeros((T, CATEGORICAL_MAX_CLASSES, 2), dtype=np.uint64)
+    for t in range(T):
+        lcm = 1
+        for x in nk[t]:
+            if x:
+                lcm = lcm * int(x) // math.gcd(lcm, int(x))
+        weights.append([lcm // int(x) if x else 0 for x in nk[t]])
+        for k, wk in enumerate(weights[t]):
+            limbs[t, k] = (wk & 0xFFFFFFFFFFFFFFFF, wk >> 64)
+    return codes, codes != 0, nk.sum(axis=1), nk, (nk > 0).sum(axis=1), weights, limbs
+
+
 def rank_rows(values):
     """Host ranking of spec S15, exact double comparisons: float64 [T, N] with NaN for missing -> (rc int16 [T, N],
     valid bool [T, N], n int64 [T], tiesum int64 [T], tie groups int64 [T])."""
@@ -1857,6 +1900,83 @@ class AssociationEngine:
         over ranksum_permute's batches."""
         return self._rank_westfall_young("ranksum_westfall_young", genes, plan, res, self.ranksum_var(plan, res["m"]),
                                          1, permutations, budget_bytes, self._ranksum_generator(plan, seed))
+
+    # -- categorical traits: the gene x K-class chi-square test (spec S20) ---------------
+    def categorical_max_classes(self):
+        return int(self.lib.scoary_categorical_max_classes())
+
+    def categorical_plan(self, codes):
+        """codes: integers [T, N], class 1 .. K (K <= categorical_max_classes()), 0 = missing.  The host side of spec
+        S20 as a CategoricalPlan."""
+        torch = _torch()
+        codes, valid, n, nk, classes, weights, limbs = categorical_host(codes)
+        if codes.shape[1] > self.ranksum_max_isolates():
+            raise ValueError("categorical_plan: %d isolates, the rank-sum generator takes at most %d"
+                             % (codes.shape[1], self.ranksum_max_isolates()))
+        return CategoricalPlan(torch.from_numpy(codes).to(self.device),
+                               self.vecrows(pack_bits_rows(valid.astype(np.uint8)), codes.shape[1]),
+                               torch.from_numpy(nk.astype(np.int32)).to(self.device),
+                               torch.from_numpy(limbs.view(np.int64)).to(self.device),
+                               codes, valid, n, nk, classes, weights, max(1, int(codes.max(initial=0))))
+
+    def categorical(self, genes, plan):
+        """The observed 2 x K table and chi-square statistic of every (trait, gene): dict of device tensors a int32
+        [T, G, 8] (carriers by class), m int32 [T, G], x2, p and v (Cramer's V) float64 [T, G]; an untestable gene
+        has (x2 0, p 1, v 0)."""
+        torch = _torch()
+        self._ranksum_fits("categorical", genes, plan)
+        T, G = plan.T, genes.G
+        out = {"a": self._empty((T, G, 8), torch.int32), "m": self._empty((T, G), torch.int32),
+               "x2": self._empty((T, G), torch.float64), "p": self._empty((T, G), torch.float64),
+               "v": self._empty((T, G), torch.float64)}
+        self._check(self.lib.scoary_categorical(
+            self.h, self._ptr(genes.tiled), self._ptr(plan.codes), self._ptr(plan.nk), G, T, plan.N, plan.K,
+            *(self._ptr(out[k]) for k in ("a", "m", "x2", "p", "v")), self._stream()), "scoary_categorical")
+        return out
+
+    def categorical_rows(self, plan, perm_base, P, seed):
+        """The permuted code rows of the permutations perm_base .. perm_base + P - 1: int16 [T, P, N], the codes
+        shuffled over the isolates that have one by the rank-sum generator (spec S15's law)."""
+        out = self._empty((plan.T, int(P), plan.N), _torch().int16)
+        self._check(self.lib.scoary_ranksum_perm_generate(
+            self.h, self._ptr(plan.codes), self._ptr(plan.valid), plan.T, plan.N, int(P), int(perm_base), 0,
+            ctypes.c_uint64(seed), self._ptr(out), self._stream()), "scoary_ranksum_perm_generate")
+        return out
+
+    def categorical_batch(self, T, N, permutations, budget_bytes=8 << 30):
+        """Permutations per batch of categorical_permute (a multiple of 64): the code rows stay under budget_bytes."""
+        per = max(2 * 64 * int(T) * int(N), 1)
+        return int(max(64, min(-(-permutations // 64) * 64, budget_bytes // per * 64)))
+
+    def permute_categorical(self, genes, plan, a_obs, rows, r):
+        """r[t, g] += #{rows[t, p] : S_p >= S_obs}, decided in integers (k_cat_permute); rows int16 [T, P, N]."""
+        torch = _torch()
+        T, G, N = plan.T, genes.G, plan.N
+        if rows.dim() != 3 or (rows.shape[0], rows.shape[2]) != (T, N) or rows.dtype != torch.int16 \
+                or not rows.is_contiguous():
+            raise ValueError("permute_categorical: rows are int16 [T, P, N], contiguous")
+        if tuple(r.shape) != (T, G) or r.dtype != torch.int32 or not r.is_contiguous():
+            raise ValueError("permute_categorical: r is int32 [T, G], contiguous")
+        self._check(self.lib.scoary_permute_categorical(
+            self.h, self._ptr(genes.tiled), self._ptr(rows), self._ptr(a_obs), self._ptr(plan.nk), self._ptr(plan.w),
+            G, T, N, int(rows.shape[1]), self._ptr(r), self._stream()), "scoary_permute_categorical")
+        return r
+
+    def categorical_permute(self, genes, plan, a_obs, permutations, seed, budget_bytes=8 << 30):
+        """r int32 [T, G] = #{pi < permutations : X2_pi >= X2_obs} under code shuffles (spec S20), in batches of
+        categorical_batch() permutations: the rank-sum generator writes a batch's code rows and k_cat_permute adds
+        its counts."""
+        torch = _torch()
+        self._ranksum_fits("categorical_permute", genes, plan)
+        T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
+        if tuple(a_obs.shape) != (T, G, 8) or a_obs.dtype != torch.int32 or not a_obs.is_contiguous():
+            raise ValueError("categorical_permute: a_obs is the observed a, int32 [T, G, 8], contiguous")
+        r = torch.zeros((T, G), dtype=torch.int32, device=self.device)
+        batch = self.categorical_batch(T, N, P, budget_bytes)
+        for base in range(0, P, batch):
+            self.permute_categorical(genes, plan, a_obs, self.categorical_rows(plan, base, min(batch, P - base), seed),
+                                     r)
+        return r
 
     # -- quantitative traits: the Hodges-Lehmann shift and its limits (spec S19) --------
     def ranksum_shift_plan(self, values):

@@ -1793,6 +1793,12 @@ def ScoaryArgumentParser(argv=None):
                    "against every gene with the Wilcoxon-Mann-Whitney rank-sum test (normal approximation with tie and "
                    "continuity corrections) and written to <trait>.ranksum.results.csv; --permute adds Empirical_p "
                    "from shuffles of the values over the isolates (single process; scoary_amd extension)")
+    a.add_argument("--categorical", dest="categorical", metavar="FILE", default=None,
+                   help="With --no_pairwise: FILE holds categorical traits (isolates in rows, one named column per "
+                   "trait, any label in the cells, NA for missing), laid out like the traits file.  Every column of up "
+                   "to 8 classes is tested against every gene with the Pearson chi-square test of the 2 x K table and "
+                   "written to <trait>.categorical.results.csv with Cramer's V; --permute adds Empirical_p from "
+                   "shuffles of the labels over the isolates (single process; scoary_amd extension)")
     a.add_argument("--quantitative-strata", dest="quantitative_strata", metavar="FILE", default=None,
                    help="With --quantitative: FILE names a stratum (lineage, cluster) for every isolate, in the format "
                    "of --permute-strata's file.  Every measured trait is additionally tested with the van Elteren "
@@ -2022,6 +2028,12 @@ def main(**kwargs):
                                                               permutations=args.permute, seed=seed,
                                                               fwer=qfwer, stepdown=qsd),
                                            genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
+        if getattr(args, "categorical", None) and rank == 0:
+            names, labels = read_categorical_file(args.categorical, args.delimiter, strains)
+            with _stage("chi-square test of the categorical traits"):
+                StoreCategoricalResults(Categorical_results(genedic, names, labels, permutations=args.permute,
+                                                            seed=seed, exits=True),
+                                        genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
         log.info("Stage seconds: load (+tree) %.2f, association (+permutations) %.2f, pairwise stage and "
                  "output %.2f" % (t_loaded - start, t_stats - t_loaded, _time.time() - t_stats))
         gene_bytes = os.path.getsize(args.genes) if os.path.isfile(args.genes) else 0
@@ -2248,6 +2260,177 @@ def StoreRanksumResults(results, genedic, max_hits, outdir, time="", delimiter="
     double-quoted.  Returns the file names."""
     return _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, RANKSUM_COLUMNS,
                                ".ranksum.results.csv", "rank-sum")
+
+
+# ---------------------------------------------------------------------------
+# --categorical FILE: the gene x K-class chi-square test of labelled traits (spec S20).  A stage and result files of
+# its own, as --quantitative has them: a label of more than two levels has no 2 x 2 table and no Fisher p.
+# ---------------------------------------------------------------------------
+CATEGORICAL_COLUMNS = ("Number_with_gene", "Number_without_gene", "Carriers_by_class", "Most_enriched_class", "Chi2",
+                       "Chi2_df", "Cramers_V", "Chi2_p", "Bonferroni_p", "Benjamini_H_p")
+# a refusal as the command line reports it / as Categorical_results raises it
+CATEGORICAL_TEXT = {
+    "no_pairwise": ("Cannot use --categorical without --no_pairwise. The chi-square test is a population "
+                    "structure-naive test of every gene",
+                    "categorical traits need no_pairwise: the chi-square test is population structure-naive"),
+    "collapse": ("Cannot use --categorical together with --collapse. The chi-square test is a test of every gene of "
+                 "the table", "categorical traits exclude collapse"),
+    "strata": ("Cannot use --categorical together with --permute-strata. The labels are shuffled over all isolates "
+               "with a label; a shuffle within strata is not implemented",
+               "categorical traits exclude strata: their labels are shuffled over all valid isolates"),
+    "ranks": ("Cannot use --categorical under more than one rank: the test runs over all genes in a single process",
+              "categorical traits need a single process"),
+    "classes": ("Cannot use --categorical with the trait %s: it has %d classes among the analysed isolates, the test "
+                "takes at most %d. Merge rare classes into one before the run",
+                "categorical trait %s has %d classes, at most %d are taken: merge rare classes"),
+}
+
+
+def categorical_classes(labels):
+    """The classes of one trait's labels (a string per isolate, None = missing): sorted as Python strings."""
+    return sorted(set(x for x in labels if x is not None))
+
+
+def _categorical_refusals(no_pairwise, collapse, strata, names=(), labels=(), exits=False):
+    """The messages of the --categorical rules that a run breaks, in the order they are reported (``exits``: as the
+    command line's exit messages, else as Categorical_results' ValueErrors).  ``names``, ``labels``: the traits, once
+    they are read."""
+    from . import _abi, dist
+    if not no_pairwise:
+        yield CATEGORICAL_TEXT["no_pairwise"][not exits]
+    if collapse:
+        yield CATEGORICAL_TEXT["collapse"][not exits]
+    if strata:
+        yield CATEGORICAL_TEXT["strata"][not exits]
+    if dist.world_rank()[0] > 1:
+        yield CATEGORICAL_TEXT["ranks"][not exits]
+    for name, row in zip(names, labels):
+        k = len(categorical_classes(row))
+        if k > _abi.CATEGORICAL_MAX_CLASSES:
+            yield CATEGORICAL_TEXT["classes"][not exits] % (name, k, _abi.CATEGORICAL_MAX_CLASSES)
+
+
+def read_categorical_file(path, delimiter, strains):
+    """--categorical FILE: a header row (its first cell is ignored, the others name the traits), then one row per
+    isolate: its name and one cell per trait, any string as the label or one of MISSING_TRAIT.  Returns (names,
+    labels [T][N] over ``strains``, None = missing): isolates the analysis does not hold are ignored, isolates of
+    ``strains`` the file does not name are missing in every trait."""
+    with open(path, "r", newline=None) as f:
+        rows = [r for r in csv.reader(f, delimiter=delimiter) if r]
+    if not rows or len(rows[0]) < 2:
+        sys.exit("Please check that the categorical traits file %s is formatted properly and contains at least one "
+                 "trait" % path)
+    names = list(rows[0][1:])
+    if len(set(names)) != len(names):
+        sys.exit("The categorical traits file %s names a trait more than once" % path)
+    col = {s: j for j, s in enumerate(strains)}
+    labels = [[None] * len(strains) for _ in names]
+    seen = set()
+    for line, row in enumerate(rows[1:], start=2):
+        iso = row[0]
+        if iso in seen:
+            sys.exit("The categorical traits file %s names isolate %s more than once (line %d)" % (path, iso, line))
+        seen.add(iso)
+        if len(row) != len(names) + 1:
+            sys.exit("The categorical traits file %s has %d cells in line %d, its header has %d"
+                     % (path, len(row), line, len(names) + 1))
+        if iso not in col:
+            continue
+        for t, cell in enumerate(row[1:]):
+            if cell not in MISSING_TRAIT:
+                labels[t][col[iso]] = cell
+    return names, labels
+
+
+def Categorical_results(genedic, names, labels, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False,
+                        strata=None, exits=False):
+    """The chi-square stage (spec S20) of the traits ``names`` with the labels [T][N] (a string per isolate, None =
+    missing) over the isolates of ``genedic``: {name: dict(classes, n, nk [K], df, a [G, K], m, x2, v, p, testable
+    [G]; r [G] and permutations with permutations >= 10)}, arrays in the gene table's order.  Raises ValueError where
+    the command line refuses --categorical (``exits``: exits with the command line's message instead)."""
+    for text in _categorical_refusals(no_pairwise, collapse, strata is not None, names, labels, exits=exits):
+        if exits:
+            sys.exit(text)
+        raise ValueError(text)
+    table = _as_table(genedic)
+    eng = get_engine()
+    N = len(table.strains)
+    if len(labels) != len(names) or any(len(row) != N for row in labels):
+        raise ValueError("categorical traits: labels must be [%d traits, %d isolates]" % (len(names), N))
+    if N > eng.ranksum_max_isolates():
+        raise ValueError("categorical traits take at most %d isolates; this analysis has %d"
+                         % (eng.ranksum_max_isolates(), N))
+    classes = [categorical_classes(row) for row in labels]
+    codes = np.zeros((len(names), N), dtype=np.int16)
+    for t, row in enumerate(labels):
+        number = {c: k + 1 for k, c in enumerate(classes[t])}
+        codes[t] = [number[x] if x is not None else 0 for x in row]
+    genes = table.on_device(eng)
+    plan = eng.categorical_plan(codes)
+    res = eng.categorical(genes, plan)
+    permutations = int(permutations)
+    r = None
+    if permutations >= 10:
+        r = eng.categorical_permute(genes, plan, res["a"], permutations, seed).cpu().numpy()
+    a, m, x2, p, v = (res[k].cpu().numpy() for k in ("a", "m", "x2", "p", "v"))
+    out = {}
+    for t, name in enumerate(names):
+        n, K = int(plan.n[t]), len(classes[t])
+        testable = (m[t] > 0) & (m[t] < n) & bool(n >= 2 and int(plan.classes[t]) >= 2)
+        out[name] = dict(classes=classes[t], n=n, nk=plan.nk_host[t, :K].copy(), df=int(plan.classes[t]) - 1,
+                         a=a[t][:, :K], m=m[t], x2=x2[t], v=v[t], p=p[t], testable=testable)
+        if r is not None:
+            out[name]["r"] = r[t]
+            out[name]["permutations"] = permutations
+        log.info("Chi-square test of %s: %d isolates with a label in %d classes, %d genes tested"
+                 % (name, n, K, int(testable.sum())))
+    return out
+
+
+def most_enriched_class(a, nk):
+    """The index of the class with the largest a_k / n_k among the non-empty ones, compared as a_k n_j against
+    a_j n_k in integers; ties go to the first class."""
+    best = None
+    for k, (ak, n) in enumerate(zip(a, nk)):
+        if n > 0 and (best is None or int(ak) * int(nk[best]) > int(a[best]) * int(n)):
+            best = k
+    return best
+
+
+def StoreCategoricalResults(results, genedic, max_hits, outdir, time="", delimiter=","):
+    """Write ``<outdir><trait><time>.categorical.results.csv`` for every trait of Categorical_results: the testable
+    genes in ascending Chi2_p (ties in file order), Bonferroni and Benjamini-Hochberg over them, every cell
+    double-quoted.  Returns the file names."""
+    table = _as_table(genedic)
+    files = []
+    for name, res in results.items():
+        with_emp = "r" in res
+        columns = ROARY_HEAD + list(CATEGORICAL_COLUMNS) + (["Empirical_p"] if with_emp else [])
+        idx = np.flatnonzero(res["testable"])
+        fname = outdir + name + time + ".categorical.results.csv"
+        with open(fname, "w") as out:
+            out.write(delimiter.join('"' + c + '"' for c in columns) + "\n")
+            if len(idx):
+                p = res["p"][idx]
+                order = np.argsort(p, kind="stable")
+                bonf, bh = bonferroni_bh(p, len(idx), order=order)
+                shown = len(idx) if max_hits is None else max(0, min(max_hits, len(idx)))
+                for k in order[:shown]:
+                    g = int(idx[k])
+                    gene = table.ids[g]
+                    cells = gene.split("_|_") if "_|_" in gene else [gene, str(table.nugn[g]),
+                                                                     str(table.annotation[g])]
+                    m, a = int(res["m"][g]), res["a"][g]
+                    cells += [_fmt(m), _fmt(res["n"] - m),
+                              "|".join("%s=%d" % (c, int(x)) for c, x in zip(res["classes"], a)),
+                              res["classes"][most_enriched_class(a, res["nk"])], _fmt(res["x2"][g]), _fmt(res["df"]),
+                              _fmt(res["v"][g]), _fmt(res["p"][g]), _fmt(bonf[k]), _fmt(bh[k])]
+                    if with_emp:
+                        cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
+                    out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
+        log.info("Storing chi-square results: %s" % fname)
+        files.append(fname)
+    return files
 
 
 # ---------------------------------------------------------------------------
@@ -2527,6 +2710,17 @@ def _validate(args, cutoffs):
             sys.exit(text)
         if not os.path.isfile(args.quantitative):
             sys.exit("Could not find the quantitative traits file: %s" % args.quantitative)
+    if getattr(args, "categorical", None):
+        for text in _categorical_refusals(args.no_pairwise, args.collapse,
+                                          bool(getattr(args, "permute_strata", None)), exits=True):
+            sys.exit(text)
+        if not os.path.isfile(args.categorical):
+            sys.exit("Could not find the categorical traits file: %s" % args.categorical)
+        # the classes are those of the analysed isolates (the header of the gene table after -s and -r): counted
+        # here, before the engine starts and the table is read
+        names, labels = read_categorical_file(args.categorical, args.delimiter, _analysed_isolates(args))
+        for text in _categorical_refusals(True, False, False, names, labels, exits=True):
+            sys.exit(text)
     qstrata = getattr(args, "quantitative_strata", None)
     if qstrata:
         if not getattr(args, "quantitative", None):

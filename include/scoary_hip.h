@@ -587,6 +587,46 @@ int scoary_categorical(scoary_handle h, const uint32_t *d_tiled, const int16_t *
 int scoary_permute_categorical(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_rows, const int32_t *d_a,
                                const int32_t *d_nk, const uint64_t *d_w, int64_t G, int64_t T, int64_t N, int64_t P,
                                int32_t *d_r, scoary_stream_t stream);
+/* ---- Categorical traits over strata: the generalized Cochran-Mantel-Haenszel test of the 2 x K x S table with label
+ * permutations within the strata (spec S21 of DESIGN.md; additive, ABI 11) ----
+ * A trait is scoary_categorical's d_codes int16 [T][N] and d_nk int32 [T][8], and d_nsk int32 [T][S][8], the class
+ * sizes inside every stratum (entries from K on are 0); the strata are d_strata uint16 [N] and d_members int32 [N] as
+ * the CMH entry points take them.  Per (trait, gene): m_s = the gene's labelled isolates of stratum s, a_k = |gene &
+ * class k| pooled, n_s = sum_k n_sk, klast = the last class with n_k > 0; the contrasts are the classes j < klast - 1
+ * (0-based), at most 7.  In ascending s, fp64, every operation rounded on its own:
+ *     E_k += (double)(m_s n_sk) / (double)n_s                                      (n_s >= 1)
+ *     c = ((double)m_s (double)(n_s - m_s)) / (((double)n_s (double)n_s) (double)(n_s - 1))         (n_s >= 2)
+ *     V_jk += c (double)B_sjk,  B_sjk = n_s n_sj [j = k] - n_sj n_sk in int64      (k <= j < 7)
+ * LDL' without pivoting in class order, rows from klast - 1 on taken as zero: u_jk = V_jk - sum_{l<k} u_jl f_kl (l
+ * ascending), f_jk = u_jk invp_k, p_j = V_jj - sum_{k<j} u_jk f_jk (k ascending); pivot j is skipped (invp_j = 0, so
+ * every multiplier of its column is 0) iff p_j <= 1e-8 V_jj, else invp_j = 1.0 / p_j; df = the pivots kept.  The FORM
+ * of a (trait, gene) is scoary_gcmh_form_doubles() = 35 doubles: E[7] (0 from klast - 1 on), f[21] (f_ij at
+ * i (i - 1) / 2 + j), invp[7].  Q(a) = sum_j (y_j y_j) invp_j, y_i = ((double)a_i - E_i) - sum_{j<i} f_ij y_j, both in
+ * ascending j.
+ *   scoary_gcmh           d_a int32 [T][G][8], d_m int32 [T][G] (m = sum m_s), d_e double [T][G][8] (E of all eight
+ *                         classes), d_form double [T][G][35], d_q = Q(a), d_df int32 [T][G], d_p = the chi-square
+ *                         upper tail of Q at df degrees of freedom (scoary_cmh_homogeneity's tail; 1 for df = 0),
+ *                         d_thr = Q (1 - 1e-6).  df = 0: the form is E and zeros, Q = 0, thr = 0.  d_scratch:
+ *                         scoary_cmh_scratch_bytes(N) bytes, the segment table of the strata, built by the call
+ *   scoary_permute_gcmh   d_r[t][g] += #{p < P : Q(a^p) >= thr}, int32 [T][G], a^p the gene's counts under row p of
+ *                         d_rows int16 [T][P][N] -- the code rows shuffled within the strata by
+ *                         scoary_vanelteren_perm_generate with the codes of the labelled isolates by (stratum,
+ *                         isolate) as d_l -- d_form and d_thr as scoary_gcmh wrote them.  The same operations as
+ *                         d_q's: an identical table gives identical bits.  The caller zeroes d_r before the first
+ *                         batch, batches add up.
+ * A code read from a row is clamped into [0, 8] before it indexes anything (scoary_permute_gcmh only compares it with
+ * the classes), a stratum and a word read from the segment table are clamped into theirs, a class size below 0 counts
+ * as 0: a bad plan or row gives wrong numbers, never an access outside the buffers.  Asynchronous on `stream`, nothing
+ * is allocated.  SCOARY_ERR_ARG: null pointer or a size < 1; SCOARY_ERR_SIZE, with nothing written: K outside [1, 8],
+ * S > scoary_perm_max_strata(), N > scoary_ranksum_max_isolates(), T > 65535, G or P >= 2^31. */
+int64_t scoary_gcmh_form_doubles(void);
+int scoary_gcmh(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_codes, const int32_t *d_nk,
+                const int32_t *d_nsk, const uint16_t *d_strata, const int32_t *d_members, int64_t G, int64_t T,
+                int64_t N, int64_t K, int64_t S, int32_t *d_a, int32_t *d_m, double *d_e, double *d_form, double *d_q,
+                int32_t *d_df, double *d_p, double *d_thr, void *d_scratch, scoary_stream_t stream);
+int scoary_permute_gcmh(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_rows, const double *d_form,
+                        const double *d_thr, const int32_t *d_nk, int64_t G, int64_t T, int64_t N, int64_t P,
+                        int32_t *d_r, scoary_stream_t stream);
 /* ---- Quantitative traits over strata: the van Elteren test with value permutations within the strata (spec S16 of
  * DESIGN.md; additive, ABI 11) ----
  * The strata are d_strata uint16 [N] (the stratum of every isolate, in [0, S)) and d_members int32 [N] (the isolates

@@ -95,6 +95,9 @@ SIGNATURES = {
     "scoary_categorical_max_classes": (_i64, []),
     "scoary_categorical": (_i32, [_vp] * 4 + [_i64] * 4 + [_vp] * 6),
     "scoary_permute_categorical": (_i32, [_vp] * 6 + [_i64] * 4 + [_vp, _vp]),
+    "scoary_gcmh_form_doubles": (_i64, []),
+    "scoary_gcmh": (_i32, [_vp] * 7 + [_i64] * 5 + [_vp] * 10),
+    "scoary_permute_gcmh": (_i32, [_vp] * 6 + [_i64] * 4 + [_vp, _vp]),
     "scoary_vanelteren": (_i32, [_vp] * 8 + [_i64] * 4 + [_vp] * 7),
     "scoary_vanelteren_perm_generate": (_i32, [_vp] * 4 + [_i64] * 6 + [_u64, _vp, _vp]),
     "scoary_vanelteren_perm_generate_bfrag": (_i32, [_vp] * 4 + [_i64] * 6 + [_u64, _vp, _vp]),

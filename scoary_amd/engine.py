@@ -197,6 +197,39 @@ def categorical_host(codes):
     return codes, codes != 0, nk.sum(axis=1), nk, (nk > 0).sum(axis=1), weights, limbs
 
 
+class GcmhPlan:
+    """The categorical traits of a generalized CMH step over strata (spec S21; AssociationEngine.gcmh_plan).  On the
+    device: ``codes`` int16 [T, N] (class 1 .. K, 0 = missing), ``l`` int16 [T, N] = the codes of the labelled isolates
+    by (stratum, isolate), ``valid`` the validity rows (vecrows), ``nk`` int32 [T, 8], ``nsk`` int32 [T, S, 8] (the
+    class sizes inside every stratum), ``strata`` int16 [N] (uint16 bit pattern) and ``members`` int32 [N].  On the
+    host: codes_host, strata_host int64 [N], n int64 [T], nk_host int64 [T, 8], nsk_host int64 [T, S, 8], ``classes``
+    (K' per trait) and ``K`` (the largest code)."""
+
+    def __init__(self, dev, codes_host, strata_host, S, n, nk_host, nsk_host, classes, K):
+        self.codes, self.l, self.valid, self.nk, self.nsk, self.strata, self.members = dev
+        self.codes_host, self.strata_host, self.S = codes_host, strata_host, int(S)
+        self.n, self.nk_host, self.nsk_host, self.classes, self.K = n, nk_host, nsk_host, classes, K
+        self.T, self.N = (int(x) for x in codes_host.shape)
+
+
+GCMH_FORM = 35                                    # scoary_gcmh_form_doubles(): E[7], f[21], invp[7]
+
+
+def gcmh_host(codes, strata, S):
+    """Host side of spec S21 on top of categorical_host: (codes int16 [T, N], valid bool [T, N], n, nk, K' as there,
+    nsk int64 [T, S, 8], l int16 [T, N] = the codes of the labelled isolates by (stratum, isolate), zeros behind)."""
+    codes, valid, n, nk, classes, _weights, _limbs = categorical_host(codes)
+    T, N = codes.shape
+    nsk = np.zeros((T, S, CATEGORICAL_MAX_CLASSES), dtype=np.int64)
+    l = np.zeros((T, N), dtype=np.int16)
+    order = np.argsort(strata, kind="stable")
+    for t in range(T):
+        who = order[valid[t, order]]
+        l[t, :who.size] = codes[t, who]
+        np.add.at(nsk[t], (strata[who], codes[t, who].astype(np.int64) - 1), 1)
+    return codes, valid, n, nk, classes, nsk, l
+
+
 def rank_rows(values):
     """Host ranking of spec S15, exact double comparisons: float64 [T, N] with NaN for missing -> (rc int16 [T, N],
     valid bool [T, N], n int64 [T], tiesum int64 [T], tie groups int64 [T])."""
@@ -1976,6 +2009,93 @@ class AssociationEngine:
         for base in range(0, P, batch):
             self.permute_categorical(genes, plan, a_obs, self.categorical_rows(plan, base, min(batch, P - base), seed),
                                      r)
+        return r
+
+    # -- categorical traits over strata: the generalized CMH test (spec S21) -------------
+    def gcmh_plan(self, codes, strata):
+        """codes: integers [T, N] as categorical_plan takes them; strata: N integers in [0, S), S = the largest + 1,
+        shared by all traits.  The host side of spec S21 as a GcmhPlan."""
+        torch = _torch()
+        st = np.asarray(strata)
+        codes = np.asarray(codes)
+        if codes.ndim != 2 or st.ndim != 1 or st.shape[0] != codes.shape[1] or st.shape[0] < 1 \
+                or not np.issubdtype(st.dtype, np.integer):
+            raise ValueError("gcmh_plan: codes must be [T, N] and strata N integers, one per isolate")
+        st = st.astype(np.int64)
+        N, S = st.shape[0], int(st.max()) + 1
+        if st.min() < 0:
+            raise ValueError("gcmh_plan: stratum indices must not be negative")
+        if S > self.strata_max()[0]:
+            raise ValueError("gcmh_plan: %d strata, the kernels take %d (scoary_perm_max_strata)"
+                             % (S, self.strata_max()[0]))
+        if N > self.ranksum_max_isolates():
+            raise ValueError("gcmh_plan: %d isolates, the rank-sum generator takes at most %d"
+                             % (N, self.ranksum_max_isolates()))
+        codes, valid, n, nk, classes, nsk, l = gcmh_host(codes, st, S)
+        members = np.argsort(st, kind="stable").astype(np.int32)
+        dev = [torch.from_numpy(np.ascontiguousarray(x)).to(self.device) for x in
+               (codes, l, nk.astype(np.int32), nsk.astype(np.int32), st.astype(np.uint16).view(np.int16), members)]
+        dev.insert(2, self.vecrows(pack_bits_rows(valid.astype(np.uint8)), N))
+        return GcmhPlan(dev, codes, st, S, n, nk, nsk, classes, max(1, int(codes.max(initial=0))))
+
+    def gcmh(self, genes, plan):
+        """The observed 2 x K x S table and generalized CMH statistic of every (trait, gene): dict of device tensors a
+        int32 [T, G, 8] (carriers by class), m int32 [T, G], e float64 [T, G, 8] (expected carriers by class), form
+        float64 [T, G, 35], q, p, thr float64 [T, G] and df int32 [T, G]; an untestable gene has (df 0, q 0, p 1)."""
+        torch = _torch()
+        self._ranksum_fits("gcmh", genes, plan)
+        T, G = plan.T, genes.G
+        out = {"a": self._empty((T, G, 8), torch.int32), "m": self._empty((T, G), torch.int32),
+               "e": self._empty((T, G, 8), torch.float64), "form": self._empty((T, G, GCMH_FORM), torch.float64),
+               "q": self._empty((T, G), torch.float64), "df": self._empty((T, G), torch.int32),
+               "p": self._empty((T, G), torch.float64), "thr": self._empty((T, G), torch.float64)}
+        scratch = self._cmh_scratch(plan.N)
+        self._check(self.lib.scoary_gcmh(
+            self.h, self._ptr(genes.tiled), self._ptr(plan.codes), self._ptr(plan.nk), self._ptr(plan.nsk),
+            self._ptr(plan.strata), self._ptr(plan.members), G, T, plan.N, plan.K, plan.S,
+            *(self._ptr(out[k]) for k in ("a", "m", "e", "form", "q", "df", "p", "thr")), self._ptr(scratch),
+            self._stream()), "scoary_gcmh")
+        return out
+
+    def gcmh_rows(self, plan, perm_base, P, seed):
+        """The permuted code rows of the permutations perm_base .. perm_base + P - 1: int16 [T, P, N], the codes
+        shuffled within the strata over the isolates that have one by the van Elteren generator (spec S16's law)."""
+        out = self._empty((plan.T, int(P), plan.N), _torch().int16)
+        self._check(self.lib.scoary_vanelteren_perm_generate(
+            self.h, self._ptr(plan.l), self._ptr(plan.valid), self._ptr(plan.strata), plan.T, plan.N, plan.S, int(P),
+            int(perm_base), 0, ctypes.c_uint64(seed), self._ptr(out), self._stream()),
+            "scoary_vanelteren_perm_generate")
+        return out
+
+    def permute_gcmh(self, genes, plan, res, rows, r):
+        """r[t, g] += #{rows[t, p] : Q_p >= thr} (k_gcmh_permute); res = gcmh(genes, plan), rows int16 [T, P, N]."""
+        torch = _torch()
+        T, G, N = plan.T, genes.G, plan.N
+        form, thr = res["form"], res["thr"]
+        if tuple(form.shape) != (T, G, GCMH_FORM) or form.dtype != torch.float64 or not form.is_contiguous() \
+                or tuple(thr.shape) != (T, G) or thr.dtype != torch.float64 or not thr.is_contiguous():
+            raise ValueError("permute_gcmh: res is the observed result of these genes and this plan")
+        if rows.dim() != 3 or (rows.shape[0], rows.shape[2]) != (T, N) or rows.dtype != torch.int16 \
+                or not rows.is_contiguous():
+            raise ValueError("permute_gcmh: rows are int16 [T, P, N], contiguous")
+        if tuple(r.shape) != (T, G) or r.dtype != torch.int32 or not r.is_contiguous():
+            raise ValueError("permute_gcmh: r is int32 [T, G], contiguous")
+        self._check(self.lib.scoary_permute_gcmh(
+            self.h, self._ptr(genes.tiled), self._ptr(rows), self._ptr(form), self._ptr(thr), self._ptr(plan.nk),
+            G, T, N, int(rows.shape[1]), self._ptr(r), self._stream()), "scoary_permute_gcmh")
+        return r
+
+    def gcmh_permute(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
+        """r int32 [T, G] = #{pi < permutations : Q_pi >= Q_obs (1 - 1e-6)} under code shuffles within the strata
+        (spec S21), in categorical_batch() permutations a batch: the van Elteren generator writes a batch's code rows
+        and k_gcmh_permute adds its counts."""
+        torch = _torch()
+        self._ranksum_fits("gcmh_permute", genes, plan)
+        T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
+        r = torch.zeros((T, G), dtype=torch.int32, device=self.device)
+        batch = self.categorical_batch(T, N, P, budget_bytes)
+        for base in range(0, P, batch):
+            self.permute_gcmh(genes, plan, res, self.gcmh_rows(plan, base, min(batch, P - base), seed), r)
         return r
 
     # -- quantitative traits: the Hodges-Lehmann shift and its limits (spec S19) --------

@@ -1799,6 +1799,11 @@ def ScoaryArgumentParser(argv=None):
                    "to 8 classes is tested against every gene with the Pearson chi-square test of the 2 x K table and "
                    "written to <trait>.categorical.results.csv with Cramer's V; --permute adds Empirical_p from "
                    "shuffles of the labels over the isolates (single process; scoary_amd extension)")
+    a.add_argument("--categorical-strata", dest="categorical_strata", metavar="FILE", default=None,
+                   help="With --categorical: FILE names a stratum (lineage, cluster) for every isolate, in the format "
+                   "of --permute-strata. Adds the generalized Cochran-Mantel-Haenszel test of every gene against "
+                   "each trait over the strata, written to <trait>.gcmh.results.csv; --permute adds Empirical_p "
+                   "from label shuffles within the strata. The chi-square results stay as they are")
     a.add_argument("--quantitative-strata", dest="quantitative_strata", metavar="FILE", default=None,
                    help="With --quantitative: FILE names a stratum (lineage, cluster) for every isolate, in the format "
                    "of --permute-strata's file.  Every measured trait is additionally tested with the van Elteren "
@@ -2034,6 +2039,12 @@ def main(**kwargs):
                 StoreCategoricalResults(Categorical_results(genedic, names, labels, permutations=args.permute,
                                                             seed=seed, exits=True),
                                         genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
+            if getattr(args, "categorical_strata", None):
+                cstrata = strata_indices(args.categorical_strata_map, strains)[0]
+                with _stage("generalized CMH test of the categorical traits"):
+                    StoreGcmhResults(Gcmh_results(genedic, names, labels, cstrata, permutations=args.permute,
+                                                  seed=seed),
+                                     genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
         log.info("Stage seconds: load (+tree) %.2f, association (+permutations) %.2f, pairwise stage and "
                  "output %.2f" % (t_loaded - start, t_stats - t_loaded, _time.time() - t_stats))
         gene_bytes = os.path.getsize(args.genes) if os.path.isfile(args.genes) else 0
@@ -2434,6 +2445,115 @@ def StoreCategoricalResults(results, genedic, max_hits, outdir, time="", delimit
 
 
 # ---------------------------------------------------------------------------
+# --categorical-strata FILE: the generalized Cochran-Mantel-Haenszel test of the labelled traits over strata (spec
+# S21), next to the chi-square stage: result files of its own, and nothing of the chi-square files changes.
+# ---------------------------------------------------------------------------
+GCMH_COLUMNS = ("Number_with_gene", "Number_without_gene", "Carriers_by_class", "Expected_by_class",
+                "Most_enriched_class", "GCMH", "GCMH_df", "GCMH_p", "Bonferroni_p", "Benjamini_H_p")
+GCMH_TEXT = {
+    "categorical": "Cannot use --categorical-strata without --categorical. Its strata are those of the generalized "
+                   "Cochran-Mantel-Haenszel test of the categorical traits",
+    "file": "Could not find the strata file of --categorical-strata: %s",
+    "strata": "The strata file %s names %d strata for the analysed isolates; --categorical-strata takes at most %d",
+}
+
+
+def Gcmh_results(genedic, names, labels, strata, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False):
+    """The generalized CMH stage (spec S21) of the traits ``names`` with the labels [T][N] (a string per isolate, None
+    = missing) and the stratum index of every isolate ``strata`` (N integers) over the isolates of ``genedic``: {name:
+    dict(classes, n, strata (those with a labelled isolate), a [G, K], e [G, K], m, q, df, p, testable [G]; r [G] and
+    permutations with permutations >= 10)}, arrays in the gene table's order.  Raises ValueError where the command
+    line refuses --categorical."""
+    for text in _categorical_refusals(no_pairwise, collapse, False, names, labels):
+        raise ValueError(text)
+    table = _as_table(genedic)
+    eng = get_engine()
+    N = len(table.strains)
+    strata = np.asarray(strata)
+    if len(labels) != len(names) or any(len(row) != N for row in labels):
+        raise ValueError("categorical traits: labels must be [%d traits, %d isolates]" % (len(names), N))
+    if strata.shape != (N,) or not np.issubdtype(strata.dtype, np.integer) or strata.min() < 0:
+        raise ValueError("categorical traits: strata must be %d stratum indices, one per isolate" % N)
+    if N > eng.ranksum_max_isolates():
+        raise ValueError("categorical traits take at most %d isolates; this analysis has %d"
+                         % (eng.ranksum_max_isolates(), N))
+    from . import _abi
+    if int(strata.max()) + 1 > _abi.PERM_MAX_STRATA:
+        raise ValueError("categorical traits take at most %d strata; these are %d"
+                         % (_abi.PERM_MAX_STRATA, int(strata.max()) + 1))
+    classes = [categorical_classes(row) for row in labels]
+    codes = np.zeros((len(names), N), dtype=np.int16)
+    for t, row in enumerate(labels):
+        number = {c: k + 1 for k, c in enumerate(classes[t])}
+        codes[t] = [number[x] if x is not None else 0 for x in row]
+    genes = table.on_device(eng)
+    plan = eng.gcmh_plan(codes, strata)
+    res = eng.gcmh(genes, plan)
+    permutations = int(permutations)
+    r = None
+    if permutations >= 10:
+        r = eng.gcmh_permute(genes, plan, res, permutations, seed).cpu().numpy()
+    a, e, m, q, df, p = (res[k].cpu().numpy() for k in ("a", "e", "m", "q", "df", "p"))
+    out = {}
+    for t, name in enumerate(names):
+        K = len(classes[t])
+        out[name] = dict(classes=classes[t], n=int(plan.n[t]), strata=int((plan.nsk_host[t].sum(axis=1) > 0).sum()),
+                         a=a[t][:, :K], e=e[t][:, :K], m=m[t], q=q[t], df=df[t], p=p[t], testable=df[t] > 0)
+        if r is not None:
+            out[name]["r"] = r[t]
+            out[name]["permutations"] = permutations
+        log.info("Generalized CMH test of %s: %d isolates with a label in %d classes and %d strata, %d genes tested"
+                 % (name, out[name]["n"], K, out[name]["strata"], int(out[name]["testable"].sum())))
+    return out
+
+
+def most_enriched_expected(a, e):
+    """The index of the class with the largest a_k / E_k over E_k > 0 (fp64 quotients); ties go to the first class."""
+    best, top = None, -1.0
+    for k, (ak, ek) in enumerate(zip(a, e)):
+        if ek > 0.0 and float(ak) / float(ek) > top:
+            best, top = k, float(ak) / float(ek)
+    return best
+
+
+def StoreGcmhResults(results, genedic, max_hits, outdir, time="", delimiter=","):
+    """Write ``<outdir><trait><time>.gcmh.results.csv`` for every trait of Gcmh_results, by StoreCategoricalResults'
+    rules: the testable genes in ascending GCMH_p (ties in file order), Bonferroni and Benjamini-Hochberg over them,
+    every cell double-quoted.  Returns the file names."""
+    table = _as_table(genedic)
+    files = []
+    for name, res in results.items():
+        with_emp = "r" in res
+        columns = ROARY_HEAD + list(GCMH_COLUMNS) + (["Empirical_p"] if with_emp else [])
+        idx = np.flatnonzero(res["testable"])
+        fname = outdir + name + time + ".gcmh.results.csv"
+        with open(fname, "w") as out:
+            out.write(delimiter.join('"' + c + '"' for c in columns) + "\n")
+            if len(idx):
+                p = res["p"][idx]
+                order = np.argsort(p, kind="stable")
+                bonf, bh = bonferroni_bh(p, len(idx), order=order)
+                shown = len(idx) if max_hits is None else max(0, min(max_hits, len(idx)))
+                for k in order[:shown]:
+                    g = int(idx[k])
+                    gene = table.ids[g]
+                    cells = gene.split("_|_") if "_|_" in gene else [gene, str(table.nugn[g]),
+                                                                     str(table.annotation[g])]
+                    m, a, e = int(res["m"][g]), res["a"][g], res["e"][g]
+                    cells += [_fmt(m), _fmt(res["n"] - m),
+                              "|".join("%s=%d" % (c, int(x)) for c, x in zip(res["classes"], a)),
+                              "|".join("%s=%s" % (c, _fmt(x)) for c, x in zip(res["classes"], e)),
+                              res["classes"][most_enriched_expected(a, e)], _fmt(res["q"][g]), _fmt(res["df"][g]),
+                              _fmt(res["p"][g]), _fmt(bonf[k]), _fmt(bh[k])]
+                    if with_emp:
+                        cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
+                    out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
+        log.info("Storing generalized CMH results: %s" % fname)
+        files.append(fname)
+    return files
+
+
+# ---------------------------------------------------------------------------
 # --quantitative-strata FILE: the van Elteren test of the measured traits over strata (spec S16), next to the
 # rank-sum stage: result files of its own, and nothing of the rank-sum files changes.
 # ---------------------------------------------------------------------------
@@ -2721,6 +2841,17 @@ def _validate(args, cutoffs):
         names, labels = read_categorical_file(args.categorical, args.delimiter, _analysed_isolates(args))
         for text in _categorical_refusals(True, False, False, names, labels, exits=True):
             sys.exit(text)
+    cstrata = getattr(args, "categorical_strata", None)
+    if cstrata:
+        if not getattr(args, "categorical", None):
+            sys.exit(GCMH_TEXT["categorical"])
+        if not os.path.isfile(cstrata):
+            sys.exit(GCMH_TEXT["file"] % cstrata)
+        args.categorical_strata_map = read_strata_file(cstrata, args.delimiter)
+        from . import _abi
+        labels = strata_indices(args.categorical_strata_map, _analysed_isolates(args))[1]
+        if len(labels) > _abi.PERM_MAX_STRATA:
+            sys.exit(GCMH_TEXT["strata"] % (cstrata, len(labels), _abi.PERM_MAX_STRATA))
     qstrata = getattr(args, "quantitative_strata", None)
     if qstrata:
         if not getattr(args, "quantitative", None):

@@ -627,6 +627,37 @@ int scoary_gcmh(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_codes
 int scoary_permute_gcmh(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_rows, const double *d_form,
                         const double *d_thr, const int32_t *d_nk, int64_t G, int64_t T, int64_t N, int64_t P,
                         int32_t *d_r, scoary_stream_t stream);
+/* ---- Categorical traits: Westfall-Young single-step maxT over the chi-square and the generalized CMH statistic
+ * (spec S22 of DESIGN.md; additive, ABI 11) ----
+ * The chi-square statistic of a cell (gene, row) with the table a_k, per trait with n = sum n_k and per gene with m =
+ * sum a^obs_k:  s = (sum over ascending k of ((double)c_k (double)c_k) inv[k]) ivm,  c_k = n a_k - m n_k in int32,
+ * inv[k] = 1.0 / (double)n_k where n_k > 0 and 0 where not, ivm = 1.0 / ((double)m (double)(n - m)) where the gene is
+ * testable by scoary_categorical's rule and 0 where not; fp64, every operation rounded on its own; X2 in the reals
+ * (not d_x2 bit for bit: that divides by n_k).  The generalized CMH statistic of a cell is Q(a) of scoary_gcmh, as
+ * scoary_permute_gcmh computes it.
+ *   scoary_cat_wy_prepare   d_inv double [T][8]; d_ivm, d_sobs, d_thr double [T][G]: s_obs = s of d_a
+ *                           (scoary_categorical's) and thr = s_obs (1.0 - 1e-9), the comparison point of the
+ *                           family-wise count: an exact X2_p >= X2_obs implies s_p >= thr
+ *   scoary_permute_cat_wy   scoary_permute_categorical with the family-wise maxima in the same pass: d_r as there, bit
+ *                           for bit, and d_maxs[t * maxs_stride + p] = max(what it held, max over g < G of s of the
+ *                           cell (g, p)) for p < P -- d_maxs points at the batch's first column inside a double
+ *                           [T][maxs_stride] array that the caller fills with zeros before the first batch; columns
+ *                           at and past P are not written.  The maximum is exact and does not depend on the order the
+ *                           blocks run in (a 64-bit unsigned atomic maximum on the bits of the non-negative double)
+ *   scoary_permute_gcmh_wy  scoary_permute_gcmh in the same way: d_r as there, bit for bit, and d_maxs the maximum of
+ *                           Q over the genes; the comparison point of the family-wise count is scoary_gcmh's d_thr
+ * Asynchronous on `stream`, nothing is allocated.  SCOARY_ERR_ARG: null pointer, size < 1, maxs_stride < P;
+ * SCOARY_ERR_SIZE, with nothing written: K outside [1, 8], N > scoary_ranksum_max_isolates(), T > 65535, G or
+ * P >= 2^31. */
+int scoary_cat_wy_prepare(scoary_handle h, const int32_t *d_a, const int32_t *d_nk, int64_t G, int64_t T, int64_t K,
+                          double *d_inv, double *d_ivm, double *d_sobs, double *d_thr, scoary_stream_t stream);
+int scoary_permute_cat_wy(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_rows, const int32_t *d_a,
+                          const int32_t *d_nk, const uint64_t *d_w, const double *d_inv, const double *d_ivm,
+                          int64_t G, int64_t T, int64_t N, int64_t P, int32_t *d_r, double *d_maxs,
+                          int64_t maxs_stride, scoary_stream_t stream);
+int scoary_permute_gcmh_wy(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_rows, const double *d_form,
+                           const double *d_thr, const int32_t *d_nk, int64_t G, int64_t T, int64_t N, int64_t P,
+                           int32_t *d_r, double *d_maxs, int64_t maxs_stride, scoary_stream_t stream);
 /* ---- Quantitative traits over strata: the van Elteren test with value permutations within the strata (spec S16 of
  * DESIGN.md; additive, ABI 11) ----
  * The strata are d_strata uint16 [N] (the stratum of every isolate, in [0, S)) and d_members int32 [N] (the isolates

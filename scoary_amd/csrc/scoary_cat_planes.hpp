@@ -1,6 +1,7 @@
 // scoary_cat_planes.hpp -- the class bit planes of a stage of permuted code rows and the popcount walk over them,
 // shared by the translation units that count a gene's 2 x K table under label permutations (scoary_categorical.hip:
-// spec S20; scoary_gcmh.hip: spec S21), so that both compile the same text.
+// spec S20; scoary_gcmh.hip: spec S21; scoary_cat_wy.hip: spec S22), so that all compile the same text; and the
+// 128-bit product of S20's integer comparison, which scoary_categorical.hip and scoary_cat_wy.hip make alike.
 #ifndef SCOARY_CAT_PLANES_HPP
 #define SCOARY_CAT_PLANES_HPP
 #include "scoary_common.hpp"
@@ -45,6 +46,13 @@ __device__ __forceinline__ void cat_count(const uint32_t* __restrict__ planes, i
       }
     }
   }
+}
+
+// d w as a signed 128-bit integer, d signed and w unsigned
+__device__ __forceinline__ __int128 cat_mul(int64_t d, uint64_t w) {
+  const uint64_t ud = (uint64_t)d;
+  const uint64_t hi = __umul64hi(ud, w) - (d < 0 ? w : 0ull);
+  return (__int128)(((unsigned __int128)hi << 64) | (unsigned __int128)(ud * w));
 }
 
 }  // namespace

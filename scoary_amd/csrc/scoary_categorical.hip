@@ -21,13 +21,6 @@
 
 namespace {
 
-// d w as a signed 128-bit integer, d signed and w unsigned
-__device__ __forceinline__ __int128 cat_mul(int64_t d, uint64_t w) {
-  const uint64_t ud = (uint64_t)d;
-  const uint64_t hi = __umul64hi(ud, w) - (d < 0 ? w : 0ull);
-  return (__int128)(((unsigned __int128)hi << 64) | (unsigned __int128)(ud * w));
-}
-
 // Observed table and statistic.  Block = 256 genes of one trait, a gene per lane; the trait's code row in LDS, a byte
 // per isolate.  A lane counts the classes 1 .. 8 of its gene's isolates in eight 16-bit fields of two 64-bit words.
 __global__ __launch_bounds__(256) void k_cat_observed(const uint4* __restrict__ tiled, int64_t Gp, int G, int N, int K,

@@ -19,43 +19,13 @@
 #include "scoary_cat_planes.hpp"
 #include "scoary_chi2.hpp"
 #include "scoary_common.hpp"
+#include "scoary_gcmh_form.hpp"
 
 namespace {
 
 constexpr int kGcmhThreads = 256;                 // k_gcmh_observed: a gene per lane
-constexpr int kGcmhMults = kCatPlanes * (kCatPlanes - 1) / 2;
-constexpr int kGcmhForm = kCatPlanes + kGcmhMults + kCatPlanes;       // E[7], f[21], invp[7]
 constexpr double kGcmhTheta = 1e-8;               // pivot j is skipped iff p_j <= theta V_jj (measured, DESIGN S21)
 constexpr double kGcmhTau = 1e-6;                 // thr = Q_obs (1 - tau): S10's band
-
-__host__ __device__ constexpr int gcmh_f(int i, int j) { return i * (i - 1) / 2 + j; }   // f_ij, j < i
-
-// Q of the counts a under a form, over the first NC contrasts (the others add +0.0 where their form entries are 0:
-// the same bits for every NC that covers the trait's contrasts).  fp64, every operation rounded on its own.
-template <int NC>
-__device__ __forceinline__ double gcmh_q(const double* __restrict__ form, const uint32_t (&a)[kCatPlanes]) {
-  double y[NC];
-#pragma unroll
-  for (int i = 0; i < NC; ++i) {
-    double x = (double)a[i] - form[i];
-#pragma unroll
-    for (int j = 0; j < i; ++j) x = x - form[kCatPlanes + gcmh_f(i, j)] * y[j];
-    y[i] = x;
-  }
-  double q = 0.0;
-#pragma unroll
-  for (int j = 0; j < NC; ++j) q += (y[j] * y[j]) * form[kCatPlanes + kGcmhMults + j];
-  return q;
-}
-
-// the last class (1-based) with n_k > 0 among the first K; wave-uniform
-__device__ __forceinline__ int gcmh_klast(const int32_t* __restrict__ nkt, int K) {
-  int klast = 0;
-#pragma unroll
-  for (int k = 0; k < kCatMaxClasses; ++k)
-    if (k < K && nkt[k] > 0) klast = k + 1;
-  return klast;
-}
 
 // Observed statistic.  Block = 256 genes of one trait, a gene per lane; the trait's code row in LDS, a byte per
 // isolate, clamped into [0, 8].  The lane walks the segment table as k_vanelteren does (stratum and word clamped: a

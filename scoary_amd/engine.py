@@ -1981,8 +1981,10 @@ class AssociationEngine:
         per = max(2 * 64 * int(T) * int(N), 1)
         return int(max(64, min(-(-permutations // 64) * 64, budget_bytes // per * 64)))
 
-    def permute_categorical(self, genes, plan, a_obs, rows, r):
-        """r[t, g] += #{rows[t, p] : S_p >= S_obs}, decided in integers (k_cat_permute); rows int16 [T, P, N]."""
+    def permute_categorical(self, genes, plan, a_obs, rows, r, maxt=None):
+        """r[t, g] += #{rows[t, p] : S_p >= S_obs}, decided in integers (k_cat_permute); rows int16 [T, P, N].
+        ``maxt`` = (inv float64 [T, 8], ivm float64 [T, G], maxs float64 [T, >= P], the batch's columns of an array of
+        zeros) picks k_cat_maxt instead (spec S22): the same counts, and the batch's maxima into maxs."""
         torch = _torch()
         T, G, N = plan.T, genes.G, plan.N
         if rows.dim() != 3 or (rows.shape[0], rows.shape[2]) != (T, N) or rows.dtype != torch.int16 \
@@ -1990,15 +1992,36 @@ class AssociationEngine:
             raise ValueError("permute_categorical: rows are int16 [T, P, N], contiguous")
         if tuple(r.shape) != (T, G) or r.dtype != torch.int32 or not r.is_contiguous():
             raise ValueError("permute_categorical: r is int32 [T, G], contiguous")
-        self._check(self.lib.scoary_permute_categorical(
+        if maxt is None:
+            self._check(self.lib.scoary_permute_categorical(
+                self.h, self._ptr(genes.tiled), self._ptr(rows), self._ptr(a_obs), self._ptr(plan.nk),
+                self._ptr(plan.w), G, T, N, int(rows.shape[1]), self._ptr(r), self._stream()),
+                "scoary_permute_categorical")
+            return r
+        inv, ivm, maxs = maxt
+        if tuple(inv.shape) != (T, 8) or tuple(ivm.shape) != (T, G) or inv.dtype != torch.float64 \
+                or ivm.dtype != torch.float64 or not inv.is_contiguous() or not ivm.is_contiguous():
+            raise ValueError("permute_categorical: inv and ivm are categorical_wy_prepare's, float64 [T, 8] and [T, G]")
+        self._check(self.lib.scoary_permute_cat_wy(
             self.h, self._ptr(genes.tiled), self._ptr(rows), self._ptr(a_obs), self._ptr(plan.nk), self._ptr(plan.w),
-            G, T, N, int(rows.shape[1]), self._ptr(r), self._stream()), "scoary_permute_categorical")
+            self._ptr(inv), self._ptr(ivm), G, T, N, int(rows.shape[1]), self._ptr(r), self._ptr(maxs),
+            self._maxs_stride("permute_categorical", maxs, T, int(rows.shape[1])), self._stream()),
+            "scoary_permute_cat_wy")
         return r
 
-    def categorical_permute(self, genes, plan, a_obs, permutations, seed, budget_bytes=8 << 30):
+    def _maxs_stride(self, what, maxs, T, P):
+        """The row stride of a batch's columns of maxs (float64 [T, >= P], unit stride along the permutations)."""
+        torch = _torch()
+        if maxs.dim() != 2 or maxs.shape[0] != T or maxs.shape[1] < P or maxs.dtype != torch.float64 \
+                or maxs.stride(1) != 1 or (T > 1 and maxs.stride(0) < P):
+            raise ValueError("%s: maxs is float64 [T, >= P], the batch's columns of a contiguous array" % what)
+        return max(int(maxs.stride(0)), P)
+
+    def categorical_permute(self, genes, plan, a_obs, permutations, seed, budget_bytes=8 << 30, maxt=None):
         """r int32 [T, G] = #{pi < permutations : X2_pi >= X2_obs} under code shuffles (spec S20), in batches of
         categorical_batch() permutations: the rank-sum generator writes a batch's code rows and k_cat_permute adds
-        its counts."""
+        its counts.  ``maxt`` = (inv, ivm, maxs float64 [T, permutations] of zeros) picks k_cat_maxt (spec S22): a
+        batch's maxima go into its columns of maxs."""
         torch = _torch()
         self._ranksum_fits("categorical_permute", genes, plan)
         T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
@@ -2008,8 +2031,36 @@ class AssociationEngine:
         batch = self.categorical_batch(T, N, P, budget_bytes)
         for base in range(0, P, batch):
             self.permute_categorical(genes, plan, a_obs, self.categorical_rows(plan, base, min(batch, P - base), seed),
-                                     r)
+                                     r, maxt=None if maxt is None else (maxt[0], maxt[1], maxt[2][:, base:]))
         return r
+
+    def categorical_wy_prepare(self, plan, a_obs):
+        """(inv float64 [T, 8], ivm, s_obs, thr float64 [T, G]) of spec S22 from the observed a of categorical():
+        the reciprocals of the class sizes and of m (n - m) (0 where the gene is untestable), the statistic of the
+        observed table by the device function of the hot path, and thr = s_obs (1 - 1e-9)."""
+        torch = _torch()
+        T = plan.T
+        if a_obs.dim() != 3 or a_obs.shape[0] != T or a_obs.shape[2] != 8 or a_obs.dtype != torch.int32 \
+                or not a_obs.is_contiguous():
+            raise ValueError("categorical_wy_prepare: a_obs is the observed a, int32 [T, G, 8], contiguous")
+        G = int(a_obs.shape[1])
+        inv = self._empty((T, 8), torch.float64)
+        ivm, sobs, thr = (self._empty((T, G), torch.float64) for _ in range(3))
+        self._check(self.lib.scoary_cat_wy_prepare(
+            self.h, self._ptr(a_obs), self._ptr(plan.nk), G, T, plan.K, self._ptr(inv), self._ptr(ivm),
+            self._ptr(sobs), self._ptr(thr), self._stream()), "scoary_cat_wy_prepare")
+        return inv, ivm, sobs, thr
+
+    def categorical_westfall_young(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
+        """Westfall-Young single-step maxT over the chi-square statistic (spec S22) of the step ``res`` =
+        categorical(genes, plan): (r, r_fwer, maxs) -- r int32 [T, G] as categorical_permute returns it, r_fwer int32
+        [T, G] = #{pi : maxs[t, pi] >= thr[t, g]}, maxs float64 [T, permutations] -- from one pass of k_cat_maxt over
+        categorical_permute's batches."""
+        torch = _torch()
+        inv, ivm, _sobs, thr = self.categorical_wy_prepare(plan, res["a"])
+        maxs = torch.zeros((plan.T, int(permutations)), dtype=torch.float64, device=self.device)
+        r = self.categorical_permute(genes, plan, res["a"], permutations, seed, budget_bytes, maxt=(inv, ivm, maxs))
+        return r, self.r_fwer_max(maxs, thr), maxs
 
     # -- categorical traits over strata: the generalized CMH test (spec S21) -------------
     def gcmh_plan(self, codes, strata):
@@ -2067,8 +2118,10 @@ class AssociationEngine:
             "scoary_vanelteren_perm_generate")
         return out
 
-    def permute_gcmh(self, genes, plan, res, rows, r):
-        """r[t, g] += #{rows[t, p] : Q_p >= thr} (k_gcmh_permute); res = gcmh(genes, plan), rows int16 [T, P, N]."""
+    def permute_gcmh(self, genes, plan, res, rows, r, maxt=None):
+        """r[t, g] += #{rows[t, p] : Q_p >= thr} (k_gcmh_permute); res = gcmh(genes, plan), rows int16 [T, P, N].
+        ``maxt`` = maxs float64 [T, >= P], the batch's columns of an array of zeros, picks k_gcmh_maxt instead (spec
+        S22): the same counts, and the batch's maxima of Q into maxs."""
         torch = _torch()
         T, G, N = plan.T, genes.G, plan.N
         form, thr = res["form"], res["thr"]
@@ -2080,23 +2133,41 @@ class AssociationEngine:
             raise ValueError("permute_gcmh: rows are int16 [T, P, N], contiguous")
         if tuple(r.shape) != (T, G) or r.dtype != torch.int32 or not r.is_contiguous():
             raise ValueError("permute_gcmh: r is int32 [T, G], contiguous")
-        self._check(self.lib.scoary_permute_gcmh(
+        if maxt is None:
+            self._check(self.lib.scoary_permute_gcmh(
+                self.h, self._ptr(genes.tiled), self._ptr(rows), self._ptr(form), self._ptr(thr), self._ptr(plan.nk),
+                G, T, N, int(rows.shape[1]), self._ptr(r), self._stream()), "scoary_permute_gcmh")
+            return r
+        self._check(self.lib.scoary_permute_gcmh_wy(
             self.h, self._ptr(genes.tiled), self._ptr(rows), self._ptr(form), self._ptr(thr), self._ptr(plan.nk),
-            G, T, N, int(rows.shape[1]), self._ptr(r), self._stream()), "scoary_permute_gcmh")
+            G, T, N, int(rows.shape[1]), self._ptr(r), self._ptr(maxt),
+            self._maxs_stride("permute_gcmh", maxt, T, int(rows.shape[1])), self._stream()), "scoary_permute_gcmh_wy")
         return r
 
-    def gcmh_permute(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
+    def gcmh_permute(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30, maxt=None):
         """r int32 [T, G] = #{pi < permutations : Q_pi >= Q_obs (1 - 1e-6)} under code shuffles within the strata
         (spec S21), in categorical_batch() permutations a batch: the van Elteren generator writes a batch's code rows
-        and k_gcmh_permute adds its counts."""
+        and k_gcmh_permute adds its counts.  ``maxt`` = maxs float64 [T, permutations] of zeros picks k_gcmh_maxt (spec
+        S22): a batch's maxima go into its columns of maxs."""
         torch = _torch()
         self._ranksum_fits("gcmh_permute", genes, plan)
         T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
         r = torch.zeros((T, G), dtype=torch.int32, device=self.device)
         batch = self.categorical_batch(T, N, P, budget_bytes)
         for base in range(0, P, batch):
-            self.permute_gcmh(genes, plan, res, self.gcmh_rows(plan, base, min(batch, P - base), seed), r)
+            self.permute_gcmh(genes, plan, res, self.gcmh_rows(plan, base, min(batch, P - base), seed), r,
+                              maxt=None if maxt is None else maxt[:, base:])
         return r
+
+    def gcmh_westfall_young(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
+        """Westfall-Young single-step maxT over the generalized CMH statistic (spec S22) of the step ``res`` =
+        gcmh(genes, plan): (r, r_fwer, maxs) -- r int32 [T, G] as gcmh_permute returns it, r_fwer int32 [T, G] =
+        #{pi : maxs[t, pi] >= thr[t, g]} with S21's thr, maxs float64 [T, permutations] -- from one pass of
+        k_gcmh_maxt over gcmh_permute's batches."""
+        torch = _torch()
+        maxs = torch.zeros((plan.T, int(permutations)), dtype=torch.float64, device=self.device)
+        r = self.gcmh_permute(genes, plan, res, permutations, seed, budget_bytes, maxt=maxs)
+        return r, self.r_fwer_max(maxs, res["thr"]), maxs
 
     # -- quantitative traits: the Hodges-Lehmann shift and its limits (spec S19) --------
     def ranksum_shift_plan(self, values):

@@ -1804,6 +1804,11 @@ def ScoaryArgumentParser(argv=None):
                    "of --permute-strata. Adds the generalized Cochran-Mantel-Haenszel test of every gene against "
                    "each trait over the strata, written to <trait>.gcmh.results.csv; --permute adds Empirical_p "
                    "from label shuffles within the strata. The chi-square results stay as they are")
+    a.add_argument("--categorical-fwer", dest="categorical_fwer", action="store_true", default=False,
+                   help="With --categorical and --permute X (X >= 10): add the column Westfall_Young_p to the chi-square "
+                   "results -- and, with --categorical-strata, to the generalized CMH results -- the single-step maxT "
+                   "family-wise p over all genes of the table, from the same permutations that give Empirical_p "
+                   "(single process; scoary_amd extension)")
     a.add_argument("--quantitative-strata", dest="quantitative_strata", metavar="FILE", default=None,
                    help="With --quantitative: FILE names a stratum (lineage, cluster) for every isolate, in the format "
                    "of --permute-strata's file.  Every measured trait is additionally tested with the van Elteren "
@@ -2035,15 +2040,16 @@ def main(**kwargs):
                                            genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
         if getattr(args, "categorical", None) and rank == 0:
             names, labels = read_categorical_file(args.categorical, args.delimiter, strains)
+            cfwer = bool(getattr(args, "categorical_fwer", False))
             with _stage("chi-square test of the categorical traits"):
                 StoreCategoricalResults(Categorical_results(genedic, names, labels, permutations=args.permute,
-                                                            seed=seed, exits=True),
+                                                            seed=seed, exits=True, fwer=cfwer),
                                         genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
             if getattr(args, "categorical_strata", None):
                 cstrata = strata_indices(args.categorical_strata_map, strains)[0]
                 with _stage("generalized CMH test of the categorical traits"):
                     StoreGcmhResults(Gcmh_results(genedic, names, labels, cstrata, permutations=args.permute,
-                                                  seed=seed),
+                                                  seed=seed, fwer=cfwer),
                                      genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
         log.info("Stage seconds: load (+tree) %.2f, association (+permutations) %.2f, pairwise stage and "
                  "output %.2f" % (t_loaded - start, t_stats - t_loaded, _time.time() - t_stats))
@@ -2354,12 +2360,17 @@ def read_categorical_file(path, delimiter, strains):
 
 
 def Categorical_results(genedic, names, labels, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False,
-                        strata=None, exits=False):
+                        strata=None, exits=False, fwer=False):
     """The chi-square stage (spec S20) of the traits ``names`` with the labels [T][N] (a string per isolate, None =
     missing) over the isolates of ``genedic``: {name: dict(classes, n, nk [K], df, a [G, K], m, x2, v, p, testable
-    [G]; r [G] and permutations with permutations >= 10)}, arrays in the gene table's order.  Raises ValueError where
-    the command line refuses --categorical (``exits``: exits with the command line's message instead)."""
+    [G]; r [G] and permutations with permutations >= 10; r_fwer [G] with ``fwer``, spec S22)}, arrays in the gene
+    table's order.  Raises ValueError where the command line refuses --categorical or --categorical-fwer (``exits``:
+    exits with the command line's message instead)."""
     for text in _categorical_refusals(no_pairwise, collapse, strata is not None, names, labels, exits=exits):
+        if exits:
+            sys.exit(text)
+        raise ValueError(text)
+    for text in _cat_wy_refusals(fwer, True, permutations):
         if exits:
             sys.exit(text)
         raise ValueError(text)
@@ -2380,8 +2391,10 @@ def Categorical_results(genedic, names, labels, permutations=0, seed=DEFAULT_SEE
     plan = eng.categorical_plan(codes)
     res = eng.categorical(genes, plan)
     permutations = int(permutations)
-    r = None
-    if permutations >= 10:
+    r = r_fwer = None
+    if fwer:
+        r, r_fwer = (x.cpu().numpy() for x in eng.categorical_westfall_young(genes, plan, res, permutations, seed)[:2])
+    elif permutations >= 10:
         r = eng.categorical_permute(genes, plan, res["a"], permutations, seed).cpu().numpy()
     a, m, x2, p, v = (res[k].cpu().numpy() for k in ("a", "m", "x2", "p", "v"))
     out = {}
@@ -2393,6 +2406,8 @@ def Categorical_results(genedic, names, labels, permutations=0, seed=DEFAULT_SEE
         if r is not None:
             out[name]["r"] = r[t]
             out[name]["permutations"] = permutations
+        if r_fwer is not None:
+            out[name]["r_fwer"] = r_fwer[t]
         log.info("Chi-square test of %s: %d isolates with a label in %d classes, %d genes tested"
                  % (name, n, K, int(testable.sum())))
     return out
@@ -2416,7 +2431,9 @@ def StoreCategoricalResults(results, genedic, max_hits, outdir, time="", delimit
     files = []
     for name, res in results.items():
         with_emp = "r" in res
-        columns = ROARY_HEAD + list(CATEGORICAL_COLUMNS) + (["Empirical_p"] if with_emp else [])
+        with_wy = with_emp and "r_fwer" in res
+        columns = ROARY_HEAD + list(CATEGORICAL_COLUMNS) + (["Empirical_p"] if with_emp else []) \
+            + (["Westfall_Young_p"] if with_wy else [])
         idx = np.flatnonzero(res["testable"])
         fname = outdir + name + time + ".categorical.results.csv"
         with open(fname, "w") as out:
@@ -2438,6 +2455,8 @@ def StoreCategoricalResults(results, genedic, max_hits, outdir, time="", delimit
                               _fmt(res["v"][g]), _fmt(res["p"][g]), _fmt(bonf[k]), _fmt(bh[k])]
                     if with_emp:
                         cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
+                    if with_wy:
+                        cells.append(_fmt((int(res["r_fwer"][g]) + 1.0) / (res["permutations"] + 1.0)))
                     out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
         log.info("Storing chi-square results: %s" % fname)
         files.append(fname)
@@ -2458,13 +2477,16 @@ GCMH_TEXT = {
 }
 
 
-def Gcmh_results(genedic, names, labels, strata, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False):
+def Gcmh_results(genedic, names, labels, strata, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False,
+                 fwer=False):
     """The generalized CMH stage (spec S21) of the traits ``names`` with the labels [T][N] (a string per isolate, None
     = missing) and the stratum index of every isolate ``strata`` (N integers) over the isolates of ``genedic``: {name:
     dict(classes, n, strata (those with a labelled isolate), a [G, K], e [G, K], m, q, df, p, testable [G]; r [G] and
-    permutations with permutations >= 10)}, arrays in the gene table's order.  Raises ValueError where the command
-    line refuses --categorical."""
+    permutations with permutations >= 10; r_fwer [G] with ``fwer``, spec S22)}, arrays in the gene table's order.
+    Raises ValueError where the command line refuses --categorical or --categorical-fwer."""
     for text in _categorical_refusals(no_pairwise, collapse, False, names, labels):
+        raise ValueError(text)
+    for text in _cat_wy_refusals(fwer, True, permutations):
         raise ValueError(text)
     table = _as_table(genedic)
     eng = get_engine()
@@ -2490,8 +2512,10 @@ def Gcmh_results(genedic, names, labels, strata, permutations=0, seed=DEFAULT_SE
     plan = eng.gcmh_plan(codes, strata)
     res = eng.gcmh(genes, plan)
     permutations = int(permutations)
-    r = None
-    if permutations >= 10:
+    r = r_fwer = None
+    if fwer:
+        r, r_fwer = (x.cpu().numpy() for x in eng.gcmh_westfall_young(genes, plan, res, permutations, seed)[:2])
+    elif permutations >= 10:
         r = eng.gcmh_permute(genes, plan, res, permutations, seed).cpu().numpy()
     a, e, m, q, df, p = (res[k].cpu().numpy() for k in ("a", "e", "m", "q", "df", "p"))
     out = {}
@@ -2502,6 +2526,8 @@ def Gcmh_results(genedic, names, labels, strata, permutations=0, seed=DEFAULT_SE
         if r is not None:
             out[name]["r"] = r[t]
             out[name]["permutations"] = permutations
+        if r_fwer is not None:
+            out[name]["r_fwer"] = r_fwer[t]
         log.info("Generalized CMH test of %s: %d isolates with a label in %d classes and %d strata, %d genes tested"
                  % (name, out[name]["n"], K, out[name]["strata"], int(out[name]["testable"].sum())))
     return out
@@ -2524,7 +2550,9 @@ def StoreGcmhResults(results, genedic, max_hits, outdir, time="", delimiter=",")
     files = []
     for name, res in results.items():
         with_emp = "r" in res
-        columns = ROARY_HEAD + list(GCMH_COLUMNS) + (["Empirical_p"] if with_emp else [])
+        with_wy = with_emp and "r_fwer" in res
+        columns = ROARY_HEAD + list(GCMH_COLUMNS) + (["Empirical_p"] if with_emp else []) \
+            + (["Westfall_Young_p"] if with_wy else [])
         idx = np.flatnonzero(res["testable"])
         fname = outdir + name + time + ".gcmh.results.csv"
         with open(fname, "w") as out:
@@ -2547,10 +2575,34 @@ def StoreGcmhResults(results, genedic, max_hits, outdir, time="", delimiter=",")
                               _fmt(res["p"][g]), _fmt(bonf[k]), _fmt(bh[k])]
                     if with_emp:
                         cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
+                    if with_wy:
+                        cells.append(_fmt((int(res["r_fwer"][g]) + 1.0) / (res["permutations"] + 1.0)))
                     out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
         log.info("Storing generalized CMH results: %s" % fname)
         files.append(fname)
     return files
+
+
+# ---------------------------------------------------------------------------
+# --categorical-fwer: Westfall-Young single-step maxT over the chi-square and the generalized CMH statistic (spec
+# S22): one more column, Westfall_Young_p, behind Empirical_p in the chi-square file and -- with --categorical-strata
+# -- the generalized CMH file.  Nothing of the binary step's option tables (FLAG_RULES, OPTIONAL_COLUMNS) knows of it.
+# ---------------------------------------------------------------------------
+# a refusal, worded alike on the command line and in Categorical_results / Gcmh_results (fwer=True)
+CAT_WY_TEXT = {
+    "categorical": "Cannot use --categorical-fwer without --categorical. It is the family-wise p of the tests of the "
+                   "categorical traits",
+    "permute": "Cannot use --categorical-fwer without --permute X, X >= 10. The family-wise p is counted over the "
+               "permutations of the labels",
+}
+
+
+def _cat_wy_refusals(fwer, categorical, permutations):
+    """The messages of the --categorical-fwer rules that a run breaks, in the order they are reported."""
+    if fwer and not categorical:
+        yield CAT_WY_TEXT["categorical"]
+    if fwer and int(permutations or 0) < 10:
+        yield CAT_WY_TEXT["permute"]
 
 
 # ---------------------------------------------------------------------------
@@ -2852,6 +2904,9 @@ def _validate(args, cutoffs):
         labels = strata_indices(args.categorical_strata_map, _analysed_isolates(args))[1]
         if len(labels) > _abi.PERM_MAX_STRATA:
             sys.exit(GCMH_TEXT["strata"] % (cstrata, len(labels), _abi.PERM_MAX_STRATA))
+    for text in _cat_wy_refusals(getattr(args, "categorical_fwer", False), bool(getattr(args, "categorical", None)),
+                                 args.permute):
+        sys.exit(text)
     qstrata = getattr(args, "quantitative_strata", None)
     if qstrata:
         if not getattr(args, "quantitative", None):

@@ -1,5 +1,6 @@
 // scoary_categorical.hip -- categorical traits: the Pearson chi-square test of a gene against a label of up to eight
-// classes (a 2 x K table per gene), with label permutations (spec S20 of DESIGN.md).
+// classes (a 2 x K table per gene), with label permutations (spec S20 of DESIGN.md) and their Westfall-Young maxima
+// (spec S22).
 //
 // The host numbers a trait's classes 1 .. K (0 = missing): a trait is its row of class codes (int16), the class sizes
 // n_k over the isolates with a code, and the weights w_k = lcm{n_k > 0} / n_k as two 64-bit limbs.  Everything per
@@ -9,12 +10,15 @@
 //   k_cat_observed  (observed)      a[8], m, X2, p and Cramer's V of every (trait, gene): k_ranksum's shape, a bit
 //                                   walk over the tiled matrix with the trait's code row in LDS; not the hot path
 //   k_cat_permute   (the hot path)  block = one stage of 64 permutations of one trait x a strided share of the gene
-//                                   groups.  The stage's 64 code rows stand in LDS as class bit planes, a word per
-//                                   (class, 32 isolates, permutation); a lane is a permutation, a wavefront takes four
-//                                   genes at a time and adds popc(gene word & plane word) per class -- the gene words
-//                                   are wave-uniform, a plane word is read once for the four genes; behind a gene's
-//                                   last chunk of isolates the permuted table is compared exactly with the observed
-//                                   one and the lanes' verdicts are counted
+//                                   groups (CatStage, scoary_cat_planes.hpp).  The stage's 64 code rows stand in LDS
+//                                   as class bit planes, a word per (class, 32 isolates, permutation); a lane is a
+//                                   permutation, a wavefront takes four genes at a time and adds popc(gene word &
+//                                   plane word) per class; behind a gene's last chunk of isolates the permuted table
+//                                   is compared exactly with the observed one and the lanes' verdicts are counted
+//   k_cat_maxt      (the hot path)  the same block (k_cat_permute_t<true>) with S22's statistic s of the same a_k
+//                                   next to the comparison and a running maximum of it that a lane keeps in a register
+//                                   over all gene groups its block walks; at the end of the block one 64-bit unsigned
+//                                   atomic maximum per lane.  inv, ivm: k_cat_wy_prepare's (scoary_cat_wy.hip)
 #include "scoary_cat_planes.hpp"
 #include "scoary_chi2.hpp"
 #include "scoary_common.hpp"
@@ -93,75 +97,37 @@ __global__ __launch_bounds__(256) void k_cat_observed(const uint4* __restrict__ 
   d_v[o] = v;
 }
 
-// Block = stage blockIdx.x % S (64 permutations) of trait blockIdx.y x the gene groups rng, rng + ranges, .. of
-// kCatGroup genes; wavefront w of a group counts its genes kCatHold w .. + kCatHold - 1; a lane is a permutation.
-// Per group and chunk of kCatChunk isolates: the chunk of the 64 code rows goes to LDS as class planes (a wavefront
-// reads 64 isolates of one row, coalesced, and a ballot per class gives two plane words; with one chunk in all the
-// planes are built once per block), and every wavefront counts its genes against them (cat_count).  Isolates past N
-// and permutations past P have no class, and a code that is none of 1 .. 8 matches no plane: no mask is needed and a
-// bad row gives wrong numbers only.  Behind the last chunk, per gene and lane: a_k = the count, the last non-empty
-// class a = m - the others, d_k = a_k^2 - a_obs,k^2, H = sum d_k w_hi,k, Lo = sum d_k w_lo,k, and the permutation
-// counts iff H + (Lo >> 64) >= 0 (spec S20: the sign of sum d_k L / n_k in integers).
-__global__ __launch_bounds__(kCatThreads) void k_cat_permute(const uint32_t* __restrict__ tiled, int64_t Gp, int G,
-                                                             int N, const int16_t* __restrict__ rows, int64_t P, int S,
-                                                             const int32_t* __restrict__ aobs,
-                                                             const int32_t* __restrict__ nk,
-                                                             const uint64_t* __restrict__ wt, int ranges,
-                                                             int lds_words, int32_t* __restrict__ d_r) {
+// The block of k_cat_permute (MAXT = false) and of k_cat_maxt (true): CatStage's, see scoary_cat_planes.hpp.  Behind
+// the last chunk, per gene and lane: a_k = the count, the last non-empty class a = m - the others, d_k = a_k^2 -
+// a_obs,k^2, H = sum d_k w_hi,k, Lo = sum d_k w_lo,k, and the permutation counts iff H + (Lo >> 64) >= 0 (spec S20:
+// the sign of sum d_k L / n_k in integers).  MAXT, next to it: the class's term of s from the same a_k (n, m n_k,
+// inv[k] and ivm[g] are wave-uniform) and mx = max(mx, s); mx lives across all gene groups the block walks, and at
+// the end every lane whose permutation is < P combines it into maxs[t][64 s + lane]: one atomic per lane and block,
+// never one per gene.  Permutations past P and genes >= G reach neither d_r nor maxs.
+template <bool MAXT>
+__device__ __forceinline__ void k_cat_permute_t(const uint32_t* tiled, int64_t Gp, int G, int N, const int16_t* rows,
+                                                int64_t P, int S, const int32_t* aobs, const int32_t* nk,
+                                                const uint64_t* wt, const double* d_inv, const double* d_ivm,
+                                                int ranges, int lds_words, int32_t* d_r, double* d_maxs,
+                                                int64_t maxs_stride) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   uint32_t* planes = reinterpret_cast<uint32_t*>(lds);
-  const int t = blockIdx.y, s = blockIdx.x % S, rng = blockIdx.x / S;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int t = blockIdx.y;
   const int32_t* nkt = nk + t * kCatMaxClasses;
-  int klast = 0;
+  int klast = 0, n = 0;
 #pragma unroll
   for (int k = 0; k < kCatMaxClasses; ++k)
-    if (nkt[k] > 0) klast = k + 1;
-  const bool wide = klast > 4;
-  const int nf = wide ? kCatPlanes : 3;
+    if (nkt[k] > 0) klast = k + 1, n += nkt[k];
+  CatStage st(N, G, P, S, klast);
+  const int lane = st.lane;
   const uint64_t* w = wt + (int64_t)t * 2 * kCatMaxClasses;
-  const int nw = (N + 31) / 32;
-  const int nchunks = (nw + kCatChunkWords - 1) / kCatChunkWords;
-  const int ngroups = (G + kCatGroup - 1) / kCatGroup;
-  const bool counted = (int64_t)s * 64 + lane < P;
+  const double* inv = d_inv + t * kCatMaxClasses;
 
-  // chunk c -> LDS: wavefront iteration = (permutation p, word pair wp); lanes 0 and 1 write the two words of a plane
-  auto load = [&](int c) {
-    const int npairs = lds_words / 2;
-    for (int it = wave; it < 64 * npairs; it += kCatWaves) {
-      const int p = it / npairs, wp = it - p * npairs;
-      const int64_t col = (int64_t)s * 64 + p;
-      const int i = (c * kCatChunkWords + 2 * wp) * 32 + lane;
-      int code = 0;
-      if (i < N && col < P) code = rows[((int64_t)t * P + col) * N + i];
-      for (int k = 0; k < nf; ++k) {
-        const uint64_t m64 = __ballot(code == k + 1);
-        if (lane < 2) planes[(k * lds_words + 2 * wp + lane) * 64 + p] = lane ? (uint32_t)(m64 >> 32) : (uint32_t)m64;
-      }
-    }
-  };
-
-  bool loaded = false;
-  for (int grp = rng; grp < ngroups; grp += ranges) {
-    const int g0 = grp * kCatGroup + wave * kCatHold;
-    uint32_t cnt[kCatHold][kCatPlanes];
-#pragma unroll
-    for (int j = 0; j < kCatHold; ++j)
-#pragma unroll
-      for (int k = 0; k < kCatPlanes; ++k) cnt[j][k] = 0u;
-    for (int c = 0; c < nchunks; ++c) {
-      if (!loaded || nchunks > 1) {
-        __syncthreads();
-        load(c);
-        __syncthreads();
-        loaded = true;
-      }
-      const int nquads = (min(kCatChunkWords, nw - c * kCatChunkWords) + 3) / 4;
-      const uint4* tq = reinterpret_cast<const uint4*>(tiled) + (int64_t)c * (kCatChunkWords / 4) * Gp + g0;
-      if (wide) cat_count<kCatPlanes>(planes + lane, lds_words, tq, Gp, nquads, cnt);
-      else cat_count<3>(planes + lane, lds_words, tq, Gp, nquads, cnt);
-    }
+  double mx = 0.0;
+  for (int grp = st.rng; grp < st.ngroups; grp += ranges) {
+    const int g0 = st.first_gene(grp);
+    uint32_t cnt[kCatHold][kCatPlanes] = {};
+    st.count_group(grp, planes, lds_words, tiled, Gp, rows, P, N, cnt);
 #pragma unroll
     for (int j = 0; j < kCatHold; ++j) {
       const int g = g0 + j;
@@ -172,6 +138,7 @@ __global__ __launch_bounds__(kCatThreads) void k_cat_permute(const uint32_t* __r
       for (int k = 0; k < kCatMaxClasses; ++k) m += ao[k];
       __int128 H = 0, Lo = 0;
       int sum = 0;
+      double tot = 0.0;
 #pragma unroll 1                                   // (unrolled, the sixteen limbs wait in SGPRs across the count)
       for (int k = 0; k < klast; ++k) {
         int a;
@@ -187,23 +154,38 @@ __global__ __launch_bounds__(kCatThreads) void k_cat_permute(const uint32_t* __r
         const int64_t d = (int64_t)a * a - o * o;
         H += cat_mul(d, w[2 * k + 1]);
         Lo += cat_mul(d, w[2 * k]);
+        if constexpr (MAXT) tot = cat_wy_add(tot, n, a, m * nkt[k], inv[k]);
       }
-      const bool ge = H + (Lo >> 64) >= 0;
-      const int hits = __popcll(__ballot(ge && counted));
-      if (lane == 0 && hits) atomicAdd(d_r + (int64_t)t * G + g, hits);
+      cat_hits(H + (Lo >> 64) >= 0, st.counted, lane, d_r + (int64_t)t * G + g);
+      if constexpr (MAXT) mx = fmax(mx, tot * d_ivm[(int64_t)t * G + g]);
     }
   }
+  if constexpr (MAXT)
+    if (st.counted) cat_wy_combine(d_maxs + (int64_t)t * maxs_stride + (int64_t)st.s * 64 + lane, mx);
 }
 
-int cat_check(scoary_handle h, const char* what, bool ok, int64_t G, int64_t T, int64_t N, int64_t K, int64_t P) {
-  if (int rc = check_args(h, what, ok && G >= 1 && T >= 1 && N >= 1 && P >= 1)) return rc;
-  if (K < 1 || K > kCatMaxClasses)
-    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": K outside [1, scoary_categorical_max_classes()]");
-  if (N > scoary_ranksum_max_isolates())
-    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more isolates than scoary_ranksum_max_isolates()");
-  if (T > 65535 || G > 0x7fffffffLL - 256 || P > 0x7fffffffLL)
-    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": T > 65535, G >= 2^31 or P >= 2^31");
-  return SCOARY_OK;
+// The two kernels: plain functions around the template's instances, so that their names stay the ones the build's
+// resource rules (which count instances by substring) and the timers know.
+__global__ __launch_bounds__(kCatThreads) void k_cat_permute(const uint32_t* __restrict__ tiled, int64_t Gp, int G,
+                                                             int N, const int16_t* __restrict__ rows, int64_t P, int S,
+                                                             const int32_t* __restrict__ aobs,
+                                                             const int32_t* __restrict__ nk,
+                                                             const uint64_t* __restrict__ wt, int ranges,
+                                                             int lds_words, int32_t* __restrict__ d_r) {
+  k_cat_permute_t<false>(tiled, Gp, G, N, rows, P, S, aobs, nk, wt, nullptr, nullptr, ranges, lds_words, d_r, nullptr, 0);
+}
+
+__global__ __launch_bounds__(kCatThreads) void k_cat_maxt(const uint32_t* __restrict__ tiled, int64_t Gp, int G, int N,
+                                                          const int16_t* __restrict__ rows, int64_t P, int S,
+                                                          const int32_t* __restrict__ aobs,
+                                                          const int32_t* __restrict__ nk,
+                                                          const uint64_t* __restrict__ wt,
+                                                          const double* __restrict__ d_inv,
+                                                          const double* __restrict__ d_ivm, int ranges, int lds_words,
+                                                          int32_t* __restrict__ d_r, double* __restrict__ d_maxs,
+                                                          int64_t maxs_stride) {
+  k_cat_permute_t<true>(tiled, Gp, G, N, rows, P, S, aobs, nk, wt, d_inv, d_ivm, ranges, lds_words, d_r, d_maxs,
+                        maxs_stride);
 }
 
 }  // namespace
@@ -217,7 +199,7 @@ int scoary_categorical(scoary_handle h, const uint32_t* d_tiled, const int16_t* 
                        double* d_v, scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
   if (int rc = cat_check(h, "scoary_categorical", d_tiled && d_codes && d_nk && d_a && d_m && d_x2 && d_p && d_v, G, T,
-                         N, K, 1))
+                         N, K, 1, 1))
     return rc;
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -233,28 +215,40 @@ int scoary_permute_categorical(scoary_handle h, const uint32_t* d_tiled, const i
                                const int32_t* d_nk, const uint64_t* d_w, int64_t G, int64_t T, int64_t N, int64_t P,
                                int32_t* d_r, scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
-  if (int rc = cat_check(h, "scoary_permute_categorical", d_tiled && d_rows && d_a && d_nk && d_w && d_r, G, T, N, 1,
+  if (int rc = cat_check(h, "scoary_permute_categorical", d_tiled && d_rows && d_a && d_nk && d_w && d_r, G, T, N, 1, 1,
                          P))
     return rc;
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // (the trait's classes are on the device: the LDS is sized for the seven planes of eight classes)
-  const int64_t lds_words = round_up(std::min<int64_t>((N + 31) / 32, kCatChunkWords), 4);
-  const int64_t lds = kCatPlanes * lds_words * 256;
-  if (lds > 64 * 1024 && !h->categorical_lds_optin) {
-    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cat_permute),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kCatPlanes * kCatChunkWords * 256));
-    h->categorical_lds_optin = 1;
-  }
-  // gene ranges per stage: enough blocks for four rounds over the CUs, where the gene groups allow it; a range is
-  // every ranges-th group, so that a table sorted by gene frequency spreads evenly
-  const int64_t S = (P + 63) / 64, ngroups = (G + kCatGroup - 1) / kCatGroup;
-  const int64_t ranges = std::min<int64_t>(ngroups, std::max<int64_t>(1, (4 * (int64_t)h->num_cu + S * T - 1) / (S * T)));
-  if (S * ranges > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_permute_categorical: grid too large");
+  CatLaunch lp;
+  if (int rc = cat_launch_plan(h, "scoary_permute_categorical", &k_cat_permute, kCatOptinPermute, G, T, N, P, &lp))
+    return rc;
   KernelTimer kt(h, s, "k_cat_permute");
-  hipLaunchKernelGGL(k_cat_permute, dim3((unsigned)(S * ranges), (unsigned)T), dim3(kCatThreads), (size_t)lds, s,
-                     d_tiled, scoary_tiled_genes(G), (int)G, (int)N, d_rows, P, (int)S, d_a, d_nk, d_w, (int)ranges,
-                     (int)lds_words, d_r);
+  hipLaunchKernelGGL(k_cat_permute, dim3((unsigned)(lp.S * lp.ranges), (unsigned)T), dim3(kCatThreads), (size_t)lp.lds,
+                     s, d_tiled, scoary_tiled_genes(G), (int)G, (int)N, d_rows, P, (int)lp.S, d_a, d_nk, d_w,
+                     (int)lp.ranges, (int)lp.lds_words, d_r);
+  HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+
+int scoary_permute_cat_wy(scoary_handle h, const uint32_t* d_tiled, const int16_t* d_rows, const int32_t* d_a,
+                          const int32_t* d_nk, const uint64_t* d_w, const double* d_inv, const double* d_ivm,
+                          int64_t G, int64_t T, int64_t N, int64_t P, int32_t* d_r, double* d_maxs,
+                          int64_t maxs_stride, scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (int rc = cat_check(h, "scoary_permute_cat_wy",
+                         d_tiled && d_rows && d_a && d_nk && d_w && d_inv && d_ivm && d_r && d_maxs &&
+                             maxs_stride >= P,
+                         G, T, N, 1, 1, P))
+    return rc;
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CatLaunch lp;
+  if (int rc = cat_launch_plan(h, "scoary_permute_cat_wy", &k_cat_maxt, kCatOptinMaxt, G, T, N, P, &lp)) return rc;
+  KernelTimer kt(h, s, "k_cat_maxt");
+  hipLaunchKernelGGL(k_cat_maxt, dim3((unsigned)(lp.S * lp.ranges), (unsigned)T), dim3(kCatThreads), (size_t)lp.lds, s,
+                     d_tiled, scoary_tiled_genes(G), (int)G, (int)N, d_rows, P, (int)lp.S, d_a, d_nk, d_w, d_inv, d_ivm,
+                     (int)lp.ranges, (int)lp.lds_words, d_r, d_maxs, maxs_stride);
   HIP_TRY(h, hipGetLastError());
   return SCOARY_OK;
 }

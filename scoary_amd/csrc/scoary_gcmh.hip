@@ -1,6 +1,6 @@
 // scoary_gcmh.hip -- categorical traits over strata: the generalized Cochran-Mantel-Haenszel test of a gene against a
 // label of up to eight classes (a 2 x K x S table per gene), with label permutations within the strata (spec S21 of
-// DESIGN.md).
+// DESIGN.md) and their Westfall-Young maxima (spec S22).
 //
 // A trait is its row of class codes (int16, 1 .. K, 0 = missing), its pooled class sizes n_k and the per-stratum
 // class sizes n_sk; the strata are the CMH entry points' (the stratum of every isolate and the isolates by stratum).
@@ -13,9 +13,12 @@
 //   k_gcmh_observed  (observed)      a[8], m, E[8], the form, Q, df, p and the threshold of every (trait, gene):
 //                                    k_vanelteren's walk over the segment table with the trait's code row in LDS, E and
 //                                    V folded at every change of stratum, LDL' without pivoting; not the hot path
-//   k_gcmh_permute   (the hot path)  k_cat_permute's blocks, class planes and popcount walk (scoary_cat_planes.hpp);
-//                                    behind a gene's last chunk of isolates a lane computes its permutation's Q from
-//                                    the form (wave-uniform reads) and the lanes with Q >= thr are counted
+//   k_gcmh_permute   (the hot path)  k_cat_permute's blocks, class planes and popcount walk (CatStage,
+//                                    scoary_cat_planes.hpp); behind a gene's last chunk of isolates a lane computes its
+//                                    permutation's Q from the form (wave-uniform reads) and the lanes with Q >= thr are
+//                                    counted
+//   k_gcmh_maxt      (the hot path)  the same block (k_gcmh_permute_t<true>) with a lane's running maximum of the Q it
+//                                    computes for the count, and k_cat_maxt's atomic at the end of the block
 #include "scoary_cat_planes.hpp"
 #include "scoary_chi2.hpp"
 #include "scoary_common.hpp"
@@ -149,67 +152,28 @@ __global__ __launch_bounds__(kGcmhThreads) void k_gcmh_observed(
   d_thr[o] = q * (1.0 - kGcmhTau);
 }
 
-// k_cat_permute's block: stage blockIdx.x % S (64 permutations) of trait blockIdx.y x the gene groups rng, rng +
-// ranges, .. of kCatGroup genes; wavefront w of a group counts its genes kCatHold w .. + kCatHold - 1; a lane is a
-// permutation.  The planes are loaded and walked as there (cat_count; isolates past N and permutations past P have no
-// class, a code that is none of 1 .. 8 matches no plane: a bad row gives wrong numbers only).  Behind the last chunk,
-// per gene and lane: Q of the counts of the classes before the last non-empty one -- that one needs no plane and no
-// count -- under the gene's form, read wave-uniformly (three contrasts while the last non-empty class is at most the
-// fourth, else seven), and the permutation counts iff Q >= thr.  A form of zeros (df = 0) has Q = 0 = thr by itself.
-__global__ __launch_bounds__(kCatThreads) void k_gcmh_permute(const uint32_t* __restrict__ tiled, int64_t Gp, int G,
-                                                              int N, const int16_t* __restrict__ rows, int64_t P, int S,
-                                                              const double* __restrict__ form,
-                                                              const double* __restrict__ thr,
-                                                              const int32_t* __restrict__ nk, int ranges,
-                                                              int lds_words, int32_t* __restrict__ d_r) {
+// The block of k_gcmh_permute (MAXT = false) and of k_gcmh_maxt (true): CatStage's, see scoary_cat_planes.hpp.  Behind
+// the last chunk, per gene and lane: Q of the counts of the classes before the last non-empty one -- that one needs no
+// plane and no count -- under the gene's form, read wave-uniformly (three contrasts while the last non-empty class is
+// at most the fourth, else seven), and the permutation counts iff Q >= thr.  A form of zeros (df = 0) has Q = 0 = thr
+// by itself.  MAXT: mx = max(mx, Q) next to the count -- Q = 0 is the identity of the maximum -- kept across all gene
+// groups the block walks, and one combine per lane whose permutation is < P at the end of the block.
+template <bool MAXT>
+__device__ __forceinline__ void k_gcmh_permute_t(const uint32_t* tiled, int64_t Gp, int G, int N, const int16_t* rows,
+                                                 int64_t P, int S, const double* form, const double* thr,
+                                                 const int32_t* nk, int ranges, int lds_words, int32_t* d_r,
+                                                 double* d_maxs, int64_t maxs_stride) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   uint32_t* planes = reinterpret_cast<uint32_t*>(lds);
-  const int t = blockIdx.y, s = blockIdx.x % S, rng = blockIdx.x / S;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool wide = gcmh_klast(nk + t * kCatMaxClasses, kCatMaxClasses) > 4;
-  const int nf = wide ? kCatPlanes : 3;
-  const int nw = (N + 31) / 32;
-  const int nchunks = (nw + kCatChunkWords - 1) / kCatChunkWords;
-  const int ngroups = (G + kCatGroup - 1) / kCatGroup;
-  const bool counted = (int64_t)s * 64 + lane < P;
+  const int t = blockIdx.y;
+  CatStage st(N, G, P, S, gcmh_klast(nk + t * kCatMaxClasses, kCatMaxClasses));
+  const int lane = st.lane;
 
-  // chunk c -> LDS: wavefront iteration = (permutation p, word pair wp); lanes 0 and 1 write the two words of a plane
-  auto load = [&](int c) {
-    const int npairs = lds_words / 2;
-    for (int it = wave; it < 64 * npairs; it += kCatWaves) {
-      const int p = it / npairs, wp = it - p * npairs;
-      const int64_t col = (int64_t)s * 64 + p;
-      const int i = (c * kCatChunkWords + 2 * wp) * 32 + lane;
-      int code = 0;
-      if (i < N && col < P) code = rows[((int64_t)t * P + col) * N + i];
-      for (int k = 0; k < nf; ++k) {
-        const uint64_t m64 = __ballot(code == k + 1);
-        if (lane < 2) planes[(k * lds_words + 2 * wp + lane) * 64 + p] = lane ? (uint32_t)(m64 >> 32) : (uint32_t)m64;
-      }
-    }
-  };
-
-  bool loaded = false;
-  for (int grp = rng; grp < ngroups; grp += ranges) {
-    const int g0 = grp * kCatGroup + wave * kCatHold;
-    uint32_t cnt[kCatHold][kCatPlanes];
-#pragma unroll
-    for (int j = 0; j < kCatHold; ++j)
-#pragma unroll
-      for (int k = 0; k < kCatPlanes; ++k) cnt[j][k] = 0u;
-    for (int c = 0; c < nchunks; ++c) {
-      if (!loaded || nchunks > 1) {
-        __syncthreads();
-        load(c);
-        __syncthreads();
-        loaded = true;
-      }
-      const int nquads = (min(kCatChunkWords, nw - c * kCatChunkWords) + 3) / 4;
-      const uint4* tq = reinterpret_cast<const uint4*>(tiled) + (int64_t)c * (kCatChunkWords / 4) * Gp + g0;
-      if (wide) cat_count<kCatPlanes>(planes + lane, lds_words, tq, Gp, nquads, cnt);
-      else cat_count<3>(planes + lane, lds_words, tq, Gp, nquads, cnt);
-    }
+  double mx = 0.0;
+  for (int grp = st.rng; grp < st.ngroups; grp += ranges) {
+    const int g0 = st.first_gene(grp);
+    uint32_t cnt[kCatHold][kCatPlanes] = {};
+    st.count_group(grp, planes, lds_words, tiled, Gp, rows, P, N, cnt);
 #pragma unroll 1                                     // (unrolled, four forms wait in SGPRs across the count)
     for (int j = 0; j < kCatHold; ++j) {
       const int g = g0 + j;
@@ -223,26 +187,34 @@ __global__ __launch_bounds__(kCatThreads) void k_gcmh_permute(const uint32_t* __
 #pragma unroll
         for (int x = 1; x < kCatHold; ++x) a[k] = j == x ? cnt[x][k] : a[k];
       }
-      const double q = wide ? gcmh_q<kCatPlanes>(fo, a) : gcmh_q<3>(fo, a);
-      const bool ge = q >= thr[o];
-      const int hits = __popcll(__ballot(ge && counted));
-      if (lane == 0 && hits) atomicAdd(d_r + o, hits);
+      const double q = st.wide ? gcmh_q<kCatPlanes>(fo, a) : gcmh_q<3>(fo, a);
+      cat_hits(q >= thr[o], st.counted, lane, d_r + o);
+      if constexpr (MAXT) mx = fmax(mx, q);
     }
   }
+  if constexpr (MAXT)
+    if (st.counted) cat_wy_combine(d_maxs + (int64_t)t * maxs_stride + (int64_t)st.s * 64 + lane, mx);
 }
 
-int gcmh_check(scoary_handle h, const char* what, bool ok, int64_t G, int64_t T, int64_t N, int64_t K, int64_t S,
-               int64_t P) {
-  if (int rc = check_args(h, what, ok && G >= 1 && T >= 1 && N >= 1 && S >= 1 && P >= 1)) return rc;
-  if (K < 1 || K > kCatMaxClasses)
-    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": K outside [1, scoary_categorical_max_classes()]");
-  if (S > scoary_perm_max_strata())
-    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more strata than scoary_perm_max_strata()");
-  if (N > scoary_ranksum_max_isolates())
-    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": more isolates than scoary_ranksum_max_isolates()");
-  if (T > 65535 || G > 0x7fffffffLL - 256 || P > 0x7fffffffLL)
-    return fail(h, SCOARY_ERR_SIZE, std::string(what) + ": T > 65535, G >= 2^31 or P >= 2^31");
-  return SCOARY_OK;
+// The two kernels: plain functions around the template's instances, so that their names stay the ones the build's
+// resource rules (which count instances by substring) and the timers know.
+__global__ __launch_bounds__(kCatThreads) void k_gcmh_permute(const uint32_t* __restrict__ tiled, int64_t Gp, int G,
+                                                              int N, const int16_t* __restrict__ rows, int64_t P, int S,
+                                                              const double* __restrict__ form,
+                                                              const double* __restrict__ thr,
+                                                              const int32_t* __restrict__ nk, int ranges,
+                                                              int lds_words, int32_t* __restrict__ d_r) {
+  k_gcmh_permute_t<false>(tiled, Gp, G, N, rows, P, S, form, thr, nk, ranges, lds_words, d_r, nullptr, 0);
+}
+
+__global__ __launch_bounds__(kCatThreads) void k_gcmh_maxt(const uint32_t* __restrict__ tiled, int64_t Gp, int G, int N,
+                                                           const int16_t* __restrict__ rows, int64_t P, int S,
+                                                           const double* __restrict__ form,
+                                                           const double* __restrict__ thr,
+                                                           const int32_t* __restrict__ nk, int ranges, int lds_words,
+                                                           int32_t* __restrict__ d_r, double* __restrict__ d_maxs,
+                                                           int64_t maxs_stride) {
+  k_gcmh_permute_t<true>(tiled, Gp, G, N, rows, P, S, form, thr, nk, ranges, lds_words, d_r, d_maxs, maxs_stride);
 }
 
 }  // namespace
@@ -256,9 +228,9 @@ int scoary_gcmh(scoary_handle h, const uint32_t* d_tiled, const int16_t* d_codes
                 int64_t N, int64_t K, int64_t S, int32_t* d_a, int32_t* d_m, double* d_e, double* d_form, double* d_q,
                 int32_t* d_df, double* d_p, double* d_thr, void* d_scratch, scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
-  if (int rc = gcmh_check(h, "scoary_gcmh", d_tiled && d_codes && d_nk && d_nsk && d_strata && d_members && d_a &&
-                                                 d_m && d_e && d_form && d_q && d_df && d_p && d_thr && d_scratch,
-                          G, T, N, K, S, 1))
+  if (int rc = cat_check(h, "scoary_gcmh", d_tiled && d_codes && d_nk && d_nsk && d_strata && d_members && d_a &&
+                                                d_m && d_e && d_form && d_q && d_df && d_p && d_thr && d_scratch,
+                         G, T, N, K, S, 1))
     return rc;
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -276,26 +248,37 @@ int scoary_permute_gcmh(scoary_handle h, const uint32_t* d_tiled, const int16_t*
                         const double* d_thr, const int32_t* d_nk, int64_t G, int64_t T, int64_t N, int64_t P,
                         int32_t* d_r, scoary_stream_t stream) {
   if (!h) return SCOARY_ERR_ARG;
-  if (int rc = gcmh_check(h, "scoary_permute_gcmh", d_tiled && d_rows && d_form && d_thr && d_nk && d_r, G, T, N, 1, 1,
-                          P))
+  if (int rc = cat_check(h, "scoary_permute_gcmh", d_tiled && d_rows && d_form && d_thr && d_nk && d_r, G, T, N, 1, 1,
+                         P))
     return rc;
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // k_cat_permute's launch: the LDS is sized for the seven planes of eight classes, the same gene ranges per stage
-  const int64_t lds_words = round_up(std::min<int64_t>((N + 31) / 32, kCatChunkWords), 4);
-  const int64_t lds = kCatPlanes * lds_words * 256;
-  if (lds > 64 * 1024 && !h->gcmh_lds_optin) {
-    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gcmh_permute),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kCatPlanes * kCatChunkWords * 256));
-    h->gcmh_lds_optin = 1;
-  }
-  const int64_t S = (P + 63) / 64, ngroups = (G + kCatGroup - 1) / kCatGroup;
-  const int64_t ranges = std::min<int64_t>(ngroups, std::max<int64_t>(1, (4 * (int64_t)h->num_cu + S * T - 1) / (S * T)));
-  if (S * ranges > 0x7fffffffLL) return fail(h, SCOARY_ERR_SIZE, "scoary_permute_gcmh: grid too large");
+  CatLaunch lp;
+  if (int rc = cat_launch_plan(h, "scoary_permute_gcmh", &k_gcmh_permute, kGcmhOptinPermute, G, T, N, P, &lp)) return rc;
   KernelTimer kt(h, s, "k_gcmh_permute");
-  hipLaunchKernelGGL(k_gcmh_permute, dim3((unsigned)(S * ranges), (unsigned)T), dim3(kCatThreads), (size_t)lds, s,
-                     d_tiled, scoary_tiled_genes(G), (int)G, (int)N, d_rows, P, (int)S, d_form, d_thr, d_nk,
-                     (int)ranges, (int)lds_words, d_r);
+  hipLaunchKernelGGL(k_gcmh_permute, dim3((unsigned)(lp.S * lp.ranges), (unsigned)T), dim3(kCatThreads),
+                     (size_t)lp.lds, s, d_tiled, scoary_tiled_genes(G), (int)G, (int)N, d_rows, P, (int)lp.S, d_form,
+                     d_thr, d_nk, (int)lp.ranges, (int)lp.lds_words, d_r);
+  HIP_TRY(h, hipGetLastError());
+  return SCOARY_OK;
+}
+
+int scoary_permute_gcmh_wy(scoary_handle h, const uint32_t* d_tiled, const int16_t* d_rows, const double* d_form,
+                           const double* d_thr, const int32_t* d_nk, int64_t G, int64_t T, int64_t N, int64_t P,
+                           int32_t* d_r, double* d_maxs, int64_t maxs_stride, scoary_stream_t stream) {
+  if (!h) return SCOARY_ERR_ARG;
+  if (int rc = cat_check(h, "scoary_permute_gcmh_wy",
+                         d_tiled && d_rows && d_form && d_thr && d_nk && d_r && d_maxs && maxs_stride >= P, G, T, N, 1,
+                         1, P))
+    return rc;
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CatLaunch lp;
+  if (int rc = cat_launch_plan(h, "scoary_permute_gcmh_wy", &k_gcmh_maxt, kGcmhOptinMaxt, G, T, N, P, &lp)) return rc;
+  KernelTimer kt(h, s, "k_gcmh_maxt");
+  hipLaunchKernelGGL(k_gcmh_maxt, dim3((unsigned)(lp.S * lp.ranges), (unsigned)T), dim3(kCatThreads), (size_t)lp.lds,
+                     s, d_tiled, scoary_tiled_genes(G), (int)G, (int)N, d_rows, P, (int)lp.S, d_form, d_thr, d_nk,
+                     (int)lp.ranges, (int)lp.lds_words, d_r, d_maxs, maxs_stride);
   HIP_TRY(h, hipGetLastError());
   return SCOARY_OK;
 }

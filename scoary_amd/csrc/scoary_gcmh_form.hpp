@@ -1,6 +1,6 @@
 // scoary_gcmh_form.hpp -- the form of a (trait, gene) of the generalized CMH test (spec S21) and the quadratic Q of a
-// table under it, shared by the translation units that compute Q of a permuted table (scoary_gcmh.hip: spec S21;
-// scoary_cat_wy.hip: spec S22), so that both compile the same text and an identical table gives identical bits.
+// table under it, which k_gcmh_observed and the hot kernels of scoary_gcmh.hip (specs S21 and S22) compute by this one
+// text, so that an identical table gives identical bits.
 #ifndef SCOARY_GCMH_FORM_HPP
 #define SCOARY_GCMH_FORM_HPP
 #include "scoary_cat_planes.hpp"

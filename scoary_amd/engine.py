@@ -1828,13 +1828,20 @@ class AssociationEngine:
             G, T, plan.N, *(self._ptr(out[k]) for k in ("d", "m", "auc", "p")), self._stream()), "scoary_ranksum")
         return out
 
+    def _ranksum_generate(self, src, plan, perm_base, P, seed, bfrag=None):
+        """The rows ``src`` int16 [T, N] of ``plan`` shuffled over its valid isolates (spec S15's law) under the
+        permutations perm_base .. perm_base + P - 1: int16 [T, P, N], or written into ``bfrag`` as the matrix-core
+        kernel's B operand."""
+        name = "scoary_ranksum_perm_generate" if bfrag is None else "scoary_ranksum_perm_generate_bfrag"
+        out = self._empty((plan.T, int(P), plan.N), _torch().int16) if bfrag is None else bfrag
+        self._check(getattr(self.lib, name)(
+            self.h, self._ptr(src), self._ptr(plan.valid), plan.T, plan.N, int(P), int(perm_base), 0,
+            ctypes.c_uint64(seed), self._ptr(out), self._stream()), name)
+        return out
+
     def ranksum_values(self, plan, perm_base, P, seed):
         """The permuted centred ranks of the permutations perm_base .. perm_base + P - 1: int16 [T, P, N]."""
-        out = self._empty((plan.T, int(P), plan.N), _torch().int16)
-        self._check(self.lib.scoary_ranksum_perm_generate(
-            self.h, self._ptr(plan.rc), self._ptr(plan.valid), plan.T, plan.N, int(P), int(perm_base), 0,
-            ctypes.c_uint64(seed), self._ptr(out), self._stream()), "scoary_ranksum_perm_generate")
-        return out
+        return self._ranksum_generate(plan.rc, plan, perm_base, P, seed)
 
     def ranksum_batch(self, T, N, permutations, budget_bytes=8 << 30):
         """Permutations per batch of ranksum_permute (a multiple of 64): the B operand stays under budget_bytes."""
@@ -1909,11 +1916,7 @@ class AssociationEngine:
                                   self._ranksum_generator(plan, seed))
 
     def _ranksum_generator(self, plan, seed):
-        def generate(nb, base, bfrag):
-            self._check(self.lib.scoary_ranksum_perm_generate_bfrag(
-                self.h, self._ptr(plan.rc), self._ptr(plan.valid), plan.T, plan.N, nb, base, 0,
-                ctypes.c_uint64(seed), self._ptr(bfrag), self._stream()), "scoary_ranksum_perm_generate_bfrag")
-        return generate
+        return lambda nb, base, bfrag: self._ranksum_generate(plan.rc, plan, base, nb, seed, bfrag)
 
     def ranksum_var(self, plan, m):
         """S15's var float64 [T, G] of the observed m (ranksum()'s), 0 where the gene is untestable."""
@@ -1970,11 +1973,7 @@ class AssociationEngine:
     def categorical_rows(self, plan, perm_base, P, seed):
         """The permuted code rows of the permutations perm_base .. perm_base + P - 1: int16 [T, P, N], the codes
         shuffled over the isolates that have one by the rank-sum generator (spec S15's law)."""
-        out = self._empty((plan.T, int(P), plan.N), _torch().int16)
-        self._check(self.lib.scoary_ranksum_perm_generate(
-            self.h, self._ptr(plan.codes), self._ptr(plan.valid), plan.T, plan.N, int(P), int(perm_base), 0,
-            ctypes.c_uint64(seed), self._ptr(out), self._stream()), "scoary_ranksum_perm_generate")
-        return out
+        return self._ranksum_generate(plan.codes, plan, perm_base, P, seed)
 
     def categorical_batch(self, T, N, permutations, budget_bytes=8 << 30):
         """Permutations per batch of categorical_permute (a multiple of 64): the code rows stay under budget_bytes."""
@@ -1987,11 +1986,7 @@ class AssociationEngine:
         zeros) picks k_cat_maxt instead (spec S22): the same counts, and the batch's maxima into maxs."""
         torch = _torch()
         T, G, N = plan.T, genes.G, plan.N
-        if rows.dim() != 3 or (rows.shape[0], rows.shape[2]) != (T, N) or rows.dtype != torch.int16 \
-                or not rows.is_contiguous():
-            raise ValueError("permute_categorical: rows are int16 [T, P, N], contiguous")
-        if tuple(r.shape) != (T, G) or r.dtype != torch.int32 or not r.is_contiguous():
-            raise ValueError("permute_categorical: r is int32 [T, G], contiguous")
+        self._check_rows_r("permute_categorical", rows, r, T, G, N)
         if maxt is None:
             self._check(self.lib.scoary_permute_categorical(
                 self.h, self._ptr(genes.tiled), self._ptr(rows), self._ptr(a_obs), self._ptr(plan.nk),
@@ -2017,22 +2012,39 @@ class AssociationEngine:
             raise ValueError("%s: maxs is float64 [T, >= P], the batch's columns of a contiguous array" % what)
         return max(int(maxs.stride(0)), P)
 
+    @staticmethod
+    def _check_rows_r(what, rows, r, T, G, N):
+        """The code rows and the counter of permute_categorical and permute_gcmh."""
+        torch = _torch()
+        if rows.dim() != 3 or (rows.shape[0], rows.shape[2]) != (T, N) or rows.dtype != torch.int16 \
+                or not rows.is_contiguous():
+            raise ValueError("%s: rows are int16 [T, P, N], contiguous" % what)
+        if tuple(r.shape) != (T, G) or r.dtype != torch.int32 or not r.is_contiguous():
+            raise ValueError("%s: r is int32 [T, G], contiguous" % what)
+
+    def _cat_permute(self, genes, plan, permutations, budget_bytes, rows_of, launch):
+        """The permutation loop of categorical_permute and gcmh_permute: batches of categorical_batch() permutations,
+        ``rows_of(base, nb)`` writes a batch's code rows and ``launch(rows, r, base)`` adds the batch's counts to r
+        int32 [T, G], which is returned."""
+        T, N, P = plan.T, plan.N, int(permutations)
+        r = _torch().zeros((T, genes.G), dtype=_torch().int32, device=self.device)
+        batch = self.categorical_batch(T, N, P, budget_bytes)
+        for base in range(0, P, batch):
+            launch(rows_of(base, min(batch, P - base)), r, base)
+        return r
+
     def categorical_permute(self, genes, plan, a_obs, permutations, seed, budget_bytes=8 << 30, maxt=None):
         """r int32 [T, G] = #{pi < permutations : X2_pi >= X2_obs} under code shuffles (spec S20), in batches of
         categorical_batch() permutations: the rank-sum generator writes a batch's code rows and k_cat_permute adds
         its counts.  ``maxt`` = (inv, ivm, maxs float64 [T, permutations] of zeros) picks k_cat_maxt (spec S22): a
         batch's maxima go into its columns of maxs."""
-        torch = _torch()
         self._ranksum_fits("categorical_permute", genes, plan)
-        T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
-        if tuple(a_obs.shape) != (T, G, 8) or a_obs.dtype != torch.int32 or not a_obs.is_contiguous():
+        if tuple(a_obs.shape) != (plan.T, genes.G, 8) or a_obs.dtype != _torch().int32 or not a_obs.is_contiguous():
             raise ValueError("categorical_permute: a_obs is the observed a, int32 [T, G, 8], contiguous")
-        r = torch.zeros((T, G), dtype=torch.int32, device=self.device)
-        batch = self.categorical_batch(T, N, P, budget_bytes)
-        for base in range(0, P, batch):
-            self.permute_categorical(genes, plan, a_obs, self.categorical_rows(plan, base, min(batch, P - base), seed),
-                                     r, maxt=None if maxt is None else (maxt[0], maxt[1], maxt[2][:, base:]))
-        return r
+        return self._cat_permute(
+            genes, plan, permutations, budget_bytes, lambda base, nb: self.categorical_rows(plan, base, nb, seed),
+            lambda rows, r, base: self.permute_categorical(
+                genes, plan, a_obs, rows, r, maxt=None if maxt is None else (maxt[0], maxt[1], maxt[2][:, base:])))
 
     def categorical_wy_prepare(self, plan, a_obs):
         """(inv float64 [T, 8], ivm, s_obs, thr float64 [T, G]) of spec S22 from the observed a of categorical():
@@ -2111,12 +2123,7 @@ class AssociationEngine:
     def gcmh_rows(self, plan, perm_base, P, seed):
         """The permuted code rows of the permutations perm_base .. perm_base + P - 1: int16 [T, P, N], the codes
         shuffled within the strata over the isolates that have one by the van Elteren generator (spec S16's law)."""
-        out = self._empty((plan.T, int(P), plan.N), _torch().int16)
-        self._check(self.lib.scoary_vanelteren_perm_generate(
-            self.h, self._ptr(plan.l), self._ptr(plan.valid), self._ptr(plan.strata), plan.T, plan.N, plan.S, int(P),
-            int(perm_base), 0, ctypes.c_uint64(seed), self._ptr(out), self._stream()),
-            "scoary_vanelteren_perm_generate")
-        return out
+        return self._vanelteren_generate(plan.l, plan, perm_base, P, seed)
 
     def permute_gcmh(self, genes, plan, res, rows, r, maxt=None):
         """r[t, g] += #{rows[t, p] : Q_p >= thr} (k_gcmh_permute); res = gcmh(genes, plan), rows int16 [T, P, N].
@@ -2128,11 +2135,7 @@ class AssociationEngine:
         if tuple(form.shape) != (T, G, GCMH_FORM) or form.dtype != torch.float64 or not form.is_contiguous() \
                 or tuple(thr.shape) != (T, G) or thr.dtype != torch.float64 or not thr.is_contiguous():
             raise ValueError("permute_gcmh: res is the observed result of these genes and this plan")
-        if rows.dim() != 3 or (rows.shape[0], rows.shape[2]) != (T, N) or rows.dtype != torch.int16 \
-                or not rows.is_contiguous():
-            raise ValueError("permute_gcmh: rows are int16 [T, P, N], contiguous")
-        if tuple(r.shape) != (T, G) or r.dtype != torch.int32 or not r.is_contiguous():
-            raise ValueError("permute_gcmh: r is int32 [T, G], contiguous")
+        self._check_rows_r("permute_gcmh", rows, r, T, G, N)
         if maxt is None:
             self._check(self.lib.scoary_permute_gcmh(
                 self.h, self._ptr(genes.tiled), self._ptr(rows), self._ptr(form), self._ptr(thr), self._ptr(plan.nk),
@@ -2149,15 +2152,11 @@ class AssociationEngine:
         (spec S21), in categorical_batch() permutations a batch: the van Elteren generator writes a batch's code rows
         and k_gcmh_permute adds its counts.  ``maxt`` = maxs float64 [T, permutations] of zeros picks k_gcmh_maxt (spec
         S22): a batch's maxima go into its columns of maxs."""
-        torch = _torch()
         self._ranksum_fits("gcmh_permute", genes, plan)
-        T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
-        r = torch.zeros((T, G), dtype=torch.int32, device=self.device)
-        batch = self.categorical_batch(T, N, P, budget_bytes)
-        for base in range(0, P, batch):
-            self.permute_gcmh(genes, plan, res, self.gcmh_rows(plan, base, min(batch, P - base), seed), r,
-                              maxt=None if maxt is None else maxt[:, base:])
-        return r
+        return self._cat_permute(
+            genes, plan, permutations, budget_bytes, lambda base, nb: self.gcmh_rows(plan, base, nb, seed),
+            lambda rows, r, base: self.permute_gcmh(genes, plan, res, rows, r,
+                                                    maxt=None if maxt is None else maxt[:, base:]))
 
     def gcmh_westfall_young(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
         """Westfall-Young single-step maxT over the generalized CMH statistic (spec S22) of the step ``res`` =
@@ -2257,11 +2256,15 @@ class AssociationEngine:
     def vanelteren_values(self, plan, perm_base, P, seed):
         """The score rows of the permutations perm_base .. perm_base + P - 1, shuffled within strata: int16
         [T, P, N]."""
-        out = self._empty((plan.T, int(P), plan.N), _torch().int16)
-        self._check(self.lib.scoary_vanelteren_perm_generate(
-            self.h, self._ptr(plan.l), self._ptr(plan.valid), self._ptr(plan.strata), plan.T, plan.N, plan.S, int(P),
-            int(perm_base), 0, ctypes.c_uint64(seed), self._ptr(out), self._stream()),
-            "scoary_vanelteren_perm_generate")
+        return self._vanelteren_generate(plan.l, plan, perm_base, P, seed)
+
+    def _vanelteren_generate(self, src, plan, perm_base, P, seed, bfrag=None):
+        """_ranksum_generate with the rows shuffled within the plan's strata (spec S16's law)."""
+        name = "scoary_vanelteren_perm_generate" if bfrag is None else "scoary_vanelteren_perm_generate_bfrag"
+        out = self._empty((plan.T, int(P), plan.N), _torch().int16) if bfrag is None else bfrag
+        self._check(getattr(self.lib, name)(
+            self.h, self._ptr(src), self._ptr(plan.valid), self._ptr(plan.strata), plan.T, plan.N, plan.S, int(P),
+            int(perm_base), 0, ctypes.c_uint64(seed), self._ptr(out), self._stream()), name)
         return out
 
     def vanelteren_permute(self, genes, plan, d_obs, permutations, seed, budget_bytes=8 << 30):
@@ -2272,12 +2275,7 @@ class AssociationEngine:
                                   self._vanelteren_generator(plan, seed))
 
     def _vanelteren_generator(self, plan, seed):
-        def generate(nb, base, bfrag):
-            self._check(self.lib.scoary_vanelteren_perm_generate_bfrag(
-                self.h, self._ptr(plan.l), self._ptr(plan.valid), self._ptr(plan.strata), plan.T, plan.N, plan.S, nb,
-                base, 0, ctypes.c_uint64(seed), self._ptr(bfrag), self._stream()),
-                "scoary_vanelteren_perm_generate_bfrag")
-        return generate
+        return lambda nb, base, bfrag: self._vanelteren_generate(plan.l, plan, base, nb, seed, bfrag)
 
     def vanelteren_westfall_young(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
         """Westfall-Young single-step maxT over the van Elteren statistic (spec S17, cc = 0) of the step ``res`` =

@@ -2123,45 +2123,71 @@ def _ranksum_refusals(no_pairwise, collapse, strata, exits=False):
         yield RANKSUM_TEXT["ranks"][not exits]
 
 
+def _read_side_traits(path, delimiter, strains, what, cell, empty):
+    """The trait file of a side stage (``what``: "quantitative" or "categorical"): a header row (its first cell is
+    ignored, the others name the traits), then one row per isolate: its name and one cell per trait.  Returns
+    (names, ``empty(T, N)`` over ``strains`` with ``cell(text, path, isolate, trait, line)`` -- which parses or
+    refuses -- in the place of every cell that is none of MISSING_TRAIT): isolates the analysis does not hold are
+    ignored, isolates of ``strains`` the file does not name are missing in every trait."""
+    with open(path, "r", newline=None) as f:
+        rows = [r for r in csv.reader(f, delimiter=delimiter) if r]
+    if not rows or len(rows[0]) < 2:
+        sys.exit("Please check that the %s traits file %s is formatted properly and contains at least one "
+                 "trait" % (what, path))
+    names = list(rows[0][1:])
+    if len(set(names)) != len(names):
+        sys.exit("The %s traits file %s names a trait more than once" % (what, path))
+    col = {s: j for j, s in enumerate(strains)}
+    out = empty(len(names), len(strains))
+    seen = set()
+    for line, row in enumerate(rows[1:], start=2):
+        iso = row[0]
+        if iso in seen:
+            sys.exit("The %s traits file %s names isolate %s more than once (line %d)" % (what, path, iso, line))
+        seen.add(iso)
+        if len(row) != len(names) + 1:
+            sys.exit("The %s traits file %s has %d cells in line %d, its header has %d"
+                     % (what, path, len(row), line, len(names) + 1))
+        if iso not in col:
+            continue
+        for t, text in enumerate(row[1:]):
+            if text not in MISSING_TRAIT:
+                out[t][col[iso]] = cell(text, path, iso, names[t], line)
+    return names, out
+
+
 def read_quantitative_file(path, delimiter, strains):
     """--quantitative FILE: a header row (its first cell is ignored, the others name the traits), then one row per
     isolate: its name and one cell per trait, a number (float()) or one of MISSING_TRAIT.  Returns (names, float64
     [T, N] over ``strains`` with nan = missing): isolates the analysis does not hold are ignored, isolates of
     ``strains`` the file does not name are missing in every trait."""
-    with open(path, "r", newline=None) as f:
-        rows = [r for r in csv.reader(f, delimiter=delimiter) if r]
-    if not rows or len(rows[0]) < 2:
-        sys.exit("Please check that the quantitative traits file %s is formatted properly and contains at least one "
-                 "trait" % path)
-    names = list(rows[0][1:])
-    if len(set(names)) != len(names):
-        sys.exit("The quantitative traits file %s names a trait more than once" % path)
-    col = {s: j for j, s in enumerate(strains)}
-    values = np.full((len(names), len(strains)), np.nan, dtype=np.float64)
-    seen = set()
-    for line, row in enumerate(rows[1:], start=2):
-        iso = row[0]
-        if iso in seen:
-            sys.exit("The quantitative traits file %s names isolate %s more than once (line %d)" % (path, iso, line))
-        seen.add(iso)
-        if len(row) != len(names) + 1:
-            sys.exit("The quantitative traits file %s has %d cells in line %d, its header has %d"
-                     % (path, len(row), line, len(names) + 1))
-        if iso not in col:
-            continue
-        for t, cell in enumerate(row[1:]):
-            if cell in MISSING_TRAIT:
-                continue
-            try:
-                x = float(cell)
-            except ValueError:
-                x = np.nan
-            if not np.isfinite(x):
-                sys.exit("The quantitative traits file %s has the cell %r for isolate %s, trait %s (line %d): a cell "
-                         "is a finite number or one of %s" % (path, cell, iso, names[t], line,
-                                                              ",".join(repr(m) for m in MISSING_TRAIT)))
-            values[t, col[iso]] = x
-    return names, values
+    def number(text, path, iso, trait, line):
+        try:
+            x = float(text)
+        except ValueError:
+            x = np.nan
+        if not np.isfinite(x):
+            sys.exit("The quantitative traits file %s has the cell %r for isolate %s, trait %s (line %d): a cell "
+                     "is a finite number or one of %s" % (path, text, iso, trait, line,
+                                                          ",".join(repr(m) for m in MISSING_TRAIT)))
+        return x
+    return _read_side_traits(path, delimiter, strains, "quantitative", number,
+                             lambda T, N: np.full((T, N), np.nan, dtype=np.float64))
+
+
+def _side_stage_limits(what, eng, N, strata=None):
+    """The ValueErrors the side stages share (``what``: "quantitative" or "categorical"): more isolates than the
+    generators take and, for a stratified stage, strata that are not N stratum indices or too many."""
+    if strata is not None and (strata.shape != (N,) or not np.issubdtype(strata.dtype, np.integer)
+                               or strata.min() < 0):
+        raise ValueError("%s traits: strata must be %d stratum indices, one per isolate" % (what, N))
+    if N > eng.ranksum_max_isolates():
+        raise ValueError("%s traits take at most %d isolates; this analysis has %d"
+                         % (what, eng.ranksum_max_isolates(), N))
+    from . import _abi
+    if strata is not None and int(strata.max()) + 1 > _abi.PERM_MAX_STRATA:
+        raise ValueError("%s traits take at most %d strata; these are %d"
+                         % (what, _abi.PERM_MAX_STRATA, int(strata.max()) + 1))
 
 
 def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False,
@@ -2186,9 +2212,7 @@ def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, n
     if values.ndim != 2 or values.shape != (len(names), len(table.strains)):
         raise ValueError("quantitative traits: values must be [%d traits, %d isolates]"
                          % (len(names), len(table.strains)))
-    if values.shape[1] > eng.ranksum_max_isolates():
-        raise ValueError("quantitative traits take at most %d isolates; this analysis has %d"
-                         % (eng.ranksum_max_isolates(), values.shape[1]))
+    _side_stage_limits("quantitative", eng, values.shape[1])
     genes = table.on_device(eng)
     plan = eng.ranksum_plan(values)
     res = eng.ranksum(genes, plan)
@@ -2225,21 +2249,24 @@ def Ranksum_results(genedic, names, values, permutations=0, seed=DEFAULT_SEED, n
     return out
 
 
-def _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, test_columns, suffix, what):
-    """The result files of a rank test's stage (StoreRanksumResults, StoreVanElterenResults): per trait the testable
-    genes in ascending p (ties in file order), Bonferroni and Benjamini-Hochberg over them, every cell
-    double-quoted."""
+# the columns of a side stage's permutation counts and their keys: (count + 1) / (permutations + 1), only next to r
+PERMUTATION_COLUMNS = (("Empirical_p", "r"), ("Westfall_Young_p", "r_fwer"), ("Westfall_Young_stepdown_p", "r_sd"))
+
+
+def _store_side_results(results, genedic, max_hits, outdir, time, delimiter, test_columns, cells, suffix, what,
+                        rank=False):
+    """The result files of a side stage (the four Store*Results below): per trait the testable genes in ascending p
+    (ties in file order), Bonferroni and Benjamini-Hochberg over them, every cell double-quoted.  ``test_columns``
+    name the stage's fixed columns: the two carrier counts, the test's own -- their cells are ``cells(res, g)`` --
+    and the two adjusted p.  Behind them come the columns a result carries the keys for: with ``rank`` the shift and
+    its limits, then Empirical_p, Westfall_Young_p and, with ``rank``, Westfall_Young_stepdown_p."""
     table = _as_table(genedic)
     files = []
     for name, res in results.items():
-        with_emp = "r" in res
-        with_fwer = with_emp and "r_fwer" in res
-        with_sd = with_emp and "r_sd" in res
-        with_shift = all(key in res for _column, key in RANK_SHIFT_COLUMNS)
+        with_shift = rank and all(key in res for _column, key in RANK_SHIFT_COLUMNS)
+        counts = [(column, key) for column, key in PERMUTATION_COLUMNS[:3 if rank else 2] if "r" in res and key in res]
         columns = ROARY_HEAD + list(test_columns) + \
-            ([column for column, _key in RANK_SHIFT_COLUMNS] if with_shift else []) + \
-            (["Empirical_p"] if with_emp else []) + \
-            (["Westfall_Young_p"] if with_fwer else []) + (["Westfall_Young_stepdown_p"] if with_sd else [])
+            ([column for column, _key in RANK_SHIFT_COLUMNS] if with_shift else []) + [column for column, _key in counts]
         idx = np.flatnonzero(res["testable"])
         fname = outdir + name + time + suffix
         with open(fname, "w") as out:
@@ -2252,31 +2279,29 @@ def _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, tes
                 for k in order[:shown]:
                     g = int(idx[k])
                     gene = table.ids[g]
-                    cells = gene.split("_|_") if "_|_" in gene else [gene, str(table.nugn[g]),
-                                                                     str(table.annotation[g])]
+                    row = gene.split("_|_") if "_|_" in gene else [gene, str(table.nugn[g]),
+                                                                   str(table.annotation[g])]
                     m = int(res["m"][g])
-                    cells += [_fmt(m), _fmt(res["n"] - m), _fmt(res["auc"][g]), _fmt(res["p"][g]), _fmt(bonf[k]),
-                              _fmt(bh[k])]
+                    row += [_fmt(m), _fmt(res["n"] - m)] + cells(res, g) + [_fmt(bonf[k]), _fmt(bh[k])]
                     if with_shift:           # an infinite limit is _fmt's "inf" / "-inf", as in the odds ratio's limits
-                        cells += [_fmt(res[key][g]) for _column, key in RANK_SHIFT_COLUMNS]
-                    if with_emp:
-                        cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
-                    if with_fwer:
-                        cells.append(_fmt((int(res["r_fwer"][g]) + 1.0) / (res["permutations"] + 1.0)))
-                    if with_sd:
-                        cells.append(_fmt((int(res["r_sd"][g]) + 1.0) / (res["permutations"] + 1.0)))
-                    out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
+                        row += [_fmt(res[key][g]) for _column, key in RANK_SHIFT_COLUMNS]
+                    row += [_fmt((int(res[key][g]) + 1.0) / (res["permutations"] + 1.0)) for _column, key in counts]
+                    out.write(delimiter.join('"' + c + '"' for c in row) + "\n")
         log.info("Storing %s results: %s" % (what, fname))
         files.append(fname)
     return files
+
+
+def _rank_cells(res, g):
+    return [_fmt(res["auc"][g]), _fmt(res["p"][g])]
 
 
 def StoreRanksumResults(results, genedic, max_hits, outdir, time="", delimiter=","):
     """Write ``<outdir><trait><time>.ranksum.results.csv`` for every trait of Ranksum_results: the testable genes in
     ascending Rank_sum_p (ties in file order), Bonferroni and Benjamini-Hochberg over them, every cell
     double-quoted.  Returns the file names."""
-    return _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, RANKSUM_COLUMNS,
-                               ".ranksum.results.csv", "rank-sum")
+    return _store_side_results(results, genedic, max_hits, outdir, time, delimiter, RANKSUM_COLUMNS, _rank_cells,
+                               ".ranksum.results.csv", "rank-sum", rank=True)
 
 
 # ---------------------------------------------------------------------------
@@ -2308,6 +2333,17 @@ def categorical_classes(labels):
     return sorted(set(x for x in labels if x is not None))
 
 
+def _class_codes(labels, N):
+    """(classes, codes) of the labels [T][N]: every trait's classes (categorical_classes) and its isolates' class
+    numbers, 1 .. K in that order and 0 = missing, int16 [T, N]."""
+    classes = [categorical_classes(row) for row in labels]
+    codes = np.zeros((len(labels), N), dtype=np.int16)
+    for t, row in enumerate(labels):
+        number = {c: k + 1 for k, c in enumerate(classes[t])}
+        codes[t] = [number[x] if x is not None else 0 for x in row]
+    return classes, codes
+
+
 def _categorical_refusals(no_pairwise, collapse, strata, names=(), labels=(), exits=False):
     """The messages of the --categorical rules that a run breaks, in the order they are reported (``exits``: as the
     command line's exit messages, else as Categorical_results' ValueErrors).  ``names``, ``labels``: the traits, once
@@ -2332,31 +2368,8 @@ def read_categorical_file(path, delimiter, strains):
     isolate: its name and one cell per trait, any string as the label or one of MISSING_TRAIT.  Returns (names,
     labels [T][N] over ``strains``, None = missing): isolates the analysis does not hold are ignored, isolates of
     ``strains`` the file does not name are missing in every trait."""
-    with open(path, "r", newline=None) as f:
-        rows = [r for r in csv.reader(f, delimiter=delimiter) if r]
-    if not rows or len(rows[0]) < 2:
-        sys.exit("Please check that the categorical traits file %s is formatted properly and contains at least one "
-                 "trait" % path)
-    names = list(rows[0][1:])
-    if len(set(names)) != len(names):
-        sys.exit("The categorical traits file %s names a trait more than once" % path)
-    col = {s: j for j, s in enumerate(strains)}
-    labels = [[None] * len(strains) for _ in names]
-    seen = set()
-    for line, row in enumerate(rows[1:], start=2):
-        iso = row[0]
-        if iso in seen:
-            sys.exit("The categorical traits file %s names isolate %s more than once (line %d)" % (path, iso, line))
-        seen.add(iso)
-        if len(row) != len(names) + 1:
-            sys.exit("The categorical traits file %s has %d cells in line %d, its header has %d"
-                     % (path, len(row), line, len(names) + 1))
-        if iso not in col:
-            continue
-        for t, cell in enumerate(row[1:]):
-            if cell not in MISSING_TRAIT:
-                labels[t][col[iso]] = cell
-    return names, labels
+    return _read_side_traits(path, delimiter, strains, "categorical", lambda text, *_where: text,
+                             lambda T, N: [[None] * N for _ in range(T)])
 
 
 def Categorical_results(genedic, names, labels, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False,
@@ -2379,14 +2392,8 @@ def Categorical_results(genedic, names, labels, permutations=0, seed=DEFAULT_SEE
     N = len(table.strains)
     if len(labels) != len(names) or any(len(row) != N for row in labels):
         raise ValueError("categorical traits: labels must be [%d traits, %d isolates]" % (len(names), N))
-    if N > eng.ranksum_max_isolates():
-        raise ValueError("categorical traits take at most %d isolates; this analysis has %d"
-                         % (eng.ranksum_max_isolates(), N))
-    classes = [categorical_classes(row) for row in labels]
-    codes = np.zeros((len(names), N), dtype=np.int16)
-    for t, row in enumerate(labels):
-        number = {c: k + 1 for k, c in enumerate(classes[t])}
-        codes[t] = [number[x] if x is not None else 0 for x in row]
+    _side_stage_limits("categorical", eng, N)
+    classes, codes = _class_codes(labels, N)
     genes = table.on_device(eng)
     plan = eng.categorical_plan(codes)
     res = eng.categorical(genes, plan)
@@ -2427,40 +2434,13 @@ def StoreCategoricalResults(results, genedic, max_hits, outdir, time="", delimit
     """Write ``<outdir><trait><time>.categorical.results.csv`` for every trait of Categorical_results: the testable
     genes in ascending Chi2_p (ties in file order), Bonferroni and Benjamini-Hochberg over them, every cell
     double-quoted.  Returns the file names."""
-    table = _as_table(genedic)
-    files = []
-    for name, res in results.items():
-        with_emp = "r" in res
-        with_wy = with_emp and "r_fwer" in res
-        columns = ROARY_HEAD + list(CATEGORICAL_COLUMNS) + (["Empirical_p"] if with_emp else []) \
-            + (["Westfall_Young_p"] if with_wy else [])
-        idx = np.flatnonzero(res["testable"])
-        fname = outdir + name + time + ".categorical.results.csv"
-        with open(fname, "w") as out:
-            out.write(delimiter.join('"' + c + '"' for c in columns) + "\n")
-            if len(idx):
-                p = res["p"][idx]
-                order = np.argsort(p, kind="stable")
-                bonf, bh = bonferroni_bh(p, len(idx), order=order)
-                shown = len(idx) if max_hits is None else max(0, min(max_hits, len(idx)))
-                for k in order[:shown]:
-                    g = int(idx[k])
-                    gene = table.ids[g]
-                    cells = gene.split("_|_") if "_|_" in gene else [gene, str(table.nugn[g]),
-                                                                     str(table.annotation[g])]
-                    m, a = int(res["m"][g]), res["a"][g]
-                    cells += [_fmt(m), _fmt(res["n"] - m),
-                              "|".join("%s=%d" % (c, int(x)) for c, x in zip(res["classes"], a)),
-                              res["classes"][most_enriched_class(a, res["nk"])], _fmt(res["x2"][g]), _fmt(res["df"]),
-                              _fmt(res["v"][g]), _fmt(res["p"][g]), _fmt(bonf[k]), _fmt(bh[k])]
-                    if with_emp:
-                        cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
-                    if with_wy:
-                        cells.append(_fmt((int(res["r_fwer"][g]) + 1.0) / (res["permutations"] + 1.0)))
-                    out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
-        log.info("Storing chi-square results: %s" % fname)
-        files.append(fname)
-    return files
+    def cells(res, g):
+        a = res["a"][g]
+        return ["|".join("%s=%d" % (c, int(x)) for c, x in zip(res["classes"], a)),
+                res["classes"][most_enriched_class(a, res["nk"])], _fmt(res["x2"][g]), _fmt(res["df"]),
+                _fmt(res["v"][g]), _fmt(res["p"][g])]
+    return _store_side_results(results, genedic, max_hits, outdir, time, delimiter, CATEGORICAL_COLUMNS, cells,
+                               ".categorical.results.csv", "chi-square")
 
 
 # ---------------------------------------------------------------------------
@@ -2494,20 +2474,8 @@ def Gcmh_results(genedic, names, labels, strata, permutations=0, seed=DEFAULT_SE
     strata = np.asarray(strata)
     if len(labels) != len(names) or any(len(row) != N for row in labels):
         raise ValueError("categorical traits: labels must be [%d traits, %d isolates]" % (len(names), N))
-    if strata.shape != (N,) or not np.issubdtype(strata.dtype, np.integer) or strata.min() < 0:
-        raise ValueError("categorical traits: strata must be %d stratum indices, one per isolate" % N)
-    if N > eng.ranksum_max_isolates():
-        raise ValueError("categorical traits take at most %d isolates; this analysis has %d"
-                         % (eng.ranksum_max_isolates(), N))
-    from . import _abi
-    if int(strata.max()) + 1 > _abi.PERM_MAX_STRATA:
-        raise ValueError("categorical traits take at most %d strata; these are %d"
-                         % (_abi.PERM_MAX_STRATA, int(strata.max()) + 1))
-    classes = [categorical_classes(row) for row in labels]
-    codes = np.zeros((len(names), N), dtype=np.int16)
-    for t, row in enumerate(labels):
-        number = {c: k + 1 for k, c in enumerate(classes[t])}
-        codes[t] = [number[x] if x is not None else 0 for x in row]
+    _side_stage_limits("categorical", eng, N, strata)
+    classes, codes = _class_codes(labels, N)
     genes = table.on_device(eng)
     plan = eng.gcmh_plan(codes, strata)
     res = eng.gcmh(genes, plan)
@@ -2546,41 +2514,13 @@ def StoreGcmhResults(results, genedic, max_hits, outdir, time="", delimiter=",")
     """Write ``<outdir><trait><time>.gcmh.results.csv`` for every trait of Gcmh_results, by StoreCategoricalResults'
     rules: the testable genes in ascending GCMH_p (ties in file order), Bonferroni and Benjamini-Hochberg over them,
     every cell double-quoted.  Returns the file names."""
-    table = _as_table(genedic)
-    files = []
-    for name, res in results.items():
-        with_emp = "r" in res
-        with_wy = with_emp and "r_fwer" in res
-        columns = ROARY_HEAD + list(GCMH_COLUMNS) + (["Empirical_p"] if with_emp else []) \
-            + (["Westfall_Young_p"] if with_wy else [])
-        idx = np.flatnonzero(res["testable"])
-        fname = outdir + name + time + ".gcmh.results.csv"
-        with open(fname, "w") as out:
-            out.write(delimiter.join('"' + c + '"' for c in columns) + "\n")
-            if len(idx):
-                p = res["p"][idx]
-                order = np.argsort(p, kind="stable")
-                bonf, bh = bonferroni_bh(p, len(idx), order=order)
-                shown = len(idx) if max_hits is None else max(0, min(max_hits, len(idx)))
-                for k in order[:shown]:
-                    g = int(idx[k])
-                    gene = table.ids[g]
-                    cells = gene.split("_|_") if "_|_" in gene else [gene, str(table.nugn[g]),
-                                                                     str(table.annotation[g])]
-                    m, a, e = int(res["m"][g]), res["a"][g], res["e"][g]
-                    cells += [_fmt(m), _fmt(res["n"] - m),
-                              "|".join("%s=%d" % (c, int(x)) for c, x in zip(res["classes"], a)),
-                              "|".join("%s=%s" % (c, _fmt(x)) for c, x in zip(res["classes"], e)),
-                              res["classes"][most_enriched_expected(a, e)], _fmt(res["q"][g]), _fmt(res["df"][g]),
-                              _fmt(res["p"][g]), _fmt(bonf[k]), _fmt(bh[k])]
-                    if with_emp:
-                        cells.append(_fmt((int(res["r"][g]) + 1.0) / (res["permutations"] + 1.0)))
-                    if with_wy:
-                        cells.append(_fmt((int(res["r_fwer"][g]) + 1.0) / (res["permutations"] + 1.0)))
-                    out.write(delimiter.join('"' + c + '"' for c in cells) + "\n")
-        log.info("Storing generalized CMH results: %s" % fname)
-        files.append(fname)
-    return files
+    def cells(res, g):
+        a, e = res["a"][g], res["e"][g]
+        return ["|".join("%s=%d" % (c, int(x)) for c, x in zip(res["classes"], a)),
+                "|".join("%s=%s" % (c, _fmt(x)) for c, x in zip(res["classes"], e)),
+                res["classes"][most_enriched_expected(a, e)], _fmt(res["q"][g]), _fmt(res["df"][g]), _fmt(res["p"][g])]
+    return _store_side_results(results, genedic, max_hits, outdir, time, delimiter, GCMH_COLUMNS, cells,
+                               ".gcmh.results.csv", "generalized CMH")
 
 
 # ---------------------------------------------------------------------------
@@ -2639,16 +2579,7 @@ def VanElteren_results(genedic, names, values, strata, permutations=0, seed=DEFA
     if values.ndim != 2 or values.shape != (len(names), len(table.strains)):
         raise ValueError("quantitative traits: values must be [%d traits, %d isolates]"
                          % (len(names), len(table.strains)))
-    if strata.shape != (len(table.strains),) or not np.issubdtype(strata.dtype, np.integer) or strata.min() < 0:
-        raise ValueError("quantitative traits: strata must be %d stratum indices, one per isolate"
-                         % len(table.strains))
-    if values.shape[1] > eng.ranksum_max_isolates():
-        raise ValueError("quantitative traits take at most %d isolates; this analysis has %d"
-                         % (eng.ranksum_max_isolates(), values.shape[1]))
-    from . import _abi
-    if int(strata.max()) + 1 > _abi.PERM_MAX_STRATA:
-        raise ValueError("quantitative traits take at most %d strata; these are %d"
-                         % (_abi.PERM_MAX_STRATA, int(strata.max()) + 1))
+    _side_stage_limits("quantitative", eng, len(table.strains), strata)
     genes = table.on_device(eng)
     plan = eng.vanelteren_plan(values, strata)
     res = eng.vanelteren(genes, plan)
@@ -2682,8 +2613,8 @@ def StoreVanElterenResults(results, genedic, max_hits, outdir, time="", delimite
     """Write ``<outdir><trait><time>.vanelteren.results.csv`` for every trait of VanElteren_results, by
     StoreRanksumResults' rules: the testable genes in ascending Van_Elteren_p (ties in file order), Bonferroni and
     Benjamini-Hochberg over them, every cell double-quoted.  Returns the file names."""
-    return _store_rank_results(results, genedic, max_hits, outdir, time, delimiter, VANELTEREN_COLUMNS,
-                               ".vanelteren.results.csv", "van Elteren")
+    return _store_side_results(results, genedic, max_hits, outdir, time, delimiter, VANELTEREN_COLUMNS, _rank_cells,
+                               ".vanelteren.results.csv", "van Elteren", rank=True)
 
 
 # ---------------------------------------------------------------------------

@@ -445,3 +445,51 @@ def test_sizes_past_the_limits_and_a_short_stride_are_refused_with_nothing_writt
         eng.permute_categorical(gm, plan, obs["a"], rows, r, maxt=(inv, ivm, maxs[:, :P - 1]))
     with pytest.raises(ValueError, match="maxs is float64"):
         eng.permute_gcmh(gm, gplan, gobs, rows, r, maxt=maxs[:, :P - 1].to(torch.float32))
+
+
+def test_the_lds_opt_in_is_taken_once_per_kernel_on_a_fresh_engine():
+    """The four hot kernels on an engine of their own, each first at N = 1152 (36 plane words, 64 512 B of LDS: no
+    opt-in), then at N = 1153 (40 words, 71 680 B: the kernel's first launch that needs the opt-in), then at N = 1153
+    again (the handle's bit is set): counts and maxima are the restatement's, bit for bit, every time."""
+    import torch
+    from scoary_amd.engine import AssociationEngine
+    G, T, P, K, S = 70, 1, 65, 5, 3
+    fresh = AssociationEngine(0)
+    try:
+        want = {}
+        for N in (1152, 1153, 1153):
+            rng = np.random.default_rng(N)
+            genes = (rng.random((G, N)) < rng.uniform(0.05, 0.95, (G, 1))).astype(np.uint8)
+            codes = rng.integers(0, K + 1, (T, N))
+            strata = rng.integers(0, S, N)
+            strata[0] = S - 1
+            gm = fresh.pack_dense(genes)
+            plan, gplan = fresh.categorical_plan(codes), fresh.gcmh_plan(codes, strata)
+            obs, gobs = fresh.categorical(gm, plan), fresh.gcmh(gm, gplan)
+            inv, ivm, _sobs, _thr = fresh.categorical_wy_prepare(plan, obs["a"])
+            rows, grows = fresh.categorical_rows(plan, 0, P, SEED), fresh.gcmh_rows(gplan, 0, P, SEED)
+            zeros = lambda: torch.zeros((T, G), dtype=torch.int32, device=fresh.device)            # noqa: E731
+            maxs, gmaxs = _maxs_with_sentinels(fresh, T, P), _maxs_with_sentinels(fresh, T, P)
+            got = dict(r=fresh.permute_categorical(gm, plan, obs["a"], rows, zeros()),
+                       r_maxt=fresh.permute_categorical(gm, plan, obs["a"], rows, zeros(), maxt=(inv, ivm, maxs)),
+                       g=fresh.permute_gcmh(gm, gplan, gobs, grows, zeros()),
+                       g_maxt=fresh.permute_gcmh(gm, gplan, gobs, grows, zeros(), maxt=gmaxs), maxs=maxs, gmaxs=gmaxs)
+            got = {k: v.cpu().numpy() for k, v in got.items()}
+            if N not in want:                                            # (the third round repeats the second's inputs)
+                nk = cs.sizes(codes[0].tolist(), 8)
+                a_obs, a_perm = _tables(genes, codes)[0], _tables(genes, rows.cpu().numpy())[0]
+                ivm_t = np.array([ws.ivm_of(a.tolist(), nk) for a in a_obs])
+                w = np.array(cs.weights(nk), dtype=object)
+                exact = ((a_perm.astype(object) ** 2) @ w >= ((a_obs.astype(object) ** 2) @ w)[None]).sum(axis=0)
+                sp = _gspec(genes, codes[0], strata, S)
+                cells = gs.q_many(_tables(genes, grows[0].cpu().numpy()), sp["form"])
+                want[N] = dict(r=exact.astype(np.int64), maxs=ws.maxs(ws.stats(a_perm, nk, ivm_t)),
+                               g=(cells >= sp["thr"][None]).sum(axis=0), gmaxs=ws.maxs(cells))
+                assert 0 < want[N]["r"].sum() < G * P and 0 < want[N]["g"].sum() < G * P and want[N]["maxs"].min() > 0
+            for plain, fused, col in (("r", "r_maxt", "maxs"), ("g", "g_maxt", "gmaxs")):
+                assert np.array_equal(got[plain][0], want[N][plain]), (N, plain)
+                assert np.array_equal(got[fused][0], want[N][plain]), (N, fused)
+                assert np.array_equal(_bits(got[col][0, :P]), _bits(want[N][col])), (N, col)
+                assert (got[col][:, P:] == SENTINEL).all()
+    finally:
+        fresh.close()

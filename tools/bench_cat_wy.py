@@ -1,6 +1,7 @@
-"""The Westfall-Young kernels of the categorical traits (spec S22) against the kernels they restate, at cfg3's geometry
-with one trait on one MI355X: G = 50 000 genes (Roary-like frequencies from synth), N = 2000 isolates, P = 10 000 label
-permutations, K = 4 and K = 8 classes, 10 strata for the generalized CMH pair.
+"""The Westfall-Young kernels of the categorical traits (spec S22) against the plain kernels they extend, at cfg3's
+geometry with one trait on one MI355X: G = 50 000 genes (Roary-like frequencies from synth), N = 2000 isolates (or
+``isolates``: up to 1280 k_cat_permute fits two blocks on a CU), P = 10 000 label permutations, K = 4 and K = 8
+classes, 10 strata for the generalized CMH pair.
 
 Timed, every repeat in the same process after warm-up, the variants alternating inside a repeat, each by device events
 (set_timing / kernel_ms):
@@ -9,8 +10,9 @@ Timed, every repeat in the same process after warm-up, the variants alternating 
 Before anything is timed the counts of the fused pass are held to the plain pass's, and r_fwer to r_fwer >= r.
 Reported: median, min and max of each and the two ratios with the plain kernel's run-to-run spread -- reported, not
 gated: the alternative to the fused pass is a second full pass, a ratio of 2.  Raw lines on stdout
-(profiles/cat_wy.txt).
-    python tools/bench_cat_wy.py [repeats] [warmup]"""
+(profiles/cat_wy.txt); every sample on a "raw" line, for an A/B of two builds (SCOARY_HIP_LIB, build_alt.sh:
+profiles/cat_block.txt).
+    python tools/bench_cat_wy.py [repeats] [warmup] [isolates]"""
 import datetime
 import json
 import os
@@ -26,18 +28,20 @@ from scoary_amd.engine import AssociationEngine
 
 REPEATS = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 WARMUP = int(sys.argv[2]) if len(sys.argv) > 2 else 2
+ISOLATES = int(sys.argv[3]) if len(sys.argv) > 3 else None
 STRATA = 10
 SHARES = {4: [0.4, 0.3, 0.2, 0.1], 8: [0.3, 0.2, 0.15, 0.1, 0.1, 0.05, 0.05, 0.05]}
 
 if not torch.cuda.is_available():
     sys.exit("bench_cat_wy needs an MI355X: there is nothing to time without one")
 
-genes, _traits, P, seed = synth.make_config("cfg3", T=1)
+genes, _traits, P, seed = synth.make_config("cfg3", T=1, N=ISOLATES)
 G, N = genes.shape
 eng = AssociationEngine(0)
 gm = eng.pack_dense(genes)
-print("date %s  shape G=%d N=%d T=1 P=%d S=%d  repeats %d warm-up %d" % (
-    datetime.date.today().isoformat(), G, N, P, STRATA, REPEATS, WARMUP), flush=True)
+print("date %s  shape G=%d N=%d T=1 P=%d S=%d  repeats %d warm-up %d  library %s" % (
+    datetime.date.today().isoformat(), G, N, P, STRATA, REPEATS, WARMUP, os.environ.get("SCOARY_HIP_LIB", "the tree's")),
+    flush=True)
 
 
 def timed(fn, kernel):
@@ -89,6 +93,7 @@ for K in (4, 8):
                     t[kernel].append(ms)
     for kernel, xs in t.items():
         line("K=%d %s" % (K, kernel), xs)
+        print("raw N=%d K=%d %s %s" % (N, K, kernel, " ".join("%.4f" % x for x in xs)), flush=True)
     med = {k: statistics.median(v) for k, v in t.items()}
     for plain, fused in (("k_cat_permute", "k_cat_maxt"), ("k_gcmh_permute", "k_gcmh_maxt")):
         print("K=%d: %s / %s = %.3f (%s's spread %.3f ms, %.1f %% of its median)" % (

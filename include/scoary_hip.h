@@ -658,6 +658,51 @@ int scoary_permute_cat_wy(scoary_handle h, const uint32_t *d_tiled, const int16_
 int scoary_permute_gcmh_wy(scoary_handle h, const uint32_t *d_tiled, const int16_t *d_rows, const double *d_form,
                            const double *d_thr, const int32_t *d_nk, int64_t G, int64_t T, int64_t N, int64_t P,
                            int32_t *d_r, double *d_maxs, int64_t maxs_stride, scoary_stream_t stream);
+/* ---- Categorical traits: Westfall-Young step-down maxT over the chi-square and the generalized CMH statistic
+ * (spec S23 of DESIGN.md; additive, ABI 11) ----
+ * S22's statistic s of a cell with the genes of a trait walked in rank order: order[t][k] = the gene at rank k of trait
+ * t, ranks by descending comparison point thr (scoary_cat_wy_prepare's d_thr, or scoary_gcmh's) and ascending gene
+ * index among equals: one stable descending sort of thr, made by the caller.  u[k] of a permuted row = the maximum of s
+ * over the genes at the ranks k and behind, 0.0 behind the last.
+ *   scoary_cat_stepdown_scratch_bytes   the size of d_scratch for batches of up to P permutations of the chi-square
+ *       test (gcmh = 0) or the generalized CMH test (gcmh = 1).  With Gs = G rounded up to 1024 and Qs = ceil(ceil(N /
+ *       32) / 4), in this order: rows uint32 [T][Qs][Gs][4], a tiled matrix per trait by POSITION -- position 1024 sg +
+ *       64 i + 4 w + j holds rank 1024 sg + 64 w + 4 i + j (i, w < 16, j < 4) --; then per position, gcmh = 0: a_obs
+ *       int32 [T][Gs][8], ivm double [T][Gs], thr double [T][Gs]; gcmh = 1: form double [T][Gs][35], thr double [T][Gs];
+ *       then gmax double [T][Gs / 64][64 ceil(P / 64)].  Everything before gmax does not depend on P.
+ *   scoary_cat_stepdown_gather          once per analysis, chi-square: the rows and per-position values from d_tiled,
+ *       d_order int32 [T][G], d_a (scoary_categorical's), d_ivm and d_thr (scoary_cat_wy_prepare's).  A position whose
+ *       rank is >= G holds a zero row, zeros and thr = +inf; an entry of d_order outside [0, G) makes such a position
+ *       too (its rank is counted like any other: s = 0 in every row, u >= +inf never).
+ *   scoary_gcmh_stepdown_gather         the same for the generalized CMH test: d_form and d_thr are scoary_gcmh's.
+ *   scoary_permute_cat_stepdown         one batch of P permutations -- d_rows int16 [T][P][N], the columns perm_base ..
+ *       perm_base + P - 1 -- in three launches on `stream`: d_r_rank[t * G + k] += scoary_permute_categorical's count of
+ *       the gene at rank k (d_nk, d_w as there), d_c_rank[t * G + k] += #{columns < P : u[k] >= thr of rank k}, doubles
+ *       compared exactly, and d_maxs[t * maxs_stride + perm_base + p] = u[0] of column p < P -- written, not combined,
+ *       and equal to scoary_permute_cat_wy's maximum bit for bit (d_inv: scoary_cat_wy_prepare's).  d_maxs is the whole
+ *       double [T][maxs_stride] array.  The caller zeroes d_r_rank and d_c_rank (int32 [T][G]) before the first batch.
+ *   scoary_permute_gcmh_stepdown        the same with s = Q under the position's form and the rows shuffled within the
+ *       strata: d_r_rank adds scoary_permute_gcmh's count, d_maxs is scoary_permute_gcmh_wy's.
+ * Ranks at and past G and columns at and past P reach none of d_r_rank, d_c_rank, d_maxs; their cells of gmax hold
+ * anything.  No block waits for another and gmax has one writer per cell; the counts are integer atomic additions.
+ * Asynchronous on `stream`, nothing is allocated.  SCOARY_ERR_ARG: null pointer, size < 1, perm_base < 0, maxs_stride
+ * < perm_base + P; SCOARY_ERR_SIZE, with nothing written: N > scoary_ranksum_max_isolates(), T > 65535, G >= 2^31 -
+ * 1024, P >= 2^31, a grid past 2^31 - 1 blocks.  scoary_cat_stepdown_scratch_bytes returns 0 for a null handle, a
+ * size < 1 or such a G. */
+int64_t scoary_cat_stepdown_scratch_bytes(scoary_handle h, int64_t G, int64_t T, int64_t N, int64_t P, int64_t gcmh);
+int scoary_cat_stepdown_gather(scoary_handle h, const uint32_t *d_tiled, const int32_t *d_order, const int32_t *d_a,
+                               const double *d_ivm, const double *d_thr, int64_t G, int64_t T, int64_t N,
+                               void *d_scratch, scoary_stream_t stream);
+int scoary_gcmh_stepdown_gather(scoary_handle h, const uint32_t *d_tiled, const int32_t *d_order, const double *d_form,
+                                const double *d_thr, int64_t G, int64_t T, int64_t N, void *d_scratch,
+                                scoary_stream_t stream);
+int scoary_permute_cat_stepdown(scoary_handle h, void *d_scratch, const int16_t *d_rows, const int32_t *d_nk,
+                                const uint64_t *d_w, const double *d_inv, int64_t G, int64_t T, int64_t N, int64_t P,
+                                int64_t perm_base, int32_t *d_r_rank, int32_t *d_c_rank, double *d_maxs,
+                                int64_t maxs_stride, scoary_stream_t stream);
+int scoary_permute_gcmh_stepdown(scoary_handle h, void *d_scratch, const int16_t *d_rows, const int32_t *d_nk,
+                                 int64_t G, int64_t T, int64_t N, int64_t P, int64_t perm_base, int32_t *d_r_rank,
+                                 int32_t *d_c_rank, double *d_maxs, int64_t maxs_stride, scoary_stream_t stream);
 /* ---- Quantitative traits over strata: the van Elteren test with value permutations within the strata (spec S16 of
  * DESIGN.md; additive, ABI 11) ----
  * The strata are d_strata uint16 [N] (the stratum of every isolate, in [0, S)) and d_members int32 [N] (the isolates

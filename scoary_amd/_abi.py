@@ -101,6 +101,11 @@ SIGNATURES = {
     "scoary_cat_wy_prepare": (_i32, [_vp] * 3 + [_i64] * 3 + [_vp] * 5),
     "scoary_permute_cat_wy": (_i32, [_vp] * 8 + [_i64] * 4 + [_vp, _vp, _i64, _vp]),
     "scoary_permute_gcmh_wy": (_i32, [_vp] * 6 + [_i64] * 4 + [_vp, _vp, _i64, _vp]),
+    "scoary_cat_stepdown_scratch_bytes": (_i64, [_vp] + [_i64] * 5),
+    "scoary_cat_stepdown_gather": (_i32, [_vp] * 6 + [_i64] * 3 + [_vp, _vp]),
+    "scoary_gcmh_stepdown_gather": (_i32, [_vp] * 5 + [_i64] * 3 + [_vp, _vp]),
+    "scoary_permute_cat_stepdown": (_i32, [_vp] * 6 + [_i64] * 5 + [_vp] * 3 + [_i64, _vp]),
+    "scoary_permute_gcmh_stepdown": (_i32, [_vp] * 4 + [_i64] * 5 + [_vp] * 3 + [_i64, _vp]),
     "scoary_vanelteren": (_i32, [_vp] * 8 + [_i64] * 4 + [_vp] * 7),
     "scoary_vanelteren_perm_generate": (_i32, [_vp] * 4 + [_i64] * 6 + [_u64, _vp, _vp]),
     "scoary_vanelteren_perm_generate_bfrag": (_i32, [_vp] * 4 + [_i64] * 6 + [_u64, _vp, _vp]),

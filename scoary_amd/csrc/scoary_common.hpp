@@ -28,7 +28,7 @@ struct scoary_ctx {
   int cmh_exact_lds_optin = 0;   // k_cmh_exact with it
   int cmh_exact_odds_lds_optin = 0;   // k_cmh_odds_exact with it
   int ranksum_lds_optin = 0;   // bit 0: k_ranksum_labels, bit 1: k_permute_ranksum with it
-  int cat_lds_optin = 0;   // bits 0 .. 3: k_cat_permute, k_cat_maxt, k_gcmh_permute, k_gcmh_maxt with it
+  int cat_lds_optin = 0;   // bits 0 .. 3: k_cat_permute, k_cat_maxt, k_gcmh_permute, k_gcmh_maxt with it; 4 .. 7: S23's
   int mfma_route = SCOARY_MFMA_ROUTE_AUTO;  // scoary_set_mfma_route: which list slots take the matrix-core kernel
   int fisher_route = SCOARY_FISHER_ROUTE_AUTO;     // scoary_set_fisher_route: the kernels of scoary_fisher_lists_chained
   uint32_t* scipy_primes = nullptr;  // scoary_fisher_scipy's prime table and reciprocals (device,

@@ -2380,6 +2380,129 @@ class AssociationEngine:
         return self._rank_stepdown("vanelteren_stepdown", genes, plan, res, res["var"], 0, permutations, budget_bytes,
                                    self._vanelteren_generator(plan, seed))
 
+    # -- categorical traits: step-down maxT over the chi-square and the gcmh statistic (spec S23) --
+    def cat_stepdown_batch(self, G, T, N, permutations, budget_bytes=8 << 30):
+        """Permutations per batch of the categorical step-down passes (a multiple of 64): the code rows and gmax -- 8
+        bytes per (trait, run of 64 ranks, column) -- stay under budget_bytes together."""
+        per = max(2 * 64 * int(T) * int(N), 1) + 8 * int(T) * (-(-int(G) // 1024) * 16) * 64
+        return int(max(64, min(-(-permutations // 64) * 64, budget_bytes // per * 64)))
+
+    def _cat_stepdown_scratch(self, what, genes, order32, thr, T, N, batch, gcmh):
+        torch = _torch()
+        G = genes.G
+        for x, dt, name in ((order32, torch.int32, "order32"), (thr, torch.float64, "thr")):
+            if tuple(x.shape) != (T, G) or x.dtype != dt or not x.is_contiguous():
+                raise ValueError("%s: %s is %s [T, G], contiguous" % (what, name, dt))
+        if genes.N != int(N):
+            raise ValueError("%s: the gene matrix is not the one of the plan" % what)
+        need = int(self.lib.scoary_cat_stepdown_scratch_bytes(self.h, G, T, int(N), int(batch), int(gcmh)))
+        if need < 1:
+            raise ValueError("%s: sizes outside what the step-down passes take" % what)
+        return self._empty((need,), torch.uint8)
+
+    def cat_stepdown_gather(self, genes, order32, a_obs, ivm, thr, N, batch):
+        """The scratch of the chi-square step-down passes for batches of up to ``batch`` permutations, with every
+        trait's gene rows, a_obs, ivm and thr gathered into position order (k_cat_sd_gather: once per analysis)."""
+        torch = _torch()
+        T, G = (int(x) for x in thr.shape)
+        if tuple(a_obs.shape) != (T, G, 8) or a_obs.dtype != torch.int32 or not a_obs.is_contiguous() \
+                or tuple(ivm.shape) != (T, G) or ivm.dtype != torch.float64 or not ivm.is_contiguous():
+            raise ValueError("cat_stepdown_gather: a_obs is int32 [T, G, 8] and ivm float64 [T, G], contiguous")
+        scratch = self._cat_stepdown_scratch("cat_stepdown_gather", genes, order32, thr, T, N, batch, 0)
+        self._check(self.lib.scoary_cat_stepdown_gather(
+            self.h, self._ptr(genes.tiled), self._ptr(order32), self._ptr(a_obs), self._ptr(ivm), self._ptr(thr),
+            G, T, int(N), self._ptr(scratch), self._stream()), "scoary_cat_stepdown_gather")
+        return scratch
+
+    def gcmh_stepdown_gather(self, genes, order32, form, thr, N, batch):
+        """cat_stepdown_gather for the generalized CMH test: form float64 [T, G, 35] and thr are gcmh()'s."""
+        torch = _torch()
+        T, G = (int(x) for x in thr.shape)
+        if tuple(form.shape) != (T, G, GCMH_FORM) or form.dtype != torch.float64 or not form.is_contiguous():
+            raise ValueError("gcmh_stepdown_gather: form is float64 [T, G, %d], contiguous" % GCMH_FORM)
+        scratch = self._cat_stepdown_scratch("gcmh_stepdown_gather", genes, order32, thr, T, N, batch, 1)
+        self._check(self.lib.scoary_gcmh_stepdown_gather(
+            self.h, self._ptr(genes.tiled), self._ptr(order32), self._ptr(form), self._ptr(thr), G, T, int(N),
+            self._ptr(scratch), self._stream()), "scoary_gcmh_stepdown_gather")
+        return scratch
+
+    @staticmethod
+    def _check_stepdown_batch(what, rows, r_rank, c_rank, maxs, T, G, N):
+        torch = _torch()
+        AssociationEngine._check_rows_r(what, rows, r_rank, T, G, N)
+        AssociationEngine._check_rows_r(what, rows, c_rank, T, G, N)
+        if maxs.dim() != 2 or maxs.shape[0] != T or maxs.dtype != torch.float64 or not maxs.is_contiguous():
+            raise ValueError("%s: maxs is the whole float64 [T, permutations] array, contiguous" % what)
+
+    def permute_cat_stepdown(self, scratch, plan, inv, rows, G, perm_base, r_rank, c_rank, maxs):
+        """One batch of the three chi-square step-down launches: the code rows ``rows`` int16 [T, P, N], the
+        permutations perm_base .. perm_base + P - 1, add to r_rank and c_rank (int32 [T, G], by rank position) and
+        write their columns of maxs (float64 [T, stride]).  inv: categorical_wy_prepare's."""
+        self._check_stepdown_batch("permute_cat_stepdown", rows, r_rank, c_rank, maxs, plan.T, int(G), plan.N)
+        self._check(self.lib.scoary_permute_cat_stepdown(
+            self.h, self._ptr(scratch), self._ptr(rows), self._ptr(plan.nk), self._ptr(plan.w), self._ptr(inv), int(G),
+            plan.T, plan.N, int(rows.shape[1]), int(perm_base), self._ptr(r_rank), self._ptr(c_rank), self._ptr(maxs),
+            int(maxs.shape[1]), self._stream()), "scoary_permute_cat_stepdown")
+
+    def permute_gcmh_stepdown(self, scratch, plan, rows, G, perm_base, r_rank, c_rank, maxs):
+        """permute_cat_stepdown for the generalized CMH test, the rows shuffled within the strata."""
+        self._check_stepdown_batch("permute_gcmh_stepdown", rows, r_rank, c_rank, maxs, plan.T, int(G), plan.N)
+        self._check(self.lib.scoary_permute_gcmh_stepdown(
+            self.h, self._ptr(scratch), self._ptr(rows), self._ptr(plan.nk), int(G), plan.T, plan.N,
+            int(rows.shape[1]), int(perm_base), self._ptr(r_rank), self._ptr(c_rank), self._ptr(maxs),
+            int(maxs.shape[1]), self._stream()), "scoary_permute_gcmh_stepdown")
+
+    def _cat_stepdown(self, genes, plan, thr, permutations, budget_bytes, gather, rows_of, launch):
+        """Spec S23 over one categorical test: (r, r_fwer, r_sd, maxs) from one run -- the sort by thr and the gather
+        (``gather(order32, batch)`` returns the scratch), the batch loop with the test's row generator
+        (``launch(scratch, rows, base, r_rank, c_rank, maxs)``), then the host tail.  k_cat_maxt / k_gcmh_maxt are not
+        launched: maxs is u[0]."""
+        torch = _torch()
+        T, G, N, P = plan.T, genes.G, plan.N, int(permutations)
+        order32, tt = self.rank_stepdown_order(thr)
+        batch = self.cat_stepdown_batch(G, T, N, P, budget_bytes)
+        scratch = gather(order32, min(batch, P))
+        r_rank = torch.zeros((T, G), dtype=torch.int32, device=self.device)
+        c_rank = torch.zeros((T, G), dtype=torch.int32, device=self.device)
+        maxs = torch.zeros((T, P), dtype=torch.float64, device=self.device)
+        for base in range(0, P, batch):
+            launch(scratch, rows_of(base, min(batch, P - base)), base, r_rank, c_rank, maxs)
+        r = torch.empty_like(r_rank)
+        r.scatter_(1, order32.to(torch.int64), r_rank)
+        return r, self.r_fwer_max(maxs, thr), self.rank_stepdown_tail(c_rank, tt, order32), maxs
+
+    def categorical_stepdown(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
+        """Westfall-Young step-down maxT over the chi-square statistic (spec S23) of the step ``res`` =
+        categorical(genes, plan): (r, r_fwer, r_sd, maxs) -- r, r_fwer and maxs as categorical_westfall_young returns
+        them, bit for bit, and r_sd int32 [T, G] with r <= r_sd <= r_fwer; (r_sd + 1) / (permutations + 1) is the
+        adjusted p.  The step-down is over all genes of the matrix: gene shards do not compose."""
+        self._ranksum_fits("categorical_stepdown", genes, plan)
+        a_obs = res["a"]
+        inv, ivm, _sobs, thr = self.categorical_wy_prepare(plan, a_obs)
+        if a_obs.shape[1] != genes.G:
+            raise ValueError("categorical_stepdown: res is the observed result of these genes and this plan")
+        return self._cat_stepdown(
+            genes, plan, thr, permutations, budget_bytes,
+            lambda order32, batch: self.cat_stepdown_gather(genes, order32, a_obs, ivm, thr, plan.N, batch),
+            lambda base, nb: self.categorical_rows(plan, base, nb, seed),
+            lambda scratch, rows, base, r_rank, c_rank, maxs: self.permute_cat_stepdown(
+                scratch, plan, inv, rows, genes.G, base, r_rank, c_rank, maxs))
+
+    def gcmh_stepdown(self, genes, plan, res, permutations, seed, budget_bytes=8 << 30):
+        """categorical_stepdown over the generalized CMH statistic (spec S23) of the step ``res`` = gcmh(genes, plan),
+        the rows shuffled within the strata: r, r_fwer and maxs are gcmh_westfall_young's, bit for bit."""
+        torch = _torch()
+        self._ranksum_fits("gcmh_stepdown", genes, plan)
+        form, thr = res["form"], res["thr"]
+        if tuple(thr.shape) != (plan.T, genes.G) or thr.dtype != torch.float64 or not thr.is_contiguous():
+            raise ValueError("gcmh_stepdown: res is the observed result of these genes and this plan")
+        return self._cat_stepdown(
+            genes, plan, thr, permutations, budget_bytes,
+            lambda order32, batch: self.gcmh_stepdown_gather(genes, order32, form, thr, plan.N, batch),
+            lambda base, nb: self.gcmh_rows(plan, base, nb, seed),
+            lambda scratch, rows, base, r_rank, c_rank, maxs: self.permute_gcmh_stepdown(
+                scratch, plan, rows, genes.G, base, r_rank, c_rank, maxs))
+
     # -- timing (bench.py) ------------------------------------------------------
     def set_timing(self, on):
         self._check(self.lib.scoary_set_timing(self.h, 1 if on else 0), "scoary_set_timing")

@@ -1809,6 +1809,12 @@ def ScoaryArgumentParser(argv=None):
                    "results -- and, with --categorical-strata, to the generalized CMH results -- the single-step maxT "
                    "family-wise p over all genes of the table, from the same permutations that give Empirical_p "
                    "(single process; scoary_amd extension)")
+    a.add_argument("--categorical-fwer-stepdown", dest="categorical_fwer_stepdown", action="store_true",
+                   default=False,
+                   help="With --categorical and --permute X (X >= 10): add the column Westfall_Young_stepdown_p to the "
+                   "chi-square results -- and, with --categorical-strata, to the generalized CMH results -- the "
+                   "step-down maxT family-wise p: a gene is compared with the genes at its rank and behind, so the p "
+                   "is never above Westfall_Young_p (single process; scoary_amd extension)")
     a.add_argument("--quantitative-strata", dest="quantitative_strata", metavar="FILE", default=None,
                    help="With --quantitative: FILE names a stratum (lineage, cluster) for every isolate, in the format "
                    "of --permute-strata's file.  Every measured trait is additionally tested with the van Elteren "
@@ -2041,16 +2047,19 @@ def main(**kwargs):
         if getattr(args, "categorical", None) and rank == 0:
             names, labels = read_categorical_file(args.categorical, args.delimiter, strains)
             cfwer = bool(getattr(args, "categorical_fwer", False))
+            csd = bool(getattr(args, "categorical_fwer_stepdown", False))
             with _stage("chi-square test of the categorical traits"):
                 StoreCategoricalResults(Categorical_results(genedic, names, labels, permutations=args.permute,
-                                                            seed=seed, exits=True, fwer=cfwer),
-                                        genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
+                                                            seed=seed, exits=True, fwer=cfwer, stepdown=csd),
+                                        genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter,
+                                        stepdown=csd)
             if getattr(args, "categorical_strata", None):
                 cstrata = strata_indices(args.categorical_strata_map, strains)[0]
                 with _stage("generalized CMH test of the categorical traits"):
                     StoreGcmhResults(Gcmh_results(genedic, names, labels, cstrata, permutations=args.permute,
-                                                  seed=seed, fwer=cfwer),
-                                     genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
+                                                  seed=seed, fwer=cfwer, stepdown=csd),
+                                     genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter,
+                                     stepdown=csd)
         log.info("Stage seconds: load (+tree) %.2f, association (+permutations) %.2f, pairwise stage and "
                  "output %.2f" % (t_loaded - start, t_stats - t_loaded, _time.time() - t_stats))
         gene_bytes = os.path.getsize(args.genes) if os.path.isfile(args.genes) else 0
@@ -2254,17 +2263,19 @@ PERMUTATION_COLUMNS = (("Empirical_p", "r"), ("Westfall_Young_p", "r_fwer"), ("W
 
 
 def _store_side_results(results, genedic, max_hits, outdir, time, delimiter, test_columns, cells, suffix, what,
-                        rank=False):
+                        rank=False, stepdown=False):
     """The result files of a side stage (the four Store*Results below): per trait the testable genes in ascending p
     (ties in file order), Bonferroni and Benjamini-Hochberg over them, every cell double-quoted.  ``test_columns``
     name the stage's fixed columns: the two carrier counts, the test's own -- their cells are ``cells(res, g)`` --
     and the two adjusted p.  Behind them come the columns a result carries the keys for: with ``rank`` the shift and
-    its limits, then Empirical_p, Westfall_Young_p and, with ``rank``, Westfall_Young_stepdown_p."""
+    its limits, then Empirical_p, Westfall_Young_p and, with ``rank`` or ``stepdown``, Westfall_Young_stepdown_p (the
+    categorical stages ask for it with ``stepdown``: a result that merely carries r_sd gets no column there)."""
     table = _as_table(genedic)
     files = []
     for name, res in results.items():
         with_shift = rank and all(key in res for _column, key in RANK_SHIFT_COLUMNS)
-        counts = [(column, key) for column, key in PERMUTATION_COLUMNS[:3 if rank else 2] if "r" in res and key in res]
+        counts = [(column, key) for column, key in PERMUTATION_COLUMNS[:3 if rank or stepdown else 2]
+                  if "r" in res and key in res]
         columns = ROARY_HEAD + list(test_columns) + \
             ([column for column, _key in RANK_SHIFT_COLUMNS] if with_shift else []) + [column for column, _key in counts]
         idx = np.flatnonzero(res["testable"])
@@ -2373,17 +2384,22 @@ def read_categorical_file(path, delimiter, strains):
 
 
 def Categorical_results(genedic, names, labels, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False,
-                        strata=None, exits=False, fwer=False):
+                        strata=None, exits=False, fwer=False, stepdown=False):
     """The chi-square stage (spec S20) of the traits ``names`` with the labels [T][N] (a string per isolate, None =
     missing) over the isolates of ``genedic``: {name: dict(classes, n, nk [K], df, a [G, K], m, x2, v, p, testable
-    [G]; r [G] and permutations with permutations >= 10; r_fwer [G] with ``fwer``, spec S22)}, arrays in the gene
-    table's order.  Raises ValueError where the command line refuses --categorical or --categorical-fwer (``exits``:
-    exits with the command line's message instead)."""
+    [G]; r [G] and permutations with permutations >= 10; r_fwer [G] with ``fwer``, spec S22; r_sd [G] with
+    ``stepdown``, spec S23)}, arrays in the gene table's order.  Raises ValueError where the command line refuses
+    --categorical, --categorical-fwer or --categorical-fwer-stepdown (``exits``: exits with the command line's message
+    instead)."""
     for text in _categorical_refusals(no_pairwise, collapse, strata is not None, names, labels, exits=exits):
         if exits:
             sys.exit(text)
         raise ValueError(text)
     for text in _cat_wy_refusals(fwer, True, permutations):
+        if exits:
+            sys.exit(text)
+        raise ValueError(text)
+    for text in _cat_sd_refusals(stepdown, True, permutations):
         if exits:
             sys.exit(text)
         raise ValueError(text)
@@ -2398,8 +2414,11 @@ def Categorical_results(genedic, names, labels, permutations=0, seed=DEFAULT_SEE
     plan = eng.categorical_plan(codes)
     res = eng.categorical(genes, plan)
     permutations = int(permutations)
-    r = r_fwer = None
-    if fwer:
+    r = r_fwer = r_sd = None
+    if stepdown:                 # the step-down run gives all three counts; the single-step one costs nothing extra
+        r, r_fwer, r_sd = (x.cpu().numpy() for x in eng.categorical_stepdown(genes, plan, res, permutations, seed)[:3])
+        r_fwer = r_fwer if fwer else None
+    elif fwer:
         r, r_fwer = (x.cpu().numpy() for x in eng.categorical_westfall_young(genes, plan, res, permutations, seed)[:2])
     elif permutations >= 10:
         r = eng.categorical_permute(genes, plan, res["a"], permutations, seed).cpu().numpy()
@@ -2415,6 +2434,8 @@ def Categorical_results(genedic, names, labels, permutations=0, seed=DEFAULT_SEE
             out[name]["permutations"] = permutations
         if r_fwer is not None:
             out[name]["r_fwer"] = r_fwer[t]
+        if r_sd is not None:
+            out[name]["r_sd"] = r_sd[t]
         log.info("Chi-square test of %s: %d isolates with a label in %d classes, %d genes tested"
                  % (name, n, K, int(testable.sum())))
     return out
@@ -2430,17 +2451,18 @@ def most_enriched_class(a, nk):
     return best
 
 
-def StoreCategoricalResults(results, genedic, max_hits, outdir, time="", delimiter=","):
+def StoreCategoricalResults(results, genedic, max_hits, outdir, time="", delimiter=",", stepdown=False):
     """Write ``<outdir><trait><time>.categorical.results.csv`` for every trait of Categorical_results: the testable
     genes in ascending Chi2_p (ties in file order), Bonferroni and Benjamini-Hochberg over them, every cell
-    double-quoted.  Returns the file names."""
+    double-quoted.  ``stepdown`` (--categorical-fwer-stepdown): Westfall_Young_stepdown_p from the results' r_sd, the
+    last column.  Returns the file names."""
     def cells(res, g):
         a = res["a"][g]
         return ["|".join("%s=%d" % (c, int(x)) for c, x in zip(res["classes"], a)),
                 res["classes"][most_enriched_class(a, res["nk"])], _fmt(res["x2"][g]), _fmt(res["df"]),
                 _fmt(res["v"][g]), _fmt(res["p"][g])]
     return _store_side_results(results, genedic, max_hits, outdir, time, delimiter, CATEGORICAL_COLUMNS, cells,
-                               ".categorical.results.csv", "chi-square")
+                               ".categorical.results.csv", "chi-square", stepdown=stepdown)
 
 
 # ---------------------------------------------------------------------------
@@ -2458,15 +2480,18 @@ GCMH_TEXT = {
 
 
 def Gcmh_results(genedic, names, labels, strata, permutations=0, seed=DEFAULT_SEED, no_pairwise=True, collapse=False,
-                 fwer=False):
+                 fwer=False, stepdown=False):
     """The generalized CMH stage (spec S21) of the traits ``names`` with the labels [T][N] (a string per isolate, None
     = missing) and the stratum index of every isolate ``strata`` (N integers) over the isolates of ``genedic``: {name:
     dict(classes, n, strata (those with a labelled isolate), a [G, K], e [G, K], m, q, df, p, testable [G]; r [G] and
-    permutations with permutations >= 10; r_fwer [G] with ``fwer``, spec S22)}, arrays in the gene table's order.
-    Raises ValueError where the command line refuses --categorical or --categorical-fwer."""
+    permutations with permutations >= 10; r_fwer [G] with ``fwer``, spec S22; r_sd [G] with ``stepdown``, spec S23)},
+    arrays in the gene table's order.  Raises ValueError where the command line refuses --categorical,
+    --categorical-fwer or --categorical-fwer-stepdown."""
     for text in _categorical_refusals(no_pairwise, collapse, False, names, labels):
         raise ValueError(text)
     for text in _cat_wy_refusals(fwer, True, permutations):
+        raise ValueError(text)
+    for text in _cat_sd_refusals(stepdown, True, permutations):
         raise ValueError(text)
     table = _as_table(genedic)
     eng = get_engine()
@@ -2480,8 +2505,11 @@ def Gcmh_results(genedic, names, labels, strata, permutations=0, seed=DEFAULT_SE
     plan = eng.gcmh_plan(codes, strata)
     res = eng.gcmh(genes, plan)
     permutations = int(permutations)
-    r = r_fwer = None
-    if fwer:
+    r = r_fwer = r_sd = None
+    if stepdown:
+        r, r_fwer, r_sd = (x.cpu().numpy() for x in eng.gcmh_stepdown(genes, plan, res, permutations, seed)[:3])
+        r_fwer = r_fwer if fwer else None
+    elif fwer:
         r, r_fwer = (x.cpu().numpy() for x in eng.gcmh_westfall_young(genes, plan, res, permutations, seed)[:2])
     elif permutations >= 10:
         r = eng.gcmh_permute(genes, plan, res, permutations, seed).cpu().numpy()
@@ -2496,6 +2524,8 @@ def Gcmh_results(genedic, names, labels, strata, permutations=0, seed=DEFAULT_SE
             out[name]["permutations"] = permutations
         if r_fwer is not None:
             out[name]["r_fwer"] = r_fwer[t]
+        if r_sd is not None:
+            out[name]["r_sd"] = r_sd[t]
         log.info("Generalized CMH test of %s: %d isolates with a label in %d classes and %d strata, %d genes tested"
                  % (name, out[name]["n"], K, out[name]["strata"], int(out[name]["testable"].sum())))
     return out
@@ -2510,17 +2540,17 @@ def most_enriched_expected(a, e):
     return best
 
 
-def StoreGcmhResults(results, genedic, max_hits, outdir, time="", delimiter=","):
+def StoreGcmhResults(results, genedic, max_hits, outdir, time="", delimiter=",", stepdown=False):
     """Write ``<outdir><trait><time>.gcmh.results.csv`` for every trait of Gcmh_results, by StoreCategoricalResults'
     rules: the testable genes in ascending GCMH_p (ties in file order), Bonferroni and Benjamini-Hochberg over them,
-    every cell double-quoted.  Returns the file names."""
+    every cell double-quoted; ``stepdown`` as there.  Returns the file names."""
     def cells(res, g):
         a, e = res["a"][g], res["e"][g]
         return ["|".join("%s=%d" % (c, int(x)) for c, x in zip(res["classes"], a)),
                 "|".join("%s=%s" % (c, _fmt(x)) for c, x in zip(res["classes"], e)),
                 res["classes"][most_enriched_expected(a, e)], _fmt(res["q"][g]), _fmt(res["df"][g]), _fmt(res["p"][g])]
     return _store_side_results(results, genedic, max_hits, outdir, time, delimiter, GCMH_COLUMNS, cells,
-                               ".gcmh.results.csv", "generalized CMH")
+                               ".gcmh.results.csv", "generalized CMH", stepdown=stepdown)
 
 
 # ---------------------------------------------------------------------------
@@ -2543,6 +2573,32 @@ def _cat_wy_refusals(fwer, categorical, permutations):
         yield CAT_WY_TEXT["categorical"]
     if fwer and int(permutations or 0) < 10:
         yield CAT_WY_TEXT["permute"]
+
+
+# ---------------------------------------------------------------------------
+# --categorical-fwer-stepdown: Westfall-Young step-down maxT over the chi-square and the generalized CMH statistic
+# (spec S23): the column Westfall_Young_stepdown_p, the last of the chi-square file and -- with --categorical-strata
+# -- the generalized CMH file, behind Westfall_Young_p where --categorical-fwer is given too.  Either flag works
+# without the other.
+# ---------------------------------------------------------------------------
+CAT_SD_TEXT = {
+    "categorical": "Cannot use --categorical-fwer-stepdown without --categorical. It is the step-down family-wise p "
+                   "of the tests of the categorical traits",
+    "permute": "Cannot use --categorical-fwer-stepdown without --permute X, X >= 10. The family-wise p is counted "
+               "over the permutations of the labels",
+}
+# (rule, the run breaks it): in the order they are reported
+CAT_SD_FLAG_RULES = (
+    ("categorical", lambda categorical, permutations: not categorical),
+    ("permute", lambda categorical, permutations: int(permutations or 0) < 10),
+)
+
+
+def _cat_sd_refusals(stepdown, categorical, permutations):
+    """The messages of the --categorical-fwer-stepdown rules that a run breaks, in the order they are reported."""
+    for key, broken in CAT_SD_FLAG_RULES:
+        if stepdown and broken(categorical, permutations):
+            yield CAT_SD_TEXT[key]
 
 
 # ---------------------------------------------------------------------------
@@ -2837,6 +2893,9 @@ def _validate(args, cutoffs):
             sys.exit(GCMH_TEXT["strata"] % (cstrata, len(labels), _abi.PERM_MAX_STRATA))
     for text in _cat_wy_refusals(getattr(args, "categorical_fwer", False), bool(getattr(args, "categorical", None)),
                                  args.permute):
+        sys.exit(text)
+    for text in _cat_sd_refusals(getattr(args, "categorical_fwer_stepdown", False),
+                                 bool(getattr(args, "categorical", None)), args.permute):
         sys.exit(text)
     qstrata = getattr(args, "quantitative_strata", None)
     if qstrata:

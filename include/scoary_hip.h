@@ -703,6 +703,34 @@ int scoary_permute_cat_stepdown(scoary_handle h, void *d_scratch, const int16_t 
 int scoary_permute_gcmh_stepdown(scoary_handle h, void *d_scratch, const int16_t *d_rows, const int32_t *d_nk,
                                  int64_t G, int64_t T, int64_t N, int64_t P, int64_t perm_base, int32_t *d_r_rank,
                                  int32_t *d_c_rank, double *d_maxs, int64_t maxs_stride, scoary_stream_t stream);
+/* ---- Covariate-adjusted score tests: the logistic and the linear Rao score test of a gene next to up to eight
+ * covariates (spec S24 of DESIGN.md; additive, ABI 11) ----
+ * The host fits the null model of a trait (intercept and covariates, no gene) over its valid isolates and hands over
+ * d_rows double [T][q + 1][N] -- row 0 the residuals r_i, row 1 + j the weighted design column z_ij = w_i x_ij (j < q;
+ * x_i0 = 1, so row 1 holds the weights), every row 0.0 at an isolate outside the valid set --, the validity bits
+ * d_valid uint32 [T][Wp], d_chol double [T][q (q + 1) / 2] = the lower Cholesky factor L of A = sum w_i x_i x_i',
+ * packed by rows, and for the linear kind d_rss double [T] = the null model's residual sum of squares (not read and
+ * may be null for linear = 0).  Per (trait, gene), n = popc(valid), fp64, every operation rounded on its own:
+ *     m = popc(gene & valid);  U = sum r_i, b_j = sum z_ij over the gene's valid isolates in ascending isolate order,
+ *     each a running sum from +0.0;  L u = b by forward substitution (s = b_i; s = s - L_ij u_j for ascending j < i;
+ *     u_i = s / L_ii; ascending i);  Vg = b_0 - (sum of u_j u_j from 0.0 in ascending j)
+ *     testable: 0 < m < n and Vg > 2^-26 b_0 (and, linear, df = n - q - 1 >= 1); else (stat 0, beta 0, se 0, p 1)
+ *     beta = U / Vg
+ *     linear = 0:  stat = (U U) / Vg, se = 1 / sqrt(Vg), p = the chi-square upper tail of stat at one degree of
+ *                  freedom (scoary_cmh_homogeneity's tail)
+ *     linear = 1:  RSS1 = rss - (U U) / Vg;  se = sqrt((RSS1 / df) / Vg), stat = t = beta / se, p = the two-sided tail
+ *                  of Student's t at df (within 1e-10 relative of the true tail above 1e-290).  RSS1 <= 0: se 0,
+ *                  t = +inf or -inf by the sign of U and p 0, or (t 0, p 1) where U = 0
+ *   scoary_score_max_covariates()  8: q = 1 + covariates is in [1, 9]
+ *   scoary_score          d_m int32 [T][G]; d_u, d_vg, d_stat, d_beta, d_se, d_p double [T][G]; d_b double [T][G][q]
+ * Only isolates below N with their validity bit enter any sum.  Asynchronous on `stream`, nothing is allocated.
+ * SCOARY_ERR_ARG: null pointer, a size < 1, linear not 0 or 1; SCOARY_ERR_SIZE, with nothing written: q outside [1, 9],
+ * T > 65535, G or N >= 2^31. */
+int64_t scoary_score_max_covariates(void);
+int scoary_score(scoary_handle h, const uint32_t *d_tiled, const double *d_rows, const uint32_t *d_valid,
+                 const double *d_chol, const double *d_rss, int64_t G, int64_t T, int64_t N, int64_t q, int64_t linear,
+                 int32_t *d_m, double *d_u, double *d_b, double *d_vg, double *d_stat, double *d_beta, double *d_se,
+                 double *d_p, scoary_stream_t stream);
 /* ---- Quantitative traits over strata: the van Elteren test with value permutations within the strata (spec S16 of
  * DESIGN.md; additive, ABI 11) ----
  * The strata are d_strata uint16 [N] (the stratum of every isolate, in [0, S)) and d_members int32 [N] (the isolates

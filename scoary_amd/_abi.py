@@ -18,6 +18,8 @@ PERM_MAX_STRATA = 1024
 PERM_STRATA_MAX_ISOLATES = 20479
 # scoary_categorical_max_classes(): the classes a categorical trait may have (spec S20), known here for the same reason
 CATEGORICAL_MAX_CLASSES = 8
+# scoary_score_max_covariates(): the covariates a score test adjusts for (spec S24), known here for the same reason
+SCORE_MAX_COVARIATES = 8
 
 _i64, _u64, _i32, _vp, _cp = (ctypes.c_int64, ctypes.c_uint64, ctypes.c_int,
                               ctypes.c_void_p, ctypes.c_char_p)
@@ -106,6 +108,8 @@ SIGNATURES = {
     "scoary_gcmh_stepdown_gather": (_i32, [_vp] * 5 + [_i64] * 3 + [_vp, _vp]),
     "scoary_permute_cat_stepdown": (_i32, [_vp] * 6 + [_i64] * 5 + [_vp] * 3 + [_i64, _vp]),
     "scoary_permute_gcmh_stepdown": (_i32, [_vp] * 4 + [_i64] * 5 + [_vp] * 3 + [_i64, _vp]),
+    "scoary_score_max_covariates": (_i64, []),
+    "scoary_score": (_i32, [_vp] * 6 + [_i64] * 5 + [_vp] * 9),
     "scoary_vanelteren": (_i32, [_vp] * 8 + [_i64] * 4 + [_vp] * 7),
     "scoary_vanelteren_perm_generate": (_i32, [_vp] * 4 + [_i64] * 6 + [_u64, _vp, _vp]),
     "scoary_vanelteren_perm_generate_bfrag": (_i32, [_vp] * 4 + [_i64] * 6 + [_u64, _vp, _vp]),
@@ -189,5 +193,7 @@ def load():
         raise ScoaryHipError("the library's strata limits differ from the binding's")
     if lib.scoary_categorical_max_classes() != CATEGORICAL_MAX_CLASSES:
         raise ScoaryHipError("the library's class limit differs from the binding's")
+    if lib.scoary_score_max_covariates() != SCORE_MAX_COVARIATES:
+        raise ScoaryHipError("the library's covariate limit differs from the binding's")
     _lib = lib
     return lib

@@ -230,6 +230,164 @@ def gcmh_host(codes, strata, S):
     return codes, valid, n, nk, classes, nsk, l
 
 
+class ScorePlan:
+    """The null models of a score-test step (spec S24; AssociationEngine.score_plan), ``kind`` "logistic" or "linear"
+    with q = 1 + covariates design columns.  On the device: ``rows`` float64 [T, q + 1, N] (row 0 the residuals r_i,
+    row 1 + j the weighted design column w_i x_ij; all zero at an isolate outside the trait's valid set), ``valid``
+    the validity rows (vecrows), ``chol`` float64 [T, q (q + 1) / 2] (the lower Cholesky factor of A packed by rows)
+    and ``rss`` float64 [T] (the null model's residual sum of squares, 0 for the logistic kind).  On the host: the
+    same as rows_host, valid_host (bool [T, N]), chol_host, rss_host, ``n`` int64 [T], ``coef`` float64 [T, q] (the
+    null model's coefficients on the scaled columns) and ``skipped`` (per trait None, or why S24 refuses its null
+    model: a key of SCORE_SKIPS; such a trait has no valid isolate and every gene of it is untestable)."""
+
+    def __init__(self, dev, host, kind, q):
+        self.rows, self.valid, self.chol, self.rss = dev
+        self.rows_host, self.valid_host, self.chol_host, self.rss_host = (host[k] for k in ("rows", "valid", "chol",
+                                                                                            "rss"))
+        self.n, self.coef, self.skipped = host["n"], host["coef"], host["skipped"]
+        self.kind, self.q = kind, int(q)
+        self.T, self.N = (int(x) for x in self.valid_host.shape)
+
+
+SCORE_MAX_COVARIATES = _abi.SCORE_MAX_COVARIATES
+SCORE_KINDS = ("logistic", "linear")
+# why S24 refuses the null model of a trait, in the order the rules are tried
+SCORE_SKIPS = {
+    "few": "it has %d isolates with a value and every covariate, the model of %d columns needs more than %d",
+    "constant": "a covariate is constant over its %d isolates with a value and every covariate",
+    "one_class": "all of its %d isolates with a value and every covariate are in one class",
+    "collinear": "the covariates are collinear over its isolates with a value and every covariate",
+    "separated": "the logistic null model does not converge: the covariates separate its classes",
+}
+SCORE_PIVOT = 2.0 ** -40
+SCORE_MAX_ITER, SCORE_STEP = 50, 1e-10
+
+
+def _score_cholesky(A):
+    """The lower Cholesky factor of the small matrix A, or None where a pivot is <= 2^-40 of the largest diagonal
+    entry (S24: collinear columns) or not finite."""
+    q = A.shape[0]
+    top = float(A.diagonal().max())
+    L = np.zeros((q, q))
+    for i in range(q):
+        for j in range(i + 1):
+            s = A[i, j] - float(np.dot(L[i, :j], L[j, :j]))
+            if i == j:
+                if not s > SCORE_PIVOT * top:
+                    return None
+                L[i, i] = np.sqrt(s)
+            else:
+                L[i, j] = s / L[j, j]
+    return L
+
+
+def _score_solve(L, v):
+    """A^-1 v from A's lower Cholesky factor."""
+    q = L.shape[0]
+    u = np.zeros(q)
+    for i in range(q):
+        u[i] = (v[i] - np.dot(L[i, :i], u[:i])) / L[i, i]
+    x = np.zeros(q)
+    for i in range(q - 1, -1, -1):
+        x[i] = (u[i] - np.dot(L[i + 1:, i], x[i + 1:])) / L[i, i]
+    return x
+
+
+def _score_null(y, X, kind):
+    """The null fit of S24 on the design X [n, q]: (coef, w, r, L) or the key of SCORE_SKIPS that refuses it."""
+    n, q = X.shape
+    if kind == "linear":
+        L = _score_cholesky(X.T @ X)
+        if L is None:
+            return "collinear"
+        coef = _score_solve(L, X.T @ y)
+        return coef, np.ones(n), y - X @ coef, L
+    coef = np.zeros(q)
+    with np.errstate(all="ignore"):
+        converged = False
+        for it in range(SCORE_MAX_ITER + 1):
+            mu = 1.0 / (1.0 + np.exp(-(X @ coef)))
+            w = mu * (1.0 - mu)
+            r = y - mu
+            L = _score_cholesky((X * w[:, None]).T @ X)
+            if L is None:
+                return "separated" if it else "collinear"      # at 0 every weight is 1/4: the columns themselves
+            if converged:                                      # mu, w, r and L are those of the last step's end
+                return coef, w, r, L
+            if it == SCORE_MAX_ITER:
+                break
+            step = _score_solve(L, X.T @ r)
+            if not np.all(np.isfinite(step)):
+                return "separated"
+            coef = coef + step
+            converged = np.max(np.abs(step)) <= SCORE_STEP
+    return "separated"
+
+
+def score_host(values, covariates, kind="logistic"):
+    """Host side of spec S24, pure numpy: values float64 [T, N] (nan = missing; 0 / 1 for the logistic kind),
+    covariates float64 [c, N] (nan = missing), 0 <= c <= 8.  Per trait the valid set (the isolates with the value
+    and every covariate), the design (ones; every covariate less its mean over the valid set, divided by its largest
+    absolute centred value) and the null fit: Newton steps from 0 for the logistic kind (at most 50, converged at a
+    largest step <= 1e-10), least squares by the Cholesky factor of X'X for the linear one.  Returns a dict: rows
+    float64 [T, q + 1, N], valid bool [T, N], chol float64 [T, q (q + 1) / 2], rss float64 [T], n int64 [T], coef
+    float64 [T, q], skipped [T] (None or the key of SCORE_SKIPS that refuses the trait: its rows and valid set are
+    empty, its factor is the identity)."""
+    if kind not in SCORE_KINDS:
+        raise ValueError("score_plan: kind must be one of %s" % ", ".join(repr(k) for k in SCORE_KINDS))
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    if values.ndim != 2:
+        raise ValueError("score_plan: values must be a [T, N] array")
+    T, N = values.shape
+    covariates = np.zeros((0, N)) if covariates is None else np.ascontiguousarray(covariates, dtype=np.float64)
+    if covariates.ndim != 2 or covariates.shape[1] != N:
+        raise ValueError("score_plan: covariates must be a [c, %d] array, one row per covariate" % N)
+    c = covariates.shape[0]
+    if c > SCORE_MAX_COVARIATES:
+        raise ValueError("score_plan: %d covariates, at most %d are taken" % (c, SCORE_MAX_COVARIATES))
+    if np.isinf(values).any() or np.isinf(covariates).any():
+        raise ValueError("score_plan: a value or a covariate is infinite")
+    if kind == "logistic" and not np.all(np.isnan(values) | (values == 0.0) | (values == 1.0)):
+        raise ValueError("score_plan: a binary trait is 0, 1 or nan")
+    q = c + 1
+    tri = np.tril_indices(q)
+    out = dict(rows=np.zeros((T, q + 1, N)), valid=np.zeros((T, N), dtype=bool), chol=np.zeros((T, len(tri[0]))),
+               rss=np.zeros(T), n=np.zeros(T, dtype=np.int64), coef=np.zeros((T, q)), skipped=[None] * T)
+    out["chol"][:] = np.eye(q)[tri]
+    have = ~np.isnan(covariates).any(axis=0)
+    for t in range(T):
+        V = np.flatnonzero(~np.isnan(values[t]) & have)
+        n = V.size
+        fit = None
+        if n <= q + 1:
+            fit = "few"
+        else:
+            y = values[t, V]
+            centred = covariates[:, V] - (np.add.accumulate(covariates[:, V], axis=1)[:, -1] / float(n))[:, None]
+            scale = np.abs(centred).max(axis=1) if c else np.zeros(0)
+            if c and (np.any(covariates[:, V].max(axis=1) == covariates[:, V].min(axis=1)) or not np.all(scale > 0)):
+                fit = "constant"
+            elif kind == "logistic" and y.min() == y.max():
+                fit = "one_class"
+            else:
+                X = np.concatenate([np.ones((1, n)), centred / scale[:, None]]).T
+                fit = _score_null(y, X, kind)
+        if isinstance(fit, str):
+            out["skipped"][t] = fit
+            out["n"][t] = n                  # what the warning names; the plan's valid set stays empty
+            continue
+        coef, w, r, L = fit
+        out["valid"][t, V] = True
+        out["n"][t] = n
+        out["coef"][t] = coef
+        out["rows"][t][0, V] = r
+        out["rows"][t][1:, V] = (X * w[:, None]).T
+        out["chol"][t] = L[tri]
+        if kind == "linear":
+            out["rss"][t] = np.add.accumulate(r * r)[-1] if n else 0.0          # ascending isolate order
+    return out
+
+
 def rank_rows(values):
     """Host ranking of spec S15, exact double comparisons: float64 [T, N] with NaN for missing -> (rc int16 [T, N],
     valid bool [T, N], n int64 [T], tiesum int64 [T], tie groups int64 [T])."""
@@ -2502,6 +2660,46 @@ class AssociationEngine:
             lambda base, nb: self.gcmh_rows(plan, base, nb, seed),
             lambda scratch, rows, base, r_rank, c_rank, maxs: self.permute_gcmh_stepdown(
                 scratch, plan, rows, genes.G, base, r_rank, c_rank, maxs))
+
+    # -- covariate-adjusted score tests (spec S24) --------------------------------------
+    def score_max_covariates(self):
+        return int(self.lib.scoary_score_max_covariates())
+
+    def score_plan(self, values, covariates, kind="logistic"):
+        """values: float64 [T, N], nan = missing (0 / 1 for kind "logistic"); covariates: float64 [c, N], nan =
+        missing, 0 <= c <= score_max_covariates() (None: intercept only).  The null models of spec S24 as a
+        ScorePlan; a trait whose null model S24 refuses is named in plan.skipped and has no testable gene."""
+        return self.score_plan_of(score_host(values, covariates, kind), kind)
+
+    def score_plan_of(self, host, kind):
+        """The ScorePlan of a dict as score_host returns it: its rows, validity bits, factors and residual sums of
+        squares go to the device as they are."""
+        torch = _torch()
+        N = host["valid"].shape[1]
+        dev = (torch.from_numpy(np.ascontiguousarray(host["rows"], dtype=np.float64)).to(self.device),
+               self.vecrows(pack_bits_rows(host["valid"].astype(np.uint8)), N),
+               torch.from_numpy(np.ascontiguousarray(host["chol"], dtype=np.float64)).to(self.device),
+               torch.from_numpy(np.ascontiguousarray(host["rss"], dtype=np.float64)).to(self.device))
+        return ScorePlan(dev, host, kind, host["coef"].shape[1])
+
+    def score(self, genes, plan):
+        """The score test of every (trait, gene) against the plan's null models: dict of device tensors m int32
+        [T, G] (carriers among the trait's valid isolates), U, Vg, beta, se, p float64 [T, G], b float64 [T, G, q] and
+        the statistic as ``stat`` (logistic: the score chi-square at one degree of freedom) or ``t`` (linear:
+        Student's t at n - q - 1); an untestable gene has (statistic 0, beta 0, se 0, p 1)."""
+        torch = _torch()
+        if genes.N != plan.N:
+            raise ValueError("score: the plan has %d isolates, the gene matrix %d" % (plan.N, genes.N))
+        T, G = plan.T, genes.G
+        stat = "t" if plan.kind == "linear" else "stat"
+        out = {"m": self._empty((T, G), torch.int32), "b": self._empty((T, G, plan.q), torch.float64)}
+        out.update((k, self._empty((T, G), torch.float64)) for k in ("U", "Vg", stat, "beta", "se", "p"))
+        self._check(self.lib.scoary_score(
+            self.h, self._ptr(genes.tiled), self._ptr(plan.rows), self._ptr(plan.valid), self._ptr(plan.chol),
+            self._ptr(plan.rss), G, T, plan.N, plan.q, int(plan.kind == "linear"),
+            *(self._ptr(out[k]) for k in ("m", "U", "b", "Vg", stat, "beta", "se", "p")), self._stream()),
+            "scoary_score")
+        return out
 
     # -- timing (bench.py) ------------------------------------------------------
     def set_timing(self, on):

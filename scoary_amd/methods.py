@@ -1793,6 +1793,14 @@ def ScoaryArgumentParser(argv=None):
                    "against every gene with the Wilcoxon-Mann-Whitney rank-sum test (normal approximation with tie and "
                    "continuity corrections) and written to <trait>.ranksum.results.csv; --permute adds Empirical_p "
                    "from shuffles of the values over the isolates (single process; scoary_amd extension)")
+    a.add_argument("--covariates", dest="covariates", metavar="FILE", default=None,
+                   help="With --no_pairwise: FILE holds up to 8 numeric covariates (isolates in rows, one named column "
+                   "per covariate, NA for missing), laid out like the --quantitative file: the axes of an MDS or PCA "
+                   "of the core genome, sampling year, genome size.  Every trait of the traits file is tested against "
+                   "every gene with the logistic score test next to them, written to <trait>.logistic.results.csv "
+                   "with the one-step odds ratio; with --quantitative every measured trait gets the linear score "
+                   "test (ordinary least squares' t test of the gene), written to <column>.linear.results.csv "
+                   "(single process, no permutation columns; scoary_amd extension)")
     a.add_argument("--categorical", dest="categorical", metavar="FILE", default=None,
                    help="With --no_pairwise: FILE holds categorical traits (isolates in rows, one named column per "
                    "trait, any label in the cells, NA for missing), laid out like the traits file.  Every column of up "
@@ -2060,6 +2068,19 @@ def main(**kwargs):
                                                   seed=seed, fwer=cfwer, stepdown=csd),
                                      genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter,
                                      stepdown=csd)
+        if getattr(args, "covariates", None) and rank == 0:
+            cnames, covariates = read_covariates_file(args.covariates, args.delimiter, strains)
+            for text in _score_refusals(True, False, cnames, covariates, source=args.covariates, exits=True):
+                sys.exit(text)
+            names, values = binary_trait_values(traitsdic, strains)
+            with _stage("logistic score test of the traits"):
+                StoreScoreResults(Score_results(genedic, names, values, cnames, covariates, kind="logistic"),
+                                  genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
+            if getattr(args, "quantitative", None):
+                names, values = read_quantitative_file(args.quantitative, args.delimiter, strains)
+                with _stage("linear score test of the quantitative traits"):
+                    StoreScoreResults(Score_results(genedic, names, values, cnames, covariates, kind="linear"),
+                                      genedic, args.max_hits, args.outdir, time=stamp, delimiter=args.delimiter)
         log.info("Stage seconds: load (+tree) %.2f, association (+permutations) %.2f, pairwise stage and "
                  "output %.2f" % (t_loaded - start, t_stats - t_loaded, _time.time() - t_stats))
         gene_bytes = os.path.getsize(args.genes) if os.path.isfile(args.genes) else 0
@@ -2766,6 +2787,151 @@ def _shift_level(args):
     return RANK_SHIFT_LEVEL if level is None else level
 
 
+# ---------------------------------------------------------------------------
+# --covariates FILE: covariate-adjusted score tests (spec S24).  The logistic score test of every binary trait of
+# the traits file and, with --quantitative, the linear score test of every measured trait, each next to the file's
+# up to eight numeric columns.  Stages and result files of their own, no permutation columns: labels are not
+# exchangeable given continuous covariates.
+# ---------------------------------------------------------------------------
+LOGISTIC_COLUMNS = ("Number_with_gene", "Number_without_gene", "Beta", "Std_err", "Odds_ratio", "Score_chi2",
+                    "Score_p", "Bonferroni_p", "Benjamini_H_p")
+LINEAR_COLUMNS = ("Number_with_gene", "Number_without_gene", "Beta", "Std_err", "T_stat", "Linear_p", "Bonferroni_p",
+                  "Benjamini_H_p")
+# a refusal as the command line reports it / as Score_results raises it
+SCORE_TEXT = {
+    "no_pairwise": ("Cannot use --covariates without --no_pairwise. The score test is a test of every gene; the "
+                    "covariates are its answer to population structure",
+                    "covariates need no_pairwise: the score test is a test of every gene"),
+    "collapse": ("Cannot use --covariates together with --collapse. The score test is a test of every gene of the "
+                 "table", "covariates exclude collapse"),
+    "ranks": ("Cannot use --covariates under more than one rank: the test runs over all genes in a single process",
+              "covariates need a single process"),
+    "columns": ("Cannot use --covariates with the %d columns of %s: the score test adjusts for at most %d. Keep the "
+                "leading axes of the structure and the confounders that matter",
+                "%d covariates (%s), at most %d are taken"),
+    "isolates": ("The covariates file %s names none of the analysed isolates",
+                 "the covariates (%s) are missing for every isolate"),
+}
+# the one warning line of a trait whose null model S24 refuses (engine.SCORE_SKIPS says why)
+SCORE_SKIPPED = "WARNING: Skipping the %s score test of %s: %s. No results file is written for it."
+
+
+def _score_refusals(no_pairwise, collapse, names=None, covariates=None, source="", exits=False):
+    """The messages of the --covariates rules that a run breaks, in the order they are reported (``exits``: as the
+    command line's exit messages, else as Score_results' ValueErrors).  ``names`` and ``covariates`` ([c, N], nan =
+    missing), where they are known: the rules on the file itself, ``source`` its path."""
+    if not no_pairwise:
+        yield SCORE_TEXT["no_pairwise"][not exits]
+    if collapse:
+        yield SCORE_TEXT["collapse"][not exits]
+    from . import _abi, dist
+    if dist.world_rank()[0] > 1:
+        yield SCORE_TEXT["ranks"][not exits]
+    if names is not None and len(names) > _abi.SCORE_MAX_COVARIATES:
+        yield SCORE_TEXT["columns"][not exits] % ((len(names), source, _abi.SCORE_MAX_COVARIATES) if exits else
+                                                  (len(names), ", ".join(names), _abi.SCORE_MAX_COVARIATES))
+    if covariates is not None and len(covariates) and not (~np.isnan(np.asarray(covariates))).any():
+        yield SCORE_TEXT["isolates"][not exits] % (source if exits else ", ".join(names or []))
+
+
+def read_covariates_file(path, delimiter, strains):
+    """--covariates FILE: the layout of the --quantitative file, a header row (its first cell is ignored, the others
+    name the covariates), then one row per isolate: its name and one cell per covariate, a finite number or one of
+    MISSING_TRAIT.  Returns (names, float64 [c, N] over ``strains`` with nan = missing)."""
+    def number(text, path, iso, column, line):
+        try:
+            x = float(text)
+        except ValueError:
+            x = np.nan
+        if not np.isfinite(x):
+            sys.exit("The covariates file %s has the cell %r for isolate %s, covariate %s (line %d): a cell is a "
+                     "finite number or one of %s" % (path, text, iso, column, line,
+                                                     ",".join(repr(m) for m in MISSING_TRAIT)))
+        return x
+    return _read_side_traits(path, delimiter, strains, "covariates", number,
+                             lambda T, N: np.full((T, N), np.nan, dtype=np.float64))
+
+
+def binary_trait_values(traitsdic, strains):
+    """The traits of the traits file as the score test takes them: (names, float64 [T, N] over ``strains``: 1.0, 0.0
+    or nan for an isolate without a value)."""
+    names = list(traitsdic)
+    values = np.full((len(names), len(strains)), np.nan, dtype=np.float64)
+    for t, name in enumerate(names):
+        for i, s in enumerate(strains):
+            v = traitsdic[name].get(s)
+            if v in ("0", "1"):
+                values[t, i] = float(v)
+    return names, values
+
+
+def Score_results(genedic, names, values, covariate_names, covariates, kind="logistic", no_pairwise=True,
+                  collapse=False):
+    """The score-test stage (spec S24) of the traits ``names`` with the values float64 [T, N] (nan = missing; 0 / 1
+    for ``kind`` "logistic") next to the covariates float64 [c, N] over the isolates of ``genedic``: {name: dict(n,
+    kind, m, beta, se, stat, p, testable [G])}, arrays in the gene table's order.  A trait whose null model S24
+    refuses gets one warning line and no entry.  Raises ValueError where the command line refuses --covariates."""
+    for text in _score_refusals(no_pairwise, collapse, list(covariate_names), covariates):
+        raise ValueError(text)
+    table = _as_table(genedic)
+    eng = get_engine()
+    values = np.asarray(values, dtype=np.float64)
+    covariates = np.asarray(covariates, dtype=np.float64).reshape(len(covariate_names), -1)
+    if values.ndim != 2 or values.shape != (len(names), len(table.strains)) or \
+            covariates.shape[1] != len(table.strains):
+        raise ValueError("covariates: values must be [%d traits, %d isolates] and the covariates [%d, %d]"
+                         % (len(names), len(table.strains), len(covariate_names), len(table.strains)))
+    from .engine import SCORE_SKIPS
+    genes = table.on_device(eng)
+    plan = eng.score_plan(values, covariates, kind)
+    res = {k: v.cpu().numpy() for k, v in eng.score(genes, plan).items()}
+    stat = res["t" if kind == "linear" else "stat"]
+    out = {}
+    for t, name in enumerate(names):
+        n = int(plan.n[t])
+        if plan.skipped[t] is not None:
+            why = SCORE_SKIPS[plan.skipped[t]]
+            log.warning(SCORE_SKIPPED % (kind, name, why % {"few": (n, plan.q, plan.q + 1), "constant": (n,),
+                                                             "one_class": (n,)}.get(plan.skipped[t], ())))
+            continue
+        testable = (res["m"][t] > 0) & (res["m"][t] < n) & (res["Vg"][t] > 2.0 ** -26 * res["b"][t, :, 0])
+        if kind == "linear":
+            testable &= n - plan.q - 1 >= 1
+        out[name] = dict(n=n, kind=kind, m=res["m"][t], beta=res["beta"][t], se=res["se"][t], stat=stat[t],
+                         p=res["p"][t], testable=testable)
+        log.info("%s score test of %s next to %d covariates: %d isolates with a value and every covariate, %d genes "
+                 "tested" % (kind.capitalize(), name, plan.q - 1, n, int(testable.sum())))
+    return out
+
+
+def _odds(beta):
+    with np.errstate(over="ignore"):
+        return float(np.exp(beta))
+
+
+def _logistic_cells(res, g):
+    beta = float(res["beta"][g])
+    return [_fmt(beta), _fmt(res["se"][g]), _fmt(_odds(beta)), _fmt(res["stat"][g]), _fmt(res["p"][g])]
+
+
+def _linear_cells(res, g):
+    return [_fmt(res["beta"][g]), _fmt(res["se"][g]), _fmt(res["stat"][g]), _fmt(res["p"][g])]
+
+
+def StoreScoreResults(results, genedic, max_hits, outdir, time="", delimiter=","):
+    """Write ``<outdir><trait><time>.logistic.results.csv`` (or ``.linear.results.csv``) for every trait of
+    Score_results: the testable genes in ascending p (ties in file order), Bonferroni and Benjamini-Hochberg over
+    them, every cell double-quoted; the carrier counts are over the trait's valid isolates.  Returns the file
+    names."""
+    files = []
+    for kind, columns, cells in (("logistic", LOGISTIC_COLUMNS, _logistic_cells),
+                                 ("linear", LINEAR_COLUMNS, _linear_cells)):
+        of_kind = {name: res for name, res in results.items() if res["kind"] == kind}
+        files += _store_side_results(of_kind, genedic, max_hits, outdir, time, delimiter, columns, cells,
+                                     ".%s.results.csv" % kind, "%s score test" % kind)
+    return files
+
+
 class _LevelCounter(logging.Handler):
     def __init__(self):
         super().__init__(logging.WARNING)
@@ -2879,6 +3045,16 @@ def _validate(args, cutoffs):
         # here, before the engine starts and the table is read
         names, labels = read_categorical_file(args.categorical, args.delimiter, _analysed_isolates(args))
         for text in _categorical_refusals(True, False, False, names, labels, exits=True):
+            sys.exit(text)
+    if getattr(args, "covariates", None):
+        for text in _score_refusals(args.no_pairwise, args.collapse, exits=True):
+            sys.exit(text)
+        if not os.path.isfile(args.covariates):
+            sys.exit("Could not find the covariates file: %s" % args.covariates)
+        # the file's own rules, on the analysed isolates (the header of the gene table after -s and -r): checked
+        # here, before the engine starts and the table is read
+        names, covariates = read_covariates_file(args.covariates, args.delimiter, _analysed_isolates(args))
+        for text in _score_refusals(True, False, names, covariates, source=args.covariates, exits=True):
             sys.exit(text)
     cstrata = getattr(args, "categorical_strata", None)
     if cstrata:

@@ -731,6 +731,36 @@ int scoary_score(scoary_handle h, const uint32_t *d_tiled, const double *d_rows,
                  const double *d_chol, const double *d_rss, int64_t G, int64_t T, int64_t N, int64_t q, int64_t linear,
                  int32_t *d_m, double *d_u, double *d_b, double *d_vg, double *d_stat, double *d_beta, double *d_se,
                  double *d_p, scoary_stream_t stream);
+/* ---- The saddlepoint-corrected p of the logistic score test (spec S25 of DESIGN.md; additive, ABI 11) ----
+ * Runs behind scoary_score with linear = 0, on its outputs d_u, d_b, d_vg, d_stat, d_p as they are, its d_rows (only
+ * row 1 of a trait, the weights w_i = mu_i (1 - mu_i), is read), d_valid and d_chol, and d_spa_rows double
+ * [T][q + 1][N]: row 0 the fitted mu_i of the null model, row 1 + j the scaled design column x_ij (row 1 is ones).
+ * Per (trait, gene), values and not bits (exp and log1p on the device are not libm's):
+ *     stat < cutoff2:  status 0, spa_p = the bits of d_p, z = t = 0, nothing else is computed
+ *     else  c = A^-1 b (L u = b, L' c = u), g~_i = g_i - sum_j x_ij c_j over the valid isolates, and the two tails
+ *           of S = sum g~_i (y_i - mu_i) at x = +|U| and x = -|U|: 0 beyond the end of S's support, the point mass
+ *           at the end itself (within 1e-9 relative), else 1/2 erfc(|z| / sqrt 2) with z = omega + log(v / omega) /
+ *           omega, omega = sign(t^) sqrt(2 (t^ x - K(t^))), v = t^ sqrt(K''(t^)), at the root t^ of K'(t) = x (within
+ *           1e-10 relative), K the cumulant generating function of S;  status 1, spa_p = min(1, upper + lower tail)
+ *           status 2, spa_p = the bits of d_p:  a side's search did not end within 60 evaluations, or t^ x - K, K'' or
+ *           v / omega is not positive and finite, or z has not the sign of x (z and t then hold what the sides left)
+ *   d_spa_p double [T][G]; d_spa_z, d_spa_t double [T][G][2] (side 0: x = +|U|, side 1: x = -|U|; z = 0 and t = +inf
+ *   / -inf on a side that is a point mass or beyond the support); d_spa_status int32 [T][G]
+ *   scoary_score_spa_max_isolates()     65 536: a pair is one wavefront's walk over the isolates
+ *   scoary_score_spa_scratch_bytes(G, T)  the bytes of d_scratch, which is aligned to 8 bytes (a counter, the work
+ *                                         list, four doubles a pair; 0 for sizes refused)
+ * Only isolates below N with their validity bit enter any sum, whatever the rows hold elsewhere.  Asynchronous on
+ * `stream`, nothing is allocated, no host round trip (the work list's length stays on the device).  SCOARY_ERR_ARG:
+ * null pointer, d_scratch not aligned to 8 bytes, a size < 1, cutoff2 below 0.01 or not finite; SCOARY_ERR_SIZE,
+ * with nothing launched and nothing written: q outside [1, 9], N above scoary_score_spa_max_isolates(), T > 65535,
+ * G T >= 2^31. */
+int64_t scoary_score_spa_max_isolates(void);
+int64_t scoary_score_spa_scratch_bytes(int64_t G, int64_t T);
+int scoary_score_spa(scoary_handle h, const uint32_t *d_tiled, const double *d_spa_rows, const double *d_rows,
+                     const uint32_t *d_valid, const double *d_chol, const double *d_u, const double *d_b,
+                     const double *d_vg, const double *d_stat, const double *d_p, int64_t G, int64_t T, int64_t N,
+                     int64_t q, double cutoff2, double *d_spa_p, double *d_spa_z, double *d_spa_t,
+                     int32_t *d_spa_status, void *d_scratch, scoary_stream_t stream);
 /* ---- Quantitative traits over strata: the van Elteren test with value permutations within the strata (spec S16 of
  * DESIGN.md; additive, ABI 11) ----
  * The strata are d_strata uint16 [N] (the stratum of every isolate, in [0, S)) and d_members int32 [N] (the isolates

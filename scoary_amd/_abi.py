@@ -110,6 +110,9 @@ SIGNATURES = {
     "scoary_permute_gcmh_stepdown": (_i32, [_vp] * 4 + [_i64] * 5 + [_vp] * 3 + [_i64, _vp]),
     "scoary_score_max_covariates": (_i64, []),
     "scoary_score": (_i32, [_vp] * 6 + [_i64] * 5 + [_vp] * 9),
+    "scoary_score_spa_max_isolates": (_i64, []),
+    "scoary_score_spa_scratch_bytes": (_i64, [_i64, _i64]),
+    "scoary_score_spa": (_i32, [_vp] * 11 + [_i64] * 4 + [ctypes.c_double] + [_vp] * 6),
     "scoary_vanelteren": (_i32, [_vp] * 8 + [_i64] * 4 + [_vp] * 7),
     "scoary_vanelteren_perm_generate": (_i32, [_vp] * 4 + [_i64] * 6 + [_u64, _vp, _vp]),
     "scoary_vanelteren_perm_generate_bfrag": (_i32, [_vp] * 4 + [_i64] * 6 + [_u64, _vp, _vp]),

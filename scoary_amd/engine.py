@@ -238,7 +238,10 @@ class ScorePlan:
     and ``rss`` float64 [T] (the null model's residual sum of squares, 0 for the logistic kind).  On the host: the
     same as rows_host, valid_host (bool [T, N]), chol_host, rss_host, ``n`` int64 [T], ``coef`` float64 [T, q] (the
     null model's coefficients on the scaled columns) and ``skipped`` (per trait None, or why S24 refuses its null
-    model: a key of SCORE_SKIPS; such a trait has no valid isolate and every gene of it is untestable)."""
+    model: a key of SCORE_SKIPS; such a trait has no valid isolate and every gene of it is untestable).  For spec S25:
+    ``spa_rows_host`` float64 [T, q + 1, N] (row 0 the fitted mu_i, row 1 + j the design column x_ij) where the plan's
+    maker gave mu and design, else None, and ``spa_rows``, the same on the device from the first
+    AssociationEngine.score_spa on (None before: a run without it moves no byte of them)."""
 
     def __init__(self, dev, host, kind, q):
         self.rows, self.valid, self.chol, self.rss = dev
@@ -247,6 +250,11 @@ class ScorePlan:
         self.n, self.coef, self.skipped = host["n"], host["coef"], host["skipped"]
         self.kind, self.q = kind, int(q)
         self.T, self.N = (int(x) for x in self.valid_host.shape)
+        self.spa_rows = self.spa_rows_host = None
+        if host.get("mu") is not None and host.get("design") is not None:
+            self.spa_rows_host = np.ascontiguousarray(
+                np.concatenate([np.asarray(host["mu"], dtype=np.float64)[:, None, :],
+                                np.asarray(host["design"], dtype=np.float64)], axis=1))
 
 
 SCORE_MAX_COVARIATES = _abi.SCORE_MAX_COVARIATES
@@ -294,14 +302,15 @@ def _score_solve(L, v):
 
 
 def _score_null(y, X, kind):
-    """The null fit of S24 on the design X [n, q]: (coef, w, r, L) or the key of SCORE_SKIPS that refuses it."""
+    """The null fit of S24 on the design X [n, q]: (coef, w, r, L, mu) or the key of SCORE_SKIPS that refuses it
+    (mu: the fitted values, which S25 reads)."""
     n, q = X.shape
     if kind == "linear":
         L = _score_cholesky(X.T @ X)
         if L is None:
             return "collinear"
         coef = _score_solve(L, X.T @ y)
-        return coef, np.ones(n), y - X @ coef, L
+        return coef, np.ones(n), y - X @ coef, L, X @ coef
     coef = np.zeros(q)
     with np.errstate(all="ignore"):
         converged = False
@@ -313,7 +322,7 @@ def _score_null(y, X, kind):
             if L is None:
                 return "separated" if it else "collinear"      # at 0 every weight is 1/4: the columns themselves
             if converged:                                      # mu, w, r and L are those of the last step's end
-                return coef, w, r, L
+                return coef, w, r, L, mu
             if it == SCORE_MAX_ITER:
                 break
             step = _score_solve(L, X.T @ r)
@@ -332,7 +341,8 @@ def score_host(values, covariates, kind="logistic"):
     largest step <= 1e-10), least squares by the Cholesky factor of X'X for the linear one.  Returns a dict: rows
     float64 [T, q + 1, N], valid bool [T, N], chol float64 [T, q (q + 1) / 2], rss float64 [T], n int64 [T], coef
     float64 [T, q], skipped [T] (None or the key of SCORE_SKIPS that refuses the trait: its rows and valid set are
-    empty, its factor is the identity)."""
+    empty, its factor is the identity), and for spec S25 mu float64 [T, N] (the fitted values of the null model) and
+    design float64 [T, q, N] (the scaled design columns, row 0 ones), both zero outside the valid set."""
     if kind not in SCORE_KINDS:
         raise ValueError("score_plan: kind must be one of %s" % ", ".join(repr(k) for k in SCORE_KINDS))
     values = np.ascontiguousarray(values, dtype=np.float64)
@@ -352,7 +362,8 @@ def score_host(values, covariates, kind="logistic"):
     q = c + 1
     tri = np.tril_indices(q)
     out = dict(rows=np.zeros((T, q + 1, N)), valid=np.zeros((T, N), dtype=bool), chol=np.zeros((T, len(tri[0]))),
-               rss=np.zeros(T), n=np.zeros(T, dtype=np.int64), coef=np.zeros((T, q)), skipped=[None] * T)
+               rss=np.zeros(T), n=np.zeros(T, dtype=np.int64), coef=np.zeros((T, q)), skipped=[None] * T,
+               mu=np.zeros((T, N)), design=np.zeros((T, q, N)))
     out["chol"][:] = np.eye(q)[tri]
     have = ~np.isnan(covariates).any(axis=0)
     for t in range(T):
@@ -376,13 +387,15 @@ def score_host(values, covariates, kind="logistic"):
             out["skipped"][t] = fit
             out["n"][t] = n                  # what the warning names; the plan's valid set stays empty
             continue
-        coef, w, r, L = fit
+        coef, w, r, L, mu = fit
         out["valid"][t, V] = True
         out["n"][t] = n
         out["coef"][t] = coef
         out["rows"][t][0, V] = r
         out["rows"][t][1:, V] = (X * w[:, None]).T
         out["chol"][t] = L[tri]
+        out["mu"][t, V] = mu
+        out["design"][t][:, V] = X.T
         if kind == "linear":
             out["rss"][t] = np.add.accumulate(r * r)[-1] if n else 0.0          # ascending isolate order
     return out
@@ -2699,6 +2712,47 @@ class AssociationEngine:
             self._ptr(plan.rss), G, T, plan.N, plan.q, int(plan.kind == "linear"),
             *(self._ptr(out[k]) for k in ("m", "U", "b", "Vg", stat, "beta", "se", "p")), self._stream()),
             "scoary_score")
+        return out
+
+    # -- the saddlepoint-corrected p of the logistic score test (spec S25) ----------------
+    def score_spa_max_isolates(self):
+        return int(self.lib.scoary_score_spa_max_isolates())
+
+    def score_spa(self, genes, plan, score_out, cutoff=2.0):
+        """The saddlepoint p of every (trait, gene) behind ``score_out`` = score(genes, plan) of a logistic plan: dict
+        of device tensors p float64 [T, G], z and t float64 [T, G, 2] (side 0: the upper tail at +|U|, side 1: the
+        lower at -|U|) and status int32 [T, G]: 0 = the score chi-square is below cutoff^2 and p is Score_p's bits,
+        1 = the saddlepoint p, 2 = no saddlepoint p could be formed and p is Score_p's bits."""
+        torch = _torch()
+        if plan.kind != "logistic":
+            raise ValueError("score_spa: the saddlepoint p belongs to the logistic score test, the plan is %s"
+                             % plan.kind)
+        cutoff = float(cutoff)
+        if not (np.isfinite(cutoff) and cutoff >= 0.1):
+            raise ValueError("score_spa: the cutoff must be a finite number of at least 0.1, not %r" % cutoff)
+        if genes.N != plan.N:
+            raise ValueError("score_spa: the plan has %d isolates, the gene matrix %d" % (plan.N, genes.N))
+        T, G, q = plan.T, genes.G, plan.q
+        shapes = {"U": (T, G), "b": (T, G, q), "Vg": (T, G), "stat": (T, G), "p": (T, G)}
+        for k, shape in shapes.items():
+            if k not in score_out or tuple(score_out[k].shape) != shape or score_out[k].dtype != torch.float64 \
+                    or not score_out[k].is_contiguous():
+                raise ValueError("score_spa: score_out[%r] must be the float64 %s tensor of score(genes, plan)"
+                                 % (k, list(shape)))
+        if plan.N > self.score_spa_max_isolates():
+            raise ValueError("score_spa: %d isolates, at most %d are taken" % (plan.N, self.score_spa_max_isolates()))
+        if plan.spa_rows is None:
+            if plan.spa_rows_host is None or plan.spa_rows_host.shape != (T, q + 1, plan.N):
+                raise ValueError("score_spa: the plan carries no fitted values and design (score_host's mu and design)")
+            plan.spa_rows = torch.from_numpy(plan.spa_rows_host).to(self.device)
+        out = {"p": self._empty((T, G), torch.float64), "z": self._empty((T, G, 2), torch.float64),
+               "t": self._empty((T, G, 2), torch.float64), "status": self._empty((T, G), torch.int32)}
+        scratch = self._empty((int(self.lib.scoary_score_spa_scratch_bytes(G, T)),), torch.uint8)
+        self._check(self.lib.scoary_score_spa(
+            self.h, self._ptr(genes.tiled), self._ptr(plan.spa_rows), self._ptr(plan.rows), self._ptr(plan.valid),
+            self._ptr(plan.chol), *(self._ptr(score_out[k]) for k in ("U", "b", "Vg", "stat", "p")),
+            G, T, plan.N, q, cutoff * cutoff, *(self._ptr(out[k]) for k in ("p", "z", "t", "status")),
+            self._ptr(scratch), self._stream()), "scoary_score_spa")
         return out
 
     # -- timing (bench.py) ------------------------------------------------------

@@ -16,6 +16,9 @@
 //                     across the wavefront by an exchange in which every lane ends with the same bits, and made scalar
 //                     (readfirstlane): the Newton search and its bracket are scalar code.  Per side it leaves t^ and
 //                     what kind of side it is (beyond the support, the point mass, a root, no root within the cap).
+//                     The cap is 100 evaluations, the restatement's: the rule counted in Python over the tests'
+//                     problems (profiles/score_spa_tests.txt) takes up to 64 where the bracket's upper end sits at
+//                     K'' ~ 0 and the search goes on by midpoints, and a side at the cap costs its pair the answer.
 //   k_spa_sums<Q>     the same walk once more per side: K and K'' at the root, or the logarithm of the point mass.
 //   k_spa_finish      one lane per work item: omega, v, z, the two tails, SPA_p and the status.
 // Three kernels behind the list and not one, because hipcc keeps the coefficients of every fp64 library function
@@ -28,7 +31,7 @@ namespace {
 
 constexpr int kSpaMaxQ = 9;                          // design columns: S24's limit
 constexpr int kSpaMaxIsolates = 65536;               // an item is one wavefront's walk: 1024 isolates per lane at most
-constexpr int kSpaMaxEvals = 60;                     // evaluations of K' and K'' a side's search may take (S25)
+constexpr int kSpaMaxEvals = 100;                    // evaluations of K' and K'' a side's search may take (S25)
 constexpr double kSpaStep = 1e-11;                   // the search ends with an applied step of at most this, relative
 constexpr double kSpaEdge = 1e-9;                    // S25's epsilon: |x - s_hi| <= epsilon s_hi is the point mass
 constexpr int kSpaHeadBytes = 256;                   // the counter's own lines in front of the work list

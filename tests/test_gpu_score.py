@@ -193,6 +193,76 @@ def test_one_isolate_and_rows_that_are_not_zero_outside_the_valid_set(eng):
             assert np.array_equal(res["m"][:, 0], valid.sum(axis=1))
 
 
+LADDER_DF = (0, 1, 2, 3, 38, 39, 40, 41, 2000)
+LADDER_CELLS = 120                               # (trait, gene) cells of a ladder, at the least
+
+
+def _ladder(df):
+    """A linear plan made by hand whose t statistics are a ladder: q = 1, every weight 1, chol = [sqrt(n)], every
+    isolate valid, n = df + 2; gene g is the single carrier g, so U = r_g and Vg = 1 - 1/n, over G = min(n - 1, 60)
+    genes and as many traits as give 120 cells (n = 3 has two genes).  Cell k of K (trait by trait) aims at
+    |t| = 1e-8 (t_top / 1e-8)^(k / (K - 1)), a geometric ladder, through r = +-sqrt(y rss Vg) with
+    y = t^2 / (df + t^2) = U^2 / (Vg rss), odd cells negative; t_top^2 = df min(10^(600 / df), 2^50) is where the
+    tail is 1e-300, or as close to rss as a double lets U^2 / Vg come (rss1 is then a few ulps of rss: at df < 39
+    the ladder ends above 1e-280).  rss differs from trait to trait.  The last two genes of trait 0 have
+    U^2 / Vg = 4 rss, one with U > 0 and one with U < 0: rss1 < 0, t = +-inf, p = 0.
+    Returns (host dict for score_plan_of, genes)."""
+    n = df + 2
+    G = min(n - 1, 60)
+    T = -(-LADDER_CELLS // G)
+    K = T * G
+    rows = np.zeros((T, 2, n))
+    rows[:, 1] = 1.0
+    rss = 1.0 + 0.37 * np.arange(T)
+    vg = 1.0 - (1.0 / math.sqrt(n)) ** 2
+    top2 = max(df, 1) * min(10.0 ** min(600.0 / max(df, 1), 300.0), 2.0 ** 50)
+    for k in range(K):
+        t, g = divmod(k, G)
+        t2 = (1e-8 * (math.sqrt(top2) / 1e-8) ** (k / (K - 1.0))) ** 2
+        y = t2 / (max(df, 1) + t2)
+        if t == 0 and g >= G - 2:
+            y = 4.0
+        rows[t, 0, g] = (-1.0 if (k if y < 4.0 else g) % 2 else 1.0) * math.sqrt(y * rss[t] * vg)
+    host = dict(rows=rows, valid=np.ones((T, n), dtype=bool), chol=np.full((T, 1), math.sqrt(n)), rss=rss,
+                n=np.full(T, n), coef=np.zeros((T, 1)), skipped=[None] * T)
+    return host, np.eye(n, dtype=np.uint8)[:G]
+
+
+@pytest.mark.parametrize("df", LADDER_DF)
+def test_student_tail_ladder(eng, df):
+    """t_tail at the degrees of freedom the other shapes do not reach: df = 1, 2, 3 (lgamma at 0.5 to 1.5, the
+    branch switch of the fraction at x < 1/2), 38 to 41 (a = 19 to 20.5: lgamma gives way to the series at a = 20),
+    2000, and df = 0 (every gene untestable); |t| from 1e-8, where the tail is next to 1, to tails below 1e-280
+    where df allows it, half of them negative, and t = +-inf.  Held as every other shape is: the sums and the
+    statistic bit for bit, p within 1e-10 relative of mpmath at 50 digits at the device's own t."""
+    host, genes = _ladder(df)
+    T, G = len(host["rss"]), len(genes)
+    plan = eng.score_plan_of(host, "linear")
+    res = {k: v.cpu().numpy() for k, v in eng.score(eng.pack_dense(genes), plan).items()}
+    assert np.array_equal(plan.rows.cpu().numpy(), host["rows"])
+    want = _expected(host["rows"], host["valid"], host["chol"], host["rss"], genes, "linear")
+    tested = _compare(res, want, "linear", "ladder df=%d" % df)
+    if df == 0:
+        assert tested == 0 and G == 1 and np.all(res["p"] == 1.0) and not res["t"].any()
+    else:
+        assert tested == T * G and want[0][0]["df"] == df
+        _ladder_reaches(res["t"], res["p"], df)
+
+
+def _ladder_reaches(t, p, df):
+    """What the ladder is there for, on the statistics and tails [T, G] as they came out: both infinite statistics,
+    half of the finite ones negative, |t| from below 2e-8 (a tail next to 1) to the top, tails below 1e-280 where a
+    double lets rss1 get small enough for them (df >= 38; at df = 1, 2, 3 the top is |t| above 1e7)."""
+    G = t.shape[1]
+    assert sorted(t[0, G - 2:].tolist()) == [-math.inf, math.inf] and not p[0, G - 2:].any()
+    finite = np.isfinite(t)
+    assert finite.sum() >= t.size - 4                                # a top rung may round to rss1 <= 0
+    assert 0.45 <= (t[finite] < 0).mean() <= 0.55
+    assert 0.0 < np.abs(t[finite]).min() < 2e-8 and 1.0 - 1e-7 < p[finite].max() < 1.0
+    assert (p[finite] < 1e-280).any() if df >= 38 else np.abs(t[finite]).max() > 1e7
+    assert np.unique(np.abs(t[finite])).size >= finite.sum() - 2
+
+
 def test_a_skipped_trait_has_no_testable_gene(eng):
     rng = np.random.default_rng(25)
     N, G = 40, 30

@@ -6,7 +6,11 @@ word edge, invalid isolates in the middle of a row, q = 1, 3 and 9, one gene and
 trait and one at 5 % positives with rare genes of its own; genes of one and two carriers, of all but one, a perfectly
 predictive gene of the balanced and of the rare trait, a gene in the span of the covariates) and at three cutoffs: one
 that leaves the work list empty, the default, and the least, 0.1, where the list holds every testable pair; a problem
-whose pairs fall back, held to the status and to Score_p's bits; then the refusals."""
+whose pairs fall back, held to the status and to Score_p's bits; then the refusals.  Every instance q = 1 .. 9 runs (n97 .. n199).  Through
+score_spa_cases.fabricate, which makes the device list chosen pairs alone: rows of 4099 isolates and of
+scoary_score_spa_max_isolates(); the ends of the support on both sides (beyond it, the point mass from either side of
+the end, roots next to it); NaN in the rows of every invalid isolate; more pairs than k_spa_select's grid covers in
+one stride, a pair's result whatever else is listed, and a scratch buffer left by a longer list."""
 import math
 
 import numpy as np
@@ -56,8 +60,33 @@ def _case(eng, name):
     return _CACHE[name]
 
 
+def _hold(res, host, w, t, g, where):
+    """The device's outputs ``res`` of the pair (t, g) against the restatement's ``w``: the status exactly; at status
+    0 and 2 Score_p's bits (and zeros at 0); at status 1 t^ within 1e-9 relative, z within 1e-9 max(1, |z|), infinite
+    t^ and z = 0 on a side beyond the support or at the point mass, p within 1e-10 relative of the normal tails at
+    the device's own z (the restatement's tail on such a side)."""
+    assert int(res["status"][t, g]) == w["status"], where + (float(host["stat"][t, g]),)
+    if w["status"] != 1:
+        assert _bits(res["p"][t, g]) == _bits(host["p"][t, g]), where
+        if w["status"] == 0:
+            assert not res["z"][t, g].any() and not res["t"][t, g].any(), where
+        return
+    tails = []
+    for s in range(2):
+        t_dev, z_dev = float(res["t"][t, g, s]), float(res["z"][t, g, s])
+        if math.isinf(w["t"][s]):                                      # the point mass, or beyond the support
+            assert t_dev == w["t"][s] and z_dev == 0.0, where + (s, t_dev, z_dev)
+            tails.append(w["tails"][s])
+            continue
+        assert abs(t_dev - w["t"][s]) <= 1e-9 * abs(w["t"][s]), where + (s, t_dev, w["t"][s])
+        assert abs(z_dev - w["z"][s]) <= 1e-9 * max(1.0, abs(w["z"][s])), where + (s, z_dev, w["z"][s])
+        tails.append(sc.normal_tail(z_dev))
+    ref = min(1.0, tails[0] + tails[1])
+    assert abs(float(res["p"][t, g]) - ref) <= 1e-10 * ref, where + (float(res["p"][t, g]), ref)
+
+
 @pytest.mark.parametrize("cutoff", list(CUTOFFS))
-@pytest.mark.parametrize("name", list(sc.SHAPES))
+@pytest.mark.parametrize("name", list(sc.EVERY_PAIR))
 def test_score_spa_matches_the_restatement(eng, name, cutoff):
     import torch
     N, G, c = sc.SHAPES[name]
@@ -75,25 +104,9 @@ def test_score_spa_matches_the_restatement(eng, name, cutoff):
         for g in range(G):
             w, where = want[t][g], (name, cutoff, t, g)
             assert w["status"] != 2, where                             # score_spa_cases.py: no problem has one
-            assert int(res["status"][t, g]) == w["status"], where + (float(host["stat"][t, g]),)
+            _hold(res, host, w, t, g, where)
             counts[w["status"]] += 1
             rare += t == 2 and w["status"] == 1
-            if w["status"] == 0:
-                assert _bits(res["p"][t, g]) == _bits(host["p"][t, g]), where
-                assert not res["z"][t, g].any() and not res["t"][t, g].any(), where
-                continue
-            tails = []
-            for s in range(2):
-                t_dev, z_dev = float(res["t"][t, g, s]), float(res["z"][t, g, s])
-                if math.isinf(w["t"][s]):                              # the point mass, or beyond the support
-                    assert t_dev == w["t"][s] and z_dev == 0.0, where + (s, t_dev, z_dev)
-                    tails.append(w["tails"][s])
-                    continue
-                assert abs(t_dev - w["t"][s]) <= 1e-9 * abs(w["t"][s]), where + (s, t_dev, w["t"][s])
-                assert abs(z_dev - w["z"][s]) <= 1e-9 * max(1.0, abs(w["z"][s])), where + (s, z_dev, w["z"][s])
-                tails.append(sc.normal_tail(z_dev))
-            ref = min(1.0, tails[0] + tails[1])
-            assert abs(float(res["p"][t, g]) - ref) <= 1e-10 * ref, where + (float(res["p"][t, g]), ref)
     if cutoff == "empty list":
         assert counts[1] == 0
     else:
@@ -102,6 +115,10 @@ def test_score_spa_matches_the_restatement(eng, name, cutoff):
             assert rare >= 5 and res["status"][2, 3] == 1
             if c <= 2:                                                 # its own perfectly predictive gene: a point mass
                 assert res["t"][2, 3, 0] == math.inf                   # (eight covariates move it off the end)
+            if name in ("n113", "n150"):                               # three and five leave it there, four, six and
+                assert res["t"][2, 3, 0] == math.inf                   # seven do not
+            elif c > 2:
+                assert math.isfinite(res["t"][2, 3, 0])
             if sc.RARE[N] < 0.1:                                       # the regime S25 is for: Score_p far too small
                 assert max(res["p"][2, g] / host["p"][2, g] for g in range(3)) > 1e3
     if cutoff == "every pair":
@@ -128,6 +145,183 @@ def test_pairs_that_fall_back_keep_score_p(eng):
             if want[t, g] != 1:
                 assert _bits(res["p"][t, g]) == _bits(host["p"][t, g]), (t, g)
     assert (res["p"][want == 2] > 0.5).all()                           # statistics of 0.08: nothing lost
+
+
+def _listed(eng, gm, plan, genes, score, pairs, U=None, cutoff=sp.MIN_CUTOFF):
+    """score_spa with S24's outputs ``score`` (numpy) fabricated so that the device lists exactly ``pairs`` (U moved
+    where ``U`` says): (the device's outputs as numpy, the fabricated outputs, the restatement of ``pairs`` as a
+    dict), the pairs held to the restatement and every other pair to status 0, Score_p's bits and zeros."""
+    import torch
+    fab = sc.fabricate(score, pairs, U)
+    dev = {k: torch.from_numpy(fab[k]).to(eng.device) for k in ("U", "b", "Vg", "stat", "p")}
+    res = {k: v.cpu().numpy() for k, v in eng.score_spa(gm, plan, dev, cutoff).items()}
+    want = sc.restate(plan.spa_rows.cpu().numpy(), plan.rows.cpu().numpy()[:, 1], plan.valid_host,
+                      plan.chol.cpu().numpy(), genes, fab, cutoff, pairs=pairs)
+    for t, g in pairs:
+        _hold(res, fab, want[t, g], t, g, (t, g))
+    _unlisted(res, fab, pairs)
+    return res, fab, want
+
+
+def _unlisted(res, score, pairs):
+    """Every pair outside ``pairs``: status 0, the bits of Score_p, zeros."""
+    rest = np.ones(res["status"].shape, dtype=bool)
+    rest[tuple(np.array(pairs).T)] = False
+    assert not res["status"][rest].any() and not res["z"][rest].any() and not res["t"][rest].any()
+    assert np.array_equal(_bits(res["p"])[rest], _bits(score["p"])[rest])
+    assert np.all(res["status"][~rest] != 0)
+
+
+def _s24(eng, genes, values, cov):
+    gm = eng.pack_dense(genes)
+    plan = eng.score_plan(values, cov, "logistic")
+    score = eng.score(gm, plan)
+    return gm, plan, score, {k: v.cpu().numpy() for k, v in score.items()}
+
+
+@pytest.mark.parametrize("name", list(sc.SUBSET))
+def test_long_rows(eng, name):
+    """65 strides of the lanes with a short last one (N = 4099: a word tail, and a tail of the tiled matrix's groups of
+    four words), and scoary_score_spa_max_isolates() itself, 1024 isolates a lane: the listed pairs of
+    score_spa_cases.LISTED, the only ones restated, at the default cutoff."""
+    N, G, c = sc.SHAPES[name]
+    if name == "n65536":
+        assert N == eng.score_spa_max_isolates()
+    genes, values, cov = sc.problem(name)
+    gm, plan, _score, host = _s24(eng, genes, values, cov)
+    assert plan.skipped == [None, "one_class", None] and plan.q == c + 1 and plan.N == N
+    pairs = list(sc.LISTED[name])
+    res, _fab, want = _listed(eng, gm, plan, genes, host, pairs, cutoff=sp.CUTOFF)
+    assert all(want[pair]["status"] == 1 for pair in pairs)
+    if name == "n4099":
+        assert len(pairs) == 12 and res["t"][0, G - 4].tolist() == [math.inf, -math.inf] and res["t"][2, 3, 0] == math.inf
+        assert all(res["p"][2, g] > 1e3 * host["p"][2, g] for g in range(3))
+        assert sum(math.isfinite(x) and x != 0.0 for x in res["t"].ravel().tolist()) == 21
+
+
+def test_the_ends_of_the_support_on_both_sides(eng):
+    """score_spa_cases.ends_problem: the perfectly anti-predictive gene (U < 0: the point mass of side 1, nothing on
+    side 0) as it is; then U moved by fabricate to s_end (1 + k 1e-9) -- k = 3 beyond the support, k = +-0.5 the point
+    mass -- and to s_end (1 - delta), delta = 1e-2 and 1e-4, a root next to the end, with s_end = s_hi (side 0) and
+    |s_lo| (side 1).  0.5e-9 and 3e-9 are far from the 1e-16 by which the device's ends differ from fsum's."""
+    genes, values, cov = sc.ends_problem()
+    G = len(genes)
+    gm, plan, score, host = _s24(eng, genes, values, cov)
+    real = {k: v.cpu().numpy() for k, v in eng.score_spa(gm, plan, score, sp.MIN_CUTOFF).items()}
+    P = (plan.spa_rows.cpu().numpy(), plan.rows.cpu().numpy()[:, 1], plan.valid_host, plan.chol.cpu().numpy(), genes)
+    anti = sc.restate(*P, host, sp.MIN_CUTOFF, pairs=[(0, G - 1), (0, G - 5)])
+    for g in (G - 1, G - 5):
+        _hold(real, host, anti[0, g], 0, g, ("as it is", g))
+    w = anti[0, G - 1]
+    assert host["U"][0, G - 1] < 0.0 and w["status"] == 1 and w["t"] == [math.inf, -math.inf]
+    assert real["t"][0, G - 1].tolist() == [math.inf, -math.inf] and not real["z"][0, G - 1].any()
+    mass = sp.point_mass(sc.items_of(*P, host, 0, G - 1), False)
+    assert w["tails"][0] == 0.0 and mass > 0.0 and abs(real["p"][0, G - 1] - mass) <= 1e-10 * mass
+    assert real["t"][0, G - 5].tolist() == [math.inf, -math.inf]          # trait 0 itself: the same mass, on side 0
+    assert abs(real["p"][0, G - 5] - real["p"][0, G - 1]) <= 1e-9 * mass
+
+    U, what = sc.ends_moves(*P, host)
+    pairs = list(U)
+    res, _fab, want = _listed(eng, gm, plan, genes, host, pairs, U)
+    seen = {}
+    for pair, (side, kind, v) in what.items():
+        assert want[pair]["status"] == 1 and res["status"][pair] == 1, (pair, side, kind, v)
+        seen[side, kind, v] = seen.get((side, kind, v), 0) + 1
+        far = -math.inf if side else math.inf
+        if kind == "k":
+            assert res["t"][pair][side] == far and res["z"][pair][side] == 0.0 and want[pair]["t"][side] == far
+            assert (want[pair]["tails"][side] == 0.0) == (v > 1.0)
+        else:
+            assert math.isfinite(res["t"][pair][side]) and abs(res["t"][pair][side]) > 10.0
+    assert all(seen[side, "k", k] == 1 for side in (0, 1) for k in sc.ENDS_K)
+    assert all(seen[side, "delta", d] >= 2 for side in (0, 1) for d in sc.ENDS_DELTA)
+
+
+@pytest.mark.parametrize("name", ["n65", "n150"])
+def test_invalid_isolates_are_skipped_by_their_bit(eng, name):
+    """S25: isolates outside the valid set and pad bits are skipped by the validity bit, never by relying on zero
+    rows.  NaN at every invalid isolate of every row of spa_rows and of S24's rows, every bit of the tiled matrix at
+    and past isolate N set: the outputs keep their bits (q = 9 and q = 6)."""
+    import torch
+    from types import SimpleNamespace
+    from scoary_amd.engine import GeneMatrix
+    N, G, c = sc.SHAPES[name]
+    genes, gm, plan, score, _before, _host, _every = _case(eng, name)
+    good = {k: v.cpu().numpy() for k, v in eng.score_spa(gm, plan, score, sp.MIN_CUTOFF).items()}
+    T, q = sc.T, c + 1
+    invalid = torch.from_numpy(~plan.valid_host).to(eng.device)                       # [T, N]
+    assert int(invalid.sum()) >= N + 2 * 3                                            # a whole trait and more
+    poisoned = SimpleNamespace(valid=plan.valid, chol=plan.chol)
+    for key in ("spa_rows", "rows"):
+        rows = getattr(plan, key).clone()
+        rows.masked_fill_(invalid[:, None, :], float("nan"))
+        assert int(torch.isnan(rows).sum()) == (q + 1) * int(invalid.sum())
+        setattr(poisoned, key, rows)
+    tiled = gm.tiled.clone()
+    for w in range(N // 32, tiled.shape[0] * 4):
+        fill = -1 if 32 * w >= N else -(1 << (N - 32 * w))           # as int32: the bits from N - 32 w up
+        tiled[w // 4, :, w % 4] |= fill
+    outs = [torch.full((T * G * k,), float("nan"), dtype=torch.float64, device=eng.device) for k in (1, 2, 2)]
+    outs.append(torch.full((T * G,), 77, dtype=torch.int32, device=eng.device))
+    scratch = torch.zeros(int(eng.lib.scoary_score_spa_scratch_bytes(G, T)), dtype=torch.uint8, device=eng.device)
+    assert _raw(eng, GeneMatrix(tiled, G, N), poisoned, score, G, T, N, q, sp.MIN_CUTOFF ** 2, outs, scratch) == 0
+    torch.cuda.synchronize()
+    assert (good["status"] == 1).sum() >= 100
+    for o, key in zip(outs, ("p", "z", "t", "status")):
+        got = o.cpu().numpy()
+        if key == "status":
+            assert np.array_equal(got, good[key].ravel())
+        else:
+            assert not np.isnan(got).any(), key
+            assert np.array_equal(_bits(got), _bits(good[key].ravel())), key
+
+
+def test_select_strides_and_the_list_is_free(eng):
+    """score_spa_cases.wide_problem, 525 000 pairs: k_spa_select's 2048 blocks of 256 lanes take a second stride.
+    64 listed pairs (pair 0, the last, both sides of pair 524 288, ten neighbours) are held to the restatement and
+    every other pair to Score_p's bits.  Listed next to 20 000 others they keep their bits: sums is indexed by list
+    position and the list's order comes from atomics, but a pair's result does not depend on the list.  Then the
+    first list again on the scratch buffer the longer list left: the first run's outputs bit for bit."""
+    import torch
+    N, G, T = sc.WIDE
+    genes, values, cov = sc.wide_problem()
+    gm, plan, _score, host = _s24(eng, genes, values, cov)
+    assert T * G > 2048 * 256 and plan.skipped == [None] * T and plan.q == 1
+    pairs = sc.wide_listed(host["stat"])
+    assert len(pairs) == 64
+    first, fab1, want = _listed(eng, gm, plan, genes, host, pairs)
+    assert all(w["status"] == 1 for w in want.values())
+
+    rng = np.random.default_rng(sc.WIDE_SEED + 2)
+    free = host["stat"] >= sp.MIN_CUTOFF ** 2          # pairs a run could list (where U is the rounding residue of 0,
+                                                       # a statistic of 1e-31, S25 itself gives z = 1e14 and p = 0)
+    free[tuple(np.array(pairs).T)] = False
+    others = [divmod(o, G) for o in rng.choice(np.flatnonzero(free.ravel()), 20000, replace=False).tolist()]
+    fab2 = sc.fabricate(host, pairs + others)
+
+    def run(fab, scratch):
+        dev = {k: torch.from_numpy(fab[k]).to(eng.device) for k in ("U", "b", "Vg", "stat", "p")}
+        outs = [torch.full((T * G * k,), float("nan"), dtype=torch.float64, device=eng.device) for k in (1, 2, 2)]
+        outs.append(torch.full((T * G,), 77, dtype=torch.int32, device=eng.device))
+        assert _raw(eng, gm, plan, dev, G, T, N, 1, sp.MIN_CUTOFF ** 2, outs, scratch) == 0
+        torch.cuda.synchronize()
+        return {k: o.cpu().numpy().reshape(first[k].shape) for k, o in zip(("p", "z", "t", "status"), outs)}
+
+    scratch = torch.zeros(int(eng.lib.scoary_score_spa_scratch_bytes(G, T)), dtype=torch.uint8, device=eng.device)
+    second = run(fab2, scratch)
+    at = tuple(np.array(pairs).T)
+    for k in ("p", "z", "t"):
+        assert np.array_equal(_bits(second[k][at]), _bits(first[k][at])), k
+    assert np.array_equal(second["status"][at], first["status"][at])
+    there = tuple(np.array(others).T)
+    assert np.isin(second["status"][there], (1, 2)).all() and (second["status"][there] == 1).sum() >= 19000
+    assert ((second["p"][there] > 0.0) & (second["p"][there] <= 1.0)).all()
+    _unlisted(second, fab2, pairs + others)
+    assert int(scratch[:4].view(torch.int32)[0]) == 20064             # the longer list's counter, list and sums
+    third = run(fab1, scratch)
+    for k in ("p", "z", "t"):
+        assert np.array_equal(_bits(third[k]), _bits(first[k])), k
+    assert np.array_equal(third["status"], first["status"])
 
 
 def _raw(eng, gm, plan, score, G, T, N, q, cutoff2, outs, scratch, missing=()):

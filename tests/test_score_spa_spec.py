@@ -4,6 +4,7 @@ root against mpmath at 50 digits, and the laws of the specification: the point m
 the side beyond the support, the cutoff, a gene and its complement, and no fallback on the problems the device is
 held to (score_spa_cases.py)."""
 import math
+import os
 
 import mpmath
 import numpy as np
@@ -212,16 +213,56 @@ def test_a_gene_and_its_complement_get_the_same_p():
     assert done >= 5
 
 
-@pytest.mark.parametrize("name", list(sc.SHAPES))
-def test_no_fallback_on_the_problems_the_device_is_held_to(name):
-    genes, values, cov = sc.problem(name)
+_PROBLEMS = {}
+
+
+def _problem(name):
+    """A problem of score_spa_cases on the host, once: (what restate takes before the score, S24's outputs, the
+    listed pairs, the restatement at the least cutoff -- [T][G], or the dict of the listed pairs --, host, values).
+    name: a shape, "fallback", "ends" (ends_problem as it is), "ends moved" (its fabricated ends), "wide"."""
+    if name in _PROBLEMS:
+        return _PROBLEMS[name]
+    subset = None
+    if name == "wide":
+        genes, values, cov = sc.wide_problem()
+        subset = sc.wide_candidates()
+    elif name.startswith("ends"):
+        genes, values, cov = sc.ends_problem()
+    else:
+        genes, values, cov = sc.fallback_problem() if name == "fallback" else sc.problem(name)
     host = score_host(values, cov, "logistic")
-    assert host["skipped"] == [None, "one_class", None]
-    score = sc.s24(host, genes)
     spa_rows = np.concatenate([host["mu"][:, None, :], host["design"]], axis=1)
+    P = (spa_rows, host["rows"][:, 1], host["valid"], host["chol"], genes)
+    score = sc.s24(host, genes, subset)
+    listed = None
+    if name in sc.SUBSET:
+        listed = list(sc.LISTED[name])
+    elif name == "wide":
+        listed = sc.wide_listed(score["stat"])
+    elif name == "ends moved":
+        U, _what = sc.ends_moves(*P, score)
+        listed = list(U)
+        score = sc.fabricate(score, listed, U)
+    if listed is None:
+        every = sc.restate(*P, score, sp.MIN_CUTOFF)
+        listed = [(t, g) for t in range(len(every)) for g in range(len(genes)) if every[t][g]["status"]]
+    else:
+        every = sc.restate(*P, sc.fabricate(score, listed), sp.MIN_CUTOFF, pairs=listed)
+    _PROBLEMS[name] = (P, score, listed, every, host, values)
+    return _PROBLEMS[name]
+
+
+# the shapes whose trait 2 is itself a point mass as gene 3 (more covariates move that gene off the end of the support)
+OWN_GENE_AT_THE_END = ("n64", "n130", "n600", "n97", "n113", "n150")
+
+
+@pytest.mark.parametrize("name", list(sc.EVERY_PAIR))
+def test_no_fallback_on_the_problems_the_device_is_held_to(name):
+    P, score, _listed, every, host, values = _problem(name)
+    spa_rows, genes = P[0], P[4]
+    assert host["skipped"] == [None, "one_class", None]
     assert spa_rows.shape == (sc.T, sc.SHAPES[name][2] + 2, sc.SHAPES[name][0])
     assert not spa_rows.transpose(0, 2, 1)[~host["valid"]].any()          # zero outside the valid sets
-    every = sc.restate(spa_rows, host["rows"][:, 1], host["valid"], host["chol"], genes, score, sp.MIN_CUTOFF)
     status = np.array([[r["status"] for r in row] for row in every])
     assert not (status == 2).any()
     assert np.array_equal(status == 1, score["testable"] & (score["stat"] >= sp.MIN_CUTOFF ** 2))
@@ -234,12 +275,127 @@ def test_no_fallback_on_the_problems_the_device_is_held_to(name):
         assert (score["stat"][2] >= sp.CUTOFF ** 2).sum() >= 5 and (status == 0).sum() > sc.T
         if sc.SHAPES[name][2] <= 2:                                        # the rare trait's own (eight covariates
             assert every[2][3]["t"][0] == math.inf                         # move that gene off the end of the support)
+        assert (every[2][3]["t"][0] == math.inf) == (name in OWN_GENE_AT_THE_END)
     if sc.RARE[N] < 0.1:                                                   # 5 % positives, rare genes, real statistics
         n, pos = int(host["n"][2]), np.nansum(values[2])
         assert 0.04 <= pos / n <= 0.07
         for g in range(3):
             m = int(genes[g][host["valid"][2]].sum())
             assert m <= 0.07 * n and score["stat"][2, g] > 30 and every[2][g]["p"] > 1e3 * score["p"][2, g]
+
+
+def test_every_instance_has_a_shape():
+    """q = 1 .. 9: every instance of the search and of the sums runs in some shape that is restated over every pair."""
+    assert {sc.SHAPES[name][2] + 1 for name in sc.EVERY_PAIR} == set(range(1, 10))
+    new = [sc.SHAPES[name] for name in ("n97", "n113", "n128", "n150", "n177", "n199")]
+    assert all(96 <= N <= 200 and G == 70 for N, G, _c in new) and sum(N % 32 != 0 for N, _G, _c in new) >= 3
+    assert len({N for N, _G, _c in sc.SHAPES.values()}) == len(sc.SHAPES) == len(sc.RARE) == len(sc.SEEDS)
+
+
+@pytest.mark.parametrize("name", list(sc.SUBSET) + ["wide"])
+def test_the_listed_pairs_of_the_long_and_wide_problems_have_status_1(name):
+    """n4099, n65536 and wide_problem are held through listed pairs: each testable, none falling back; n4099's
+    include the rare genes, a point mass on each of two traits and a side beyond the support."""
+    P, score, listed, every, host, _values = _problem(name)
+    assert len(listed) == len(set(listed)) == {"n4099": 12, "n65536": 2, "wide": 64}[name]
+    assert all(score["testable"][pair] and every[pair]["status"] == 1 for pair in listed)
+    if name == "n4099":
+        G = len(P[4])
+        assert host["skipped"] == [None, "one_class", None] and {(2, 0), (2, 1), (2, 2), (0, G - 4)} <= set(listed)
+        assert every[0, G - 4]["t"] == [math.inf, -math.inf] and every[2, 3]["t"][0] == math.inf
+        assert all(score["stat"][2, g] > 30 and every[2, g]["p"] > 1e3 * score["p"][2, g] for g in range(3))
+    if name == "n65536":
+        assert host["skipped"] == [None, "one_class", None] and P[0].shape[2] == 65536
+    if name == "wide":
+        N, G, Tn = sc.WIDE
+        at = sorted(t * G + g for t, g in listed)
+        assert Tn * G > 2048 * 256 and at[0] == 0 and at[-1] == Tn * G - 1 and host["skipped"] == [None] * Tn
+        assert {524286, 524287, 524288, 524289} <= set(at) and set(range(262144, 262154)) <= set(at)
+
+
+def test_the_ends_of_the_support_on_both_sides():
+    """ends_problem: the perfectly anti-predictive gene has U < 0, the point mass below and nothing above; the moved
+    pairs are beyond the support (tail 0), at the point mass from either side of the end (its tail, an infinite t^),
+    and at roots a hundredth and a ten-thousandth of the support from the end, of which at least two per side and
+    distance end within 80 evaluations with status 1 -- on side 0 and on side 1."""
+    P, score, _listed, every, _host, _values = _problem("ends")
+    G = len(P[4])
+    anti = every[0][G - 1]
+    items = sc.items_of(*P, score, 0, G - 1)
+    lo, _hi = sp.support(items)
+    assert score["U"][0, G - 1] < 0.0 and abs(score["U"][0, G - 1] - lo) <= 1e-12 * abs(lo)
+    assert anti["status"] == 1 and anti["t"] == [math.inf, -math.inf] and anti["tails"][0] == 0.0
+    assert abs(anti["p"] - sp.point_mass(items, False)) <= 1e-10 * anti["p"] and anti["p"] > 0.0
+    assert abs(anti["p"] - every[0][G - 5]["p"]) <= 1e-9 * anti["p"]      # trait 0 itself: the same mass, above
+    _P, fab, listed, moved, _host, _values = _problem("ends moved")
+    _U, what = sc.ends_moves(*P, score)
+    assert list(what) == listed
+    kept = {}
+    for pair, (side, kind, v) in what.items():
+        r = moved[pair]
+        assert r["status"] == 1, (pair, side, kind, v)
+        kept[side, kind, v] = kept.get((side, kind, v), 0) + 1
+        if kind == "k":
+            assert math.isinf(r["t"][side]) and r["z"][side] == 0.0
+            assert (r["tails"][side] == 0.0) if v > 1.0 else (0.0 < r["tails"][side] < 1e-30), (pair, r)
+        else:
+            assert math.isfinite(r["t"][side]) and abs(r["t"][side]) > 10.0
+    assert kept == dict([((side, "k", k), 1) for side in (0, 1) for k in sc.ENDS_K] +
+                        [((side, "delta", d), kept.get((side, "delta", d))) for side in (0, 1) for d in sc.ENDS_DELTA])
+    assert all(kept[side, "delta", d] >= 2 for side in (0, 1) for d in sc.ENDS_DELTA)
+
+
+CENSUS = list(sc.EVERY_PAIR) + ["fallback"] + list(sc.SUBSET) + ["ends", "ends moved", "wide"]
+CENSUS_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "score_spa_tests.txt")
+CENSUS_ROOM = 80
+
+
+def _census():
+    """{problem: [(t, g, side, evaluations, rules, status, root)]}: score_spa_cases.device_search over every listed
+    side of every problem the device is held to, at the least cutoff."""
+    out = {}
+    for name in CENSUS:
+        P, score, listed, every, _host, _values = _problem(name)
+        out[name] = sc.census(*P, score, listed, every)
+    return out
+
+
+def census_text(census):
+    """The text of profiles/score_spa_tests.txt below its head: per problem the searched sides by evaluations."""
+    edges = (0, 10, 20, 30, 40, 50, 60, 80, sc.DEVICE_MAX_EVALS + 1)
+    lines = ["%-11s %5s  " % ("problem", "sides") + " ".join("%7s" % ("%d-%d" % (a, b - 1)) for a, b in
+                                                              zip(edges, edges[1:])) + "   max  at the cap"]
+    for name, rows in census.items():
+        evals = [r[3] for r in rows]
+        hist = [sum(a <= e < b for e in evals) for a, b in zip(edges, edges[1:])]
+        lines.append("%-11s %5d  " % (name, len(rows)) + " ".join("%7d" % h for h in hist) +
+                     " %5d  %d" % (max(evals), sum(r[6] is None for r in rows)))
+    for rule in sc.RULES:
+        lines.append("rule %-18s sides %d" % (rule + ":", sum(rule in r[4] for rows in census.values() for r in rows)))
+    return "\n".join(lines) + "\n"
+
+
+def test_search_census():
+    """The device's search rule (score_spa_cases.device_search) over every searched side of every problem the device
+    is held to: each of its five rules is used; no side of a pair with the restatement's status 1 stops at the cap of
+    100 evaluations, or takes more than 80 -- a condition on the problems, which leaves 20 evaluations to the device's
+    own rounding (its sums are not math.fsum's; how many evaluations it takes has not been measured).  The side that
+    takes 64, above the cap of 60 that S25 had: n600, trait 0, the perfectly predictive gene, the lower side.
+    Running this file as a program from the repository root writes the census to profiles/score_spa_tests.txt."""
+    census = _census()
+    used = set().union(*(r[4] for rows in census.values() for r in rows))
+    assert used == set(sc.RULES)
+    for name, rows in census.items():
+        for t, g, side, evals, _rules, status, root in rows:
+            if status == 1:
+                assert root is not None and evals <= CENSUS_ROOM, (name, t, g, side, evals)
+    G = sc.SHAPES["n600"][1]
+    slow = [r for r in census["n600"] if r[:3] == (0, G - 4, 1)]
+    assert len(slow) == 1 and slow[0][3] > 60 and slow[0][5] == 1       # the side the cap of 60 sent to Score_p
+    assert max(r[3] for rows in census.values() for r in rows if r[5] == 1) == max(r[3] for r in census["n600"])
+    with open(CENSUS_FILE) as f:
+        text = f.read()
+    assert all(("\n%-11s " % name) in text for name in CENSUS) and all(rule in text for rule in sc.RULES)
 
 
 def test_the_fallback_problem_falls_back_where_it_is_meant_to():
@@ -257,3 +413,42 @@ def test_the_fallback_problem_falls_back_where_it_is_meant_to():
         assert every[t][g]["p"] == score["p"][t, g] and 0.05 < score["stat"][t, g] < 0.1
         assert not (genes[g] * np.nan_to_num(values[t]))[host["valid"][t]].any()
     assert not any(r["status"] == 2 for row in sc.at_cutoff(every, score, sp.CUTOFF) for r in row)
+
+
+if __name__ == "__main__":
+    HEAD = """score_spa_tests: the census of the device's search rule over the problems of the device tests
+(tests/test_score_spa_spec.py::test_search_census; written by `PYTHONPATH=. python tests/test_score_spa_spec.py`).
+
+score_spa_cases.device_search is S25's "The search (device)" in plain Python with the sums by math.fsum.  It was run
+over every searched side (not beyond the support, not a point mass) of every pair that the device tests list, at the
+least cutoff 0.1.  Columns: sides by evaluations of K', K''; the most; sides that stop at the cap of 100.
+A CPU census: deterministic, no GPU.  NOT MEASURED: how many evaluations the device itself takes.  Its sums round
+differently from math.fsum, and near the rounding floor of K' that changes which rule a step takes.  The tests hold
+the problems to at most 80 evaluations where the restatement has status 1; the 20 up to the cap are the room left for
+that difference, and nobody has measured how much of it is used.
+
+The slowest side: n600, trait 0, gene G - 4 (the perfectly predictive gene, stat 561, |U| at 0.999996 of the lower
+end of the support), the lower side: %d evaluations -- above the cap of 60 that S25 had until this census, under which
+the pair could only get Score_p.  Its trace: 15 Newton steps that creep up, one 4t step to where K'' is about 0, 23
+midpoints, then Newton and midpoint in turn at the rounding floor of K'.  About 30 %% of the sides of n64 and n600
+take 30 to 49 evaluations in that slow mode (midpoints while the upper end of the bracket sits where K'' is about 0).
+
+Mutation check of the device tests (tests/test_gpu_score_spa.py on one MI355X, libraries built from mutated copies
+of scoary_score_spa.hip outside the tree; which tests go red):
+  isolates skipped by a zero weight instead of the validity bit   test_invalid_isolates_are_skipped_by_their_bit
+                                                                   alone, both shapes (every older test passes)
+  sums indexed by o %% count in k_spa_finish                        test_select_strides_and_the_list_is_free and 27 more
+  log(m) and log1p(-m) swapped in the point-mass walk              test_the_ends_of_the_support_on_both_sides, and
+                                                                   the restated shapes
+  the row step xi += N dropped at j = 4                            n128, n150, n177, n199 (q = 5 .. 8) and n65
+  the cap back at 60 in device_search (CPU)                        test_search_census: n600, trait 0, gene 66, side 1
+(The mu[i] load moved in front of the validity test was not built: its value is unused on the path that returns
+false, so the compiler is free to drop it; the mutant above is the form of that mistake that survives a compiler.)
+
+"""
+    census = _census()
+    G = sc.SHAPES["n600"][1]
+    slow = [r[3] for r in census["n600"] if r[:3] == (0, G - 4, 1)][0]
+    with open(CENSUS_FILE, "w") as f:
+        f.write(HEAD % slow + census_text(census))
+    print(open(CENSUS_FILE).read())
